@@ -6,11 +6,20 @@ seeded region growing, seed + constrain losses, backward) -> backbone backward -
 16 images per GPU (BASELINE.json configs[2]; configs[3] at N=8).  Synthetic inputs are resident in HBM before the timed region.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode train|supervision|infer|crf-fullres|test-ms|train-f]
-  N>1: python bench.py --gpus N re-executes itself as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
-       --master-addr 127.0.0.1 ... bench.py --gpus N ...` (one rank per GPU over RCCL); started under that launcher
-       already (WORLD_SIZE set) it runs as a rank.  Fewer than N GPUs visible: one line saying so, exit status 1.
+                  [--full] [--dump-outputs DIR]
+  N>1: python bench.py --gpus N starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
+       --master-addr 127.0.0.1 ... bench.py --gpus N ...` as a child process (one rank per GPU over RCCL) and exits with its
+       status; started under that launcher already (WORLD_SIZE set) it runs as a rank.  Fewer than N GPUs visible: one line
+       saying so, exit status 1.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run of --mode train or train-f sets up, warms up, times the K steps and prints the
+contract fields (`value`, `ms_per_step`, ...) with the figures that follow from the timed steps alone (backbone TFLOP/s).
+--dump-outputs DIR then also writes what the last timed step computed as DIR/<name>.npy (float32 / float64): the losses the
+step returns and the trainable parameters it updated (each whole up to PARAM_SAMPLE elements, a larger one at PARAM_SAMPLE
+fixed, seeded positions); the other modes write their own results (supervision: losses and the gradient to the logits;
+infer: seeds; crf-fullres: marginals; test-ms: mask).  The inputs are seeded: the same arguments give the same inputs.
+
+--full adds, for --mode train on one rank, what the headline does not need (the --no-* switches still drop single parts):
   roofline      — the dominant hot-path kernel (mean-field filter = permutohedral splat/blur/slice): modelled LDS bytes per
                   launch / HIP-event time per launch, measured in a separate untimed pass (the event brackets cost ~5 us each)
   cpu_baseline  — the CPU oracle (a port of the reference's CPU path) timed on this box's host cores on a bounded sample of
@@ -21,6 +30,8 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                   cpu_baseline: supervision (hot path alone, 16 images), supervision_b1, infer_b1 (BASELINE.json configs[1]),
                   crf_fullres, train_f (the reference's stage 2: VGG16-ASPP 321x321, batch 16), train_f_resnet101_513
                   (BASELINE.json configs[4] on one GPU, batch 10)
+  also          — other_rooflines (region growing), supervision_ms_per_step and the weight checksum of a single process (a
+                  run under a process group always all-gathers the checksums: its figure stands on the replicas agreeing)
 """
 import argparse
 import json
@@ -174,7 +185,38 @@ def _counter_file(stem, kernel):
     return None, {"file": None, "match": False}
 
 
-def crf_fullres_record(device, steps, warmup, cpu=True, size=321):
+PARAM_SAMPLE = 65536                    # elements kept of each trainable parameter in --dump-outputs (VGG16-ASPP: 5.3 MB in all)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def param_sample(net):
+    """the trainable parameters as the last step left them: each whole up to PARAM_SAMPLE elements, a larger one at PARAM_SAMPLE
+    positions drawn by a generator seeded with the parameter's index (the same elements in every run and every build)"""
+    out = {}
+    for i, (name, p) in enumerate(n_p for n_p in net.named_parameters() if n_p[1].requires_grad):
+        flat = p.detach().reshape(-1)
+        if flat.numel() > PARAM_SAMPLE:
+            idx = np.sort(np.random.default_rng(i).choice(flat.numel(), PARAM_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out["param." + name] = flat
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float64 kept, everything else as float32"""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, over the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def crf_fullres_record(device, steps, warmup, cpu=True, size=321, dump=None):
     """SURVEY 8f-1, training/tools/test-ms.py:84-111: the test-time dense CRF at image resolution — log-probability unaries,
     scale_factor 1, 21 labels, 10 iterations — through krahenbuhl2013's object API with device pointers (dsrg_amd.crf.DenseCRF;
     what CRF_device does per call).  One step = one image: unary + pairwise set-up (both lattices are built) + inference.
@@ -307,6 +349,8 @@ def crf_fullres_record(device, steps, warmup, cpu=True, size=321):
                             "eight_copies_equal": batch_same},
            "sizes": [{k: v for k, v in o.items() if k not in ("q", "im", "un", "dt")} for o in out_sizes],
            "roofline": roofline}
+    if dump is not None:
+        dump.update({"q_%dx%d" % (o["H"], o["W"]): o["q"] for o in out_sizes})      # each size's last timed call
     if cpu:
         from oracle import oracle as O
         t0 = time.perf_counter()
@@ -318,7 +362,7 @@ def crf_fullres_record(device, steps, warmup, cpu=True, size=321):
     return rec
 
 
-def test_ms_record(device, steps, warmup, cpu=True):
+def test_ms_record(device, steps, warmup, cpu=True, dump=None):
     """the reference's test-time loop end to end for one image per step (training/tools/test-ms.py:84-111, run.sh:6,10): three forwards at
     241 / 321 / 401, each score map zoomed to the image, summed, softmax, clip, log, full-resolution dense CRF (10 iterations, scale 1),
     arg-max — inference.predict_mask_ms on synthetic VOC-sized images (375 x 500), random-init VGG16-ASPP in eval mode.  Only the
@@ -360,6 +404,8 @@ def test_ms_record(device, steps, warmup, cpu=True):
         mask = one(i)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump is not None:
+        dump["mask"] = np.asarray(mask)
     # the same loop with the CRFs of earlier images in flight under the next image's forwards (inference.predict_masks_ms_many): how
     # a whole split (1 449 / 10 582 images) is run
     npipe = max(64, steps)
@@ -417,7 +463,7 @@ def test_ms_record(device, steps, warmup, cpu=True):
     return rec
 
 
-def infer_record(device, rank, B, steps, warmup, use_graph=True):
+def infer_record(device, rank, B, steps, warmup, use_graph=True, dump=None):
     """BASELINE.json configs[1]: VGG16-ASPP forward (bf16 autocast, fp32 heads, eval mode) + Softmax + dense CRF + seeded
     region growing on the network's own scores, no losses, no backward — the inference-only supervision path."""
     from dsrg_amd import ops, synthetic as S
@@ -496,6 +542,8 @@ def infer_record(device, rank, B, steps, warmup, use_graph=True):
         seeds = one()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump is not None:
+        dump["seeds"] = seeds.float()                            # a copy: the context's buffers are reused below
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     lg = torch.from_numpy(batch_np["logits"]).to(device)
     e0.record()
@@ -616,7 +664,7 @@ def srg_roofline(ops, B, C, N, logits, images, labels, cues, ctx):
                     "growth): the time is two kernel boundaries plus one memory round trip each, not bandwidth"}
 
 
-def supervision_record(device, rank, B, steps, warmup, cpu=True, cpu_target_s=10.0, size=321):
+def supervision_record(device, rank, B, steps, warmup, cpu=True, cpu_target_s=10.0, size=321, dump=None):
     """the supervision path on fixed fc8 logits: Softmax -> CRF -> SRG -> losses -> backward (dsrg_supervision_step); size = the
     input images' side: 321 -> 41 x 41 score maps (train-s), 513 -> 65 x 65 (the ResNet-101 / 513 configuration's map size)"""
     from dsrg_amd import ops, synthetic as S
@@ -632,9 +680,11 @@ def supervision_record(device, rank, B, steps, warmup, cpu=True, cpu_target_s=10
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        losses, _, _ = ops.supervision_step(logits, images, labels, cues, ctx=ctx)
+        losses, grad, _ = ops.supervision_step(logits, images, labels, cues, ctx=ctx)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump is not None:
+        dump.update(losses=losses.clone(), grad_logits=grad.clone())      # copies: the profiling pass below reuses the buffers
     nprof = max(3, min(steps, 20))
     ctx.profile_start(nprof * 10 + 16)                           # the filter launches bracketed in a separate, untimed pass
     for _ in range(nprof):
@@ -734,7 +784,13 @@ def main():
     ap.add_argument("--no-modes", action="store_true", help="--mode train: skip the sub-records of the other configurations")
     ap.add_argument("--no-graph", action="store_true", help="--mode infer: launch the backbone forward eagerly instead of replaying a hipGraph")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket filter launches with HIP events")
-    ap.add_argument("--sub", action="store_true", help="(internal) a sub-record of the default run: short CPU baseline, one core only")
+    ap.add_argument("--sub", action="store_true", help="(internal) a sub-record of the --full run: short CPU baseline, one core only")
+    ap.add_argument("--full", action="store_true",
+                    help="--mode train: also the filter roofline pass, the float32 leg and precision comparison, the CPU baselines, "
+                         "the sub-records of the other configurations and the weight checksum of a single process (a plain "
+                         "run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if not torch.cuda.is_available():
@@ -756,7 +812,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))            # a child process: this one has the HIP runtime up already
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -785,25 +842,34 @@ def main():
     cpu = not args.no_cpu_baseline and world == 1
     if args.batch is None:
         args.batch = 1 if args.mode == "infer" else 16
+    dump = {} if args.dump_outputs and rank == 0 else None
     if args.mode == "crf-fullres":
-        rec = crf_fullres_record(device, args.steps, args.warmup, cpu=cpu, size=args.size)
+        rec = crf_fullres_record(device, args.steps, args.warmup, cpu=cpu, size=args.size, dump=dump)
         if rank == 0:
+            if dump is not None:
+                write_outputs(args.dump_outputs, dump)
             print(json.dumps(rec))
         return finish()
     if args.mode == "test-ms":
-        rec = test_ms_record(device, args.steps, args.warmup, cpu=cpu)
+        rec = test_ms_record(device, args.steps, args.warmup, cpu=cpu, dump=dump)
         if rank == 0:
+            if dump is not None:
+                write_outputs(args.dump_outputs, dump)
             print(json.dumps(rec))
         return finish()
     if args.mode == "infer":
-        rec = infer_record(device, rank, args.batch, args.steps, args.warmup, use_graph=not args.no_graph)
+        rec = infer_record(device, rank, args.batch, args.steps, args.warmup, use_graph=not args.no_graph, dump=dump)
         if rank == 0:
+            if dump is not None:
+                write_outputs(args.dump_outputs, dump)
             print(json.dumps(rec))
         return finish()
     if args.mode == "supervision":
         rec = supervision_record(device, rank, args.batch, args.steps, args.warmup, cpu=cpu, cpu_target_s=5.0 if args.sub else 10.0,
-                                 size=args.size)
+                                 size=args.size, dump=dump)
         if rank == 0:
+            if dump is not None:
+                write_outputs(args.dump_outputs, dump)
             if cpu and not args.sub:
                 try:
                     rec["cpu_baseline_all_cores"] = cpu_baseline_all_cores()
@@ -859,16 +925,23 @@ def main():
         rank_ms = [float(t.item()) / args.steps * 1e3 for t in ts]
         dt = max(float(t.item()) for t in ts)                     # the job's time is its slowest rank's
 
+    # what the last timed step computed, before any further step moves the weights: its losses and the parameters it updated
+    if dump is not None:
+        dump["losses" if retrainer is None else "loss"] = losses.float()
+        dump.update(param_sample((retrainer or trainer).net))
+        write_outputs(args.dump_outputs, dump)
+
     # replicas in lock step?  every rank all-gathers a 64-bit checksum pair of its parameters and momentum buffers (a
-    # data-parallel number is only a number if the ranks still hold the same weights); outside the timed region
+    # data-parallel number is only a number if the ranks still hold the same weights); outside the timed region.  A single process
+    # has nothing to compare: there the checksum is one of the --full extras
     weights_equal, weight_words = None, None
-    if trainer is not None:
+    if trainer is not None and (dist is not None or args.full):
         weights_equal, weight_words = trainer.weights_equal_across_ranks()
 
     # the dominant hot-path kernel inside the train step: a separate, untimed pass with every filter launch bracketed by HIP
     # events on its launch stream (the brackets cost ~5 us each: they must not sit in the timed region)
     filt_ms, filt_n, ev_overhead = 0.0, 0, 0.0
-    if args.mode == "train" and not args.no_profile:
+    if args.mode == "train" and args.full and not args.no_profile:
         nprof = max(3, min(args.steps, 10))
         ctx.profile_start(nprof * 10 + 16)
         for _ in range(nprof):
@@ -879,7 +952,7 @@ def main():
 
     # supervision-only time per step on this rank (same inputs; untimed region)
     sup_ms = None
-    if args.mode == "train":
+    if args.mode == "train" and args.full:
         for _ in range(3):
             ops.supervision_step(logits_fixed, images, labels, cues, ctx=ctx)
         torch.cuda.synchronize()
@@ -895,7 +968,8 @@ def main():
         total_images = B * world * args.steps
         other = []
         if args.mode == "train":
-            other.append(srg_roofline(ops, B, C, N, logits_fixed, images, labels, cues, ctx))
+            if args.full:
+                other.append(srg_roofline(ops, B, C, N, logits_fixed, images, labels, cues, ctx))
             tf = count_flops_per_image() * 3 * B * world * args.steps / dt / 1e12 / world
             other.append({"kernel": "backbone convolutions (hipBLASLt / MIOpen / CK / own direct kernels, MFMA bf16), whole step per GPU",
                           "bound": "mfma", "achieved": tf, "peak": 2500.0, "unit": "TFLOP/s", "frac": tf / 2500.0,
@@ -951,7 +1025,7 @@ def main():
             out["legs"] = {"bf16": {"value": out["value"], "ms_per_step": out["ms_per_step"], "steps": args.steps,
                                     "dtype": out["dtype"], "backbone_tflops": out["backbone_tflops"],
                                     "mfma_peak_tflops": 2500.0, "mfma_frac": out["backbone_tflops"] / 2500.0}}
-        if args.mode == "train" and world == 1 and not args.no_fp32:
+        if args.mode == "train" and world == 1 and args.full and not args.no_fp32:
             # the reference's backbone arithmetic is Caffe float32: the same step with a float32 backbone, for the SAME number
             # of timed steps, and how far the two loss trajectories drift apart
             del trainer
@@ -978,7 +1052,7 @@ def main():
                 out["config"]["bf16_vs_fp32_loss_gap_300_steps_max"] = out["legs"]["loss_gap_300_steps"]["max"]
             except Exception as e:                       # never let the comparison cost the bench line
                 out["legs"]["precision_legs_error"] = str(e)[:200]
-        if args.mode == "train" and world == 1 and cpu:
+        if args.mode == "train" and world == 1 and args.full and cpu:
             out["cpu_baseline"] = cpu_baseline(batch_np)
             try:
                 out["cpu_baseline_all_cores"] = cpu_baseline_all_cores()
@@ -986,7 +1060,7 @@ def main():
                 out["cpu_baseline_all_cores"] = {"error": str(e)[:200]}
         else:
             out["cpu_baseline"] = None
-        if args.mode == "train" and world == 1 and not args.no_modes:
+        if args.mode == "train" and world == 1 and args.full and not args.no_modes:
             # the other quoted configurations, bounded, each with its own roofline and CPU baseline: driver-timed alongside
             # the headline (BASELINE.json configs[1]; the hot path alone at 16 images and at one).  Each runs
             # in a fresh process (this one keeps its GPU context but is idle): measured inside this process, after the

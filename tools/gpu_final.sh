@@ -1,5 +1,5 @@
 #!/bin/bash
-# end-of-round measurement set: gpu tests, default bench line, rocprof kernel stats (train step, supervision, full-res CRF),
+# end-of-round measurement set: gpu tests, --full bench line, rocprof kernel stats (train step, supervision, full-res CRF),
 # PMC passes (HBM traffic, LDS counters, MFMA busy) parsed into the JSON files bench.py replays, implicit-GEMM probe, parity
 # sweeps, phase traces.   usage: bash tools/gpu_final.sh outdir [commit]      (commit: stamped into the counter files)
 OUT=${1:-gpurun_out/final}
@@ -8,7 +8,7 @@ mkdir -p $OUT
 export PYTHONPATH=$PWD
 ROOT=$PWD
 timeout 1800 python -m pytest tests -q -m gpu > $OUT/pytest.log 2>&1; echo "pytest rc=$? $(tail -1 $OUT/pytest.log)"
-# counters first: the default bench line below replays them (bench.py drops figures whose kernel sources changed since)
+# counters first: the --full bench line below replays them (bench.py drops figures whose kernel sources changed since)
 bash tools/gpu_pmc.sh $OUT/pmc sup_fetch sup_write sup_lds fr_fetch fr_write train_mfma
 python tools/pmc_parse.py $OUT/pmc/sup_fetch_counter_collection.csv $OUT/pmc/sup_write_counter_collection.csv $OUT/pmc_traffic.json $COMMIT > /dev/null 2>$OUT/pmc_parse.err
 python tools/pmc_parse.py $OUT/pmc/fr_fetch_counter_collection.csv $OUT/pmc/fr_write_counter_collection.csv $OUT/pmc_traffic_fullres.json $COMMIT > /dev/null 2>>$OUT/pmc_parse.err
@@ -16,7 +16,7 @@ python tools/pmc_lds_parse.py $OUT/pmc/sup_lds_counter_collection.csv $OUT/lds_c
 python tools/pmc_mfma.py $OUT/pmc/train_mfma_counter_collection.csv 3 > $OUT/mfma_utilisation.txt 2>>$OUT/pmc_parse.err
 mkdir -p profiles
 for f in pmc_traffic pmc_traffic_fullres lds_counters; do [ -s $OUT/$f.json ] && cp $OUT/$f.json profiles/r06_$f.json; done
-timeout 1500 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
+timeout 1500 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_t -o train -- python $ROOT/bench.py --steps 20 --warmup 8 --no-fp32 --no-cpu-baseline --no-modes --no-profile > $ROOT/$OUT/bench_train_rocprof.json 2> $ROOT/$OUT/rocprof_train.err
 timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_s -o sup -- python $ROOT/bench.py --mode supervision --steps 50 --warmup 10 --no-cpu-baseline > $ROOT/$OUT/bench_sup_rocprof.json 2> $ROOT/$OUT/rocprof_sup.err

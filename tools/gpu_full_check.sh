@@ -1,12 +1,12 @@
 #!/bin/bash
-# full GPU check of the tree: gpu test suite, default bench line, rocprof kernel stats of the supervision path
+# full GPU check of the tree: gpu test suite, --full bench line, rocprof kernel stats of the supervision path
 # usage: bash tools/gpu_full_check.sh outdir
 OUT=${1:-gpurun_out/full}
 mkdir -p $OUT
 export PYTHONPATH=$PWD
 timeout 1500 python -m pytest tests -x -q -m gpu > $OUT/pytest.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest.log
 tail -3 $OUT/pytest.log
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
 ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof -o sup -- python $ROOT/bench.py --mode supervision --steps 50 --warmup 10 --no-cpu-baseline > $ROOT/$OUT/bench_sup_rocprof.json 2> $ROOT/$OUT/rocprof.err
