@@ -82,6 +82,8 @@ SIGNATURES = {
     "dsrg_seed_loss_plain": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dsrg_expand_loss": (_i, [_i, _i, _i, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp]),
     "dsrg_confusion_matrix": (_i, [_sz, _vp, _vp, _i, _i, _vp, _vp]),
+    "dsrg_multiscale_unary": (_i, [_i, _i, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _i, _i,
+                                   _f, _vp, _vp, _vp, _vp]),
     "dsrg_im2col3x3_nhwc16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "dsrg_relu_bwd_bias_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, ctypes.c_long, _i, ctypes.c_float, _vp]),
     "dsrg_col2im3x3_nhwc_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -808,9 +808,10 @@ class GraphedForward(object):
     and buffers are static at test time, and every HIP kernel of this package launches on torch's current stream, which is
     the capture stream.  The eager warm-up runs first so that TunableOp has picked its GEMM solutions and the kernels have
     reserved their LDS outside the capture.  __call__(x) copies x into the captured input buffer and returns the captured
-    output buffer (overwritten by the next call)."""
+    output buffer (overwritten by the next call).  capture_error_mode: torch.cuda.graph's; "thread_local" lets other host threads
+    (the CRF workers of the test-time loop) allocate and synchronise while this thread captures."""
 
-    def __init__(self, net, example, amp_dtype=torch.bfloat16, warmup=3):
+    def __init__(self, net, example, amp_dtype=torch.bfloat16, warmup=3, capture_error_mode="global"):
         if net.training:
             raise ValueError("GraphedForward captures an eval-mode forward (dropout would replay one mask)")
         self.net, self.amp = net, amp_dtype
@@ -823,7 +824,7 @@ class GraphedForward(object):
         torch.cuda.current_stream().wait_stream(warm)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with torch.cuda.graph(self.graph, capture_error_mode=capture_error_mode):
             self.out = self._fwd()
 
     def _fwd(self):

@@ -490,6 +490,11 @@ extern "C" int dsrg_confusion_matrix(size_t n, const unsigned char *gt, const un
     if ((n && (!gt || !pred)) || !hist) return set_error(DSRG_ERR_INVALID, "NULL argument");
     return launch_confusion(n, gt, pred, nclass, rule_lt, hist, static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_multiscale_unary(int K, int C, const float *const *scores, const int32_t *h, const int32_t *w, int H, int W,
+                                     float eps, float *unary, int32_t *amax, float *sum, void *stream) {
+    // every argument is checked before the first device call
+    return launch_multiscale_unary(K, C, scores, h, w, H, W, eps, unary, amax, sum, static_cast<hipStream_t>(stream));
+}
 extern "C" int dsrg_im2col3x3_nhwc16(const void *in, void *out, int B, int H, int W, int C, int dilation, void *stream) {
     if (!in || !out || B < 1 || H < 1 || W < 1 || C < 1 || dilation < 1) return set_error(DSRG_ERR_INVALID, "bad argument");
     return launch_im2col3x3(in, out, B, H, W, C, dilation, static_cast<hipStream_t>(stream));

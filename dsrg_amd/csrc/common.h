@@ -221,6 +221,8 @@ int launch_expand_loss(int B, int C, int HW, const float *p, const float *stat, 
                        float *grad, double *terms, hipStream_t stream);
 int launch_confusion(size_t n, const unsigned char *gt, const unsigned char *pred, int nclass, int rule_lt,
                      unsigned long long *hist, hipStream_t stream);
+int launch_multiscale_unary(int K, int C, const float *const *scores, const int32_t *h, const int32_t *w, int H, int W, float eps,
+                            float *unary, int32_t *amax, float *sum_out, hipStream_t stream);
 int launch_im2col3x3(const void *in, void *out, int B, int H, int W, int C, int dil, hipStream_t stream);
 int launch_col2im3x3(const void *cols, void *out, int B, int H, int W, int C, int dil, hipStream_t stream);
 int launch_relu_bwd_bias(const void *g, const void *y, void *gm, float *bias_grad, float *part, int part_blocks,

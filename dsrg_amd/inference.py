@@ -3,6 +3,8 @@ full-resolution dense CRF on log-probabilities, pseudo-label generation, and the
 
   preprocess            <-> training/tools/test-ms.py:68-81
   predict_mask_ms       <-> training/tools/test-ms.py:84-111        (run.sh:6,10: pseudo labels / final test)
+  preprocess_relative   <-> training/tools/test-ms-f.py:100-112
+  predict_mask_ms_f     <-> training/tools/test-ms-f.py:115-142     (run.sh step 4: the final test at relative scales)
   predict_train_gt      <-> training/tools/generate_train_gt.py:78-106
   ConfusionMatrix       <-> training/tools/evaluate.py:17-68
 
@@ -10,7 +12,9 @@ The network runs in PyTorch-ROCm; resampling uses align-corners bilinear interpo
 sampling scipy.ndimage.zoom(order=1) performs ((in-1)/(out-1) mapping); the CRF is
 krahenbuhl2013.CRF (device-resident form crf.CRF_device) -> libdsrg_hip.so (global-memory lattice path for full-resolution maps).
 """
+import collections
 import contextlib
+import math
 
 import numpy as np
 import torch
@@ -59,21 +63,43 @@ class GraphedForward(object):
     state), made at the first call with that shape and replayed afterwards.  A batch-1 forward is ~40 launches of 10-30 us of GPU
     work each; issued one by one from Python it takes 1.4 ms whatever the map size (host-bound), replayed it takes what the GPU needs.
     The graph re-reads (and re-packs) the parameters at every replay, so in-place weight updates are seen; the returned tensor is the
-    graph's static output: consume it before the next call with the same shape."""
+    graph's static output: consume it before the next call with the same shape.
 
-    def __init__(self, net):
+    The relative scales of test-ms-f.py give every image size its own three input shapes.  max_shapes: keep at most that many
+    graphs, dropping (and freeing) the least recently used one before a new capture; capture_after = n: a shape runs eagerly
+    until its n-th call, which captures it, so one-off shapes are never captured.  The defaults (no bound, capture at the first
+    call) keep every shape's graph."""
+
+    def __init__(self, net, max_shapes=None, capture_after=1):
+        if max_shapes is not None and int(max_shapes) < 1:
+            raise ValueError("max_shapes must be at least 1")
         self.net = net
-        self._g = {}
+        self.max_shapes = None if max_shapes is None else int(max_shapes)
+        self.capture_after = max(1, int(capture_after))
+        self._g = collections.OrderedDict()        # key -> graph, least recently used first
+        self._calls = collections.Counter()        # key -> calls so far (while not captured)
 
     def __call__(self, x):
         amp = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else None
         key = (tuple(x.shape), x.dtype, amp)
         g = self._g.get(key)
-        if g is None:
-            from .backbone import GraphedForward as _OneShape
-            if self.net.training:
-                raise RuntimeError("GraphedForward needs an eval-mode network (no dropout stream inside a graph)")
-            g = self._g[key] = _OneShape(self.net, x, amp_dtype=amp)
+        if g is not None:
+            self._g.move_to_end(key)
+            return g(x)
+        if self.net.training:
+            raise RuntimeError("GraphedForward needs an eval-mode network (no dropout stream inside a graph)")
+        self._calls[key] += 1
+        if self._calls[key] < self.capture_after:
+            # what the captured graph runs (backbone.GraphedForward._fwd), issued eagerly
+            with torch.no_grad(), torch.autocast("cuda", dtype=amp, enabled=amp is not None):
+                return self.net(x).contiguous()
+        if self.max_shapes is not None:
+            while len(self._g) >= self.max_shapes:
+                self._g.popitem(last=False)        # the graph and its private memory pool go with the last reference
+        from .backbone import GraphedForward as _OneShape
+        # a capture may now begin while the CRF workers of a *_many generator are busy on their own streams: only this thread's
+        # calls are held to the capture rules
+        g = self._g[key] = _OneShape(self.net, x, amp_dtype=amp, capture_error_mode="thread_local")
         return g(x)
 
 
@@ -114,7 +140,6 @@ def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", for
     masks in order: the forwards of image i + 1 (on the caller's stream; `forward`: a GraphedForward) run while the CRFs of the images
     before it are in flight on `in_flight` worker streams (crf.CRF_device_many; batch > 1: consecutive same-sized images share one
     batched CRF call).  Same masks as predict_mask_ms image by image."""
-    from .crf import CRF_device_many
 
     def pairs():
         for image in images:
@@ -122,6 +147,13 @@ def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", for
             unary = torch.log(probs).permute(1, 2, 0).contiguous()
             yield torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device), unary
 
+    yield from _crf_in_flight(pairs(), device, in_flight, batch)
+
+
+def _crf_in_flight(pairs, device, in_flight, batch):
+    """the CRF half of the *_many generators: (image, unary) pairs -> (H,W) int64 masks in order, CRFs on worker streams while the
+    pairs (the forwards) are produced on a forward stream of their own"""
+    from .crf import CRF_device_many
     # the CRF workers come back from the library three times per image and need the interpreter lock for a few lines each time; the
     # caller's thread, busy issuing torch ops, would keep it for Python's default 5 ms switch interval — longer than a whole CRF
     import sys
@@ -135,10 +167,89 @@ def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", for
         if fstream is not None:
             fstream.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(fstream):
-            for lab in CRF_device_many(pairs(), scale_factor=1.0, want="map", in_flight=in_flight, batch=batch):
+            for lab in CRF_device_many(pairs, scale_factor=1.0, want="map", in_flight=in_flight, batch=batch):
                 yield lab.cpu().numpy().astype(np.int64)
     finally:
         sys.setswitchinterval(interval)
+
+
+# ---- the final test at relative scales (test-ms-f.py, run.sh step 4) ----------------------------------------------------------------
+def relative_size(n, factor):
+    """the length scipy.ndimage.zoom gives an axis of n samples zoomed by `factor`, as the reference ran it: scipy 0.18
+    (python-dependencies.txt:15) computes int(round(n * factor)) and the reference ran under Python 2 (test-ms-f.py:154 is a print
+    statement), whose round() takes halves away from zero: 334 * 0.75 = 250.5 -> 251, 338 * 1.25 = 422.5 -> 423 (Python 3's
+    half-to-even round gives 250 / 422).  This follows from reading the two versions' code; no Python 2 run has confirmed it."""
+    x = n * float(factor)
+    f = math.floor(x)
+    return int(f + 1 if x - f >= 0.5 else f)
+
+
+def preprocess_relative(image, factor, device="cuda"):
+    """test-ms-f.py:100-112: image (H,W,3) RGB uint8/float zoomed by `factor` (order 1, float64 blend as in _zoom) to
+    (relative_size(H), relative_size(W)), BGR, mean-subtracted -> (1,3,h,w) float32"""
+    H, W = image.shape[0], image.shape[1]
+    x = torch.from_numpy(np.ascontiguousarray(np.asarray(image))).to(device).to(torch.float32).permute(2, 0, 1)[None]
+    x = _zoom(x, relative_size(H, factor), relative_size(W, factor))
+    x = x[:, [2, 1, 0]]
+    return x - torch.tensor(MEAN_PIXEL, dtype=torch.float32, device=device).view(1, 3, 1, 1)
+
+
+def _relative_scores(net, image, scales, device, forward):
+    """the forwards of test-ms-f.py:121-126 -> list of (1,C,h,w) float32 score maps, one per scale"""
+    out, shapes = [], set()
+    with _eval_mode(net):
+        for s in scales:
+            x = preprocess_relative(image, s, device)
+            sc = (forward or net)(x).float()
+            if forward is not None and tuple(x.shape) in shapes:
+                sc = sc.clone()                  # a graph's static output: a later replay of the same shape would overwrite it
+            shapes.add(tuple(x.shape))
+            out.append(sc.contiguous())
+    return out
+
+
+def _relative_unary(net, image, scales, device, forward, fused, smooth):
+    """test-ms-f.py:121-134 -> (H,W,C) float32 log-probabilities (smooth) or (H,W) arg-max labels.  fused: one
+    dsrg_multiscale_unary launch after the forwards; otherwise the torch composition (_zoom, sum, softmax, clamp, log)"""
+    d1, d2 = image.shape[0], image.shape[1]
+    scores = _relative_scores(net, image, scales, device, forward)
+    if fused:
+        from . import ops
+        return ops.multiscale_unary(scores, d1, d2, eps=0.00001, want="unary" if smooth else "argmax")
+    total = None
+    for sc in scores:
+        z = _zoom(sc, d1, d2)
+        total = z if total is None else total + z
+    probs = _probs_from_scores(total[0])
+    if smooth:
+        return torch.log(probs).permute(1, 2, 0).contiguous()
+    return probs.argmax(0)
+
+
+@torch.no_grad()
+def predict_mask_ms_f(net, image, scales=(0.75, 1.0, 1.25), smooth=True, device="cuda", forward=None, fused=True):
+    """test-ms-f.py:115-142 -> (H,W) int64 label mask: forwards at `scales` relative to the image's own size, the fused
+    multi-scale unary, then the full-resolution CRF (smooth) or the arg-max.  forward: see multiscale_scores (a GraphedForward,
+    best bounded: GraphedForward(net, max_shapes=..., capture_after=2)); fused=False: the torch composition, for A/B runs"""
+    out = _relative_unary(net, image, scales, device, forward, fused, smooth)
+    if smooth:
+        img = torch.as_tensor(np.asarray(image).astype('ubyte'), device=out.device)
+        return CRF_device(img, out, scale_factor=1.0, want="map").cpu().numpy().astype(np.int64)
+    return out.cpu().numpy().astype(np.int64)
+
+
+@torch.no_grad()
+def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda", forward=None, in_flight=3, batch=1, fused=True):
+    """predict_mask_ms_f (smooth) over many images, as predict_masks_ms_many does it for test-ms.py: a generator of (H,W) int64 masks
+    in order, the forwards of the next image running while the CRFs of the images before it are in flight.  Same masks as
+    predict_mask_ms_f image by image."""
+
+    def pairs():
+        for image in images:
+            unary = _relative_unary(net, image, scales, device, forward, fused, True)
+            yield torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device), unary
+
+    yield from _crf_in_flight(pairs(), device, in_flight, batch)
 
 
 @torch.no_grad()

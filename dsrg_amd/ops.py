@@ -372,6 +372,46 @@ def confusion_matrix(gt, pred, nclass, rule_lt=False, hist=None):
     return hist
 
 
+_MS_OUTPUTS = ("unary", "argmax", "sum")
+
+
+def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",)):
+    """test-ms.py:90-103 / test-ms-f.py:121-134 after the forwards, in one launch (dsrg_multiscale_unary): the K score maps
+    zoomed to H x W, summed in scale order, softmax over labels clamped at eps.  scores: list of (1, C, h_k, w_k) float32 CUDA
+    tensors (sizes may differ).  want: names among "unary" ((H, W, C) f32 log-probabilities, the layout CRF_device takes),
+    "argmax" ((H, W) int32, the first maximum) and "sum" ((H, W, C) f32 summed scores, for parity checks).  A string returns
+    that one tensor, a sequence a tuple in its order.  Runs on torch's current stream."""
+    single = isinstance(want, str)
+    names = (want,) if single else tuple(want)
+    for n in names:
+        if n not in _MS_OUTPUTS:
+            raise ValueError("unknown output %r (choose from %s)" % (n, ", ".join(_MS_OUTPUTS)))
+    if not names:
+        raise ValueError("want names no output")
+    scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
+    if not scores:
+        raise ValueError("no score maps")
+    C = scores[0].shape[1]
+    for s in scores:
+        if s.dim() != 4 or s.shape[0] != 1 or s.shape[1] != C:
+            raise ValueError("score maps must be (1, C, h, w) with one C; got %s" % (tuple(s.shape),))
+    K, dev = len(scores), scores[0].device
+    out = {}
+    if "unary" in names:
+        out["unary"] = torch.empty((H, W, C), dtype=torch.float32, device=dev)
+    if "argmax" in names:
+        out["argmax"] = torch.empty((H, W), dtype=torch.int32, device=dev)
+    if "sum" in names:
+        out["sum"] = torch.empty((H, W, C), dtype=torch.float32, device=dev)
+    ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scores])
+    hs = (ctypes.c_int32 * K)(*[s.shape[2] for s in scores])
+    ws = (ctypes.c_int32 * K)(*[s.shape[3] for s in scores])
+    check(_lib.lib().dsrg_multiscale_unary(K, int(C), ptrs, hs, ws, int(H), int(W), float(eps), _ptr(out.get("unary")),
+                                           _ptr(out.get("argmax")), _ptr(out.get("sum")), _stream()))
+    res = tuple(out[n] for n in names)
+    return res[0] if single else res
+
+
 def supervision_step(logits, images, labels, cues, th1=0.99, th2=0.85, scale_factor=12.0, maxiter=10,
                      ctx=None, want_blobs=False, prepared=False):
     """The five Python layers of train-s.prototxt:746-810, forward and backward, in one

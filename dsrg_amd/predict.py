@@ -1,0 +1,99 @@
+"""`python -m dsrg_amd.predict`: the test runs of run.sh on a list of images, writing one label PNG per image.
+
+  --mode ms    <-> training/tools/test-ms.py    (absolute sizes, default 241,321,401; pseudo labels)
+  --mode ms-f  <-> training/tools/test-ms-f.py  (sizes relative to each image, default 0.75,1,1.25; the final test)
+  --mode ms --scales 481 --class 81  <-> training/tools/test-coco.py:108-135 (single-scale COCO test)
+
+Reads DIR/JPEGImages/<id>.jpg for every id of --images, writes OUT/<id>.png: 8-bit grayscale class ids, what
+training/tools/evaluate.py reads (and `python -m dsrg_amd.evaluate`).  The network is VGG16-ASPP with the weights of --model
+(checkpoint.load_weights: .caffemodel, .npz or a torch file), run under bf16 autocast (--fp32: float32, the reference's
+precision); forwards replay from captured HIP graphs (inference.GraphedForward, bounded for the relative scales) while the
+CRFs of earlier images are in flight (inference.predict_masks_ms_many / predict_masks_ms_f_many).
+"""
+import argparse
+import os
+import sys
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="multi-scale test: label PNGs for a list of images")
+    p.add_argument("--mode", choices=("ms", "ms-f"), required=True,
+                   help="ms: absolute sizes (test-ms.py); ms-f: sizes relative to each image (test-ms-f.py)")
+    p.add_argument("--model", required=True, help="weights (.caffemodel, .npz or torch file)")
+    p.add_argument("--images", required=True, help="list of image ids, one per line")
+    p.add_argument("--dir", required=True, help="dataset root holding JPEGImages/")
+    p.add_argument("--output", required=True, help="directory for the <id>.png label maps")
+    p.add_argument("--smooth", action="store_true", help="dense-CRF post-processing (as the reference's --smooth)")
+    p.add_argument("--scales", default=None,
+                   help="comma-separated: sizes in pixels (ms; default 241,321,401) or factors (ms-f; default 0.75,1,1.25)")
+    p.add_argument("--class", dest="num_classes", type=int, default=21, help="number of classes including background")
+    p.add_argument("--fp32", action="store_true", help="float32 forwards instead of bf16 autocast")
+    p.add_argument("--in-flight", type=int, default=3, help="CRFs in flight under the next image's forwards")
+    p.add_argument("--max-graphs", type=int, default=12, help="ms-f: captured forward graphs kept (least recently used dropped)")
+    return p.parse_args(argv)
+
+
+def read_ids(path):
+    return [l.strip() for l in open(path) if l.strip()]
+
+
+def read_image(path):
+    """(H,W,3) RGB uint8, as pylab.imread gives a JPEG"""
+    import numpy as np
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"))
+
+
+def write_mask(path, mask):
+    import numpy as np
+    from PIL import Image
+    Image.fromarray(np.asarray(mask).astype(np.uint8), mode="L").save(path)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    import torch
+    from . import inference as I
+    from .backbone import VGG16ASPP
+    from .checkpoint import load_weights
+    from ._lib import require_gpu
+
+    require_gpu()
+    if a.mode == "ms":
+        scales = tuple(int(s) for s in a.scales.split(",")) if a.scales else (241, 321, 401)
+    else:
+        scales = tuple(float(s) for s in a.scales.split(",")) if a.scales else (0.75, 1.0, 1.25)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    net = VGG16ASPP(num_classes=a.num_classes).to(dev).to(memory_format=torch.channels_last).eval()
+    load_weights(net, a.model)
+    ids = read_ids(a.images)
+    os.makedirs(a.output, exist_ok=True)
+    images = (read_image(os.path.join(a.dir, "JPEGImages", i + ".jpg")) for i in ids)
+
+    if a.mode == "ms":
+        fwd = I.GraphedForward(net)                         # one graph per fixed size
+    else:                                                   # every image size has its own shapes: keep the common ones
+        fwd = I.GraphedForward(net, max_shapes=a.max_graphs, capture_after=2)
+    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=not a.fp32):
+        if a.smooth:
+            if a.mode == "ms":
+                masks = I.predict_masks_ms_many(net, images, sizes=scales, device=dev, forward=fwd, in_flight=a.in_flight)
+            else:
+                masks = I.predict_masks_ms_f_many(net, images, scales=scales, device=dev, forward=fwd, in_flight=a.in_flight)
+        elif a.mode == "ms":
+            masks = (I.predict_mask_ms(net, im, smooth=False, sizes=scales, device=dev, forward=fwd) for im in images)
+        else:
+            masks = (I.predict_mask_ms_f(net, im, scales=scales, smooth=False, device=dev, forward=fwd) for im in images)
+        n = 0
+        for img_id, mask in zip(ids, masks):
+            write_mask(os.path.join(a.output, img_id + ".png"), mask)
+            n += 1
+            if n % 100 == 0:
+                print("%d %s" % (n, img_id), flush=True)
+    print("wrote %d masks to %s" % (n, a.output))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

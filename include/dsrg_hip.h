@@ -254,6 +254,18 @@ int dsrg_expand_loss(int B, int C, int HW, const float *probs_dev, const float *
  * nclass <= 127. */
 int dsrg_confusion_matrix(size_t n, const unsigned char *gt_dev, const unsigned char *pred_dev, int nclass, int rule_lt,
                           unsigned long long *hist_dev, void *stream);
+/* The full-resolution tail of the multi-scale test (training/tools/test-ms.py:90-103, test-ms-f.py:121-134) in one launch:
+ * K score maps (batch 1, (C, h_k, w_k) f32 NCHW, sizes may differ; scores_dev is a HOST array of K device pointers, h_host /
+ * w_host host arrays of their sizes) are each zoomed to H x W (order-1 zoom, (in-1)/(out-1) mapping, blended in double and
+ * rounded once to f32), summed in f32 in scale order (S), and turned into p = max(softmax_c(S), eps).  Outputs, each optional
+ * (NULL = not written, at least one required), label-fastest:
+ *   unary_dev  (H, W, C) f32: log(p), the unary CRF_device takes; 16-byte aligned
+ *   argmax_dev (H, W) int32: the first maximum of S (a maximum of p: the smooth=False result)
+ *   sum_dev    (H, W, C) f32: S itself (parity tests); 16-byte aligned
+ * 1 <= K <= 8, 1 <= C <= 96, H, W, h_k, w_k >= 1, H*W*C < 2^31; every argument is checked before the first device call.
+ * Stream-ordered, no host synchronisation, no handle (callable from any host thread); bit-reproducible (no atomics). */
+int dsrg_multiscale_unary(int K, int C, const float *const *scores_dev, const int32_t *h_host, const int32_t *w_host, int H, int W,
+                          float eps, float *unary_dev, int32_t *argmax_dev, float *sum_dev, void *stream);
 
 /* Backbone plumbing (no reference counterpart; Caffe's im2col lives in the external framework): NHWC im2col
  * of a 3x3, stride-1, "same"-padded, dilated convolution for 2-byte elements (bf16/fp16), C % 8 == 0:
