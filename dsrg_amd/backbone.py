@@ -11,25 +11,35 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-
 import os as _os
-# output channels from which the weight gradient of a 3x3 convolution at the 41x41 stages is the GEMM im2col(x)^T @ g
-# (tools/wgrad_ab.sh measures the alternatives)
-_WGRAD_MIN_COUT = int(_os.environ.get("DSRG_WGRAD_MIN_COUT", "512"))
-# conv1_2 / conv2_1 / conv2_2 by the direct MFMA kernel: "1" all of them, "64" only conv1_2, "0" none (MIOpen / im2col + GEMM)
-_DIRECT_CONV = _os.environ.get("DSRG_DIRECT_CONV", "1")
-_DIRECT_C3 = _os.environ.get("DSRG_DIRECT_C3", "1") == "1"          # conv1_1 (3 -> 64) forward with bias + ReLU in one pass (0: MIOpen + 2 passes)
-_DIRECT_FN = _os.environ.get("DSRG_DIRECT_FN", "1") == "1"         # conv1_1 … conv2_2 take the float32 master parameters (_DirectConvFn; 0: through autocast's casts)
-_FUSE_POOL = _os.environ.get("DSRG_FUSE_POOL", "1") == "1"           # pool1-3 inside the conv node: pool backward + ReLU mask + bias gradient in one pass
-_GEMM_1X1_BWD = _os.environ.get("DSRG_GEMM_1X1_BWD", "1") == "1"   # 1x1 layers (fc7): both gradients as hipBLASLt GEMMs (0: MIOpen/CK)
-_DIRECT_WGRAD = _os.environ.get("DSRG_DIRECT_WGRAD", "1") == "1"   # their weight gradients by the direct kernel too (0: MIOpen)
-_GEMM_DGRAD_MAX_MAP = int(_os.environ.get("DSRG_GEMM_DGRAD_MAX_MAP", "2048"))   # largest map (pixels) whose 3x3 data gradient is im2col(g) + GEMM
-_WGRAD_T = _os.environ.get("DSRG_WGRAD_T", "1") == "1"     # g^T @ im2col(x) (1) or im2col(x)^T @ g (0): same numbers, other solution
+
+from . import ops
+
+# Which kernels a convolution runs is decided from what the call observes (device, dtype, layout, shape), by measured thresholds:
+# output channels from which the weight gradient of a 3x3 convolution at the 41x41 stages is the GEMM g^T @ im2col(x) (round 2, A/B
+# on one box: 932.8 / 931.4 images/s with 1024, 939.9 / 938.9 with 512, 934.1 / 932.4 with 256; see _ConvFn.backward)
+_WGRAD_MIN_COUT = 512
+# largest map (pixels) whose 3x3 data gradient is im2col(g) + GEMM: the 41x41 stages.  Larger maps: the im2col of g costs more than it
+# saves (81x81, again with nontemporal im2col stores: 1 221 / 1 225 against 1 233 / 1 227 images/s)
+_GEMM_DGRAD_MAX_MAP = 2048
+# largest map (pixels) whose 3x3 weight gradient is a GEMM over im2col(x), the matrix the forward keeps for it: the 41x41 stages again
+# (MIOpen's wrw 650 TFLOP/s on fc6 there; 883 -> 902 images/s in round 1)
+_GEMM_WGRAD_MAX_MAP = 2048
+# fewest 256 x 256 output tiles for which a layer takes the implicit-GEMM kernels: one image at 41x41 is 14 tiles of 72 K-steps for
+# 256 CUs, where the library GEMM's small-M kernels win (batch-1 inference 740 against 970 images/s; see _igemm_route)
+_IGEMM_MIN_TILES = 64
+# The two switches left are the references of comparisons (tests/test_gpu_igemm.py, tools/igemm_route_diag.py assign them between
+# two runs): module globals read at call time, never captured at import or construction.
 # 3x3 layers with >= 256 output channels (conv3_x, conv4_x, conv5_x, fc6_k) through the implicit-GEMM kernels (csrc/conv_igemm.hip:
 # no im2col matrix in the forward, the data gradient or the weight gradient; the four fc6_k in one launch); "0": the im2col +
 # hipBLASLt route of rounds 1-3
 _IGEMM = _os.environ.get("DSRG_IGEMM", "1") == "1"
-_FC7_IGEMM = _os.environ.get("DSRG_FC7_IGEMM", "1") == "1"   # fc7_k forward by the 1x1 implicit-GEMM launch when Dropout follows (mask fused)
+# (_FUSE_CHAIN: below, beside _GradLink)
+
+
+def _bf16_run(x):
+    """do the convolution kernels see x in bf16: it is bf16 already, or autocast to bf16 will cast it"""
+    return x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)
 
 
 def _im2col_gemm(x, weight, bias, dilation, relu, want_cols=False):
@@ -43,8 +53,7 @@ def _im2col_gemm(x, weight, bias, dilation, relu, want_cols=False):
     if k == 1:
         a = xn.reshape(-1, C)
     elif (C * x.element_size()) % 16 == 0 and x.element_size() in (2, 4):
-        from .ops import im2col3x3_nhwc                               # one bandwidth-bound HIP kernel (16-byte channel groups)
-        a = im2col3x3_nhwc(xn, dilation)
+        a = ops.im2col3x3_nhwc(xn, dilation)                          # one bandwidth-bound HIP kernel (16-byte channel groups)
     else:
         p = dilation
         xp = F.pad(xn, (0, 0, p, p, p, p))
@@ -63,6 +72,19 @@ def _im2col_gemm(x, weight, bias, dilation, relu, want_cols=False):
     return (out, a) if want_cols else out
 
 
+def _relu_bias_backward(g, pool, code, out_shape, relu, y, scale):
+    """first step of a conv node's backward when its consumer left nothing in the _GradLink: the incoming bf16 gradient -> (gradient
+    of the pre-activation, channels_last; bias gradient), one fused HIP pass.  pool: the node ended in the 3x3 max pool — its backward
+    masks with the ReLU the window codes carry (ops.maxpool3x3_bwd_relu); relu: mask by the sign of the output y and the Dropout
+    scale (ops.relu_bwd_bias); neither (e.g. the 21-channel fc8 outputs): the column sums alone"""
+    if pool is not None:
+        return ops.maxpool3x3_bwd_relu(g, code, out_shape, pool[0])
+    if relu:
+        return ops.relu_bwd_bias(g, y, scale)
+    g = g.contiguous(memory_format=torch.channels_last)
+    return g, ops.bias_grad(g)
+
+
 class _ConvFn(torch.autograd.Function):
     """3x3 / 1x1 stride-1 'same' convolution (+ ReLU (+ Dropout)).  Forward: explicit NHWC im2col + one hipBLASLt GEMM
     when `gemm` (at the 41x41 stages, 76 % of the backbone flops, MIOpen's forward kernels reach ~180 TFLOP/s on MI355X,
@@ -78,17 +100,15 @@ class _ConvFn(torch.autograd.Function):
         cols = None
         # 64 / 128 channels on both sides (conv1_2 at full resolution, conv2_1 / conv2_2 at half): the direct MFMA kernel
         # (weights in registers, bias + ReLU in the epilogue; csrc/conv_direct.hip) — MIOpen's implicit GEMM runs conv1_2 at
-        # ~255 TFLOP/s, the im2col route would move 1.9 GB there and 0.96 GB for conv2_2
+        # ~255 TFLOP/s, the im2col route would move 1.9 GB there and 0.96 GB for conv2_2; conv1_1 (3 -> 64) with bias + ReLU in one pass
         shape = tuple(weight.shape[:2])
         direct = k == 3 and dilation == 1 and x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and (
-            (_DIRECT_CONV == "1" and shape[0] in (64, 128) and shape[1] in (64, 128)) or (_DIRECT_CONV == "64" and shape == (64, 64))
-            or (_DIRECT_CONV == "1" and _DIRECT_C3 and shape == (64, 3)))
+            (shape[0] in (64, 128) and shape[1] in (64, 128)) or shape == (64, 3))
         if direct:
-            from .ops import conv3x3_direct
-            out = conv3x3_direct(x, weight, bias, relu)
+            out = ops.conv3x3_direct(x, weight, bias, relu)
         elif gemm:
             # the im2col matrix is kept for the layers whose weight gradient is a GEMM too (see backward)
-            keep = k == 3 and weight.shape[0] >= _WGRAD_MIN_COUT and x.shape[1] % 8 == 0 and x.shape[2] * x.shape[3] <= 2048
+            keep = k == 3 and weight.shape[0] >= _WGRAD_MIN_COUT and x.shape[1] % 8 == 0 and x.shape[2] * x.shape[3] <= _GEMM_WGRAD_MAX_MAP
             out = _im2col_gemm(x, weight, bias, dilation, relu, want_cols=keep)
             if keep:
                 out, cols = out
@@ -103,10 +123,9 @@ class _ConvFn(torch.autograd.Function):
             # conv + ReLU + 3x3 max pool as one autograd node (conv1_2, conv2_2, conv3_3): the pool's backward then masks with
             # this ReLU and sums the bias gradient in the same pass (ops.maxpool3x3_bwd_relu) instead of handing an unmasked
             # gradient to a separate relu_bwd_bias pass — three fewer passes over the largest activations of the net
-            from .ops import maxpool3x3_fwd
             # (relu_input: the window codes carry this ReLU's mask, so the backward never reads the full-resolution output again
             # and the node does not keep it)
-            pooled, code = maxpool3x3_fwd(out, pool[0], pool[1], relu_input=True)
+            pooled, code = ops.maxpool3x3_fwd(out, pool[0], pool[1], relu_input=True)
         ctx.save_for_backward(x, weight, out if (relu and pool is None) else None, cols, code)
         ctx.out_shape = tuple(out.shape)
         ctx.dilation, ctx.k, ctx.relu, ctx.scale, ctx.gemm = dilation, k, relu, 1.0 / (1.0 - drop_p), gemm
@@ -125,23 +144,14 @@ class _ConvFn(torch.autograd.Function):
         x, weight, y, cols, code = ctx.saved_tensors
         pad = ctx.dilation * (ctx.k // 2)
         cout = weight.shape[0]
-        fused = g.dtype == torch.bfloat16 and ((cout % 8 == 0 and cout <= 2048) or (not ctx.relu and cout <= 256))
-        gb_left = ctx.link_out.take(g) if ctx.link_out is not None else None
-        if gb_left is not None:
-            # the consumer's data gradient came masked by this node's ReLU, with the bias gradient beside it
-            gb = gb_left
-            fused = True
-        elif ctx.pool is not None:                                      # forward guaranteed bf16, ReLU, no dropout, cout | 2048
-            from .ops import maxpool3x3_bwd_relu
-            g, gb = maxpool3x3_bwd_relu(g, code, ctx.out_shape, ctx.pool[0])
-            fused = True
-        elif fused and ctx.relu:
-            from .ops import relu_bwd_bias
-            g, gb = relu_bwd_bias(g, y, ctx.scale)
+        # do the fused passes take g: always behind a link or a pool (forward guaranteed bf16, ReLU, no dropout, cout | 2048)
+        gb = ctx.link_out.take(g) if ctx.link_out is not None else None
+        fused = gb is not None or ctx.pool is not None or (
+            g.dtype == torch.bfloat16 and ((cout % 8 == 0 and cout <= 2048) or (not ctx.relu and cout <= 256)))
+        if gb is not None:
+            pass                                       # g came masked by this node's ReLU, its bias gradient beside it
         elif fused:
-            from .ops import bias_grad                                  # e.g. the 21-channel fc8 outputs
-            g = g.contiguous(memory_format=torch.channels_last)
-            gb = bias_grad(g)
+            g, gb = _relu_bias_backward(g, ctx.pool, code, ctx.out_shape, ctx.relu, y, ctx.scale)
         else:
             if ctx.relu:
                 g = g * (y > 0) * ctx.scale
@@ -149,9 +159,9 @@ class _ConvFn(torch.autograd.Function):
         # data gradient of a 3x3 'same' convolution = the forward convolution of g with the flipped, transposed kernel:
         # the im2col + hipBLASLt route again (~1.2 PFLOP/s at the 41x41 stages against 550-630 TFLOP/s for CK's dgrad)
         gemm_dgrad = ctx.gemm and ctx.k == 3 and ctx.needs_input_grad[0] and g.dtype in (torch.bfloat16, torch.float32) \
-            and cout % 8 == 0 and x.shape[2] * x.shape[3] <= _GEMM_DGRAD_MAX_MAP    # larger maps: the im2col of g costs more than it saves (81x81, again with nontemporal im2col stores: 1 221 / 1 225 against 1 233 / 1 227 images/s)
+            and cout % 8 == 0 and x.shape[2] * x.shape[3] <= _GEMM_DGRAD_MAX_MAP
         gx = None
-        gemm_1x1 = _GEMM_1X1_BWD and ctx.gemm and ctx.k == 1 and g.dtype in (torch.bfloat16, torch.float32) and cout % 8 == 0 \
+        gemm_1x1 = ctx.gemm and ctx.k == 1 and g.dtype in (torch.bfloat16, torch.float32) and cout % 8 == 0 \
             and x.shape[1] % 8 == 0 and g.dtype == x.dtype
         if gemm_1x1:
             # fc7 (1024 -> 1024, 1x1): both gradients are plain GEMMs over the NHWC matrices (MIOpen's wrw 120 us and CK's dgrad
@@ -163,49 +173,42 @@ class _ConvFn(torch.autograd.Function):
             gemm_dgrad = True
         elif ctx.direct and ctx.needs_input_grad[0] and g.dtype == torch.bfloat16 and x.shape[1] in (64, 128):
             # the data gradient is the same convolution with the kernel flipped and its channel axes swapped
-            from .ops import conv3x3_direct, conv3x3_direct_dgrad
             if _FUSE_CHAIN and ctx.link_in is not None:
-                gx, gb_below = conv3x3_direct_dgrad(g, weight.flip(2, 3).transpose(0, 1), x)
+                gx, gb_below = ops.conv3x3_direct_dgrad(g, weight.flip(2, 3).transpose(0, 1), x)
                 ctx.link_in.leave(gx, gb_below)
             else:
-                gx = conv3x3_direct(g, weight.flip(2, 3).transpose(0, 1), None, False)
+                gx = ops.conv3x3_direct(g, weight.flip(2, 3).transpose(0, 1), None, False)
             gemm_dgrad = True
         elif gemm_dgrad and cout > x.shape[1] and x.shape[1] % 8 == 0 and g.dtype == torch.bfloat16:
             # more output than input channels (fc6: 1024 vs 512): g @ W^T first, then gather the nine taps (col2im) —
             # half the traffic of an im2col of the wide g
-            from .ops import col2im3x3_nhwc
             B_, cin, H_, W_ = x.shape
             wmat = weight.permute(2, 3, 1, 0).reshape(9 * cin, cout)
-            gx = col2im3x3_nhwc(torch.mm(g.permute(0, 2, 3, 1).reshape(-1, cout), wmat.t()), B_, H_, W_, cin, ctx.dilation)
+            gx = ops.col2im3x3_nhwc(torch.mm(g.permute(0, 2, 3, 1).reshape(-1, cout), wmat.t()), B_, H_, W_, cin, ctx.dilation)
         elif gemm_dgrad:
             gx = _im2col_gemm(g, weight.flip(2, 3).transpose(0, 1), None, ctx.dilation, False)
-        # weight gradient = im2col(x)^T @ g, again one hipBLASLt GEMM (K = B*H*W), for the 41x41 layers with >= 512 output
-        # channels: the 512 -> 1024 dilated fc6 layers (MIOpen's wrw 650 TFLOP/s there; 883 -> 902 images/s in round 1) and,
+        # weight gradient = im2col(x)^T @ g, taken as its transpose g^T @ im2col(x), again one hipBLASLt GEMM (K = B*H*W), for the
+        # 41x41 layers with >= 512 output channels: the 512 -> 1024 dilated fc6 layers (MIOpen's wrw 650 TFLOP/s there; 883 -> 902 images/s in round 1) and,
         # since the hipBLASLt solutions are picked by TunableOp, the 512 -> 512 / 256 -> 512 layers too (round 2, A/B on one
         # box: 932.8 / 931.4 images/s with the 1024 threshold, 939.9 / 938.9 with 512, 934.1 / 932.4 with 256; the transposed
         # product g^T @ im2col(x) another +0.6 %)
-        gemm_wgrad = gemm_dgrad and x.shape[2] * x.shape[3] <= 2048 and x.shape[1] % 8 == 0 and cout >= _WGRAD_MIN_COUT
+        gemm_wgrad = gemm_dgrad and x.shape[2] * x.shape[3] <= _GEMM_WGRAD_MAX_MAP and x.shape[1] % 8 == 0 and cout >= _WGRAD_MIN_COUT
         gw = None
         if gemm_1x1:
             x2d = x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])       # NHWC memory of a channels_last activation
             gw = torch.mm(g2d.t(), x2d).view(cout, x.shape[1], 1, 1)
             gemm_wgrad = True
-        elif ctx.direct and _DIRECT_WGRAD and g.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and \
+        elif ctx.direct and g.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and \
                 (x.shape[1], cout) in ((3, 64), (64, 64), (64, 128), (128, 128)):
             # the narrow full-resolution layers again: MIOpen's wrw kernels run them at ~250 TFLOP/s (conv1_2: 0.48 ms)
-            from .ops import conv3x3_wgrad
-            gw = conv3x3_wgrad(x, g)
+            gw = ops.conv3x3_wgrad(x, g)
             gemm_wgrad = True
         elif gemm_wgrad:
             cin = x.shape[1]
             if cols is None or cols.dtype != g.dtype:
-                from .ops import im2col3x3_nhwc
-                cols = im2col3x3_nhwc(x.permute(0, 2, 3, 1).contiguous(), ctx.dilation)  # (M, 9*Cin)
+                cols = ops.im2col3x3_nhwc(x.permute(0, 2, 3, 1).contiguous(), ctx.dilation)  # (M, 9*Cin)
             g2d = g.permute(0, 2, 3, 1).reshape(-1, cout)                                # (M, Cout), NHWC memory
-            if _WGRAD_T:
-                gw = torch.mm(g2d.t(), cols).view(cout, 3, 3, cin).permute(0, 3, 1, 2)
-            else:
-                gw = torch.mm(cols.t(), g2d).view(3, 3, cin, cout).permute(3, 2, 0, 1)
+            gw = torch.mm(g2d.t(), cols).view(cout, 3, 3, cin).permute(0, 3, 1, 2)
         mask = [ctx.needs_input_grad[0] and not gemm_dgrad, not gemm_wgrad, not fused]
         gx2 = gw2 = gb2 = None
         if any(mask):
@@ -245,7 +248,6 @@ class _GradLink:
 
 
 _FUSE_CHAIN = _os.environ.get("DSRG_FUSE_CHAIN", "1") != "0"
-_MERGED_BWD = _os.environ.get("DSRG_MERGED_BWD", "1") != "0"     # data + weight gradient of a single-group 3x3 layer in one launch
 # (measured and dropped in round 5: packing every wide layer's kernels on a second stream at the start of the step, under the
 # HBM-bound conv1_x / conv2_x — 1 822 -> 1 798 images/s: the packs then compete with those kernels for the same HBM)
 # (measured and dropped in round 5: the weight gradient of an implicit-GEMM layer on a second stream beside its data gradient,
@@ -272,41 +274,37 @@ class _IgemmConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, k, dils, relu, drop_p, pool, n, links_in, links_out, *t):
-        from .ops import conv_igemm, conv_igemm_supported, pack_conv_weight_pair, dropout_seed
         xs, ws, bs = t[:n], t[n:2 * n], t[2 * n:3 * n]
         xs = [x if x.dtype == torch.bfloat16 else x.bfloat16() for x in xs]
         packs_d = [None] * n
         fb = [b.detach().float().contiguous() for b in bs]
-        # Dropout behind the ReLU rides in the implicit-GEMM epilogue (mask = f(seed, branch, position), p in steps of 1/256)
-        fused_drop = drop_p > 0.0 and relu and (k == 3 or _FC7_IGEMM)
-        scale = 1.0
-        if fused_drop:
-            scale = 256.0 / (256 - min(255, int(drop_p * 256.0 + 0.5)))
-        elif drop_p > 0.0:
-            scale = 1.0 / (1.0 - drop_p)
-        seed = dropout_seed() if fused_drop else 0
+        # Dropout rides in the implicit-GEMM epilogue (mask = f(seed, branch, position), p in steps of 1/256), always behind a ReLU:
+        # GemmConv2d refuses fuse_dropout without fuse_relu and VGG16ASPP's grouped calls pass relu=True, so no caller needs a
+        # Dropout pass of its own behind this node
+        if drop_p > 0.0 and not relu:
+            raise ValueError("_IgemmConvFn: Dropout needs the ReLU in front of it")
+        fused_drop = drop_p > 0.0
+        scale = 256.0 / (256 - min(255, int(drop_p * 256.0 + 0.5))) if fused_drop else 1.0
+        seed = ops.dropout_seed() if fused_drop else 0
         if links_in is not None and not all(lk is not None for lk in links_in):
             links_in = None
         if k == 3:
             # both packed forms of every kernel from the float32 master in one pass each; the data-gradient form waits for backward
-            need_d = any(ctx.needs_input_grad[8:8 + n]) and conv_igemm_supported(ws[0].shape[0], ws[0].shape[1], 3)
-            packs = [pack_conv_weight_pair(w, True, need_d) for w in ws]
+            need_d = any(ctx.needs_input_grad[8:8 + n]) and ops.conv_igemm_supported(ws[0].shape[0], ws[0].shape[1], 3)
+            packs = [ops.pack_conv_weight_pair(w, True, need_d) for w in ws]
             packs_d = [p[1] for p in packs]
-            outs = conv_igemm(xs, [p[0] for p in packs], fb, dils, 3, relu, drop_p if fused_drop else 0.0, seed)
+            outs = ops.conv_igemm(xs, [p[0] for p in packs], fb, dils, 3, relu, drop_p, seed)
         elif fused_drop:
             # fc7_k with Dropout behind it: one 1x1 implicit-GEMM launch for all branches with the mask in its epilogue beats four
             # hipBLASLt GEMMs + four dropout passes
-            packs = [pack_conv_weight_pair(w, True, links_in is not None and _FUSE_CHAIN) for w in ws]
+            packs = [ops.pack_conv_weight_pair(w, True, links_in is not None and _FUSE_CHAIN) for w in ws]
             packs_d = [p[1] for p in packs]
-            outs = conv_igemm(xs, [p[0] for p in packs], fb, dils, 1, relu, drop_p, seed)
+            outs = ops.conv_igemm(xs, [p[0] for p in packs], fb, dils, 1, relu, drop_p, seed)
         else:
             outs = [_im2col_gemm(x, w.to(torch.bfloat16), b.to(torch.bfloat16), 1, relu) for x, w, b in zip(xs, ws, bs)]
-        if drop_p > 0.0 and not fused_drop:
-            outs = [torch.ops.aten.native_dropout(o, drop_p, True)[0] for o in outs]      # o = relu * mask / (1 - p)
         code, pooled = None, None
         if pool is not None:                                                             # n == 1 (conv3_3)
-            from .ops import maxpool3x3_fwd
-            pooled, code = maxpool3x3_fwd(outs[0], pool[0], pool[1], relu_input=True)    # the codes carry the ReLU mask
+            pooled, code = ops.maxpool3x3_fwd(outs[0], pool[0], pool[1], relu_input=True)       # the codes carry the ReLU mask
         ctx.save_for_backward(code, *xs, *ws, *(outs if (relu and pool is None) else ()))
         ctx.out_shape = tuple(outs[0].shape)
         # where a data-parallel reducer wants the weight gradients written (dsrg_amd/reducer.py: the parameters' bucket slots)
@@ -322,47 +320,35 @@ class _IgemmConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gs):
-        from .ops import (conv_igemm, conv_igemm_dgrad, conv_igemm_supported, conv_igemm_wgrad, conv_igemm_wgrad_supported,
-                          pack_conv_weight, relu_bwd_bias, bias_grad, maxpool3x3_bwd_relu)
         n = ctx.n
         code, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:]
-        xs, ws, ys = saved[:n], saved[n:2 * n], saved[2 * n:]
+        xs, ws, ys = saved[:n], saved[n:2 * n], saved[2 * n:] or (None,) * n      # outputs: kept for a ReLU without a pool only
         cout, cin = ws[0].shape[0], ws[0].shape[1]
         gms, gbs = [], []
         cl = torch.channels_last
         for i, g in enumerate(gs):
-            lk = ctx.links_out[i] if ctx.links_out is not None else None
-            gb_left = lk.take(g) if lk is not None else None
-            if gb_left is not None:
-                # the consumer's data gradient came masked by this node's ReLU (+ Dropout) with the bias gradient beside it
-                gm, gb = g, gb_left
-            elif ctx.pool is not None:
-                gm, gb = maxpool3x3_bwd_relu(g, code, ctx.out_shape, ctx.pool[0])
-            elif ctx.relu:
-                gm, gb = relu_bwd_bias(g, ys[i], ctx.scale)
-            else:
-                gm = g.contiguous(memory_format=torch.channels_last)
-                gb = bias_grad(gm)
+            gm, gb = g, ctx.links_out[i].take(g) if ctx.links_out is not None else None
+            if gb is None:        # else the consumer's data gradient came masked by this node's ReLU (+ Dropout), the bias gradient beside it
+                gm, gb = _relu_bias_backward(g, ctx.pool, code, ctx.out_shape, ctx.relu, ys[i], ctx.scale)
             gms.append(gm); gbs.append(gb)
         need_x = [ctx.needs_input_grad[8 + i] for i in range(n)]
         gxs = [None] * n
         # inputs that are another node's ReLU outputs with no other consumer: that node's backward rides in this data gradient
-        absorb = _FUSE_CHAIN and ctx.links_in is not None and all(need_x) and conv_igemm_supported(cout, cin, ctx.k) and \
+        absorb = _FUSE_CHAIN and ctx.links_in is not None and all(need_x) and ops.conv_igemm_supported(cout, cin, ctx.k) and \
             cin >= 256 and all(x.is_contiguous(memory_format=cl) for x in xs)
-        if _MERGED_BWD and n == 1 and ctx.k == 3 and need_x[0] and conv_igemm_supported(cout, cin, 3) and \
-                conv_igemm_wgrad_supported(cin, cout, 3) and xs[0].is_contiguous(memory_format=cl):
+        if n == 1 and ctx.k == 3 and need_x[0] and ops.conv_igemm_supported(cout, cin, 3) and \
+                ops.conv_igemm_wgrad_supported(cin, cout, 3) and xs[0].is_contiguous(memory_format=cl):
             # one launch for both gradients of the layer (ops.conv_igemm_backward): the data gradient's tiles and the weight gradient's
             # workgroups share a grid, so the CUs a 212-tile data gradient leaves idle do weight-gradient work
-            from .ops import conv_igemm_backward
-            pd = ctx.packs_d[0] if ctx.packs_d[0] is not None else pack_conv_weight(ws[0], for_dgrad=True)
-            gx, gw, gb_below = conv_igemm_backward(gms[0], pd, xs[0], ctx.dils[0], xs[0] if absorb else None,
-                                                   ctx.links_in[0].scale if absorb else 1.0, gw_out=ctx.gw_out[0])
+            pd = ctx.packs_d[0] if ctx.packs_d[0] is not None else ops.pack_conv_weight(ws[0], for_dgrad=True)
+            gx, gw, gb_below = ops.conv_igemm_backward(gms[0], pd, xs[0], ctx.dils[0], xs[0] if absorb else None,
+                                                       ctx.links_in[0].scale if absorb else 1.0, gw_out=ctx.gw_out[0])
             if absorb:
                 ctx.links_in[0].leave(gx, gb_below)
             return (None,) * 8 + (gx, _landed(gw, ctx.gw_out[0])) + tuple(gbs)
         if absorb:
-            packs_d = [p if p is not None else pack_conv_weight(w, for_dgrad=True) for p, w in zip(ctx.packs_d, ws)]
-            gxs, gb_below = conv_igemm_dgrad(gms, packs_d, list(xs), ctx.dils, ctx.k, ctx.links_in[0].scale)
+            packs_d = [p if p is not None else ops.pack_conv_weight(w, for_dgrad=True) for p, w in zip(ctx.packs_d, ws)]
+            gxs, gb_below = ops.conv_igemm_dgrad(gms, packs_d, list(xs), ctx.dils, ctx.k, ctx.links_in[0].scale)
             for lk, gx_, gb_ in zip(ctx.links_in, gxs, gb_below):
                 lk.leave(gx_, gb_)
         if ctx.k == 1:
@@ -373,19 +359,19 @@ class _IgemmConvFn(torch.autograd.Function):
                     g2d = gms[i].permute(0, 2, 3, 1).reshape(-1, cout)
                     B_, _, H_, W_ = xs[i].shape
                     gxs[i] = torch.mm(g2d, ws[i].to(torch.bfloat16).reshape(cout, cin)).view(B_, H_, W_, cin).permute(0, 3, 1, 2)
-            gws = [_landed(gw, o) for gw, o in zip(conv_igemm_wgrad(list(xs), gms, ctx.dils, 1, outs=ctx.gw_out), ctx.gw_out)]
+            gws = [_landed(gw, o) for gw, o in zip(ops.conv_igemm_wgrad(list(xs), gms, ctx.dils, 1, outs=ctx.gw_out), ctx.gw_out)]
             return (None,) * 8 + tuple(gxs) + tuple(gws) + tuple(gbs)
         if any(need_x) and not absorb:
-            if conv_igemm_supported(cout, cin, 3):
-                packs_d = [p if p is not None else pack_conv_weight(w, for_dgrad=True) for p, w in zip(ctx.packs_d, ws)]
-                gxs = conv_igemm(gms, packs_d, None, ctx.dils, 3, False)
+            if ops.conv_igemm_supported(cout, cin, 3):
+                packs_d = [p if p is not None else ops.pack_conv_weight(w, for_dgrad=True) for p, w in zip(ctx.packs_d, ws)]
+                gxs = ops.conv_igemm(gms, packs_d, None, ctx.dils, 3, False)
             else:                                                                        # input channels not a multiple of 128
                 for i in range(n):
                     d = ctx.dils[i]
                     gxs[i] = torch.ops.aten.convolution_backward(gms[i], xs[i], ws[i].to(torch.bfloat16), None, [1, 1], [d, d], [d, d],
                                                                  False, [0, 0], 1, [True, False, False])[0]
-        if conv_igemm_wgrad_supported(cin, cout, 3):
-            gws = conv_igemm_wgrad(list(xs), gms, ctx.dils, 3, outs=ctx.gw_out)          # float32, the parameters' own layout
+        if ops.conv_igemm_wgrad_supported(cin, cout, 3):
+            gws = ops.conv_igemm_wgrad(list(xs), gms, ctx.dils, 3, outs=ctx.gw_out)      # float32, the parameters' own layout
             gws = [_landed(gw, o) for gw, o in zip(gws, ctx.gw_out)]
         else:
             gws = []
@@ -405,18 +391,17 @@ class _DirectConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu, pool, link_in, link_out):
-        from .ops import conv3x3_direct, pack_direct_weight_pair, maxpool3x3_fwd
         x = x if x.dtype == torch.bfloat16 else x.bfloat16()
         cl = torch.channels_last
         x = x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl)
         if weight.shape[1] == 3:
             w16, wd = weight.detach().to(torch.bfloat16), None                            # the image needs no gradient
         else:
-            w16, wd = pack_direct_weight_pair(weight, ctx.needs_input_grad[0])
-        out = conv3x3_direct(x, w16, bias.detach(), relu)
+            w16, wd = ops.pack_direct_weight_pair(weight, ctx.needs_input_grad[0])
+        out = ops.conv3x3_direct(x, w16, bias.detach(), relu)
         code, pooled = None, None
         if pool is not None:
-            pooled, code = maxpool3x3_fwd(out, pool[0], pool[1], relu_input=True)         # the codes carry the ReLU mask
+            pooled, code = ops.maxpool3x3_fwd(out, pool[0], pool[1], relu_input=True)     # the codes carry the ReLU mask
         ctx.save_for_backward(x, out if (relu and pool is None) else None, code)
         ctx.out_shape = tuple(out.shape)
         ctx.wd = wd                                    # not an input or output of the node: kept outside save_for_backward
@@ -430,48 +415,42 @@ class _DirectConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .ops import conv3x3_direct, conv3x3_direct_dgrad, conv3x3_wgrad, relu_bwd_bias, bias_grad, maxpool3x3_bwd_relu
         x, y, code = ctx.saved_tensors
         gb = ctx.link_out.take(g) if ctx.link_out is not None else None
-        if gb is not None:
-            pass                                       # g came masked by this node's ReLU, its bias gradient beside it
-        elif ctx.pool is not None:
-            g, gb = maxpool3x3_bwd_relu(g, code, ctx.out_shape, ctx.pool[0])
-        elif ctx.relu:
-            g, gb = relu_bwd_bias(g, y, 1.0)
-        else:
-            g = g.contiguous(memory_format=torch.channels_last)
-            gb = bias_grad(g)
+        if gb is None:            # else g came masked by this node's ReLU, its bias gradient beside it
+            g, gb = _relu_bias_backward(g, ctx.pool, code, ctx.out_shape, ctx.relu, y, 1.0)
         gx = None
         if ctx.needs_input_grad[0]:
             if _FUSE_CHAIN and ctx.link_in is not None:
-                gx, gb_below = conv3x3_direct_dgrad(g, ctx.wd, x)
+                gx, gb_below = ops.conv3x3_direct_dgrad(g, ctx.wd, x)
                 ctx.link_in.leave(gx, gb_below)
             else:
-                gx = conv3x3_direct(g, ctx.wd, None, False)
-        gw = conv3x3_wgrad(x, g, torch.float32, out=ctx.gw_out)
+                gx = ops.conv3x3_direct(g, ctx.wd, None, False)
+        gw = ops.conv3x3_wgrad(x, g, torch.float32, out=ctx.gw_out)
         return gx, _landed(gw, ctx.gw_out), gb, None, None, None, None
+
+
+def _pool_in_node(cout):
+    """can pool1-3 ride inside the conv node (pool backward + ReLU mask + bias gradient in one pass): the pool kernels' tiling,
+    8 | channels and (channels / 8) | 256"""
+    return cout % 8 == 0 and 256 % (cout // 8) == 0
 
 
 def _direct_route(conv, x, p, pool):
     """does this GemmConv2d call take _DirectConvFn: one of the four narrow full-resolution layers with float32 channels_last
-    master parameters under bf16 autocast, every direct kernel enabled, no Dropout, a pool only if it rides in the node"""
-    from .ops import WGRAD_CONV_SHAPES
+    master parameters under bf16 autocast, no Dropout, a pool only if it rides in the node (the node does not pool outside itself)"""
     cin, cout = conv.in_channels, conv.out_channels
-    if not (_DIRECT_FN and _DIRECT_CONV == "1" and _DIRECT_C3 and _DIRECT_WGRAD and conv.kernel_size == (3, 3) and conv.dilation == (1, 1)
-            and conv.groups == 1 and conv.bias is not None and (cin, cout) in WGRAD_CONV_SHAPES and p == 0.0):
+    if not (conv.kernel_size == (3, 3) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None
+            and (cin, cout) in ops.WGRAD_CONV_SHAPES and p == 0.0):
         return False
-    if not (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)):
+    if not _bf16_run(x):
         return False
     w = conv.weight
     if not (w.dtype == torch.float32 and conv.bias.dtype == torch.float32 and w.is_contiguous(memory_format=torch.channels_last)):
         return False
     if cin == 3 and x.requires_grad and torch.is_grad_enabled():      # no direct data gradient into three channels (the image needs none)
         return False
-    return pool is None or (_FUSE_POOL and 256 % (cout // 8) == 0)
-
-
-_IGEMM_MIN_TILES = int(_os.environ.get("DSRG_IGEMM_MIN_TILES", "64"))
+    return pool is None or _pool_in_node(cout)
 
 
 def _igemm_route(conv, x, groups=1):
@@ -481,15 +460,14 @@ def _igemm_route(conv, x, groups=1):
     970 images/s); `groups` problems share the launch (the four fc6_k)"""
     if not (_IGEMM and x.is_cuda and conv.gemm and conv.kernel_size == (3, 3) and conv.bias is not None and conv.groups == 1):
         return False
-    if not (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)):
+    if not _bf16_run(x):
         return False
     if conv.out_channels < 256:                 # conv1_x / conv2_x: the direct kernels (weights in registers) serve the narrow layers
         return False
     pixels = x.shape[0] * x.shape[2] * x.shape[3]
     if groups * ((pixels + 255) // 256) * ((conv.out_channels + 255) // 256) < _IGEMM_MIN_TILES:
         return False
-    from .ops import conv_igemm_supported
-    return conv_igemm_supported(conv.in_channels, conv.out_channels, 3)
+    return ops.conv_igemm_supported(conv.in_channels, conv.out_channels, 3)
 
 
 class GemmConv2d(nn.Conv2d):
@@ -528,31 +506,24 @@ class GemmConv2d(nn.Conv2d):
         pool = self.fuse_pool
         if x.is_cuda and self.stride == (1, 1) and self.kernel_size[0] in (1, 3) and \
                 self.padding[0] == self.dilation[0] * (self.kernel_size[0] // 2):
-            # the pool rides inside the node when its kernels apply: bf16 activations (autocast), 8 | channels, (channels / 8) | 256
-            cout = self.out_channels
-            if _igemm_route(self, x):
-                in_node = pool is not None and _FUSE_POOL and cout % 8 == 0 and 256 % (cout // 8) == 0     # the pool kernels' tiling
-                lin = getattr(x, "_dsrg_grad_link", None) if self.chain_input else None
-                lout = _GradLink() if (self.fuse_relu and pool is None and torch.is_grad_enabled()) else None
-                (out,) = _IgemmConvFn.apply(3, [self.dilation[0]], self.fuse_relu, p, pool if in_node else None, 1,
-                                            [lin] if lin is not None else None, [lout] if lout is not None else None, x, self.weight,
-                                            self.bias)
-                if lout is not None:
-                    out._dsrg_grad_link = lout
-                return out if pool is None or in_node else _pool3x3(out, pool[0], pool[1])
-            if _direct_route(self, x, p, pool):
-                lin = getattr(x, "_dsrg_grad_link", None) if self.chain_input else None
-                lout = _GradLink() if (self.fuse_relu and pool is None and torch.is_grad_enabled()) else None
-                out = _DirectConvFn.apply(x, self.weight, self.bias, self.fuse_relu, pool, lin, lout)
-                if lout is not None:
-                    out._dsrg_grad_link = lout
-                return out
-            in_node = pool is not None and _FUSE_POOL and cout % 8 == 0 and 256 % (cout // 8) == 0 and self.bias is not None and (
-                x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16))
+            igemm = _igemm_route(self, x)
+            direct = not igemm and _direct_route(self, x, p, pool)     # (refuses a pool it could not take into the node)
+            # the pool rides inside the node when its kernels apply: their tiling of the channels and, which the two routes above have
+            # checked for themselves, a bias and bf16 activations (autocast)
+            in_node = pool is not None and _pool_in_node(self.out_channels) and (
+                igemm or direct or (self.bias is not None and _bf16_run(x)))
             lin = getattr(x, "_dsrg_grad_link", None) if self.chain_input else None
-            lout = _GradLink() if (self.fuse_relu and pool is None and p == 0.0 and torch.is_grad_enabled()) else None
-            out = _ConvFn.apply(x, self.weight, self.bias, self.dilation[0], self.fuse_relu, self.gemm, p, pool if in_node else None,
-                                lin, lout)
+            # a consumer may fold this node's ReLU backward into its data gradient (_GradLink); behind Dropout only the implicit-GEMM
+            # node leaves the scale in the link (_ConvFn accepts a link without Dropout only, _direct_route takes no Dropout)
+            lout = _GradLink() if (self.fuse_relu and pool is None and (igemm or p == 0.0) and torch.is_grad_enabled()) else None
+            node_pool = pool if in_node else None
+            if igemm:
+                (out,) = _IgemmConvFn.apply(3, [self.dilation[0]], self.fuse_relu, p, node_pool, 1, [lin] if lin is not None else None,
+                                            [lout] if lout is not None else None, x, self.weight, self.bias)
+            elif direct:
+                out = _DirectConvFn.apply(x, self.weight, self.bias, self.fuse_relu, node_pool, lin, lout)
+            else:
+                out = _ConvFn.apply(x, self.weight, self.bias, self.dilation[0], self.fuse_relu, self.gemm, p, node_pool, lin, lout)
             if lout is not None:
                 out._dsrg_grad_link = lout
             return out if pool is None or in_node else _pool3x3(out, pool[0], pool[1])
@@ -575,32 +546,33 @@ class FusedDropout(nn.Identity):
     """placeholder for the Dropout layer that runs inside the GemmConv2d two slots in front of it (`fuse_dropout`)"""
 
 
+def _hip_pool_takes(x):
+    """does the HIP pooling pass take x: bf16 channels_last on the GPU, 8 | channels (16-byte channel groups)"""
+    return x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] % 8 == 0 and x.is_contiguous(memory_format=torch.channels_last)
+
+
 class _MaxPool3x3Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, stride, ceil_mode):
-        from .ops import maxpool3x3_fwd
-        out, code = maxpool3x3_fwd(x, stride, ceil_mode)
+        out, code = ops.maxpool3x3_fwd(x, stride, ceil_mode)
         ctx.save_for_backward(code)
         ctx.in_shape, ctx.stride = x.shape, stride
         return out
 
     @staticmethod
     def backward(ctx, g):
-        from .ops import maxpool3x3_bwd
         (code,) = ctx.saved_tensors
-        return maxpool3x3_bwd(g, code, ctx.in_shape, ctx.stride), None, None
+        return ops.maxpool3x3_bwd(g, code, ctx.in_shape, ctx.stride), None, None
 
 
 class _AvgPool3x3Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        from .ops import avgpool3x3_s1
-        return avgpool3x3_s1(x)
+        return ops.avgpool3x3_s1(x)
 
     @staticmethod
     def backward(ctx, g):
-        from .ops import avgpool3x3_s1
-        return avgpool3x3_s1(g)                                          # symmetric stencil: its own adjoint
+        return ops.avgpool3x3_s1(g)                                          # symmetric stencil: its own adjoint
 
 
 class AvgPool3x3(nn.AvgPool2d):
@@ -613,8 +585,7 @@ class AvgPool3x3(nn.AvgPool2d):
         super().__init__(3, 1, 1)
 
     def forward(self, x):
-        if x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] % 8 == 0 and \
-                x.is_contiguous(memory_format=torch.channels_last):
+        if _hip_pool_takes(x):
             return _AvgPool3x3Fn.apply(x)
         if x.is_cuda and x.dim() == 4 and not x.is_contiguous():
             x = x.contiguous()                                            # keep torch's kernel on its correct (NCHW) path
@@ -629,15 +600,12 @@ class MaxPool3x3(nn.MaxPool2d):
         super().__init__(3, stride, 1, ceil_mode=ceil_mode)
 
     def forward(self, x):
-        if x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] % 8 == 0 and \
-                x.is_contiguous(memory_format=torch.channels_last):
-            return _MaxPool3x3Fn.apply(x, self.stride, self.ceil_mode)
-        return super().forward(x)
+        return _pool3x3(x, self.stride, self.ceil_mode)
 
 
 def _pool3x3(x, stride, ceil_mode):
     """3x3 / pad 1 max pool outside a conv node: the HIP pass for bf16 channels_last activations, torch's otherwise"""
-    if x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] % 8 == 0 and x.is_contiguous(memory_format=torch.channels_last):
+    if _hip_pool_takes(x):
         return _MaxPool3x3Fn.apply(x, stride, ceil_mode)
     return F.max_pool2d(x, 3, stride, 1, ceil_mode=ceil_mode)
 
@@ -656,7 +624,6 @@ class _HeadsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, links, weight, bias, *xs):
-        from .ops import heads_forward
         cl = torch.channels_last
         # links: the x_k are ReLU (+ Dropout) outputs of nodes that feed these classifiers only (their backward rides along)
         ctx.links = links if (links is not None and all(lk is not None for lk in links) and
@@ -664,19 +631,18 @@ class _HeadsFn(torch.autograd.Function):
         xs = [x.contiguous(memory_format=cl) for x in xs]
         weight = weight.contiguous()
         ctx.save_for_backward(weight, *xs)
-        return heads_forward(xs, weight, bias.contiguous())
+        return ops.heads_forward(xs, weight, bias.contiguous())
 
     @staticmethod
     def backward(ctx, g):
-        from .ops import heads_backward
         weight, *xs = ctx.saved_tensors
         n, O, K = weight.shape
         if _FUSE_CHAIN and ctx.links is not None and all(ctx.needs_input_grad[3:]):
-            gxs, gw, gb_below = heads_backward(xs, weight, g, True, ctx.links[0].scale)
+            gxs, gw, gb_below = ops.heads_backward(xs, weight, g, True, ctx.links[0].scale)
             for i, lk in enumerate(ctx.links):
                 lk.leave(gxs[i], gb_below[i])
         else:
-            gxs, gw = heads_backward(xs, weight, g, need_gx=any(ctx.needs_input_grad[3:]))
+            gxs, gw = ops.heads_backward(xs, weight, g, need_gx=any(ctx.needs_input_grad[3:]))
         gb1 = g.sum((0, 2, 3))                                            # fp32, the same for every branch
         return (None, gw, gb1.unsqueeze(0).expand(n, O).contiguous()) + (tuple(gxs) if gxs is not None else (None,) * n)
 

@@ -15,7 +15,7 @@ import torch.nn.functional as F
 
 import os as _os
 
-from .backbone import VGG16ASPP, GemmConv2d, _ConvFn
+from .backbone import VGG16ASPP, GemmConv2d, _ConvFn, _bf16_run
 from .trainer import CaffeSGD
 
 _IGEMM_BN = _os.environ.get("DSRG_RESNET_IGEMM", "1") == "1"      # tools: A/B against round 5's im2col + library-GEMM bottlenecks
@@ -218,12 +218,14 @@ def _igemm_bn_route(x, conv, bn):
 
 
 def _conv_bn(x, conv, bn, relu, link_in=None, link_out=None, res=None, res_link=None):
-    """conv -> frozen-statistics BN (-> ReLU).  On the GPU, for stride-1 convolutions, the BN affine is folded into the
-    weights (W * scale per output channel, bias = shift) and the whole thing is one im2col + GEMM with the bias (and ReLU)
-    in the epilogue (backbone._ConvFn; 1x1 convolutions need no im2col at all).  gamma / beta still train: their
-    gradients flow through the weight-sized products instead of activation-sized reductions."""
-    if _IGEMM_BN and x.is_cuda and (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)) \
-            and _igemm_bn_route(x, conv, bn):
+    """conv -> frozen-statistics BN (-> ReLU), the BN affine folded into the convolution.  On the GPU, for stride-1 convolutions
+    with a constant affine map on bf16 activations (_igemm_bn_route): the implicit-GEMM kernels, scale in the packed kernel, shift
+    as the epilogue's bias, the links and the shortcut `res` as _FoldedIgemmFn.forward describes them.  Other stride-1 convolutions
+    on the GPU with 8 | input channels (float32 activations, trained gamma / beta, channel counts the kernels do not tile, small maps): W * scale per output
+    channel and bias = shift through one im2col + GEMM with the bias (and ReLU) in the epilogue (backbone._ConvFn; 1x1 convolutions
+    need no im2col at all) — gamma / beta still train there: their gradients flow through the weight-sized products instead of
+    activation-sized reductions.  Anything else (strided convolutions, the CPU): the two layers as they are."""
+    if _IGEMM_BN and x.is_cuda and _bf16_run(x) and _igemm_bn_route(x, conv, bn):
         scale, shift = bn.frozen_affine()
         return _FoldedIgemmFn.apply(x, conv.weight, scale, shift, conv.dilation[0], relu, link_in, link_out, res, res_link)
     if res is not None:
@@ -254,7 +256,7 @@ class _Bottleneck(nn.Module):
         l1, l2 = (_GradLink(), _GradLink()) if (_IGEMM_BN and _FUSE_CHAIN and torch.is_grad_enabled()) else (None, None)
         routed = lambda t, conv, bn: t.is_cuda and _igemm_bn_route(t, conv, bn)      # noqa: E731
         cl = torch.channels_last
-        bf16 = x.is_cuda and (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16))
+        bf16 = x.is_cuda and _bf16_run(x)
         r1 = bf16 and _IGEMM_BN and routed(x, self.c1, self.b1)
         # the shortcut: relu(c3(..) + idn) in the store of c3's launch; with an identity shortcut its gradient joins c1's data gradient
         # in that launch's store (rl), and where x is itself such a block output (x._dsrg_plink, set below) the ReLU backward of the
@@ -366,7 +368,7 @@ class ResNet101DeepLab(nn.Module):
     def forward(self, x):
         f = self.layers(self.stem(x))
         from .ops import conv_igemm_supported
-        if _IGEMM_BN and f.is_cuda and (f.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)) \
+        if _IGEMM_BN and f.is_cuda and _bf16_run(f) \
                 and len(self.aspp) <= 4 and 9 * len(self.aspp) * self.aspp[0].out_channels <= 2048 and conv_igemm_supported(f.shape[1], 128, 1) and \
                 f.shape[1] % 256 == 0 and \
                 f.shape[0] * f.shape[2] * f.shape[3] >= 2048 and all(m.kernel_size == (3, 3) and m.padding == m.dilation and m.stride == (1, 1)
