@@ -9,8 +9,8 @@ import os
 import torch  # noqa: F401  — loaded first so libdsrg_hip.so binds to torch's libamdhip64.so.7
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# DSRG_LIB (tools only): another build of the same library next to the shipped one, e.g. libdsrg_hip.exp3.so from
-# `make -C dsrg_amd/csrc EXP=3 exp` — for A/B measurements of kernel variants on one box
+# DSRG_LIB (tools only): another build of the same library, e.g. the absolute path of another tree's libdsrg_hip.so — for A/B
+# measurements of kernel variants on one box
 LIB_PATH = os.path.join(_HERE, os.environ.get("DSRG_LIB") or "libdsrg_hip.so")
 
 OK, ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = 0, -1, -2, -3, -4

@@ -47,7 +47,7 @@ struct dsrg_ctx_s {
 
 namespace dsrg { extern void *g_filter_dbg; extern void *g_build_dbg; extern std::atomic<int> g_filter_opts; extern std::atomic<int> g_igemm_variant; }
 // tests / tools only (not in the public header): option bits of the mean-field filter launch (meanfield.hip, kOpt*: 1 = a
-// pixel-local Gaussian lattice is evaluated by the update kernel, 2 = slot guard); -1 = back to the DSRG_FILTER_OPTS environment variable / the default (all on).  Every combination yields
+// pixel-local Gaussian lattice is evaluated by the update kernel, 2 = slot guard); -1 = back to the default (all on).  Every combination yields
 // bit-identical marginals (tests/test_gpu_parity.py).
 extern "C" __attribute__((visibility("default"))) void dsrg_debug_set_filter_opts(int opts) {
     dsrg::g_filter_opts = opts < 0 ? -1 : (opts & 3);      // bits 4 and 8 (seqCompute arithmetic, norm pass) are the launcher's own
@@ -58,7 +58,7 @@ extern "C" __attribute__((visibility("default"))) void dsrg_debug_set_filter_opt
 // wins); 5 = as 3 with the step's barrier in front of its last MFMA cluster and the next step's first fragments read before it; 6 / 7 =
 // round 4's launches (every K-step multiplied) / 3 with flat-order skipping in the weight gradient; 8 = 3 with round 5's row-aligned
 // pixel tiles for the dilated launches, 9 = 3 with the class-ordered tiles wherever legal (by default only where they run fewer
-// K-steps); -1 = back to DSRG_IGEMM_VARIANT / the default; identical results up to the summation order of a cut tile
+// K-steps); -1 = back to the default; identical results up to the summation order of a cut tile
 extern "C" __attribute__((visibility("default"))) void dsrg_debug_set_igemm_variant(int v) { dsrg::g_igemm_variant = v; }
 extern "C" __attribute__((visibility("default"))) void dsrg_debug_set_build_trace(void *dev_buf) { dsrg::g_build_dbg = dev_buf; }
 // tools only (not in the public header): device buffer of 16 u64 per filter block receiving phase timestamps

@@ -6,10 +6,6 @@
 //                   and the gather-form backward that reads the codes (no atomics, deterministic)
 #include "common.h"
 #include <algorithm>
-#ifndef DSRG_EXP
-#define DSRG_EXP 0                // experiment builds (Makefile EXP= EXPSRC=backbone_ops; tools only)
-#endif
-#include <cstdlib>
 #include <cstring>
 
 namespace dsrg {
@@ -636,8 +632,9 @@ int launch_maxpool3x3_bwd(const void *gout, const void *code, void *gin, int B, 
 // activations, FLOAT32 weights, float32 accumulation and a float32 NCHW result — the scores that feed Softmax + 1e-4, the
 // CRF and the 0.85 / 0.99 region-growing thresholds never pass through bf16.  bf16 -> f32 is exact, so the forward equals
 // the fp32 convolution of the (bf16-valued) fc7 outputs.  Skinny GEMMs (21 outputs): forward and weight gradient on the
-// f32-input MFMA (v_mfma_f32_32x32x2_f32: exact f32 fma chains at the f32 vector rate, operands straight from global
-// memory, no LDS staging), the data gradient on the VALU (output-bandwidth-bound).
+// bf16 MFMA with the float32 operand split into three bf16 terms (below), the data gradient on the VALU
+// (output-bandwidth-bound).  A weight gradient whose staging exceeds LDS takes the f32-input MFMA (v_mfma_f32_32x32x2_f32:
+// exact f32 fma chains at the f32 vector rate, operands straight from global memory).
 //   MFMA 32x32x2 operand maps (cdna_hip_programming.md §3): A[i = lane & 31][k = lane >> 5], B[k = lane >> 5][j = lane & 31],
 //   C/D: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
 namespace {
@@ -655,68 +652,6 @@ __device__ __forceinline__ void bf16x8_to_f32(const uint4 &v, float (&f)[8]) {
     f[4] = bf16_lo(v.z); f[5] = bf16_hi(v.z); f[6] = bf16_lo(v.w); f[7] = bf16_hi(v.w);
 }
 }  // namespace
-
-// one workgroup = one 32-row tile; wave k = branch k (its whole K range), partial tiles summed through LDS in branch order
-// (the reference's Eltwise SUM order, each with its own bias).  Per 8 MFMAs a lane loads 16 B of x and 32 B of W.
-__global__ __launch_bounds__(256) void heads_fwd_kernel(HeadArgs a) {
-    __shared__ float part[4][16][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int m0 = blockIdx.x * 32;
-    const int row = lane & 31, half = lane >> 5;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc[r] = 0.0f;
-    if (wave < a.nbr) {
-        const int mr = min(m0 + row, a.M - 1);                      // clamped rows are never stored
-        const uint16_t *xp = a.x[wave] + (size_t)mr * a.K + half * 8;
-        const float *wp = a.w + ((size_t)wave * a.O + min(row, a.O - 1)) * a.K + half * 8;
-        // two 16-channel steps in flight ahead of the MFMAs that consume them (K % 256 == 0)
-        uint4 xv[2];
-        float4 wv[2][2];
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            xv[u] = *reinterpret_cast<const uint4 *>(xp + u * 16);
-            wv[u][0] = *reinterpret_cast<const float4 *>(wp + u * 16);
-            wv[u][1] = *reinterpret_cast<const float4 *>(wp + u * 16 + 4);
-        }
-        for (int kb = 0; kb < a.K; kb += 32) {
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                float xf[8];
-                bf16x8_to_f32(xv[u], xf);
-                const float wf[8] = {wv[u][0].x, wv[u][0].y, wv[u][0].z, wv[u][0].w, wv[u][1].x, wv[u][1].y, wv[u][1].z, wv[u][1].w};
-                const int kn = kb + 32 + u * 16;
-                if (kn < a.K) {
-                    xv[u] = *reinterpret_cast<const uint4 *>(xp + kn);
-                    wv[u][0] = *reinterpret_cast<const float4 *>(wp + kn);
-                    wv[u][1] = *reinterpret_cast<const float4 *>(wp + kn + 4);
-                }
-#pragma unroll
-                for (int j = 0; j < 8; j++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xf[j], wf[j], acc, 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; r++) part[wave][r][lane] = acc[r];
-    __syncthreads();
-    // thread t: output column t / 8, rows 4 (t % 8) .. + 3 of the tile
-    const int col = threadIdx.x >> 3, r4 = (threadIdx.x & 7) * 4;
-    if (col < a.O) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int rr = r4 + q, m = m0 + rr;
-            if (m >= a.M) break;
-            const int hf = (rr >> 2) & 1, reg = (rr & 3) + 4 * (rr >> 3), ln = col + 32 * hf;
-            float s = 0.0f;
-            for (int k = 0; k < a.nbr; k++) {
-                const float sk = part[k][reg][ln] + (a.bias ? a.bias[k * a.O + col] : 0.0f);
-                s = k == 0 ? sk : s + sk;
-            }
-            const int b = m / a.HW, hw = m - b * a.HW;
-            a.out[((size_t)b * a.O + col) * a.HW + hw] = s;
-        }
-    }
-}
 
 // data gradient: gx_k[m][c] = sum_o g[m][o] W_k[o][c] -> bf16 (M, K) row-major.  One workgroup = 16 T rows of one branch (T
 // tiles of 16 in turn), thread = 8 channels x 8 rows; g tile through LDS (broadcast reads), W rows straight from L2.
@@ -1020,8 +955,9 @@ __device__ __forceinline__ hbf16x8 tr_frag16(DSRG_LDS_AS unsigned char *p, int s
 }
 }  // namespace
 
-// forward: as heads_fwd_kernel (wave = branch), the x fragment is the lane's 16-byte load as it is, the weight fragment its 32-byte
-// load split in three.  One workgroup = R 32-row tiles: the weight fragment (344 KB of W per workgroup, from L2) and its split are
+// forward: wave k = branch k (its whole K range), partial tiles summed through LDS in branch order (the reference's Eltwise SUM
+// order, each with its own bias); the x fragment is the lane's 16-byte load as it is, the weight fragment its 32-byte load split
+// in three.  One workgroup = R 32-row tiles: the weight fragment (344 KB of W per workgroup, from L2) and its split are
 // shared by the R tiles — R = 2 halves both per row (round 6: 97 -> see profiles/r06_fused_backward_probe.txt); the rows' arithmetic
 // is the same either way (bit-identical outputs).
 template <int R>
@@ -1174,11 +1110,6 @@ __global__ __launch_bounds__(256, 2) void heads_bwd_dw_split_kernel(HeadArgs a, 
     }
 }
 
-// DSRG_HEADS_MFMA=f32 selects the round-2a kernels on the f32-input MFMA (exact fma chains); default: the bf16 MFMA on split operands
-static bool heads_f32_mfma() {
-    static const bool f32 = [] { const char *e = getenv("DSRG_HEADS_MFMA"); return e && !strcmp(e, "f32"); }();
-    return f32;
-}
 static int heads_check(int nbr, int K, int O) {
     if (nbr < 1 || nbr > 4 || O < 1 || O > kHeadOutPad || K < 256 || K % 256 != 0)
         return set_error(DSRG_ERR_UNSUPPORTED, "heads: 1..4 branches, <= %d outputs, K a multiple of 256", kHeadOutPad);
@@ -1192,16 +1123,7 @@ int launch_heads_fwd(const void *const *x, int nbr, const float *w, const float 
     HeadArgs a;
     for (int k = 0; k < 4; k++) a.x[k] = static_cast<const uint16_t *>(x[k < nbr ? k : 0]);
     a.w = w; a.bias = bias; a.out = out; a.nbr = nbr; a.M = B * HW; a.K = K; a.O = O; a.HW = HW;
-    if (heads_f32_mfma())
-        hipLaunchKernelGGL(heads_fwd_kernel, dim3((a.M + 31) / 32), dim3(256), 0, stream, a);
-    else
-    {
-        static const int tiles = [] { const char *e = getenv("DSRG_HEAD_FWD_TILES"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 4 ? v : 2; }();      // tools: A/B
-        if (tiles == 4) hipLaunchKernelGGL(heads_fwd_split_kernel<4>, dim3((a.M + 127) / 128), dim3(256), 0, stream, a);
-        else if (tiles == 3) hipLaunchKernelGGL(heads_fwd_split_kernel<3>, dim3((a.M + 95) / 96), dim3(256), 0, stream, a);
-        else if (tiles == 2) hipLaunchKernelGGL(heads_fwd_split_kernel<2>, dim3((a.M + 63) / 64), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(heads_fwd_split_kernel<1>, dim3((a.M + 31) / 32), dim3(256), 0, stream, a);
-    }
+    hipLaunchKernelGGL(heads_fwd_split_kernel<2>, dim3((a.M + 63) / 64), dim3(256), 0, stream, a);
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
 }
@@ -1211,22 +1133,14 @@ int launch_heads_fwd(const void *const *x, int nbr, const float *w, const float 
 int heads_bwd_chunks(int M) { int c = (M + 255) / 256; return c < 1 ? 1 : (c > 128 ? 128 : c); }
 
 // 16-row tiles per workgroup of the masked data gradient (one partial bias row each): fewer rows per workgroup = more of them
-// in flight, more partial rows to write and sum (DSRG_HEAD_TILES overrides, tools only)
-static int head_mask_tiles() {
-    static const int t = [] { const char *e = getenv("DSRG_HEAD_TILES"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 64 ? v : 8; }();
-    return t;
-}
+// in flight, more partial rows to write and sum
+constexpr int kHeadMaskTiles = 8;
 // rows per workgroup of the row-strip form (heads_bwd_dx_rows_kernel): long enough to amortise the 84 KB of W a workgroup loads,
-// short enough for a few rounds of the chip (DSRG_HEAD_ROWS overrides, tools only; 0 = the tiled kernel)
-static int head_strip_rows() {
-    static const int r = [] { const char *e = getenv("DSRG_HEAD_ROWS"); const int v = e ? atoi(e) : -1; return v >= 0 && v <= 512 ? v : 64; }();
-    return r;
-}
-static bool head_strips(int K, int O) { return head_strip_rows() > 0 && O == 21 && K % 1024 == 0; }
+// short enough for a few rounds of the chip; other shapes take the tiled kernel
+constexpr int kHeadStripRows = 64;
+static bool head_strips(int K, int O) { return O == 21 && K % 1024 == 0; }
 size_t heads_bwd_relu_workspace(int nbr, int M, int K) {
-    const int kHeadMaskTiles = head_mask_tiles();
-    size_t rows = (size_t)((M + 16 * kHeadMaskTiles - 1) / (16 * kHeadMaskTiles));
-    if (head_strip_rows() > 0) rows = std::max(rows, (size_t)((M + head_strip_rows() - 1) / head_strip_rows()));
+    const size_t rows = std::max((size_t)((M + 16 * kHeadMaskTiles - 1) / (16 * kHeadMaskTiles)), (size_t)((M + kHeadStripRows - 1) / kHeadStripRows));
     return (size_t)nbr * rows * (size_t)K * sizeof(float);
 }
 
@@ -1239,7 +1153,6 @@ int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float 
     if (gx && relu_scale > 0.0f) {
         HeadMask hm;
         for (int k = 0; k < 4; k++) hm.y[k] = static_cast<const uint16_t *>(x[k < nbr ? k : 0]);
-        const int kHeadMaskTiles = head_mask_tiles();
         hm.tiles = kHeadMaskTiles; hm.scale = relu_scale;
         const int nblk = (M + 16 * kHeadMaskTiles - 1) / (16 * kHeadMaskTiles);
         if (!bias_grad || !colsum_ws || colsum_ws_bytes < heads_bwd_relu_workspace(nbr, M, K))
@@ -1247,10 +1160,10 @@ int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float 
         hm.part = static_cast<float *>(colsum_ws);
         int nblk_s = nblk;
         if (head_strips(K, O)) {
-            nblk_s = (M + head_strip_rows() - 1) / head_strip_rows();
+            nblk_s = (M + kHeadStripRows - 1) / kHeadStripRows;
             hipLaunchKernelGGL((heads_bwd_dx_rows_kernel<21, true>), dim3(nblk_s, nbr, K / 1024), dim3(256),
-                               (size_t)head_strip_rows() * 24 * sizeof(float), stream, g, w, static_cast<unsigned char *>(gx), M, K, HW,
-                               gx_branch_stride, hm, head_strip_rows());
+                               (size_t)kHeadStripRows * 24 * sizeof(float), stream, g, w, static_cast<unsigned char *>(gx), M, K, HW,
+                               gx_branch_stride, hm, kHeadStripRows);
         } else {
             hipLaunchKernelGGL(heads_bwd_dx_kernel<true>, dim3(nblk, nbr), dim3(256), 0, stream, g, w, static_cast<uint4 *>(gx), M, K, O, HW,
                                gx_branch_stride, hm);
@@ -1264,9 +1177,9 @@ int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float 
         HeadMask hm;
         memset(&hm, 0, sizeof(hm));
         if (head_strips(K, O))
-            hipLaunchKernelGGL((heads_bwd_dx_rows_kernel<21, false>), dim3((M + head_strip_rows() - 1) / head_strip_rows(), nbr, K / 1024),
-                               dim3(256), (size_t)head_strip_rows() * 24 * sizeof(float), stream, g, w, static_cast<unsigned char *>(gx), M, K, HW,
-                               gx_branch_stride, hm, head_strip_rows());
+            hipLaunchKernelGGL((heads_bwd_dx_rows_kernel<21, false>), dim3((M + kHeadStripRows - 1) / kHeadStripRows, nbr, K / 1024),
+                               dim3(256), (size_t)kHeadStripRows * 24 * sizeof(float), stream, g, w, static_cast<unsigned char *>(gx), M, K, HW,
+                               gx_branch_stride, hm, kHeadStripRows);
         else
             hipLaunchKernelGGL(heads_bwd_dx_kernel<false>, dim3((M + 15) / 16, nbr), dim3(256), 0, stream, g, w, static_cast<uint4 *>(gx), M,
                                K, O, HW, gx_branch_stride, hm);
@@ -1278,7 +1191,7 @@ int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float 
         a.w = w; a.bias = nullptr; a.out = nullptr; a.nbr = nbr; a.M = M; a.K = K; a.O = O; a.HW = HW;
         const int nch = heads_bwd_chunks(M), rows = ((M + nch - 1) / nch + 1) & ~1;
         const size_t lds = (size_t)kDwRows2 * (K * 2 + 64) + 32 * kDwGPitch * sizeof(float);
-        if (heads_f32_mfma() || lds > 160 * 1024) {
+        if (lds > 160 * 1024) {
             hipLaunchKernelGGL(heads_bwd_dw_kernel, dim3(nch, nbr), dim3(256), 0, stream, a, g, partial, rows);
         } else {
             static LdsGrant grant;

@@ -13,7 +13,7 @@
 // fragments — 288 VGPRs at one wave per SIMD (the file has 512 at that occupancy), or 144 at two:
 //     64 -> 64    a wave holds 32 of the outputs (1 tile x 36 k-steps = 144 VGPRs), 2 x 2 waves split outputs x pixels, and TWO
 //                 workgroups share a CU: the 24 KB halo fetch of a workgroup is its only memory parallelism and the kernel is
-//                 bound by exactly that (DSRG_CONV_OCC=1: all 64 outputs per wave, one workgroup per CU, 202 instead of 169 us)
+//                 bound by exactly that (all 64 outputs per wave, one workgroup per CU: 202 instead of 169 us)
 //     64 -> 128   a wave holds 64 of the outputs, 2 x 2 waves split outputs x pixels (2 M-tiles of 32 pixels per wave)
 //    128 -> 128   a wave holds 32 of the outputs (1 tile x 72 k-steps) and visits all 4 M-tiles
 //    128 -> 64    a wave holds 32 of the outputs, 2 x 2 waves split outputs x pixels
@@ -22,18 +22,6 @@
 // (v_mfma_f32_32x32x16_bf16) of an M-tile and parked in the other buffer after them.  The output tile goes back through LDS
 // for 16-byte coalesced NHWC stores.
 #include "common.h"
-#include <cstdlib>
-#include <cstring>
-
-#if defined(DSRG_EXP) && (DSRG_EXP & 16)
-#define DSRG_DIRECT_DMA 0
-#endif
-#ifndef DSRG_DIRECT_DMA
-#define DSRG_DIRECT_DMA 1                    // 1: the halo tiles of conv3x3_direct_kernel go global -> LDS by DMA (chunk-major image); 0: through registers (rounds 2-5)
-#endif
-#ifndef DSRG_EXP
-#define DSRG_EXP 0                           // experiment builds (Makefile, EXP= / EXPSRC=conv_direct): 1 no halo fetch beyond the first
-#endif                                       // tile, 2 no output stores, 4 no MFMAs — what binds the forward kernel (tools only)
 
 namespace dsrg {
 namespace {
@@ -53,11 +41,7 @@ template <int CIN, int COUT, int TPW_ = (CIN == 64 ? 2 : 1)> struct Cfg {
     static constexpr int NG = COUT / (32 * TPW);           // waves across the output channels
     static constexpr int PG = 4 / NG;                      // waves across the pixels
     static constexpr int MT = 4 / PG;                      // 32-pixel M-tiles per wave
-#if DSRG_EXP & 8
-    static constexpr int KPS = 4;
-#else
     static constexpr int KPS = WGS == 2 ? 2 : 4;           // k-steps per step of the MFMA loop (the operand prefetch unit)
-#endif
     static constexpr int SPT = CG / KPS;                   // steps per tap
     static constexpr int STEPS = 9 * SPT;
     // halo by LDS-DMA (buffer_load ... lds) where it pays (measured at batch 16, round 6: 128 -> 128 152 -> 141 us; 64 -> 64 and
@@ -67,7 +51,7 @@ template <int CIN, int COUT, int TPW_ = (CIN == 64 ? 2 : 1)> struct Cfg {
     // without padding or swizzle, and the address is lane part (pixel * 16 + kgrp * PLANE) + compile-time constant (chunk * PLANE +
     // tap offset * 16): immediate offsets, as the padded pixel-major image has (an XOR-swizzled pixel-major image makes hipcc form
     // every step's address up front and spill the register-resident weights)
-    static constexpr bool DMA = DSRG_DIRECT_DMA && CIN == 128 && COUT == 128;
+    static constexpr bool DMA = CIN == 128 && COUT == 128;
     static constexpr int CPR = CIN / 8;                    // 16-byte chunks per halo pixel (8 / 16)
     static constexpr int PB = (kHH * kHW + 63) / 64;       // 64-pixel blocks per chunk plane (3)
     static constexpr int PLANE = PB * 1024;                // bytes per chunk plane
@@ -220,11 +204,7 @@ __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direc
     const rsrc_t rmask = make_rsrc(a.mask, BWD ? (size_t)a.B * a.H * a.W * COUT * 2 : 0);
     for (; t < a.ntiles; t += gridDim.x) {
         const int tn = t + gridDim.x;
-#if DSRG_EXP & 1
-        const bool more = false;
-#else
         const bool more = tn < a.ntiles;
-#endif
         unsigned char *in = conv_lds + cur * C::BUF, *other = conv_lds + (cur ^ 1) * C::BUF;
         if (BWD) {
             int b, y0, x0;
@@ -275,14 +255,8 @@ __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direc
 #pragma unroll
                 for (int i = 0; i < C::KPS; i++)
 #pragma unroll
-                    for (int j = 0; j < C::TPW; j++) {
-#if DSRG_EXP & 4
-                        if (s == 0) acc[mt][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][s * C::KPS + i], ar[s & 1][i], acc[mt][j], 0, 0, 0);
-                        else asm volatile("" ::"v"(ar[s & 1][i]), "v"(wf[j][s * C::KPS + i]));
-#else
+                    for (int j = 0; j < C::TPW; j++)
                         acc[mt][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][s * C::KPS + i], ar[s & 1][i], acc[mt][j], 0, 0, 0);
-#endif
-                    }
                 __builtin_amdgcn_sched_barrier(0);
             }
             if constexpr (!kDma)
@@ -338,11 +312,7 @@ __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direc
                     }
                     val = make_uint4(w4[0], w4[1], w4[2], w4[3]);
                 }
-#if DSRG_EXP & 2
-                if (yy < a.H && xx < a.W && val.x == 0x12345678u)
-#else
                 if (yy < a.H && xx < a.W)
-#endif
                     *reinterpret_cast<uint4 *>(a.y + (((size_t)b * a.H + yy) * a.W + xx) * COUT + cg * 8) = val;
             }
             if (BWD) {
@@ -352,9 +322,7 @@ __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direc
         }
         if constexpr (kDma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the next halo have landed (the barrier: everybody's)
         __syncthreads();                                         // this buffer is free for the tile after next
-#if !(DSRG_EXP & 1)
         cur ^= 1;
-#endif
     }
     if (BWD) {                                                   // one partial bias row per workgroup, fixed order
         const float *red = reinterpret_cast<const float *>(conv_lds + 2 * C::BUF);        // [256 threads][8]
@@ -377,24 +345,24 @@ int variant_grid(const ConvArgs &a, int n_cus) {
     const int slots = n_cus * Cfg<CIN, COUT, TPW_>::WGS;
     return a.ntiles < slots ? a.ntiles : slots;
 }
-template <int CIN, int COUT, int TPW_>
-int launch_variant(const ConvArgs &a, int n_cus, hipStream_t stream) {
+template <int CIN, int COUT, int TPW_, bool BWD>              // BWD: the masked data gradient (a.mask set)
+int launch_variant(const ConvArgs &a, int n_cus, hipStream_t stream, int &grid) {
     using C = Cfg<CIN, COUT, TPW_>;
-    static LdsGrant grant, grant_b;
+    static LdsGrant grant;
     // (the DMA halo marks a lane outside the image with byte offset 2^31, which must lie beyond the descriptor's range)
-    if (C::DMA && !a.mask && (size_t)a.B * a.H * a.W * CIN * 2 >= ((size_t)1 << 31)) return DSRG_ERR_UNSUPPORTED;
-    const int grid = variant_grid<CIN, COUT, TPW_>(a, n_cus);    // persistent: one or two workgroups per CU
-    if (a.mask) {                                                // masked data gradient: + 8 KB of column sums
-        const size_t lds = 2 * (size_t)C::BUF + 256 * 8 * sizeof(float) + (size_t)kTH * kTW * COUT * 2;
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv3x3_direct_kernel<CIN, COUT, TPW_, true>), lds, grant_b)) return rc;
-        hipLaunchKernelGGL((conv3x3_direct_kernel<CIN, COUT, TPW_, true>), dim3(grid), dim3(256), lds, stream, a);
-    } else {
-        const size_t lds = 2 * (size_t)C::BUF;
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv3x3_direct_kernel<CIN, COUT, TPW_>), lds, grant)) return rc;
-        hipLaunchKernelGGL((conv3x3_direct_kernel<CIN, COUT, TPW_>), dim3(grid), dim3(256), lds, stream, a);
-    }
+    if (C::DMA && !BWD && (size_t)a.B * a.H * a.W * CIN * 2 >= ((size_t)1 << 31)) return DSRG_ERR_UNSUPPORTED;
+    grid = variant_grid<CIN, COUT, TPW_>(a, n_cus);              // persistent: one or two workgroups per CU
+    // (masked: + 8 KB of column sums and the tile's mask rows)
+    const size_t lds = 2 * (size_t)C::BUF + (BWD ? 256 * 8 * sizeof(float) + (size_t)kTH * kTW * COUT * 2 : 0);
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv3x3_direct_kernel<CIN, COUT, TPW_, BWD>), lds, grant)) return rc;
+    hipLaunchKernelGGL((conv3x3_direct_kernel<CIN, COUT, TPW_, BWD>), dim3(grid), dim3(256), lds, stream, a);
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
+}
+// either form of one shape
+template <int CIN, int COUT, int TPW_>
+int launch_shape(const ConvArgs &a, int n_cus, hipStream_t stream, int &grid) {
+    return a.mask ? launch_variant<CIN, COUT, TPW_, true>(a, n_cus, stream, grid) : launch_variant<CIN, COUT, TPW_, false>(a, n_cus, stream, grid);
 }
 // ------------------------------------------------------------------------------------------------------------------
 // The first layer, 3 -> 64 channels at full resolution (conv1_1, train-s.prototxt:44-64): output-bandwidth-bound (211 MB at
@@ -962,17 +930,14 @@ int launch_conv3x3_direct(const void *x, const void *w, const float *bias, void 
         DSRG_LAUNCH_CHECK();
         return DSRG_OK;
     }
-    // 64 -> 64: one output tile per wave (144 weight VGPRs) and two workgroups per CU by default — the halo loads of a
-    // workgroup are its only memory parallelism (24 KB in flight), a second one doubles it; DSRG_CONV_OCC=1: two tiles per wave
-    static const bool occ2 = [] { const char *e = getenv("DSRG_CONV_OCC"); return !(e && !strcmp(e, "1")); }();
-    int rc, grid;
-    // (the masked form of the two-workgroup variant spills a few loop-invariant addresses — 281 against 267 us for conv1_2's data
-    // gradient + the separate pass; two tiles per wave does not)
-    if (cin == 64 && cout == 64 && occ2 && !mask) { rc = launch_variant<64, 64, 1>(a, n_cus, stream); grid = variant_grid<64, 64, 1>(a, n_cus); }
-    else if (cin == 64 && cout == 64) { rc = launch_variant<64, 64, 2>(a, n_cus, stream); grid = variant_grid<64, 64, 2>(a, n_cus); }
-    else if (cin == 64) { rc = launch_variant<64, 128, 2>(a, n_cus, stream); grid = variant_grid<64, 128, 2>(a, n_cus); }
-    else if (cout == 64) { rc = launch_variant<128, 64, 1>(a, n_cus, stream); grid = variant_grid<128, 64, 1>(a, n_cus); }
-    else { rc = launch_variant<128, 128, 1>(a, n_cus, stream); grid = variant_grid<128, 128, 1>(a, n_cus); }
+    // 64 -> 64: one output tile per wave (144 weight VGPRs) and two workgroups per CU — the halo loads of a workgroup are its
+    // only memory parallelism (24 KB in flight), a second one doubles it.  The masked form of that variant spills a few
+    // loop-invariant addresses (281 against 267 us for conv1_2's data gradient + the separate pass); two tiles per wave does not
+    int rc, grid = 0;
+    if (cin == 64 && cout == 64) rc = mask ? launch_variant<64, 64, 2, true>(a, n_cus, stream, grid) : launch_variant<64, 64, 1, false>(a, n_cus, stream, grid);
+    else if (cin == 64) rc = launch_shape<64, 128, 2>(a, n_cus, stream, grid);
+    else if (cout == 64) rc = launch_shape<128, 64, 1>(a, n_cus, stream, grid);
+    else rc = launch_shape<128, 128, 1>(a, n_cus, stream, grid);
     if (rc || !colsum) return rc;
     const float *parts[1] = {a.colsum};
     float *outs[1] = {colsum};

@@ -1240,15 +1240,10 @@ static bool conv_igemm_launchable(int cin, int cout, int k) {
     return (k == 1 || k == 3) && cin >= 64 && cin % 64 == 0 && (cout == 64 || (cout >= 128 && cout % 128 == 0));
 }
 
-std::atomic<int> g_igemm_variant{-1};      // dsrg_debug_set_igemm_variant (tests / tools); -1 = DSRG_IGEMM_VARIANT or the default
+std::atomic<int> g_igemm_variant{-1};      // dsrg_debug_set_igemm_variant (tests / tools); -1 = the default, 3
 static int igemm_variant() {
-    int v = g_igemm_variant.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("DSRG_IGEMM_VARIANT");
-        v = e ? atoi(e) : 3;
-        g_igemm_variant.store(v, std::memory_order_relaxed);
-    }
-    return v;
+    const int v = g_igemm_variant.load(std::memory_order_relaxed);
+    return v < 0 ? 3 : v;
 }
 
 static int igemm_cus() {
@@ -1466,10 +1461,8 @@ int launch_conv_igemm(const void *const *x, const void *const *w, const float *c
     // whose tiles all run the same steps keep the map they were tuned with (neighbouring pixel tiles share rows in one L2)
     for (int g = 0; g < ngroups; g++)
         if (a.skip_taps && k == 3 && a.g[g].dil >= 3) a.xcd_mix = 1;
-    static const bool row_tiles_on = [] { const char *e = getenv("DSRG_IGEMM_ROW_TILES"); return !e || atoi(e) != 0; }();      // tools: A/B
-    static const bool cls_tiles_on = [] { const char *e = getenv("DSRG_IGEMM_CLASS_TILES"); return !e || atoi(e) != 0; }();    // tools: A/B
-    const bool rows_ok = a.xcd_mix && row_tiles_on && W <= kBM && conv_igemm_row_tiles(H, W);
-    if (a.xcd_mix && cls_tiles_on && igemm_variant() != 8 && H <= 255 && W <= 255) {       // 8: tests — round 5's row-aligned tiles
+    const bool rows_ok = a.xcd_mix && W <= kBM && conv_igemm_row_tiles(H, W);
+    if (a.xcd_mix && igemm_variant() != 8 && H <= 255 && W <= 255) {       // 8: tests — round 5's row-aligned tiles
         // the class order pays where its tiles run fewer K-steps than the tiling it replaces (a map of few tiles has most of them
         // straddle classes); decided once per geometry
         struct Key { int B, H, W, d[4], n, rows; bool operator<(const Key &o) const { return memcmp(this, &o, sizeof(Key)) < 0; } };
@@ -1597,8 +1590,6 @@ static int wgrad_col_tiles(int cin, int k) { return (cin == 128 && k == 3) ? (k 
 static int wgrad_ksplit(long long M, int tiles, int cus, double out_bytes = 0.0, bool xcd_mix_only = false) {
     long long best_cost = -1;
     int best = 1;
-    static const int forced = [] { const char *e = getenv("DSRG_WGRAD_KSPLIT"); return e ? atoi(e) : 0; }();     // tools only
-    if (forced >= 1 && forced <= 128 && (long long)(forced - 1) * (((M + forced - 1) / forced + 63) / 64 * 64) < M) return forced;
     for (int ks = 1; ks <= 128; ks++) {
         const long long chunk = ((M + ks - 1) / ks + 63) / 64 * 64;
         if ((long long)(ks - 1) * chunk >= M) continue;                 // an empty last split
@@ -1665,8 +1656,6 @@ int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *co
     for (int q = 0; q < ngroups; q++) wants_mix = wants_mix || (k == 3 && dil && dil[q] >= 3);      // (whatever the variant: tests compare them bit for bit)
     a.ksplit = t_force_ksplit > 0 ? t_force_ksplit
                                   : wgrad_ksplit(M, ngroups * a.tiles_n * a.tiles_c, 256, (double)ngroups * cout * k * k * cin * 4.0, wants_mix);
-    static const int grouped_ks = [] { const char *e = getenv("DSRG_WGRAD_KSPLIT_GROUPED"); return e ? atoi(e) : 0; }();        // tools: A/B
-    if (grouped_ks > 0 && ngroups == 4 && k == 3 && grouped_ks <= a.ksplit) a.ksplit = grouped_ks;
     a.kchunk = (int)(((M + a.ksplit - 1) / a.ksplit + 63) / 64 * 64);
     a.tiles_per_group = a.tiles_n * a.tiles_c * a.ksplit;
     a.stagger = igemm_variant() >= 3;
@@ -1679,12 +1668,11 @@ int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *co
         a.g[q].dil = dil ? dil[q] : 1;
         if (!a.g[q].x || !a.g[q].g || !gw[q]) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: null pointer");
     }
-    static const bool compact_on = [] { const char *e = getenv("DSRG_WGRAD_COMPACT"); return !e || atoi(e) != 0; }();      // tools: A/B
-    static const int compact_min_dil = [] { const char *e = getenv("DSRG_WGRAD_COMPACT_MIN_DIL"); return e ? atoi(e) : 1; }();     // tools: A/B (3: dilated kernels only — 1 776-1 782 against 1 800-1 807 images/s)
+    // (compact pixel order for every 3x3 layer, not the dilated ones only: 1 800-1 807 against 1 776-1 782 images/s)
     for (int q = 0; q < ngroups; q++) {
         if (a.skip_rows && k == 3 && a.g[q].dil >= 3 &&
             (a.ksplit % 8 == 0 || (8 % a.ksplit == 0 && (a.tiles_n * a.tiles_c) % (8 / a.ksplit) == 0))) a.xcd_mix = 1;
-        if (a.skip_rows && compact_on && igemm_variant() != 7 && k == 3 && cin != 128 && a.g[q].dil >= compact_min_dil) a.compact = 1;      // 7: tests — dead steps skipped in the flat pixel order
+        if (a.skip_rows && igemm_variant() != 7 && k == 3 && cin != 128 && a.g[q].dil >= 1) a.compact = 1;      // 7: tests — dead steps skipped in the flat pixel order
     }
     if (t_prep_w) {
         *t_prep_w = a;
@@ -1736,10 +1724,7 @@ int launch_conv_igemm_backward(const void *g, const void *wd, const void *x, con
     void *gxp[1] = {gx}, *gwp[1] = {gw};
     float *bgp[1] = {bias_grad};
     const int dils[1] = {dil};
-    static const bool merged_on = [] { const char *e = getenv("DSRG_IGEMM_MERGED_BWD"); return !e || atoi(e) != 0; }();      // tools: A/B
-    static const bool w_first_on = [] { const char *e = getenv("DSRG_MERGED_W_FIRST"); return !e || atoi(e) != 0; }();      // tools: A/B
-    static const bool merged_k1_on = [] { const char *e = getenv("DSRG_IGEMM_MERGED_K1"); return !e || atoi(e) != 0; }();    // tools: A/B (1x1 layers)
-    const bool can_merge = merged_on && ((k == 3 && dil < 3) || (k == 1 && merged_k1_on)) && (igemm_variant() == 3 || igemm_variant() == 1 || igemm_variant() == 8 || igemm_variant() == 9);
+    const bool can_merge = ((k == 3 && dil < 3) || k == 1) && (igemm_variant() == 3 || igemm_variant() == 1 || igemm_variant() == 8 || igemm_variant() == 9);
     IgemmBwdArgs a;
     memset(&a, 0, sizeof(a));
     int nd = 0, nw = 0, rc = DSRG_OK;
@@ -1773,8 +1758,7 @@ int launch_conv_igemm_backward(const void *g, const void *wd, const void *x, con
             // (the block order is searched too for the shapes round 6 added — 1x1 layers, channel counts below 256: their data-gradient
             // tiles are a few K-steps long, and long weight-gradient workgroups dispatched LAST would run on alone; the 3x3 layers of
             // the VGG path keep the order they were tuned with)
-            static const bool order_all = [] { const char *e = getenv("DSRG_MERGED_ORDER_ALL"); return e && atoi(e) != 0; }();     // tools: A/B
-            const bool order_free = w_first_on && (order_all || k == 1 || cin < 256 || cout < 256);
+            const bool order_free = k == 1 || cin < 256 || cout < 256;
             for (int ks = 1; ks <= cap && !known; ks++) {
                 const long long chunk = ((M + ks - 1) / ks + 63) / 64 * 64;
                 if ((long long)(ks - 1) * chunk >= M) continue;                  // an empty last split
@@ -1791,8 +1775,7 @@ int launch_conv_igemm_backward(const void *g, const void *wd, const void *x, con
                 std::lock_guard<std::mutex> lock(memo_mutex);
                 memo[key] = std::make_pair(best_ks, a.w_first);
             }
-            static const bool pick_on = [] { const char *e = getenv("DSRG_MERGED_KS"); return !e || atoi(e) != 0; }();      // tools: A/B
-            t_force_ksplit = pick_on ? best_ks : 0;
+            t_force_ksplit = best_ks;
             t_prep_w = &a.w; t_prep_grid = &nw;
             rc = launch_conv_igemm_wgrad(xp, gp, gwp, dils, 1, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout, k, 0, stream);
             t_prep_w = nullptr;

@@ -15,20 +15,15 @@
 // also forms the Gaussian message itself, in registers, and the filter launch
 // carries bilateral workgroups only.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 #include <type_traits>
 #include "common.h"
 
-// compile-time experiments on the filter kernel: make EXP=n builds libdsrg_hip.expN.so next to the shipped library and the
-// tools select it with DSRG_LIB (A/B on one box).  Measured and adopted in round 3: blur gathers batched per group of 5
+// Measured on the filter kernel and adopted in round 3: blur gathers batched per group of 5
 // slots (-0.96 us per workgroup), product gathers batched (-0.14); measured and dropped: a workgroup barrier behind the q
 // loads (+0.3), the first row term of every slot batched (0.0), term-major row sums (+1.5), neighbour-word descriptors that
 // end at M (0.0), LDS-only barriers (0.0).  Adopted later: the extras' index words and the first axis' neighbour words
 // issued behind the first barrier (-0.6, -0.2).  profiles/r03_filter_ab.txt
-#ifndef DSRG_EXP
-#define DSRG_EXP 0
-#endif
 
 namespace dsrg {
 
@@ -85,10 +80,6 @@ __device__ __forceinline__ void pv_set(float4 &v, int c, float x) {
 
 template <int V> using IC = std::integral_constant<int, V>;
 
-#if DSRG_EXP & 16
-#define g_exp_qimg (exp_qimg)
-#define g_exp_C (exp_C)
-#endif
 #define DSRG_STAMP(i_) do { if (dbg && tid == 0) dbg[(i_)] = wall_clock64(); } while (0)
 
 // one lattice (dimension D, index li of set L), planes [c0, c0+nc) of image b:
@@ -98,11 +89,7 @@ __device__ __forceinline__ void filter_lattice(const LatticeView &L, int li, con
                                                float *__restrict__ out, int nc, int N,
                                                typename PlaneVec<CPW>::type *val,
                                                typename PlaneVec<CPW>::type *inq, unsigned long long *dbg,
-                                               int lds_elems, int opts
-#if DSRG_EXP & 16
-                                               , const float *exp_qimg, int exp_C
-#endif
-                                               ) {
+                                               int lds_elems, int opts) {
     using vec_t = typename PlaneVec<CPW>::type;
     constexpr int D1 = D + 1;
     constexpr bool DEEP = VPT <= 10;             // all index words of a thread fit the register file
@@ -115,12 +102,6 @@ __device__ __forceinline__ void filter_lattice(const LatticeView &L, int li, con
 
     const uint32_t nb_bytes = sizeof(uint32_t) * (uint32_t)Mcap;
 
-#if DSRG_EXP & 8
-    const int M = L.M[li];
-    const int lat_flags = L.flags[li];
-    const int X = L.nextra[li];
-    asm volatile("" :: "s"(M), "s"(lat_flags), "s"(X));     // consumed (waited for) here, ahead of the vector loads
-#endif
     const rsrc_t r_rs = make_rsrc(L.row_start + (size_t)li * (Mcap + 2), sizeof(uint16_t) * (size_t)(Mcap + 2));
     const rsrc_t r_fp = make_rsrc(L.first_pix + (size_t)li * Mcap, sizeof(uint16_t) * (size_t)Mcap);
     const rsrc_t r_fw = make_rsrc(L.first_w + (size_t)li * Mcap, sizeof(float) * (size_t)Mcap);
@@ -140,28 +121,6 @@ __device__ __forceinline__ void filter_lattice(const LatticeView &L, int li, con
         for (int c = 0; c < CPW; c++)
             qv[p][c] = ld_f32(r_q, (uint32_t)tid * 4u, (uint32_t)p * (kWG * 4u) + (uint32_t)c * (uint32_t)N * 4u);
     }
-#if DSRG_EXP & 16
-    // PROTOTYPE, measurement only (round-4 review item 3: "fold mf_update_split_kernel into the head of the next filter launch"):
-    // the least a folded head can do — per pixel ONE pre-combined logit plane per label (21 loads where the update kernel has
-    // 63), the fp64-rounded exp of every label and their label-order sum (the softmax denominator every plane pair of the image
-    // needs).  The result only feeds an empty asm, the separate update kernel still runs: this build times the head's cost
-    // inside the filter workgroup's critical path, nothing else (profiles/r05_filter_ab.txt).
-    {
-        const float *qimg = g_exp_qimg;
-        const int Call = g_exp_C;
-        const rsrc_t r_all = make_rsrc(qimg, sizeof(float) * (size_t)Call * N);
-        float keep = 0.0f;
-#pragma unroll
-        for (int p = 0; p < PPT; p++) {
-            float mx = -INFINITY, sum = 0.0f;
-            for (int c = 0; c < Call; c++) mx = fmaxf(mx, ld_f32(r_all, (uint32_t)tid * 4u, ((uint32_t)p * kWG + (uint32_t)c * (uint32_t)N) * 4u));
-            for (int c = 0; c < Call; c++)
-                sum = sum + exp_cr(ld_f32(r_all, (uint32_t)tid * 4u, ((uint32_t)p * kWG + (uint32_t)c * (uint32_t)N) * 4u) - mx);
-            keep += sum;
-        }
-        asm volatile("" :: "v"(keep));
-    }
-#endif
     const bool norm_pass = SEQ && (opts & kOptNormPass);
     if (norm_pass) {                          // (the loads above hit valid memory — q aliases the norm vector — and are dropped)
 #pragma unroll
@@ -209,11 +168,9 @@ __device__ __forceinline__ void filter_lattice(const LatticeView &L, int li, con
 
     // the lattice's size, flags and extras count are consumed only here, behind the burst: a scalar round trip in front of
     // the first vector load would add its latency to every workgroup's start
-#if !(DSRG_EXP & 8)
     const int M = L.M[li];
     const int lat_flags = L.flags[li];
     const int X = L.nextra[li];              // entries beyond the first of their row
-#endif
     // slots k with k * kWG >= Mlim hold no vertex of this lattice: skipped when the guard is on
     const int Mlim = (opts & kOptSlotGuard) ? M : (VPT * kWG);
     constexpr bool seq = SEQ;                 // kOptSeq arithmetic: its own instantiation (a runtime test cost the
@@ -531,16 +488,10 @@ __device__ __forceinline__ void filter_lattice(const LatticeView &L, int li, con
 // bilateral ones (CPW_B planes of one image: 6 axes, M ~ 2-6 N vertices, the long ones), then the Gaussian ones (CPW_G planes
 // of one image through the lattice all images share: 3 axes), handed out by the hardware dispatcher (a software unit queue
 // was measured and lost, profiles/r02_filter_queue_ab.txt).
-// (DSRG_EXP & 64, measured and not adopted — profiles/r06_filter_ab.txt: the kernel built for TWO workgroups per CU — 64 VGPRs
-// at 1 024 threads, 112 bytes of scratch per lane for the 10-vertex instantiation — so that the 336 one-plane workgroups of a
-// 16-image batch are resident at once instead of 176 plane pairs on 176 CUs)
-#if DSRG_EXP & 64
-#define DSRG_FILTER_BOUNDS __launch_bounds__(kWG, 8)
-#else
-#define DSRG_FILTER_BOUNDS __launch_bounds__(kWG)
-#endif
+// One workgroup per CU: a build for two (64 VGPRs at 1 024 threads, 112 bytes of scratch per lane for the 10-vertex
+// instantiation, one-plane workgroups) was measured and not adopted — profiles/r06_filter_ab.txt.
 template <int CPW_B, int CPW_G, int VPT_B, int PPT, bool SEQ>
-__global__ DSRG_FILTER_BOUNDS void mf_filter_kernel(FilterArgs a) {
+__global__ __launch_bounds__(kWG) void mf_filter_kernel(FilterArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int VPT_G = (VPT_B + 1) / 2;                 // Mcap_gauss = Mcap_bilateral / 2
     unsigned long long *dbg = a.dbg ? a.dbg + (size_t)blockIdx.x * 32 : nullptr;
@@ -558,11 +509,7 @@ __global__ DSRG_FILTER_BOUNDS void mf_filter_kernel(FilterArgs a) {
         vec_t *inq = reinterpret_cast<vec_t *>(smem + a.lds_bytes) - a.N;  // [N] at the end of the region
         const size_t o = ((size_t)b * a.C + c0) * a.N;
         filter_lattice<CPW_B, VPT_B, PPT, 5, SEQ>(a.Lb, b, a.q + o, a.msg_b + o, nc, a.N, val, inq, dbg,
-                                             a.lds_bytes / (int)sizeof(vec_t), a.opts
-#if DSRG_EXP & 16
-                                             , a.q + (size_t)b * a.C * a.N, SEQ ? 1 : a.C
-#endif
-                                             );
+                                             a.lds_bytes / (int)sizeof(vec_t), a.opts);
     } else {
         using vec_t = typename PlaneVec<CPW_G>::type;
         if ((a.opts & kOptLocalGauss) && (a.Lg.flags[0] & kLatticeLocal)) return;   // the update kernel forms this message
@@ -573,11 +520,7 @@ __global__ DSRG_FILTER_BOUNDS void mf_filter_kernel(FilterArgs a) {
         vec_t *inq = reinterpret_cast<vec_t *>(smem + a.lds_bytes) - a.N;
         const size_t o = ((size_t)b * a.C + c0) * a.N;
         filter_lattice<CPW_G, VPT_G, PPT, 2, SEQ>(a.Lg, 0, a.q + o, a.msg_g + o, nc, a.N, val, inq, dbg ? dbg + 16 : nullptr,
-                                             a.lds_bytes / (int)sizeof(vec_t), a.opts
-#if DSRG_EXP & 16
-                                             , a.q + (size_t)b * a.C * a.N, 0
-#endif
-                                             );
+                                             a.lds_bytes / (int)sizeof(vec_t), a.opts);
     }
 }
 #undef DSRG_STAMP
@@ -751,16 +694,11 @@ __global__ __launch_bounds__(kUpdParts * kUpdPix) void mf_update_split_kernel(
 
 // ---------------------------------------------------------------------------------
 void *g_filter_dbg = nullptr;   // set through dsrg_debug_set_filter_trace (tools only)
-// tests / tools: kOpt* bits of the filter launch; -1 = from DSRG_FILTER_OPTS at first use (default: all on)
+// tests / tools (dsrg_debug_set_filter_opts): kOpt* bits of the filter launch; -1 = the default, all on
 std::atomic<int> g_filter_opts{-1};
 static int filter_opts() {
-    int v = g_filter_opts.load(std::memory_order_relaxed);
-    if (v < 0) {                                   // any thread may resolve the default: they all compute the same value
-        const char *e = getenv("DSRG_FILTER_OPTS");
-        v = e ? (atoi(e) & 3) : (kOptLocalGauss | kOptSlotGuard);
-        g_filter_opts.store(v, std::memory_order_relaxed);
-    }
-    return v;
+    const int v = g_filter_opts.load(std::memory_order_relaxed);
+    return v < 0 ? (kOptLocalGauss | kOptSlotGuard) : v;
 }
 
 template <int CPW_B, int CPW_G, int VPT_B, int PPT, bool SEQ>
@@ -825,11 +763,7 @@ static int plan_filter(const LatticeView &Lg, const LatticeView &Lb, const Meanf
     // (with the Gaussian workgroups out of the launch, one-plane bilateral workgroups still make ONE round of MI355X's 256 CUs
     // up to 12 images of 21 labels, and a one-plane workgroup is the shorter one: measured 14.1 / 14.3 us per launch at 8 / 12
     // images against 16.8-17.4 / 16.3-16.5 with plane pairs)
-#if DSRG_EXP & 64
-    const bool one_round_of_single_planes = gauss_local && (filter_opts() & kOptLocalGauss) && (size_t)B * C <= 512;
-#else
     const bool one_round_of_single_planes = gauss_local && (filter_opts() & kOptLocalGauss) && (size_t)B * C <= 256;
-#endif
     // (plane pairs only up to 16 vertices per thread: the 25-vertex instantiation with two planes has no registers left at 1 024
     // threads — 156 bytes of scratch per lane — where the one-plane one has none; maps of 52 .. 53 pixels a side)
     const bool pairs_fit_registers = (Lb.Mcap + kWG - 1) / kWG <= 16;

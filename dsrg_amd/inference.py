@@ -161,11 +161,9 @@ def _crf_in_flight(pairs, device, in_flight, batch):
     sys.setswitchinterval(min(interval, 1e-4))
     # ... and the forwards go to a stream of their own: on the caller's (usually the null) stream they share a hardware queue with one of
     # the CRF workers' streams or not, depending on how many streams the process made before — 178 or 240 images/s from run to run
-    import os
-    fstream = None if os.environ.get("DSRG_TEST_MS_FSTREAM", "1") == "0" else torch.cuda.Stream(device=device)      # 0: tools, A/B
+    fstream = torch.cuda.Stream(device=device)
     try:
-        if fstream is not None:
-            fstream.wait_stream(torch.cuda.current_stream(device))
+        fstream.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(fstream):
             for lab in CRF_device_many(pairs, scale_factor=1.0, want="map", in_flight=in_flight, batch=batch):
                 yield lab.cpu().numpy().astype(np.int64)

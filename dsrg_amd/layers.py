@@ -93,7 +93,6 @@ _MAX_RESIDENT = 64
 _resident = _OrderedDict()               # (address, shape, dtype) -> [epoch of the last full check, {form: digest}, device tensor,
                                          #                              misses, epoch in which WE wrote the blob (or -1)]
 _pinned = _OrderedDict()                 # (address, nbytes) -> [the array (kept alive), sightings, registered?]
-_PIN = _os.environ.get("DSRG_PYLAYERS_PIN", "1") == "1"
 _pending = []                            # downloads of the current layer call: (host array, device tensor, remember?)
 
 # ---- cost accounting (tools/pylayers_route_cost.py): seconds per (layer call, category) while `profile` is a dict
@@ -121,7 +120,7 @@ def _key(a):
 
 def _pin(a):
     """page-lock the memory of a C-contiguous host array in place once it has been seen twice at the same address; -> pinned?"""
-    if not _PIN or a.nbytes < 65536:
+    if a.nbytes < 65536:
         return False
     k = (a.ctypes.data, a.nbytes)
     e = _pinned.get(k)

@@ -18,8 +18,6 @@ import os as _os
 from .backbone import VGG16ASPP, GemmConv2d, _ConvFn, _bf16_run
 from .trainer import CaffeSGD
 
-_IGEMM_BN = _os.environ.get("DSRG_RESNET_IGEMM", "1") == "1"      # tools: A/B against round 5's im2col + library-GEMM bottlenecks
-_MERGED = _os.environ.get("DSRG_RESNET_MERGED_BWD", "1") == "1"   # tools / tests: 0 = data and weight gradient of a bottleneck convolution as two launches
 _FUSE_RES = _os.environ.get("DSRG_RESNET_FUSE_RES", "1") == "1"   # tools / tests: 0 = the shortcut's add + ReLU and its backward as passes of their own
 
 
@@ -135,7 +133,7 @@ class _FoldedIgemmFn(torch.autograd.Function):
         if not ctx.has_res and ctx.res_link is not None:
             shortcut, ctx.res_link.gm = ctx.res_link.gm, None
         gx = None
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _MERGED and conv_igemm_wgrad_launchable(cin, cout, k) and \
+        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and conv_igemm_wgrad_launchable(cin, cout, k) and \
                 x.is_contiguous(memory_format=cl):
             # the whole backward in one grid (the weight gradient's workgroups take the CUs the data gradient's tiles leave idle: a
             # 65 x 65 x 10 map is 166 pixel tiles), the scale on the weight gradient in its reduction, written into the reducer's slot
@@ -225,7 +223,7 @@ def _conv_bn(x, conv, bn, relu, link_in=None, link_out=None, res=None, res_link=
     channel and bias = shift through one im2col + GEMM with the bias (and ReLU) in the epilogue (backbone._ConvFn; 1x1 convolutions
     need no im2col at all) — gamma / beta still train there: their gradients flow through the weight-sized products instead of
     activation-sized reductions.  Anything else (strided convolutions, the CPU): the two layers as they are."""
-    if _IGEMM_BN and x.is_cuda and _bf16_run(x) and _igemm_bn_route(x, conv, bn):
+    if x.is_cuda and _bf16_run(x) and _igemm_bn_route(x, conv, bn):
         scale, shift = bn.frozen_affine()
         return _FoldedIgemmFn.apply(x, conv.weight, scale, shift, conv.dilation[0], relu, link_in, link_out, res, res_link)
     if res is not None:
@@ -253,15 +251,15 @@ class _Bottleneck(nn.Module):
         # c1's and c2's outputs are ReLU outputs with one reader each (c2, c3): on the implicit-GEMM route their ReLU backward is a
         # mask in the store of the reader's data gradient (a _GradLink per pair, as in the VGG chain) instead of a pass of its own
         from .backbone import _GradLink, _FUSE_CHAIN
-        l1, l2 = (_GradLink(), _GradLink()) if (_IGEMM_BN and _FUSE_CHAIN and torch.is_grad_enabled()) else (None, None)
+        l1, l2 = (_GradLink(), _GradLink()) if (_FUSE_CHAIN and torch.is_grad_enabled()) else (None, None)
         routed = lambda t, conv, bn: t.is_cuda and _igemm_bn_route(t, conv, bn)      # noqa: E731
         cl = torch.channels_last
         bf16 = x.is_cuda and _bf16_run(x)
-        r1 = bf16 and _IGEMM_BN and routed(x, self.c1, self.b1)
+        r1 = bf16 and routed(x, self.c1, self.b1)
         # the shortcut: relu(c3(..) + idn) in the store of c3's launch; with an identity shortcut its gradient joins c1's data gradient
         # in that launch's store (rl), and where x is itself such a block output (x._dsrg_plink, set below) the ReLU backward of the
         # block in front rides there too — no add / ReLU / mask / accumulate pass between the blocks, either way
-        fuse = _IGEMM_BN and _FUSE_RES and bf16 and self.c3.stride == (1, 1)
+        fuse = _FUSE_RES and bf16 and self.c3.stride == (1, 1)
         grad = torch.is_grad_enabled()
         rl = _ResLink() if (fuse and grad and _FUSE_CHAIN and self.down is None and r1 and x.dtype == torch.bfloat16) else None
         pin = getattr(x, "_dsrg_plink", None) if rl is not None else None
@@ -281,7 +279,7 @@ class _Bottleneck(nn.Module):
         if rl is not None:
             rl.armed = False                                              # (nobody will leave a gradient there)
         y = _conv_bn(y2, self.c3, self.b3, False, l2 if use2 else None, None)
-        if _IGEMM_BN and y.is_cuda and y.dtype == torch.bfloat16 and idn.dtype == torch.bfloat16 and y.numel() % 8 == 0:
+        if y.is_cuda and y.dtype == torch.bfloat16 and idn.dtype == torch.bfloat16 and y.numel() % 8 == 0:
             return _AddReLUFn.apply(y, idn)                               # one pass each way instead of add + threshold
         return F.relu(y + idn)
 
@@ -368,7 +366,7 @@ class ResNet101DeepLab(nn.Module):
     def forward(self, x):
         f = self.layers(self.stem(x))
         from .ops import conv_igemm_supported
-        if _IGEMM_BN and f.is_cuda and _bf16_run(f) \
+        if f.is_cuda and _bf16_run(f) \
                 and len(self.aspp) <= 4 and 9 * len(self.aspp) * self.aspp[0].out_channels <= 2048 and conv_igemm_supported(f.shape[1], 128, 1) and \
                 f.shape[1] % 256 == 0 and \
                 f.shape[0] * f.shape[2] * f.shape[3] >= 2048 and all(m.kernel_size == (3, 3) and m.padding == m.dilation and m.stride == (1, 1)
@@ -424,7 +422,7 @@ class RetrainTrainer(object):
         net = net.to(device)
         if device.type == "cuda":
             net = net.to(memory_format=torch.channels_last)
-        self.net = self.model = net
+        self.net = net
         self.reducer = None
         # the bias gradients' finishing passes as one launch behind backward: for the VGG backbone, whose nodes hand bias gradients on
         # untouched (the ResNet route's library-GEMM nodes are not checked for that)
@@ -453,7 +451,7 @@ class RetrainTrainer(object):
         self.opt.base_lr = poly_lr(self.base_lr, self.opt.iter, self.max_iter)
         x = images.contiguous(memory_format=torch.channels_last) if self.device.type == "cuda" else images
         with torch.autocast(self.device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None):
-            logits = self.model(x)
+            logits = self.net(x)
         loss = seg_softmax_loss(logits, interp_shrink(label, 8))
         from .ops import deferred_reductions
         with deferred_reductions(self.defer_bias):             # (see DSRGTrainer.step)

@@ -155,19 +155,13 @@ class DSRGTrainer(object):
         if channels_last:
             net = net.to(memory_format=torch.channels_last)
         self.net = net
-        self.model = net
         self.reducer = None
         if (world_size > 1) if ddp is None else ddp:
             # 151.5 MB of fp32 gradients per step; 32 MB buckets -> 5 all-reduces overlapped with backward, the weight-gradient
             # kernels writing straight into the buckets (dsrg_amd/reducer.py; torch's DistributedDataParallel copies every
-            # gradient into its bucket: 47 launches per step, +3.8 % at one rank — DSRG_TORCH_DDP=1 restores it for A/B runs)
-            if os.environ.get("DSRG_TORCH_DDP") == "1":
-                from torch.nn.parallel import DistributedDataParallel as DDP
-                self.model = DDP(net, device_ids=[device.index] if device.type == "cuda" else None, bucket_cap_mb=bucket_cap_mb,
-                                 gradient_as_bucket_view=True)
-            else:
-                from .reducer import BucketedAllReduce
-                self.reducer = BucketedAllReduce(list(net.parameters()), bucket_cap_mb=bucket_cap_mb)
+            # gradient into its bucket: 47 launches per step, +3.8 % at one rank)
+            from .reducer import BucketedAllReduce
+            self.reducer = BucketedAllReduce(list(net.parameters()), bucket_cap_mb=bucket_cap_mb)
         self.opt = CaffeSGD(net.caffe_param_groups())
         self.defer_bias = device.type == "cuda" and os.environ.get("DSRG_DEFER_REDUCTIONS", "1") != "0"      # 0: tools, A/B
         if snapshot is not None:
@@ -235,7 +229,7 @@ class DSRGTrainer(object):
             with torch.cuda.stream(self.side):
                 crf_prepare(images, cues.shape[1], cues.shape[2], cues.shape[3])
         with torch.autocast(self.device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None):
-            logits = self.model(x)
+            logits = self.net(x)
         logits = logits.float().contiguous()
         if self.overlap_build:
             torch.cuda.current_stream().wait_stream(self.side)

@@ -35,7 +35,7 @@ for _ in range(20):
         crf_prepare(im, cu.shape[1], cu.shape[2], cu.shape[3])
     tick("prepare", t); t = time.perf_counter()
     with torch.autocast("cuda", dtype=torch.bfloat16):
-        logits = tr.model(x)
+        logits = tr.net(x)
     logits = logits.float().contiguous()
     tick("forward", t); t = time.perf_counter()
     torch.cuda.current_stream().wait_stream(tr.side)
