@@ -10,8 +10,13 @@
 //   out[m][n] = sum over (cc, tap, c) of  x[pixel(m) + tap offset][cc*64 + c] * w[n][cc][tap][c]
 //
 //   * tile 256 pixels x 256 output channels x 64 reduction elements (one tap of one 64-channel chunk per K-step), 8 waves
-//     (2 across the channels x 4 across the pixels), v_mfma_f32_32x32x16_bf16, product taken transposed (rows = output
-//     channels, columns = pixels) so that a lane ends with runs of four consecutive channels of ONE pixel;
+//     (2 across the channels x 4 across the pixels), product taken transposed (rows = output channels, columns = pixels) so
+//     that a lane ends with runs of four consecutive channels of ONE pixel;
+//   * the forward / data-gradient body multiplies with v_mfma_f32_16x16x32_bf16: a wave's 128 channels x 64 pixels are 8 x 4
+//     blocks of 16 x 16 (128 accumulator registers, as before), a K-step is two 32-deep slices of 32 MFMAs; the four pixel
+//     fragments of a slice are held, the eight channel fragments stream through a ring three fragments ahead of their MFMAs
+//     (igemm_mma_step).  Same FLOPs, LDS bytes and DMA as on 32x32x16, bit-identical results, every layer 2-7 % faster
+//     (profiles/mfma_shape_igemm_probe.txt: the shape is a lever on the clock the chip holds under this load).  The weight-gradient body is still on v_mfma_f32_32x32x16_bf16;
 //   * both operand tiles go global -> LDS by `buffer_load_dwordx4 ... lds` (no staging registers, no ds_write pass): a wave
 //     instruction moves 8 rows of 128 bytes; the per-lane SOURCE offset is free, so the gather of the pixel rows (one
 //     128-byte line per pixel, shifted by the tap's offset) costs one v_add + one v_cndmask per load, and a pixel whose tap
@@ -41,6 +46,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int kBM = 256, kBN = 256;
@@ -50,14 +56,7 @@ constexpr uint32_t kOob = 0x80000000u;                     // beyond any descrip
 constexpr int kRowTab = 8 * kOutWave;                      // cls_tiles: the pixel of each of the tile's 256 rows (int32, -1 = none), behind
 constexpr int kRowTabBytes = kBM * 4;                      // the stages and the epilogue's staging rows
 
-// BK = reduction elements per K-step, NST = LDS stages.  (64, 2): one step in flight behind the one being multiplied;
-// (32, 4): a ring with three steps in flight (counted vmcnt: the DMA of steps s + 1, s + 2 stays in flight across the barrier of
-// step s) — same 128 KB of LDS, deeper prefetch, twice the barriers.
-__device__ __forceinline__ void wait_vm_lgkm_barrier() {
-    // as wait_vm_barrier<0>, and this wave's LDS reads have returned too (the barrier then also says "done reading")
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
+// BK = reduction elements per K-step, NST = LDS stages: (64, 2) — one step in flight behind the one being multiplied.
 template <int BK, int NST> struct ICfg {
     static constexpr int ROW = BK * 2;                     // bytes per LDS row
     static constexpr int CPR = ROW / 16;                   // 16-byte chunks per row (8 / 4)
@@ -148,20 +147,54 @@ template <int N> __device__ __forceinline__ void wait_vm_barrier() {
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
-// (the body is a device function template behind two plain kernels: hipcc 7.2's HOST pass drops the stub of a kernel TEMPLATE
-// whose body calls a lambda that uses the template's constants — no diagnostic, an undefined symbol at load time)
-// EARLY (two stages only): the step's barrier sits in front of its LAST MFMA cluster instead of behind it, and the first
-// fragments of the next step are read (from the other stage, complete and visible once the barrier is passed) before that
-// cluster — so the LDS round trip of a step's first fragments runs under MFMAs instead of holding both waves of a SIMD right
-// behind the barrier.  All fragment reads of the current stage have been issued by then (the last slice is prefetched during
-// the one before) and are waited for in front of the barrier, so the stage is free for the DMA of step s + 2 as before.
-template <int BK, int NST, bool EARLY = false>
+// One 64-deep K-step of a wave's 128 channels x 64 pixels on v_mfma_f32_16x16x32_bf16: 8 x 4 blocks of 16 x 16, two 32-deep slices of
+// 32 MFMAs.  A fragment is one ds_read_b128: lane l reads row l & 15 of a 16-row block, chunk 4 * slice + (l >> 4) through the
+// swizzle (choff[slice], IgemmFrag) — the 16 lanes of each of the instruction's four passes fall on 16 different 16-byte slots of
+// the 256-byte bank line.  The four pixel fragments of a slice are held (those of slice 1 are read under the first
+// four clusters of slice 0); the sixteen channel fragments stream through a ring, kAhead clusters (of 4 MFMAs = 64 cycles) ahead
+// of their use — double-buffering whole slices as the 32x32x16 loop did would take 96 fragment registers beside the 128
+// accumulators.  Order pinned by sched_barrier.  late_issue: called behind the fourth cluster (256 MFMA cycles into the step,
+// where the 32x32x16 loop's first cluster ended) when `late` — the staggered DMA issue of waves 4-7.
+constexpr int kAhead = 3;
+struct IgemmFrag {
+    uint32_t choff[2];
+    __device__ __forceinline__ explicit IgemmFrag(int lane) {
+        using C = ICfg<64, 2>;
+        const int l15 = lane & 15, g4 = lane >> 4;          // (fragment bases are multiples of 16 rows: the swizzle term depends on the lane only)
+#pragma unroll
+        for (int sl = 0; sl < 2; sl++) choff[sl] = (uint32_t)l15 * C::ROW + (uint32_t)(((sl * 4 + g4) ^ C::swz(l15)) << 4);
+    }
+};
+template <class LateIssue>
+__device__ __forceinline__ void igemm_mma_step(const unsigned char *P, const unsigned char *Wt, const IgemmFrag &fr, f32x4 (&acc)[8][4],
+                                               const bool late, LateIssue &&late_issue) {
+    using C = ICfg<64, 2>;
+    constexpr int RING = kAhead + 1;
+    bf16x8 bq[2][4], ar[RING];
+    auto read_w = [&](int u) { return *reinterpret_cast<const bf16x8 *>(Wt + (u & 7) * (16 * C::ROW) + fr.choff[u >> 3]); };
+#pragma unroll
+    for (int j = 0; j < 4; j++) bq[0][j] = *reinterpret_cast<const bf16x8 *>(P + j * (16 * C::ROW) + fr.choff[0]);
+#pragma unroll
+    for (int u = 0; u < kAhead; u++) ar[u] = read_w(u);
+#pragma unroll
+    for (int u = 0; u < 16; u++) {                          // cluster u: channel block u & 7 of slice u >> 3 against the slice's four pixel blocks
+        if (u + kAhead < 16) ar[(u + kAhead) % RING] = read_w(u + kAhead);
+        if (u < 4) bq[1][u] = *reinterpret_cast<const bf16x8 *>(P + u * (16 * C::ROW) + fr.choff[1]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            acc[u & 7][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ar[u % RING], bq[u >> 3][j], acc[u & 7][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (u == 3 && late) late_issue();
+    }
+}
+
 __device__ __forceinline__ void conv_igemm_body(const IgemmArgs &a, const int bid, const int nblk) {      // block bid of nblk (a merged launch passes a sub-range)
-    using C = ICfg<BK, NST>;
+    using C = ICfg<64, 2>;
     extern __shared__ __attribute__((aligned(16))) unsigned char ig_lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, kgrp = lane >> 5;
+    const int l15 = lane & 15, g4 = lane >> 4;
     const int wn = wv >> 2, wm = wv & 3;
 
     // tile of this workgroup: consecutive ids share an XCD (blockIdx % 8) in runs, n-tile fastest.
@@ -313,177 +346,89 @@ __device__ __forceinline__ void conv_igemm_body(const IgemmArgs &a, const int bi
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_void *)(Wt + i * (C::RPI * C::ROW)), 16, wbase[i], s_real * C::ROW, 0, 0);
     };
 
-    f32x16 acc[4][2];
+    f32x4 acc[8][4];
 #pragma unroll
-    for (int i = 0; i < 4; i++)
+    for (int i = 0; i < 8; i++)
 #pragma unroll
-        for (int j = 0; j < 2; j++)
+        for (int j = 0; j < 4; j++)
 #pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+            for (int r = 0; r < 4; r++) acc[i][j][r] = 0.0f;
 
-    // per-lane LDS read offsets: row l31 of a 32-row fragment, chunk (ks*2 + kgrp) ^ swizzle(row); the swizzle term depends on
-    // the lane only (fragment bases are multiples of 32 rows)
-    const int sw = C::swz(l31);
-    const uint32_t rowoff = (uint32_t)l31 * C::ROW;
-    uint32_t choff[C::KS];
-#pragma unroll
-    for (int ks = 0; ks < C::KS; ks++) choff[ks] = rowoff + (uint32_t)(((ks * 2 + kgrp) ^ sw) << 4);
-
+    const IgemmFrag fr(lane);
     // an output-channel count of 128 (mod 256) leaves the upper half of the last n-tile empty: its waves (4-7) only move data
     const bool active = n0 + wn * 128 < a.Cout;
-    constexpr int LPS = 2 * C::IPW;                         // DMA instructions per wave and step
-    if (EARLY) {
-        static_assert(!EARLY || NST == 2, "the early-barrier schedule is written for two stages");
-        bf16x8 af[2][4], bfr[2][2];
-        const bool late = a.stagger && wv >= 4 && active;
-        issue(0, 0);
-        if (nsteps > 1) { issue(1, 1); wait_vm_barrier<LPS>(); } else { wait_vm_barrier<0>(); }
-        if (active) {
-            const unsigned char *P = ig_lds + wm * (64 * C::ROW), *Wt = ig_lds + kBM * C::ROW + wn * (128 * C::ROW);
-#pragma unroll
-            for (int i = 0; i < 4; i++) af[0][i] = *reinterpret_cast<const bf16x8 *>(Wt + i * (32 * C::ROW) + choff[0]);
-#pragma unroll
-            for (int j = 0; j < 2; j++) bfr[0][j] = *reinterpret_cast<const bf16x8 *>(P + j * (32 * C::ROW) + choff[0]);
-        }
+    const bool late = a.stagger && wv >= 4 && active;
+    if (nsteps > 0) issue(0, 0);
+    // (two loops, not one with the multiply under `if (active)`: a loop in which the accumulators reach the back edge by two paths
+    // makes the register allocator copy them around it — this MFMA shape's destination is not tied to its addend)
+    if (!active) {                                          // a wave without output columns: it only moves data
         for (int s = 0; s < nsteps; s++) {
-            const int stage = s & 1;
-            const bool next = s + 1 < nsteps, more = s + 2 < nsteps;
-            if (!active) {                                  // a wave without output columns: it only moves data
-                if (next) { wait_vm_lgkm_barrier(); if (more) issue(stage, s + 2); }
-                continue;
-            }
-            const unsigned char *P = ig_lds + stage * C::STAGE + wm * (64 * C::ROW);
-            const unsigned char *Wt = ig_lds + stage * C::STAGE + kBM * C::ROW + wn * (128 * C::ROW);
-            const unsigned char *Pn = ig_lds + (stage ^ 1) * C::STAGE + wm * (64 * C::ROW);
-            const unsigned char *Wn = ig_lds + (stage ^ 1) * C::STAGE + kBM * C::ROW + wn * (128 * C::ROW);
-#pragma unroll
-            for (int ks = 0; ks < C::KS; ks++) {
-                if (ks + 1 < C::KS) {
-#pragma unroll
-                    for (int i = 0; i < 4; i++) af[(ks + 1) & 1][i] = *reinterpret_cast<const bf16x8 *>(Wt + i * (32 * C::ROW) + choff[ks + 1 < C::KS ? ks + 1 : 0]);
-#pragma unroll
-                    for (int j = 0; j < 2; j++) bfr[(ks + 1) & 1][j] = *reinterpret_cast<const bf16x8 *>(P + j * (32 * C::ROW) + choff[ks + 1 < C::KS ? ks + 1 : 0]);
-                } else if (next) {
-                    wait_vm_lgkm_barrier();                 // step s + 1 has landed for everybody; nobody reads this stage any more
-                    if (more && !late) issue(stage, s + 2);
-#pragma unroll
-                    for (int i = 0; i < 4; i++) af[C::KS & 1][i] = *reinterpret_cast<const bf16x8 *>(Wn + i * (32 * C::ROW) + choff[0]);
-#pragma unroll
-                    for (int j = 0; j < 2; j++) bfr[C::KS & 1][j] = *reinterpret_cast<const bf16x8 *>(Pn + j * (32 * C::ROW) + choff[0]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 2; j++)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks & 1][i], bfr[ks & 1][j], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (ks == C::KS - 1 && more && late) issue(stage, s + 2);
-            }
+            wait_vm_barrier<0>();
+            if (s + 1 < nsteps) issue((s & 1) ^ 1, s + 1);
         }
     } else {
-#pragma unroll
-    for (int p = 0; p < C::AHEAD; p++)
-        if (p < nsteps) issue(p, p);
-    int stage = 0;
-    for (int s = 0; s < nsteps; s++) {        // the steps behind s that are already on their way: min(AHEAD - 1, nsteps - 1 - s)
-        if (C::AHEAD >= 3 && s + 2 < nsteps) wait_vm_barrier<2 * LPS>();
-        else if (C::AHEAD >= 2 && s + 1 < nsteps) wait_vm_barrier<LPS>();
-        else wait_vm_barrier<0>();
-        const bool more = s + C::AHEAD < nsteps, late = a.stagger && wv >= 4 && active;
-        const int nstage = stage == 0 ? NST - 1 : stage - 1;                                  // the stage step s - 1 was read from
-        if (more && !late) issue(nstage, s + C::AHEAD);
-        if (active) {
-        const unsigned char *P = ig_lds + stage * C::STAGE + wm * (64 * C::ROW);
-        const unsigned char *Wt = ig_lds + stage * C::STAGE + kBM * C::ROW + wn * (128 * C::ROW);
-        // fragments of k-slice ks + 1 are read before the MFMAs of slice ks (order pinned by sched_barrier)
-        bf16x8 af[2][4], bfr[2][2];
-#pragma unroll
-        for (int i = 0; i < 4; i++) af[0][i] = *reinterpret_cast<const bf16x8 *>(Wt + i * (32 * C::ROW) + choff[0]);
-#pragma unroll
-        for (int j = 0; j < 2; j++) bfr[0][j] = *reinterpret_cast<const bf16x8 *>(P + j * (32 * C::ROW) + choff[0]);
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ks++) {
-            if (ks + 1 < C::KS) {
-#pragma unroll
-                for (int i = 0; i < 4; i++) af[(ks + 1) & 1][i] = *reinterpret_cast<const bf16x8 *>(Wt + i * (32 * C::ROW) + choff[(ks + 1) % C::KS]);
-#pragma unroll
-                for (int j = 0; j < 2; j++) bfr[(ks + 1) & 1][j] = *reinterpret_cast<const bf16x8 *>(P + j * (32 * C::ROW) + choff[(ks + 1) % C::KS]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks & 1][i], bfr[ks & 1][j], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks == 0 && more && late) issue(nstage, s + C::AHEAD);
+        for (int s = 0; s < nsteps; s++) {
+            const int stage = s & 1;
+            wait_vm_barrier<0>();
+            const bool more = s + 1 < nsteps;
+            if (more && !late) issue(stage ^ 1, s + 1);
+            igemm_mma_step(ig_lds + stage * C::STAGE + wm * (64 * C::ROW), ig_lds + stage * C::STAGE + kBM * C::ROW + wn * (128 * C::ROW), fr, acc,
+                           more && late, [&]() { issue(stage ^ 1, s + 1); });
         }
-        }
-        stage = stage + 1 == NST ? 0 : stage + 1;
-    }
     }
     __syncthreads();                                        // every wave is done reading the last stage
     if (!active) return;
 
-    // ---- epilogue: C[row = channel][col = pixel]; a lane holds channels (reg & 3) + 8 (reg >> 2) + 4 kgrp of pixel l31
+    // ---- epilogue: C[row = channel][col = pixel]; a lane holds channels 16 i + 4 g4 + reg of pixel 16 j + l15 in acc[i][j][reg]
     unsigned char *O = ig_lds + wv * kOutWave;
     const int nw = n0 + wn * 128;
     if (a.out_f32) {
-        // float32 result straight from the accumulators: 16 bytes per lane and (i, q, j) — 32-byte runs per pixel row (the layer-level
-        // prototype of the split mode; a production epilogue would stage through LDS as the bf16 one does)
+        // float32 result straight from the accumulators: 16 bytes per lane and (i, j) (the layer-level prototype of the split mode; a
+        // production epilogue would stage through LDS as the bf16 one does)
         float *y32 = reinterpret_cast<float *>(G.y);
         const float floor32 = a.relu ? 0.0f : -__builtin_inff();
 #pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int m = row_pixel(wm * 64 + j * 32 + l31);
+        for (int j = 0; j < 4; j++) {
+            const int m = row_pixel(wm * 64 + j * 16 + l15);
 #pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int n = nw + i * 32 + q * 8 + kgrp * 4;
-                    float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (G.bias) b4 = *reinterpret_cast<const float4 *>(G.bias + n);
-                    const float4 v = make_float4(fmaxf(acc[i][j][q * 4 + 0] + b4.x, floor32), fmaxf(acc[i][j][q * 4 + 1] + b4.y, floor32),
-                                                 fmaxf(acc[i][j][q * 4 + 2] + b4.z, floor32), fmaxf(acc[i][j][q * 4 + 3] + b4.w, floor32));
-                    if (m >= 0) *reinterpret_cast<float4 *>(y32 + (size_t)m * a.Cout + n) = v;
-                }
+            for (int i = 0; i < 8; i++) {
+                const int n = nw + i * 16 + g4 * 4;
+                float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (G.bias) b4 = *reinterpret_cast<const float4 *>(G.bias + n);
+                const float4 v = make_float4(fmaxf(acc[i][j][0] + b4.x, floor32), fmaxf(acc[i][j][1] + b4.y, floor32),
+                                             fmaxf(acc[i][j][2] + b4.z, floor32), fmaxf(acc[i][j][3] + b4.w, floor32));
+                if (m >= 0) *reinterpret_cast<float4 *>(y32 + (size_t)m * a.Cout + n) = v;
+            }
         }
         return;
     }
     const rsrc_t rb = make_rsrc(G.bias, G.bias ? (size_t)a.Cout * 4 : 0);      // no bias: every load is out of range = 0
     const float floor_ = (a.relu && !G.res) ? 0.0f : -__builtin_inff();        // ReLU without a branch per value (behind the residual, if any)
     const uint32_t seed_g = a.seed_lo + (uint32_t)grp * 0x9E3779B9u;              // every branch its own stream
-    float bias_r[4][4][4];
+    float bias_r[8][4];
 #pragma unroll
-    for (int i = 0; i < 4; i++)
+    for (int i = 0; i < 8; i++)
 #pragma unroll
-        for (int q = 0; q < 4; q++)
+        for (int e = 0; e < 4; e++) bias_r[i][e] = ld_f32(rb, (uint32_t)(nw + i * 16 + g4 * 4 + e) * 4u);
 #pragma unroll
-            for (int e = 0; e < 4; e++)
-                bias_r[i][q][e] = ld_f32(rb, (uint32_t)(nw + i * 32 + q * 8 + kgrp * 4 + e) * 4u);
+    for (int i = 0; i < 8; i++) {
+        const int nl = i * 16 + g4 * 4;
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int nl = i * 32 + q * 8 + kgrp * 4;
-            const float4 b4 = make_float4(bias_r[i][q][0], bias_r[i][q][1], bias_r[i][q][2], bias_r[i][q][3]);
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                float v0 = acc[i][j][q * 4 + 0] + b4.x, v1 = acc[i][j][q * 4 + 1] + b4.y;
-                float v2 = acc[i][j][q * 4 + 2] + b4.z, v3 = acc[i][j][q * 4 + 3] + b4.w;
-                v0 = fmaxf(v0, floor_) * a.out_scale; v1 = fmaxf(v1, floor_) * a.out_scale;
-                v2 = fmaxf(v2, floor_) * a.out_scale; v3 = fmaxf(v3, floor_) * a.out_scale;
-                if (a.drop_thresh) {                                             // uniform
-                    const uint32_t m = cls ? (uint32_t)rowpix[wm * 64 + j * 32 + l31] : (uint32_t)(m0 + wm * 64 + j * 32 + l31);
-                    const uint32_t h = dropout_bytes((m * (uint32_t)a.Cout + (uint32_t)(nw + nl)) >> 2, seed_g, a.seed_hi);
-                    v0 = (h & 0xffu) >= a.drop_thresh ? v0 * a.drop_scale : 0.0f;
-                    v1 = ((h >> 8) & 0xffu) >= a.drop_thresh ? v1 * a.drop_scale : 0.0f;
-                    v2 = ((h >> 16) & 0xffu) >= a.drop_thresh ? v2 * a.drop_scale : 0.0f;
-                    v3 = (h >> 24) >= a.drop_thresh ? v3 * a.drop_scale : 0.0f;
-                }
-                *reinterpret_cast<uint2 *>(O + (j * 32 + l31) * kOutRow + nl * 2) = make_uint2(pack2(v0, v1), pack2(v2, v3));
+        for (int j = 0; j < 4; j++) {
+            float v0 = acc[i][j][0] + bias_r[i][0], v1 = acc[i][j][1] + bias_r[i][1];
+            float v2 = acc[i][j][2] + bias_r[i][2], v3 = acc[i][j][3] + bias_r[i][3];
+            v0 = fmaxf(v0, floor_) * a.out_scale; v1 = fmaxf(v1, floor_) * a.out_scale;
+            v2 = fmaxf(v2, floor_) * a.out_scale; v3 = fmaxf(v3, floor_) * a.out_scale;
+            if (a.drop_thresh) {                                             // uniform
+                const uint32_t m = cls ? (uint32_t)rowpix[wm * 64 + j * 16 + l15] : (uint32_t)(m0 + wm * 64 + j * 16 + l15);
+                const uint32_t h = dropout_bytes((m * (uint32_t)a.Cout + (uint32_t)(nw + nl)) >> 2, seed_g, a.seed_hi);
+                v0 = (h & 0xffu) >= a.drop_thresh ? v0 * a.drop_scale : 0.0f;
+                v1 = ((h >> 8) & 0xffu) >= a.drop_thresh ? v1 * a.drop_scale : 0.0f;
+                v2 = ((h >> 16) & 0xffu) >= a.drop_thresh ? v2 * a.drop_scale : 0.0f;
+                v3 = (h >> 24) >= a.drop_thresh ? v3 * a.drop_scale : 0.0f;
             }
+            // (a 16-lane group of this 8-byte store: 16 pixel rows of 68 dwords, two per bank pair — 2-way, as the 32x32x16 mapping was)
+            *reinterpret_cast<uint2 *>(O + (j * 16 + l15) * kOutRow + nl * 2) = make_uint2(pack2(v0, v1), pack2(v2, v3));
         }
     }
     // the wave reads back its own rows only: LDS operations of one wave complete in order
@@ -591,9 +536,7 @@ __device__ __forceinline__ void conv_igemm_body(const IgemmArgs &a, const int bi
 }
 
 
-__global__ __launch_bounds__(512, 2) void conv_igemm_kernel_64x2(IgemmArgs a) { conv_igemm_body<64, 2>(a, (int)blockIdx.x, (int)gridDim.x); }
-__global__ __launch_bounds__(512, 2) void conv_igemm_kernel_64x2e(IgemmArgs a) { conv_igemm_body<64, 2, true>(a, (int)blockIdx.x, (int)gridDim.x); }
-__global__ __launch_bounds__(512, 2) void conv_igemm_kernel_32x4(IgemmArgs a) { conv_igemm_body<32, 4>(a, (int)blockIdx.x, (int)gridDim.x); }
+__global__ __launch_bounds__(512, 2) void conv_igemm_kernel_64x2(IgemmArgs a) { conv_igemm_body(a, (int)blockIdx.x, (int)gridDim.x); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // The same convolution with the K-steps of ALL tiles dealt out evenly ("stream-K"): the 41x41 layers have 212 tiles of 72
@@ -623,7 +566,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_sk_kernel(IgemmSkArgs k) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ig_lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, kgrp = lane >> 5;
+    const int l15 = lane & 15, g4 = lane >> 4;
     const int wn = wv >> 2, wm = wv & 3;
     int unit;
     {
@@ -637,11 +580,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_sk_kernel(IgemmSkArgs k) {
     const long long total_steps = (long long)k.tiles_total * nsteps;
     auto unit_start = [&](int u) { return (long long)u * total_steps / k.units; };
     const long long g1 = unit_start(unit + 1);
-    const int sw = C::swz(l31);
-    const uint32_t rowoff = (uint32_t)l31 * C::ROW;
-    uint32_t choff[C::KS];
-#pragma unroll
-    for (int ks = 0; ks < C::KS; ks++) choff[ks] = rowoff + (uint32_t)(((ks * 2 + kgrp) ^ sw) << 4);
+    const IgemmFrag fr(lane);
     const rsrc_t rws = make_rsrc(k.ws, (size_t)k.units * 32 * 512 * 16);
     const float floor_ = a.relu ? 0.0f : -__builtin_inff();
 
@@ -707,46 +646,28 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_sk_kernel(IgemmSkArgs k) {
                                                          (uint32_t)s * C::ROW + (uint32_t)(i * C::RPI * ktot * 2), 0, 0);
         };
 
-        f32x16 acc[4][2];
+        f32x4 acc[8][4];
 #pragma unroll
-        for (int i = 0; i < 4; i++)
+        for (int i = 0; i < 8; i++)
 #pragma unroll
-            for (int j = 0; j < 2; j++)
+            for (int j = 0; j < 4; j++)
 #pragma unroll
-                for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
+                for (int r = 0; r < 4; r++) acc[i][j][r] = 0.0f;
 
         issue(0, sb);
-        for (int s = sb; s < se; s++) {
-            const int stage = (s - sb) & 1;
-            wait_vm_barrier<0>();
-            const bool more = s + 1 < se, late = wv >= 4 && active;
-            if (more && !late) issue(stage ^ 1, s + 1);
-            if (active) {
-                const unsigned char *P = ig_lds + stage * C::STAGE + wm * (64 * C::ROW);
-                const unsigned char *Wt = ig_lds + stage * C::STAGE + kBM * C::ROW + wn * (128 * C::ROW);
-                // fragments of k-slice ks + 1 are read before the MFMAs of slice ks (order pinned by sched_barrier)
-                bf16x8 af[2][4], bfr[2][2];
-#pragma unroll
-                for (int i = 0; i < 4; i++) af[0][i] = *reinterpret_cast<const bf16x8 *>(Wt + i * (32 * C::ROW) + choff[0]);
-#pragma unroll
-                for (int j = 0; j < 2; j++) bfr[0][j] = *reinterpret_cast<const bf16x8 *>(P + j * (32 * C::ROW) + choff[0]);
-#pragma unroll
-                for (int ks = 0; ks < C::KS; ks++) {
-                    if (ks + 1 < C::KS) {
-#pragma unroll
-                        for (int i = 0; i < 4; i++) af[(ks + 1) & 1][i] = *reinterpret_cast<const bf16x8 *>(Wt + i * (32 * C::ROW) + choff[(ks + 1) % C::KS]);
-#pragma unroll
-                        for (int j = 0; j < 2; j++) bfr[(ks + 1) & 1][j] = *reinterpret_cast<const bf16x8 *>(P + j * (32 * C::ROW) + choff[(ks + 1) % C::KS]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < 4; i++)
-#pragma unroll
-                        for (int j = 0; j < 2; j++)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks & 1][i], bfr[ks & 1][j], acc[i][j], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (ks == 0 && more && late) issue(stage ^ 1, s + 1);
-                }
+        if (!active) {                                      // (two loops: see conv_igemm_body)
+            for (int s = sb; s < se; s++) {
+                wait_vm_barrier<0>();
+                if (s + 1 < se) issue(((s - sb) & 1) ^ 1, s + 1);
+            }
+        } else {
+            for (int s = sb; s < se; s++) {
+                const int stage = (s - sb) & 1;
+                wait_vm_barrier<0>();
+                const bool more = s + 1 < se, late = wv >= 4;
+                if (more && !late) issue(stage ^ 1, s + 1);
+                igemm_mma_step(ig_lds + stage * C::STAGE + wm * (64 * C::ROW), ig_lds + stage * C::STAGE + kBM * C::ROW + wn * (128 * C::ROW), fr, acc,
+                               more && late, [&]() { issue(stage ^ 1, s + 1); });
             }
         }
         __syncthreads();                                    // every wave is done reading the last stage
@@ -755,16 +676,13 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_sk_kernel(IgemmSkArgs k) {
             // ---- my first segment continues a tile an earlier workgroup starts: publish the accumulators (write-through), flag
             if (active) {
 #pragma unroll
-                for (int i = 0; i < 4; i++)
+                for (int i = 0; i < 8; i++)
 #pragma unroll
-                    for (int j = 0; j < 2; j++)
-#pragma unroll
-                        for (int q = 0; q < 4; q++) {
-                            f32x4v v = {__float_as_uint(acc[i][j][q * 4 + 0]), __float_as_uint(acc[i][j][q * 4 + 1]),
-                                        __float_as_uint(acc[i][j][q * 4 + 2]), __float_as_uint(acc[i][j][q * 4 + 3])};
-                            __builtin_amdgcn_raw_buffer_store_b128(v, rws, (uint32_t)(((i * 2 + j) * 4 + q) * 512 + tid) * 16u,
-                                                                   (uint32_t)unit * (32u * 512u * 16u), 16);      // aux 16 = sc1
-                        }
+                    for (int j = 0; j < 4; j++) {
+                        f32x4v v = {__float_as_uint(acc[i][j][0]), __float_as_uint(acc[i][j][1]), __float_as_uint(acc[i][j][2]), __float_as_uint(acc[i][j][3])};
+                        __builtin_amdgcn_raw_buffer_store_b128(v, rws, (uint32_t)((i * 4 + j) * 512 + tid) * 16u,
+                                                               (uint32_t)unit * (32u * 512u * 16u), 16);      // aux 16 = sc1
+                    }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         // every storing wave drains
             __syncthreads();
@@ -810,22 +728,22 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_sk_kernel(IgemmSkArgs k) {
                 f32x4v shares[2][kSkParts];
                 float bq[2][4];
                 auto fetch = [&](int gi, f32x4v (&dst)[kSkParts], float (&bias4)[4]) {
-                    const int i = gi >> 3, q = (gi >> 1) & 3, j = gi & 1;
-                    const uint32_t off = (uint32_t)(((i * 2 + j) * 4 + q) * 512 + tid) * 16u;
+                    const int i = gi >> 2;                  // group gi = accumulator block (i, j) = (gi >> 2, gi & 3), as published above
+                    const uint32_t off = (uint32_t)(gi * 512 + tid) * 16u;
 #pragma unroll
                     for (int p = 0; p < kSkParts; p++)
                         dst[p] = __builtin_amdgcn_raw_buffer_load_b128(rws, p < nparts ? off : kOob, (uint32_t)(unit + 1 + p) * (32u * 512u * 16u), 0);
 #pragma unroll
-                    for (int e = 0; e < 4; e++) bias4[e] = ld_f32(rb, (uint32_t)(nw + i * 32 + q * 8 + kgrp * 4 + e) * 4u);
+                    for (int e = 0; e < 4; e++) bias4[e] = ld_f32(rb, (uint32_t)(nw + i * 16 + g4 * 4 + e) * 4u);
                 };
                 fetch(0, shares[0], bq[0]);
 #pragma unroll
                 for (int gi = 0; gi < 32; gi++) {
-                    const int i = gi >> 3, q = (gi >> 1) & 3, j = gi & 1;
+                    const int i = gi >> 2, j = gi & 3;
                     if (gi + 1 < 32) fetch(gi + 1, shares[(gi + 1) & 1], bq[(gi + 1) & 1]);
                     __builtin_amdgcn_sched_barrier(0);
-                    const int nl = i * 32 + q * 8 + kgrp * 4;
-                    float s0 = acc[i][j][q * 4 + 0], s1 = acc[i][j][q * 4 + 1], s2 = acc[i][j][q * 4 + 2], s3 = acc[i][j][q * 4 + 3];
+                    const int nl = i * 16 + g4 * 4;
+                    float s0 = acc[i][j][0], s1 = acc[i][j][1], s2 = acc[i][j][2], s3 = acc[i][j][3];
 #pragma unroll
                     for (int p = 0; p < kSkParts; p++) {
                         const f32x4v pv = shares[gi & 1][p];
@@ -834,14 +752,14 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_sk_kernel(IgemmSkArgs k) {
                     float v0 = s0 + bq[gi & 1][0], v1 = s1 + bq[gi & 1][1], v2 = s2 + bq[gi & 1][2], v3 = s3 + bq[gi & 1][3];
                     v0 = fmaxf(v0, floor_) + poison; v1 = fmaxf(v1, floor_) + poison; v2 = fmaxf(v2, floor_) + poison; v3 = fmaxf(v3, floor_) + poison;
                     if (a.drop_thresh) {
-                        const uint32_t m = (uint32_t)(m0 + wm * 64 + j * 32 + l31);
+                        const uint32_t m = (uint32_t)(m0 + wm * 64 + j * 16 + l15);
                         const uint32_t h = dropout_bytes((m * (uint32_t)a.Cout + (uint32_t)(nw + nl)) >> 2, seed_g, a.seed_hi);
                         v0 = (h & 0xffu) >= a.drop_thresh ? v0 * a.drop_scale : 0.0f;
                         v1 = ((h >> 8) & 0xffu) >= a.drop_thresh ? v1 * a.drop_scale : 0.0f;
                         v2 = ((h >> 16) & 0xffu) >= a.drop_thresh ? v2 * a.drop_scale : 0.0f;
                         v3 = (h >> 24) >= a.drop_thresh ? v3 * a.drop_scale : 0.0f;
                     }
-                    *reinterpret_cast<uint2 *>(O + (j * 32 + l31) * kOutRow + nl * 2) = make_uint2(pack2(v0, v1), pack2(v2, v3));
+                    *reinterpret_cast<uint2 *>(O + (j * 16 + l15) * kOutRow + nl * 2) = make_uint2(pack2(v0, v1), pack2(v2, v3));
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll 4
@@ -1141,12 +1059,12 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_bwd_kernel(IgemmBwdArgs a) 
         if (id < a.nw_pad) {
             if (id < a.nw) conv_igemm_wgrad_body(a.w, id, a.nw);
         } else if (id - a.nw_pad < a.nd) {
-            conv_igemm_body<64, 2>(a.d, id - a.nw_pad, a.nd);
+            conv_igemm_body(a.d, id - a.nw_pad, a.nd);
         }
         return;
     }
     if (id < a.nd_pad) {
-        if (id < a.nd) conv_igemm_body<64, 2>(a.d, id, a.nd);
+        if (id < a.nd) conv_igemm_body(a.d, id, a.nd);
     } else {
         conv_igemm_wgrad_body(a.w, id - a.nd_pad, a.nw);
     }
@@ -1243,7 +1161,7 @@ static bool conv_igemm_launchable(int cin, int cout, int k) {
 std::atomic<int> g_igemm_variant{-1};      // dsrg_debug_set_igemm_variant (tests / tools); -1 = the default, 3
 static int igemm_variant() {
     const int v = g_igemm_variant.load(std::memory_order_relaxed);
-    return v < 0 ? 3 : v;
+    return (v < 0 || v == 2 || v == 5) ? 3 : v;      // (2, 5: retired experiments — a ring of four 32-deep stages, an early barrier — now the default)
 }
 
 static int igemm_cus() {
@@ -1429,8 +1347,7 @@ int launch_conv_igemm(const void *const *x, const void *const *w, const float *c
     if (a.drop_thresh > 255) a.drop_thresh = 255;
     a.drop_scale = 256.0f / (float)(256 - (int)a.drop_thresh);
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-    static LdsGrant grant[3];
-    const int variant = igemm_variant() == 2 ? 1 : 0;       // 1, 3: two stages of 64; 2: ring of four stages of 32
+    static LdsGrant grant[2];
     a.stagger = igemm_variant() >= 3;
     const bool default_form = igemm_variant() == 3 || igemm_variant() == 8 || igemm_variant() == 9;      // (8 / 9: 3 with one tiling forced)
     const dim3 block(512);
@@ -1451,7 +1368,7 @@ int launch_conv_igemm(const void *const *x, const void *const *w, const float *c
         sk.units = units;
         sk.tiles_total = tiles_total;
         constexpr size_t lds = ICfg<64, 2>::LDS;
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_sk_kernel), lds, grant[2])) return rc;
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_sk_kernel), lds, grant[1])) return rc;
         DSRG_HIP_CHECK(hipMemsetAsync(sk.flags, 0, sizeof(uint32_t) * ((size_t)units + 1), stream));      // every launch (a graph replays it)
         hipLaunchKernelGGL(conv_igemm_sk_kernel, dim3(units), block, lds, stream, sk);
         DSRG_LAUNCH_CHECK();
@@ -1513,20 +1430,9 @@ int launch_conv_igemm(const void *const *x, const void *const *w, const float *c
         *t_prep_grid = (int)grid.x;
         return DSRG_OK;
     }
-    if (igemm_variant() == 5) {                              // early barrier (see conv_igemm_body)
-        static LdsGrant grant_e;
-        constexpr size_t lds = ICfg<64, 2>::LDS;
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_kernel_64x2e), lds, grant_e)) return rc;
-        hipLaunchKernelGGL(conv_igemm_kernel_64x2e, grid, block, lds, stream, a);
-    } else if (variant == 0) {
-        constexpr size_t lds = ICfg<64, 2>::LDS;
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_kernel_64x2), lds, grant[0])) return rc;
-        hipLaunchKernelGGL(conv_igemm_kernel_64x2, grid, block, lds, stream, a);
-    } else {
-        constexpr size_t lds = ICfg<32, 4>::LDS;
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_kernel_32x4), lds, grant[1])) return rc;
-        hipLaunchKernelGGL(conv_igemm_kernel_32x4, grid, block, lds, stream, a);
-    }
+    constexpr size_t lds = ICfg<64, 2>::LDS;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_kernel_64x2), lds, grant[0])) return rc;
+    hipLaunchKernelGGL(conv_igemm_kernel_64x2, grid, block, lds, stream, a);
     DSRG_LAUNCH_CHECK();
     if (colsum) {
         const float *parts[4];

@@ -814,8 +814,9 @@ def conv_igemm_supported(cin, cout, k):
 
 
 def set_igemm_variant(v):
-    """tests / tools: the launch form of the implicit-GEMM kernels: 1 = two LDS stages of 64, 2 = ring of four stages of 32, 3 = 1 +
-    staggered DMA issue + stream-K where it wins (the default), 4 = stream-K wherever legal, 5 = early barrier, 6 = round 4's launches
+    """tests / tools: the launch form of the implicit-GEMM kernels: 1 = two LDS stages of 64, 3 = 1 +
+    staggered DMA issue + stream-K where it wins (the default), 4 = stream-K wherever legal, 2 / 5 = retired experiments (a ring of four
+    stages of 32, an early barrier): they run the default, 6 = round 4's launches
     (every K-step multiplied, flat tile maps), 7 = 3 with the weight gradient skipping dead steps of the flat pixel order instead of
     summing over each tap's live pixels; -1 = the default.  Same results (6 / 7 / 3: forward bit-identical;
     weight gradient bit-identical between 6 and 7, equal up to fp32 reassociation for 3)"""

@@ -4,10 +4,13 @@ hipBLASLt GEMM with fused bias / ReLU, solutions picked by TunableOp) for the wi
 Prints one line per layer: microseconds (median of the rounds; variants interleaved inside every round) and TFLOP/s.
 
   python tools/igemm_probe.py [--rounds 5] [--iters 10] [--batch 16]
+  python tools/igemm_probe.py --ab A B [--rounds 7]     two debug variants (ops.set_igemm_variant; -1 = the default) of the layer table,
+                                                        interleaved in every round (after --warm seconds of both): every round's time, each arm's spread, the summed table
 """
 import argparse
 import os
 import sys
+import time
 
 os.environ.setdefault("PYTORCH_TUNABLEOP_ENABLED", "1")
 os.environ.setdefault("PYTORCH_TUNABLEOP_FILENAME", "/tmp/dsrg_tunableop_probe.csv")
@@ -39,6 +42,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--ab", type=int, nargs=2, metavar=("A", "B"), default=None)
+    ap.add_argument("--warm", type=float, default=1.0, help="--ab: seconds of alternating launches per layer before the timed rounds")
     args = ap.parse_args()
     B = args.batch
     layers = [  # name, H, W, cin, cout, k, dilations (len = groups)
@@ -55,6 +60,8 @@ def main():
         ("conv3_2 256->256 81x81", 81, 81, 256, 256, 3, [1]),
         ("conv3_1 128->256 81x81", 81, 81, 128, 256, 3, [1]),
     ]
+    if args.ab:
+        return variant_ab(layers, B, args.ab, args.rounds, args.iters, args.warm)
     print("%-28s %9s %9s %9s %9s | %8s %8s | %s" % ("layer", "variant", "default", "im2col+mm", "mm only", "TF/s ig", "TF/s old", "max err"))
     for name, H, W, cin, cout, k, dils in layers:
         n = len(dils)
@@ -108,6 +115,54 @@ def main():
             flops / med["old"] / 1e6, err), flush=True)
     wgrad_probe(B, args.rounds, args.iters)
     absorb_probe(B, args.rounds, args.iters)
+
+
+def variant_ab(layers, B, ab, rounds, iters, warm_s):
+    """two variants of every layer of the table on random operands, alternating inside every round (A B A B ..), stream-K where the
+    launcher picks it (as the train step runs them).  Per layer: every round of both arms, medians, max - min of each arm; then the
+    table summed per round — the figure a decision between the two is taken on: the gain of the summed medians against twice the
+    spread of arm A's own rounds"""
+    arms = ("A = variant %d" % ab[0], "B = variant %d" % ab[1])
+    print("%s, %s; batch %d, %.1f s of warm-up per layer, %d rounds of %d launches each; microseconds per launch" % (arms + (B, warm_s, rounds, iters)))
+    tot = np.zeros((2, rounds))
+    for name, H, W, cin, cout, k, dils in layers:
+        n = len(dils)
+        torch.manual_seed(1)
+        xs = [torch.randn(B, cin, H, W, device="cuda").bfloat16().contiguous(memory_format=CL) for _ in range(n)]
+        packed = [ops.pack_conv_weight((torch.randn(cout, cin, k, k, device="cuda") * (2.0 / (cin * k * k)) ** 0.5).bfloat16()) for _ in range(n)]
+        bs = [torch.randn(cout, device="cuda") for _ in range(n)]
+
+        def run():
+            return ops.conv_igemm(xs, packed, bs, dils, k, True, stream_k=True)
+        t = np.zeros((2, rounds))
+        try:
+            outs = []
+            for v in ab:
+                ops.set_igemm_variant(v)
+                for _ in range(3):
+                    outs.append(run())
+            torch.cuda.synchronize()
+            diff = max(float((a_.float() - b_.float()).abs().max()) for a_, b_ in zip(outs[0], outs[-1]))
+            t0 = time.time()
+            while time.time() - t0 < warm_s:              # to the clock the chip holds under this load: the first milliseconds run faster
+                for v in ab:
+                    ops.set_igemm_variant(v)
+                    timed(run, iters)
+            for r in range(rounds):
+                for i, v in enumerate(ab):
+                    ops.set_igemm_variant(v)
+                    t[i, r] = timed(run, iters)
+        finally:
+            ops.set_igemm_variant(-1)
+        tot += t
+        med = np.median(t, axis=1)
+        print("%-28s A %s | med %7.1f spread %5.1f" % (name, " ".join("%7.1f" % v for v in t[0]), med[0], t[0].max() - t[0].min()))
+        print("%-28s B %s | med %7.1f spread %5.1f | B/A %.4f  max |A - B| %.3g" % ("", " ".join("%7.1f" % v for v in t[1]), med[1], t[1].max() - t[1].min(),
+                                                                                  med[1] / med[0], diff), flush=True)
+    med = np.median(tot, axis=1)
+    print("%-28s A %s | med %7.1f spread %5.1f" % ("sum of the table", " ".join("%7.1f" % v for v in tot[0]), med[0], tot[0].max() - tot[0].min()))
+    print("%-28s B %s | med %7.1f spread %5.1f | B/A %.4f" % ("", " ".join("%7.1f" % v for v in tot[1]), med[1], tot[1].max() - tot[1].min(), med[1] / med[0]))
+    print("gain of the summed medians %.1f us; twice the spread of A's rounds %.1f us" % (med[0] - med[1], 2.0 * (tot[0].max() - tot[0].min())))
 
 
 def absorb_probe(B, rounds, iters):
