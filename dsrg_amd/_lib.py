@@ -84,6 +84,10 @@ SIGNATURES = {
     "dsrg_confusion_matrix": (_i, [_sz, _vp, _vp, _i, _i, _vp, _vp]),
     "dsrg_multiscale_unary": (_i, [_i, _i, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _i, _i,
                                    _f, _vp, _vp, _vp, _vp]),
+    "dsrg_multiscale_unary_batch": (_i, [_i, _i, _i, ctypes.POINTER(_vp)] + [ctypes.POINTER(ctypes.c_int32)] * 4 +
+                                    [_f, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
+    "dsrg_preprocess_ms_batch": (_i, [_i, _i, _i, ctypes.POINTER(_vp)] + [ctypes.POINTER(ctypes.c_int32)] * 3 +
+                                 [ctypes.POINTER(_f), ctypes.POINTER(_vp), _vp]),
     "dsrg_im2col3x3_nhwc16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "dsrg_relu_bwd_bias_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, ctypes.c_long, _i, ctypes.c_float, _vp]),
     "dsrg_col2im3x3_nhwc_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -495,6 +495,18 @@ extern "C" int dsrg_multiscale_unary(int K, int C, const float *const *scores, c
     // every argument is checked before the first device call
     return launch_multiscale_unary(K, C, scores, h, w, H, W, eps, unary, amax, sum, static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_multiscale_unary_batch(int G, int K, int C, const float *const *scores, const int32_t *h, const int32_t *w,
+                                           const int32_t *H, const int32_t *W, float eps, float *const *unary,
+                                           int32_t *const *amax, float *const *sum, void *stream) {
+    // every argument is checked before the first device call
+    return launch_multiscale_unary_batch(G, K, C, scores, h, w, H, W, eps, unary, amax, sum, static_cast<hipStream_t>(stream));
+}
+extern "C" int dsrg_preprocess_ms_batch(int G, int capacity, int K, const unsigned char *const *images, const int32_t *H,
+                                        const int32_t *W, const int32_t *sizes, const float *mean, float *const *out,
+                                        void *stream) {
+    // every argument is checked before the first device call
+    return launch_preprocess_ms_batch(G, capacity, K, images, H, W, sizes, mean, out, static_cast<hipStream_t>(stream));
+}
 extern "C" int dsrg_im2col3x3_nhwc16(const void *in, void *out, int B, int H, int W, int C, int dilation, void *stream) {
     if (!in || !out || B < 1 || H < 1 || W < 1 || C < 1 || dilation < 1) return set_error(DSRG_ERR_INVALID, "bad argument");
     return launch_im2col3x3(in, out, B, H, W, C, dilation, static_cast<hipStream_t>(stream));

@@ -223,6 +223,11 @@ int launch_confusion(size_t n, const unsigned char *gt, const unsigned char *pre
                      unsigned long long *hist, hipStream_t stream);
 int launch_multiscale_unary(int K, int C, const float *const *scores, const int32_t *h, const int32_t *w, int H, int W, float eps,
                             float *unary, int32_t *amax, float *sum_out, hipStream_t stream);
+int launch_multiscale_unary_batch(int G, int K, int C, const float *const *scores, const int32_t *h, const int32_t *w,
+                                  const int32_t *H, const int32_t *W, float eps, float *const *unary, int32_t *const *amax,
+                                  float *const *sum_out, hipStream_t stream);
+int launch_preprocess_ms_batch(int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H, const int32_t *W,
+                               const int32_t *sizes, const float *mean, float *const *out, hipStream_t stream);
 int launch_im2col3x3(const void *in, void *out, int B, int H, int W, int C, int dil, hipStream_t stream);
 int launch_col2im3x3(const void *cols, void *out, int B, int H, int W, int C, int dil, hipStream_t stream);
 int launch_relu_bwd_bias(const void *g, const void *y, void *gm, float *bias_grad, float *part, int part_blocks,

@@ -12,6 +12,9 @@
 //   scale = (in - 1) / (out - 1) (0 when out == 1), src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in - 1),
 //   l1 = src - i0, l0 = 1 - l1, v = l0h * (l0w * v00 + l1w * v01) + l1h * (l0w * v10 + l1w * v11), rounded once to f32.
 // -ffp-contract=off (Makefile) keeps every product and sum rounded on its own.  No atomics: results are bit-reproducible.
+//
+// Two front ends share the body: multiscale_unary_kernel (one image) and multiscale_unary_batch_kernel (G images whose score maps
+// are the slices of K batched maps, test-ms.py's fixed sizes: blockIdx.x -> (image, block) through per-image block prefix sums).
 #include <math.h>
 #include <string.h>
 #include "common.h"
@@ -21,6 +24,7 @@ namespace dsrg {
 constexpr int kMsPix = 64;        // output pixels per workgroup
 constexpr int kMsThreads = 256;
 constexpr int kMsMaxScales = 8;
+constexpr int kMsMaxBatch = 16;   // images per batched launch (multiscale_unary_batch_kernel, preprocess_ms_batch_kernel)
 
 struct MsArgs {
     const float *s[kMsMaxScales];  // (C, h_k, w_k) score maps
@@ -28,15 +32,16 @@ struct MsArgs {
     double sh[kMsMaxScales], sw[kMsMaxScales];   // (in - 1) / (out - 1), 0 for out == 1
 };
 
+// block `blk` of one image: output pixels [64 blk, 64 blk + 64) of the H x W map
 template <int K>
-__global__ __launch_bounds__(kMsThreads) void multiscale_unary_kernel(MsArgs a, int C, int H, int W, float eps,
-                                                                      float *__restrict__ unary, int32_t *__restrict__ amax,
-                                                                      float *__restrict__ sum_out) {
+__device__ __forceinline__ void multiscale_unary_body(const MsArgs &a, int C, int H, int W, float eps, int blk,
+                                                      float *__restrict__ unary, int32_t *__restrict__ amax,
+                                                      float *__restrict__ sum_out) {
     __shared__ float s_tile[kMsPix * (kMaxLabels + 1)];     // [pixel][label], row stride Cs (odd: conflict-free columns)
     __shared__ float s_max[kMsPix], s_sum[kMsPix];
 
     const int N = H * W;
-    const int pix0 = blockIdx.x * kMsPix;
+    const int pix0 = blk * kMsPix;
     const int npb = min(kMsPix, N - pix0);
     const int Cs = C | 1;
     const int tid = threadIdx.x;
@@ -140,6 +145,45 @@ __global__ __launch_bounds__(kMsThreads) void multiscale_unary_kernel(MsArgs a, 
     }
 }
 
+template <int K>
+__global__ __launch_bounds__(kMsThreads) void multiscale_unary_kernel(MsArgs a, int C, int H, int W, float eps,
+                                                                      float *__restrict__ unary, int32_t *__restrict__ amax,
+                                                                      float *__restrict__ sum_out) {
+    multiscale_unary_body<K>(a, C, H, W, eps, (int)blockIdx.x, unary, amax, sum_out);
+}
+
+// G images in one launch.  s[k]: (Gcap, C, h_k, w_k) batched maps, image g reads slice g; blk0[g]: the first block of image g
+// (blk0[G] = the grid).  The scale factors are the doubles launch_multiscale_unary computes on the host ((in - 1) / (out - 1) is
+// one correctly rounded IEEE division on either side), so image g's outputs are those of the single-image kernel bit for bit.
+struct MsBatchArgs {
+    const float *s[kMsMaxScales];
+    int h[kMsMaxScales], w[kMsMaxScales];
+    int H[kMsMaxBatch], W[kMsMaxBatch];
+    int blk0[kMsMaxBatch + 1];
+    float *unary[kMsMaxBatch];
+    int32_t *amax[kMsMaxBatch];
+    float *sum[kMsMaxBatch];
+};
+
+template <int K>
+__global__ __launch_bounds__(kMsThreads) void multiscale_unary_batch_kernel(MsBatchArgs b, int G, int C, float eps) {
+    const int blk = (int)blockIdx.x;
+    int g = 0;
+    while (g + 1 < G && blk >= b.blk0[g + 1]) ++g;          // (uniform over the block)
+    const int H = b.H[g], W = b.W[g];
+    MsArgs a;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int h = b.h[k], w = b.w[k];
+        a.s[k] = b.s[k] + (size_t)g * C * h * w;
+        a.h[k] = h;
+        a.w[k] = w;
+        a.sh[k] = H > 1 ? (double)(h - 1) / (double)(H - 1) : 0.0;
+        a.sw[k] = W > 1 ? (double)(w - 1) / (double)(W - 1) : 0.0;
+    }
+    multiscale_unary_body<K>(a, C, H, W, eps, blk - b.blk0[g], b.unary[g], b.amax[g], b.sum[g]);
+}
+
 int check_multiscale_unary(int K, int C, const float *const *scores, const int32_t *h, const int32_t *w, int H, int W,
                            const float *unary, const int32_t *amax, const float *sum_out) {
     if (K < 1 || K > kMsMaxScales) return set_error(DSRG_ERR_INVALID, "multiscale unary: 1..%d scales, got %d", kMsMaxScales, K);
@@ -178,6 +222,55 @@ int launch_multiscale_unary(int K, int C, const float *const *scores, const int3
     switch (K) {
 #define DSRG_MS_CASE(k) \
     case k: hipLaunchKernelGGL(multiscale_unary_kernel<k>, grid, block, 0, stream, a, C, H, W, eps, unary, amax, sum_out); break;
+        DSRG_MS_CASE(1) DSRG_MS_CASE(2) DSRG_MS_CASE(3) DSRG_MS_CASE(4) DSRG_MS_CASE(5) DSRG_MS_CASE(6) DSRG_MS_CASE(7)
+        DSRG_MS_CASE(8)
+#undef DSRG_MS_CASE
+    }
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
+// all-NULL (-> 0) or all-set (-> 1) host array of G device pointers; -1: mixed
+static int output_class(const void *const *p, int G) {
+    if (!p) return 0;
+    int set = 0;
+    for (int g = 0; g < G; ++g) set += p[g] != nullptr;
+    return set == 0 ? 0 : set == G ? 1 : -1;
+}
+
+int launch_multiscale_unary_batch(int G, int K, int C, const float *const *scores, const int32_t *h, const int32_t *w,
+                                  const int32_t *H, const int32_t *W, float eps, float *const *unary, int32_t *const *amax,
+                                  float *const *sum_out, hipStream_t stream) {
+    if (G < 1 || G > kMsMaxBatch)
+        return set_error(DSRG_ERR_INVALID, "multiscale unary batch: 1..%d images, got %d", kMsMaxBatch, G);
+    if (!H || !W) return set_error(DSRG_ERR_INVALID, "multiscale unary batch: NULL image size array");
+    const int cu = output_class((const void *const *)unary, G), ca = output_class((const void *const *)amax, G),
+              cs = output_class((const void *const *)sum_out, G);
+    if (cu < 0 || ca < 0 || cs < 0)
+        return set_error(DSRG_ERR_INVALID, "multiscale unary batch: an output class must be NULL or set for every image");
+    MsBatchArgs b;
+    memset(&b, 0, sizeof(b));
+    for (int g = 0; g < G; ++g) {
+        // the single-image checks, image by image (K, C, the score maps and "no output requested" among them)
+        int rc = check_multiscale_unary(K, C, scores, h, w, H[g], W[g], cu ? unary[g] : nullptr, ca ? amax[g] : nullptr,
+                                        cs ? sum_out[g] : nullptr);
+        if (rc) return rc;
+        b.H[g] = H[g];
+        b.W[g] = W[g];
+        b.blk0[g + 1] = b.blk0[g] + (H[g] * W[g] + kMsPix - 1) / kMsPix;      // < 2^25 blocks per image
+        b.unary[g] = cu ? unary[g] : nullptr;
+        b.amax[g] = ca ? amax[g] : nullptr;
+        b.sum[g] = cs ? sum_out[g] : nullptr;
+    }
+    for (int k = 0; k < K; ++k) {
+        b.s[k] = scores[k];
+        b.h[k] = h[k];
+        b.w[k] = w[k];
+    }
+    const dim3 grid((unsigned)b.blk0[G]), block(kMsThreads);
+    switch (K) {
+#define DSRG_MS_CASE(k) \
+    case k: hipLaunchKernelGGL(multiscale_unary_batch_kernel<k>, grid, block, 0, stream, b, G, C, eps); break;
         DSRG_MS_CASE(1) DSRG_MS_CASE(2) DSRG_MS_CASE(3) DSRG_MS_CASE(4) DSRG_MS_CASE(5) DSRG_MS_CASE(6) DSRG_MS_CASE(7)
         DSRG_MS_CASE(8)
 #undef DSRG_MS_CASE

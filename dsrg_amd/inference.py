@@ -102,6 +102,13 @@ class GraphedForward(object):
         g = self._g[key] = _OneShape(self.net, x, amp_dtype=amp, capture_error_mode="thread_local")
         return g(x)
 
+    def static_input(self, shape, dtype=torch.float32):
+        """the input buffer of the graph captured for `shape` under the current autocast state, or None while there is none.  A
+        caller that writes its input there and passes that tensor to __call__ saves the copy into the buffer."""
+        amp = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else None
+        g = self._g.get((tuple(shape), dtype, amp))
+        return None if g is None else g.x
+
 
 @torch.no_grad()
 def multiscale_scores(net, image, sizes=(241, 321, 401), device="cuda", forward=None):
@@ -134,12 +141,88 @@ def predict_mask_ms(net, image, smooth=True, sizes=(241, 321, 401), device="cuda
     return probs.argmax(0).cpu().numpy()
 
 
+MAX_FORWARD_BATCH = 16      # images per group of the batched path (the limit of the two batched kernels)
+
+
+def _forward_groups(items, G):
+    """items (any iterable) G at a time, in order -> lists of exactly G entries; the tail group is padded with None, the slots
+    that the batched forwards run on zeros"""
+    G = int(G)
+    if not 1 <= G <= MAX_FORWARD_BATCH:
+        raise ValueError("forward_batch must be 1..%d, got %d" % (MAX_FORWARD_BATCH, G))
+    group = []
+    for item in items:
+        group.append(item)
+        if len(group) == G:
+            yield group
+            group = []
+    if group:
+        yield group + [None] * (G - len(group))
+
+
+def _batched_inputs(group, sizes, device, forward):
+    """one padded group of _forward_groups -> (the images on the device, list of (G, 3, S, S) network inputs, one per size).
+    uint8 images go through one dsrg_preprocess_ms_batch launch, written straight into the static inputs of `forward`'s graphs
+    where those exist; a group with other dtypes takes `preprocess` for those slots"""
+    from . import ops
+    G = len(group)
+    images = [im for im in group if im is not None]
+    arrays = [np.ascontiguousarray(np.asarray(im)) for im in images]
+    if all(a.dtype == np.uint8 for a in arrays):
+        dev_images = [torch.from_numpy(a).to(device) for a in arrays]
+        out = None
+        if isinstance(forward, GraphedForward):
+            out = [forward.static_input((G, 3, S, S)) for S in sizes]
+            if len(set(sizes)) != len(sizes) or any(o is None for o in out):
+                out = None                                  # (first group: the graphs are captured from fresh tensors)
+        return dev_images, ops.preprocess_ms_batch(dev_images, sizes, capacity=G, mean=MEAN_PIXEL, out=out)
+    dev_images = [torch.as_tensor(a.astype('ubyte'), device=device) for a in arrays]
+    xs = []
+    for S in sizes:
+        slots = [ops.preprocess_ms_batch([d], [S], mean=MEAN_PIXEL)[0] if a.dtype == np.uint8 else preprocess(a, S, device)
+                 for a, d in zip(arrays, dev_images)]
+        if len(slots) < G:
+            slots.append(torch.zeros((G - len(slots), 3, S, S), dtype=torch.float32, device=device))
+        xs.append(torch.cat(slots))
+    return dev_images, xs
+
+
+def _batched_unaries(net, group, sizes, device, forward, want):
+    """test-ms.py:89-103 for one padded group: K batched forwards and one dsrg_multiscale_unary_batch launch -> (the images on the
+    device, the `want` output of ops.multiscale_unary per image); the padding slots' results are dropped"""
+    from . import ops
+    dev_images, xs = _batched_inputs(group, sizes, device, forward)
+    scores = []
+    with _eval_mode(net):
+        for k, x in enumerate(xs):
+            sc = (forward or net)(x).float()
+            if forward is not None and sizes[k] in sizes[k + 1:]:
+                sc = sc.clone()                  # a graph's static output: the later replay of the same shape would overwrite it
+            scores.append(sc.contiguous())
+    shapes = [(im.shape[0], im.shape[1]) for im in dev_images]
+    return dev_images, ops.multiscale_unary_batch(scores, shapes, eps=0.00001, want=want)
+
+
 @torch.no_grad()
-def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", forward=None, in_flight=3, batch=1):
+def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", forward=None, in_flight=3, batch=1, forward_batch=1):
     """predict_mask_ms over many images (the loop of test-ms.py over a split's 1 449 / 10 582 images), as a generator of (H,W) int64
     masks in order: the forwards of image i + 1 (on the caller's stream; `forward`: a GraphedForward) run while the CRFs of the images
     before it are in flight on `in_flight` worker streams (crf.CRF_device_many; batch > 1: consecutive same-sized images share one
-    batched CRF call).  Same masks as predict_mask_ms image by image."""
+    batched CRF call).  Same masks as predict_mask_ms image by image.
+
+    forward_batch = G > 1: the images are taken G at a time.  test-ms.py resizes every image to the same `sizes`, so a group's
+    forwards are len(sizes) batch-G forwards (a GraphedForward holds one batch-G graph per size; the tail group is padded with
+    zero inputs) between one dsrg_preprocess_ms_batch launch and one dsrg_multiscale_unary_batch launch.  A batch-G forward need
+    not round as a batch-1 forward does: the masks are predict_mask_ms's except where two labels all but tie."""
+    sizes = tuple(sizes)
+    if int(forward_batch) != 1:
+        def batched_pairs():
+            for group in _forward_groups(images, forward_batch):
+                for pair in zip(*_batched_unaries(net, group, sizes, device, forward, "unary")):
+                    yield pair
+
+        yield from _crf_in_flight(batched_pairs(), device, in_flight, batch)
+        return
 
     def pairs():
         for image in images:
@@ -148,6 +231,25 @@ def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", for
             yield torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device), unary
 
     yield from _crf_in_flight(pairs(), device, in_flight, batch)
+
+
+@torch.no_grad()
+def predict_masks_ms_batched(net, images, smooth=True, sizes=(241, 321, 401), device="cuda", forward=None, in_flight=3, batch=1,
+                             capacity=None):
+    """predict_masks_ms_many(forward_batch=capacity) for ONE group of 1..16 images, as a list of (H,W) int64 masks.
+    smooth=False: the arg-max of the summed scores (dsrg_multiscale_unary_batch's), no CRF.  capacity (default: the number of
+    images): the batch size of the forwards, the slots beyond the images run on zeros (a tail group on the full groups' graphs)"""
+    images = list(images)
+    capacity = len(images) if capacity is None else int(capacity)
+    if not 1 <= len(images) <= capacity <= MAX_FORWARD_BATCH:
+        raise ValueError("one group holds 1..%d images within its capacity, got %d in %d" % (MAX_FORWARD_BATCH, len(images), capacity))
+    images = images + [None] * (capacity - len(images))
+    sizes = tuple(sizes)
+    if smooth:
+        dev_images, unaries = _batched_unaries(net, images, sizes, device, forward, "unary")
+        return list(_crf_in_flight(zip(dev_images, unaries), device, in_flight, batch))
+    _, labels = _batched_unaries(net, images, sizes, device, forward, "argmax")
+    return [lab.cpu().numpy().astype(np.int64) for lab in labels]
 
 
 def _crf_in_flight(pairs, device, in_flight, batch):

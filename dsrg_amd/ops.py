@@ -412,6 +412,99 @@ def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",)):
     return res[0] if single else res
 
 
+def multiscale_unary_batch(scores, shapes, eps=1e-5, want=("unary",)):
+    """multiscale_unary for the G images of a group in one launch (dsrg_multiscale_unary_batch), for the fixed sizes of
+    test-ms.py, where every image of a group has the same score map sizes.  scores: list of K (Gcap, C, h_k, w_k) float32 CUDA
+    tensors, image g reads slice g; shapes: the G <= min(Gcap, 16) output sizes (H_g, W_g).  want: as multiscale_unary.  Returns a
+    list of G entries, each what multiscale_unary(slices g, H_g, W_g, eps, want) returns, bit for bit.  Runs on torch's current
+    stream."""
+    single = isinstance(want, str)
+    names = (want,) if single else tuple(want)
+    for n in names:
+        if n not in _MS_OUTPUTS:
+            raise ValueError("unknown output %r (choose from %s)" % (n, ", ".join(_MS_OUTPUTS)))
+    if not names:
+        raise ValueError("want names no output")
+    scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
+    if not scores:
+        raise ValueError("no score maps")
+    shapes = [(int(H), int(W)) for H, W in shapes]
+    G, K, dev = len(shapes), len(scores), scores[0].device
+    if scores[0].dim() != 4:
+        raise ValueError("score maps must be (Gcap, C, h, w); got %s" % (tuple(scores[0].shape),))
+    Gcap, C = scores[0].shape[0], scores[0].shape[1]
+    for s in scores:
+        if s.dim() != 4 or s.shape[0] != Gcap or s.shape[1] != C:
+            raise ValueError("score maps must be (Gcap, C, h, w) with one Gcap and one C; got %s" % (tuple(s.shape),))
+    if not 1 <= G <= Gcap:
+        raise ValueError("%d output shapes for score maps of %d images" % (G, Gcap))
+    out = {}
+    if "unary" in names:
+        out["unary"] = [torch.empty((H, W, C), dtype=torch.float32, device=dev) for H, W in shapes]
+    if "argmax" in names:
+        out["argmax"] = [torch.empty((H, W), dtype=torch.int32, device=dev) for H, W in shapes]
+    if "sum" in names:
+        out["sum"] = [torch.empty((H, W, C), dtype=torch.float32, device=dev) for H, W in shapes]
+
+    def ptr_array(name):
+        return (ctypes.c_void_p * G)(*[t.data_ptr() for t in out[name]]) if name in out else None
+
+    ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scores])
+    hs = (ctypes.c_int32 * K)(*[s.shape[2] for s in scores])
+    ws = (ctypes.c_int32 * K)(*[s.shape[3] for s in scores])
+    Hs = (ctypes.c_int32 * G)(*[H for H, _ in shapes])
+    Ws = (ctypes.c_int32 * G)(*[W for _, W in shapes])
+    check(_lib.lib().dsrg_multiscale_unary_batch(G, K, int(C), ptrs, hs, ws, Hs, Ws, float(eps), ptr_array("unary"),
+                                                 ptr_array("argmax"), ptr_array("sum"), _stream()))
+    if single:
+        return out[names[0]]
+    return [tuple(out[n][g] for n in names) for g in range(G)]
+
+
+MEAN_PIXEL = (104.0, 117.0, 123.0)      # B, G, R (test-ms.py:79; inference.MEAN_PIXEL)
+
+
+def preprocess_ms_batch(images, sizes, capacity=None, mean=MEAN_PIXEL, out=None):
+    """inference.preprocess (test-ms.py:68-81) for a group of images at every size, in one launch (dsrg_preprocess_ms_batch).
+    images: G <= 16 contiguous (H_g, W_g, 3) RGB uint8 CUDA tensors (sizes may differ); sizes: the K <= 8 network input sizes S_k;
+    capacity >= G (default G): the batch size of the outputs, slots G.. are written as zeros.  Returns a list of K
+    (capacity, 3, S_k, S_k) float32 tensors, BGR, mean-subtracted: the inputs of K batched forwards.  out: K existing contiguous
+    float32 CUDA tensors of those shapes to write into (the static inputs of captured graphs, for one) and return.  Runs on
+    torch's current stream."""
+    images = list(images)
+    sizes = [int(s) for s in sizes]
+    G, K = len(images), len(sizes)
+    if G < 1 or K < 1:
+        raise ValueError("no images / no sizes")
+    for g, im in enumerate(images):
+        if not (torch.is_tensor(im) and im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous() and im.dim() == 3
+                and im.shape[2] == 3):
+            raise ValueError("images[%d] must be a contiguous (H, W, 3) uint8 CUDA tensor" % g)
+    cap = G if capacity is None else int(capacity)
+    if cap < G:
+        raise ValueError("capacity %d is below the %d images" % (cap, G))
+    if len(mean) != 3:
+        raise ValueError("mean must hold 3 values")
+    dev = images[0].device
+    if out is None:
+        out = [torch.empty((cap, 3, S, S), dtype=torch.float32, device=dev) for S in sizes]
+    else:
+        out = list(out)
+        if len(out) != K:
+            raise ValueError("out must hold one tensor per size")
+        for k, (o, S) in enumerate(zip(out, sizes)):
+            _f32c(o, "out[%d]" % k)
+            if tuple(o.shape) != (cap, 3, S, S):
+                raise ValueError("out[%d] must be %s, got %s" % (k, (cap, 3, S, S), tuple(o.shape)))
+    ims = (ctypes.c_void_p * G)(*[im.data_ptr() for im in images])
+    Hs = (ctypes.c_int32 * G)(*[im.shape[0] for im in images])
+    Ws = (ctypes.c_int32 * G)(*[im.shape[1] for im in images])
+    check(_lib.lib().dsrg_preprocess_ms_batch(G, cap, K, ims, Hs, Ws, (ctypes.c_int32 * K)(*sizes),
+                                              (ctypes.c_float * 3)(*[float(m) for m in mean]),
+                                              (ctypes.c_void_p * K)(*[o.data_ptr() for o in out]), _stream()))
+    return out
+
+
 def supervision_step(logits, images, labels, cues, th1=0.99, th2=0.85, scale_factor=12.0, maxiter=10,
                      ctx=None, want_blobs=False, prepared=False):
     """The five Python layers of train-s.prototxt:746-810, forward and backward, in one

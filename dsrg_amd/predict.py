@@ -8,7 +8,8 @@ Reads DIR/JPEGImages/<id>.jpg for every id of --images, writes OUT/<id>.png: 8-b
 training/tools/evaluate.py reads (and `python -m dsrg_amd.evaluate`).  The network is VGG16-ASPP with the weights of --model
 (checkpoint.load_weights: .caffemodel, .npz or a torch file), run under bf16 autocast (--fp32: float32, the reference's
 precision); forwards replay from captured HIP graphs (inference.GraphedForward, bounded for the relative scales) while the
-CRFs of earlier images are in flight (inference.predict_masks_ms_many / predict_masks_ms_f_many).
+CRFs of earlier images are in flight (inference.predict_masks_ms_many / predict_masks_ms_f_many).  --mode ms --forward-batch N
+takes the images N at a time through batch-N forwards (the absolute sizes are the same for every image).
 """
 import argparse
 import os
@@ -30,7 +31,14 @@ def parse_args(argv=None):
     p.add_argument("--fp32", action="store_true", help="float32 forwards instead of bf16 autocast")
     p.add_argument("--in-flight", type=int, default=3, help="CRFs in flight under the next image's forwards")
     p.add_argument("--max-graphs", type=int, default=12, help="ms-f: captured forward graphs kept (least recently used dropped)")
-    return p.parse_args(argv)
+    p.add_argument("--forward-batch", type=int, default=1,
+                   help="ms: images per batched forward (1..16; default 1: one image per forward)")
+    a = p.parse_args(argv)
+    if a.mode == "ms-f" and a.forward_batch != 1:
+        p.error("--forward-batch is for --mode ms only: the relative scales of ms-f give every image size its own input shapes")
+    if not 1 <= a.forward_batch <= 16:
+        p.error("--forward-batch must be 1..16")
+    return a
 
 
 def read_ids(path):
@@ -78,9 +86,14 @@ def main(argv=None):
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=not a.fp32):
         if a.smooth:
             if a.mode == "ms":
-                masks = I.predict_masks_ms_many(net, images, sizes=scales, device=dev, forward=fwd, in_flight=a.in_flight)
+                masks = I.predict_masks_ms_many(net, images, sizes=scales, device=dev, forward=fwd, in_flight=a.in_flight,
+                                                forward_batch=a.forward_batch)
             else:
                 masks = I.predict_masks_ms_f_many(net, images, scales=scales, device=dev, forward=fwd, in_flight=a.in_flight)
+        elif a.mode == "ms" and a.forward_batch > 1:
+            masks = (m for group in I._forward_groups(images, a.forward_batch)
+                     for m in I.predict_masks_ms_batched(net, [im for im in group if im is not None], smooth=False, sizes=scales,
+                                                         device=dev, forward=fwd, capacity=a.forward_batch))
         elif a.mode == "ms":
             masks = (I.predict_mask_ms(net, im, smooth=False, sizes=scales, device=dev, forward=fwd) for im in images)
         else:

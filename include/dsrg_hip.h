@@ -266,6 +266,27 @@ int dsrg_confusion_matrix(size_t n, const unsigned char *gt_dev, const unsigned 
  * Stream-ordered, no host synchronisation, no handle (callable from any host thread); bit-reproducible (no atomics). */
 int dsrg_multiscale_unary(int K, int C, const float *const *scores_dev, const int32_t *h_host, const int32_t *w_host, int H, int W,
                           float eps, float *unary_dev, int32_t *argmax_dev, float *sum_dev, void *stream);
+/* dsrg_multiscale_unary for G images in one launch (the fixed sizes of test-ms.py give every image of a group the same score
+ * map sizes): scores_dev is a HOST array of K device pointers to batched maps (Gcap, C, h_k, w_k) f32 NCHW, Gcap >= G, image g
+ * reads slice g; H_host / W_host: host arrays of the G output sizes.  unary_dev / argmax_dev / sum_dev: HOST arrays of G device
+ * pointers each (layouts and alignment as above), or NULL; a class of outputs is NULL (or all-NULL) or set for every image, and
+ * at least one class is required.  Image g's outputs equal dsrg_multiscale_unary's on slice g and (H_g, W_g) bit for bit.
+ * 1 <= G <= 16; otherwise the limits of dsrg_multiscale_unary, per image; every argument is checked before the first device
+ * call.  Stream-ordered, no host synchronisation, no handle; bit-reproducible (no atomics). */
+int dsrg_multiscale_unary_batch(int G, int K, int C, const float *const *scores_dev, const int32_t *h_host, const int32_t *w_host,
+                                const int32_t *H_host, const int32_t *W_host, float eps, float *const *unary_dev,
+                                int32_t *const *argmax_dev, float *const *sum_dev, void *stream);
+/* The network inputs of a group of test images in one launch (training/tools/test-ms.py:68-81 for G images at K sizes):
+ * images_dev is a HOST array of G device pointers to (H_g, W_g, 3) RGB uint8 images (H_host / W_host: their sizes), sizes_host K
+ * target sizes S_k, mean_host the 3 values subtracted from the B, G, R output channels, out_dev a HOST array of K device
+ * pointers to (capacity, 3, S_k, S_k) f32 NCHW tensors.  Slot g < G of output k is image g zoomed to S_k x S_k (order-1 zoom,
+ * (in-1)/(out-1) mapping, blended in double and rounded once to f32), in BGR order, minus the mean (in f32); slots G..capacity-1
+ * are written as zeros.  1 <= G <= 16, G <= capacity, 1 <= K <= 8, all sizes >= 1, H_g*W_g*3 < 2^31, capacity*3*S_k^2 < 2^31,
+ * outputs aligned to 4 bytes; every argument is checked before the first device call.  Stream-ordered, no host
+ * synchronisation, no handle; bit-reproducible (no atomics). */
+int dsrg_preprocess_ms_batch(int G, int capacity, int K, const unsigned char *const *images_dev, const int32_t *H_host,
+                             const int32_t *W_host, const int32_t *sizes_host, const float *mean_host, float *const *out_dev,
+                             void *stream);
 
 /* Backbone plumbing (no reference counterpart; Caffe's im2col lives in the external framework): NHWC im2col
  * of a 3x3, stride-1, "same"-padded, dilated convolution for 2-byte elements (bf16/fp16), C % 8 == 0:
