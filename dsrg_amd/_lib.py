@@ -52,6 +52,7 @@ SIGNATURES = {
     "dsrg_crf_add_pairwise_energy": (_i, [_vp] + [_f] * 9 + [_vp]),
     "dsrg_crf_inference": (_i, [_vp, _i, _vp]),
     "dsrg_crf_map": (_i, [_vp, _i, _vp]),
+    "dsrg_crf_map_select": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _i, _f, _vp]),
     "dsrg_crf_set_stream": (_i, [_vp, _vp, _i]),
     "dsrg_crf_synchronize": (_i, [_vp]),
     "dsrg_crf_npixels": (_i, [_vp]),
@@ -86,6 +87,8 @@ SIGNATURES = {
                                    _f, _vp, _vp, _vp, _vp]),
     "dsrg_multiscale_unary_batch": (_i, [_i, _i, _i, ctypes.POINTER(_vp)] + [ctypes.POINTER(ctypes.c_int32)] * 4 +
                                     [_f, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
+    "dsrg_train_gt_unary_batch": (_i, [_i, _i, _vp, _i, _i] + [ctypes.POINTER(ctypes.c_int32)] * 2 + [_f] +
+                                  [ctypes.POINTER(ctypes.c_int32)] * 2 + [_i, _f, _vp] + [ctypes.POINTER(_vp)] * 3 + [_vp]),
     "dsrg_preprocess_ms_batch": (_i, [_i, _i, _i, ctypes.POINTER(_vp)] + [ctypes.POINTER(ctypes.c_int32)] * 3 +
                                  [ctypes.POINTER(_f), ctypes.POINTER(_vp), _vp]),
     "dsrg_im2col3x3_nhwc16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -19,6 +19,26 @@ def _is_cuda_tensor(x):
 
 
 MAX_BATCH = 8            # images per batched object (include/dsrg_hip.h: dsrg_crf_create_batch)
+MAX_SELECT = 128         # entries per selection list (include/dsrg_hip.h: dsrg_crf_map_select)
+
+
+def select_arrays(select, n_images, nlabels):
+    """one ordered label list per image -> (flat int32 array, int32 counts, stride) as dsrg_crf_map_select /
+    dsrg_train_gt_unary_batch take them.  The library checks lengths and entries again; here the errors are ValueErrors that
+    name the image."""
+    lists = [[int(c) for c in s] for s in select]
+    if len(lists) != n_images:
+        raise ValueError("%d selection lists for %d images" % (len(lists), n_images))
+    for g, s in enumerate(lists):
+        if not 1 <= len(s) <= MAX_SELECT:
+            raise ValueError("selection list %d holds %d labels, not 1..%d" % (g, len(s), MAX_SELECT))
+        if min(s) < 0 or max(s) >= nlabels:
+            raise ValueError("selection list %d names a label outside [0, %d)" % (g, nlabels))
+    stride = max(len(s) for s in lists)
+    flat = (ctypes.c_int32 * (stride * n_images))()
+    for g, s in enumerate(lists):
+        flat[g * stride:g * stride + len(s)] = s
+    return flat, (ctypes.c_int32 * n_images)(*[len(s) for s in lists]), stride
 
 
 class DenseCRF(object):
@@ -27,6 +47,7 @@ class DenseCRF(object):
         image and result buffers hold n same-sized images back to back and whose every launch carries all of them"""
         _lib.require_gpu()
         self._h = None
+        self._nimages = None if nimages is None else int(nimages)
         h = ctypes.c_void_p()
         if nimages is None:
             check(_lib.lib().dsrg_crf_create(int(W), int(H), int(nlabels), ctypes.byref(h)))
@@ -88,14 +109,33 @@ class DenseCRF(object):
         check(_lib.lib().dsrg_crf_inference(self._h, int(n_iters), probs.ctypes.data_as(ctypes.c_void_p)))
         return probs
 
-    def map(self, n_iters=10, out=None):
+    def map(self, n_iters=10, out=None, select=None, ignore_below=None):
+        """the arg-max labels.  select: restrict them to the labels known to be in the image (generate_train_gt.py:98-104) — one
+        ordered list of 1..128 labels for a one-image object, a list of `nimages` such lists for a batched one; a pixel gets
+        sel[j], j the first index that maximises its marginal.  ignore_below (with select): pixels whose largest marginal over
+        all labels is below it get 255; None or <= 0: off."""
+        if select is None:
+            if ignore_below is not None and float(ignore_below) > 0:
+                raise ValueError("ignore_below goes with select")
+
+            def call(ptr):
+                check(_lib.lib().dsrg_crf_map(self._h, int(n_iters), ptr))
+        else:
+            nimg = self._nimages or 1
+            select = list(select)
+            if not select or not hasattr(select[0], "__len__"):
+                select = [select]                             # one flat list: the list of the object's only image
+            flat, counts, stride = select_arrays(select, nimg, self.nlabels())
+
+            def call(ptr):
+                check(_lib.lib().dsrg_crf_map_select(self._h, int(n_iters), flat, counts, stride, float(ignore_below or 0.0), ptr))
         if out is not None:
             if not (_is_cuda_tensor(out) and out.is_contiguous() and out.numel() == self.npixels() and out.element_size() == 4):
                 raise ValueError("out must be a contiguous int32 CUDA tensor of npixels values")
-            check(_lib.lib().dsrg_crf_map(self._h, int(n_iters), ctypes.c_void_p(out.data_ptr())))
+            call(ctypes.c_void_p(out.data_ptr()))
             return out
         labels = np.empty(self.npixels(), dtype=np.int32)
-        check(_lib.lib().dsrg_crf_map(self._h, int(n_iters), labels.ctypes.data_as(ctypes.c_void_p)))
+        call(labels.ctypes.data_as(ctypes.c_void_p))
         return labels
 
     def lattice_size(self, k):
@@ -145,28 +185,39 @@ def CRF(image, unary, maxiter=10, scale_factor=1.0, color_factor=13):
     return crf.inference(maxiter).reshape((height, width, labels))
 
 
-def CRF_device(image, unary, maxiter=10, scale_factor=1.0, color_factor=13, want="marginals"):
+def CRF_device(image, unary, maxiter=10, scale_factor=1.0, color_factor=13, want="marginals", select=None, ignore_below=None):
     """`CRF()` for a device-resident caller: image (H,W,3) uint8 and unary (H,W,M) float32 CUDA tensors in, a CUDA tensor
     out — (H,W,M) float32 marginals, or with want="map" the (H,W) int32 arg-max labels — without a PCIe round trip.
-    Same parameters as CRF() (CRF.py:19-37)."""
+    Same parameters as CRF() (CRF.py:19-37).  select / ignore_below (want="map" only): see DenseCRF.map."""
     import torch
     assert image.shape[:2] == unary.shape[:2]
     H, W, labels = unary.shape
     if torch.cuda.current_stream(unary.device) != torch.cuda.default_stream(unary.device):
         torch.cuda.current_stream(unary.device).synchronize()     # the object API works on the null stream
+    if want != "map" and (select is not None or ignore_below is not None):
+        raise ValueError('select / ignore_below go with want="map"')
     crf = _crf_object(W, H, labels, -unary.to(torch.float32), image, scale_factor, color_factor)
     if want == "map":
-        return crf.map(maxiter, out=torch.empty((H, W), dtype=torch.int32, device=unary.device))
+        return crf.map(maxiter, out=torch.empty((H, W), dtype=torch.int32, device=unary.device), select=select,
+                       ignore_below=ignore_below)
     return crf.inference(maxiter, out=torch.empty((H, W, labels), dtype=torch.float32, device=unary.device))
 
 
-def CRF_device_batch(images, unary, maxiter=10, scale_factor=1.0, color_factor=13, want="marginals", crf=None):
+def CRF_device_batch(images, unary, maxiter=10, scale_factor=1.0, color_factor=13, want="marginals", crf=None, select=None,
+                     ignore_below=None):
     """`CRF_device` for B same-sized images in ONE set of launches (a batched object, at most MAX_BATCH images per object; more
     are taken in chunks): images (B,H,W,3) uint8 and unary (B,H,W,M) float32 CUDA tensors -> (B,H,W,M) float32 marginals or,
     want="map", (B,H,W) int32 labels.  Each image's result equals CRF_device's on that image bit for bit.  crf: a DenseCRF(W, H,
-    M, nimages=B) to reuse (its stream setting is kept); otherwise objects come from the library's cache on the null stream."""
+    M, nimages=B) to reuse (its stream setting is kept); otherwise objects come from the library's cache on the null stream.
+    select (want="map" only): B ordered label lists, one per image, and ignore_below: see DenseCRF.map."""
     import torch
     B, H, W, M = unary.shape
+    if want != "map" and (select is not None or ignore_below is not None):
+        raise ValueError('select / ignore_below go with want="map"')
+    if select is not None:
+        select = [list(s) for s in select]
+        if len(select) != B:
+            raise ValueError("%d selection lists for %d images" % (len(select), B))
     assert tuple(images.shape) == (B, H, W, 3)
     # objects made here run on the CALLER's stream (bound for the call, unbound before they go back to the library's cache): no
     # host synchronisation of the caller's stream up front and no detour over the null stream, which serialises every other stream
@@ -185,7 +236,8 @@ def CRF_device_batch(images, unary, maxiter=10, scale_factor=1.0, color_factor=1
             obj.add_pairwise_energy(_BILATERAL_W, sxy_b, sxy_b, color_factor, color_factor, color_factor, _GAUSS_W, sxy_g, sxy_g,
                                     images[b0:b0 + n].to(torch.uint8).contiguous())
             if want == "map":
-                obj.map(maxiter, out=out[b0:b0 + n])
+                obj.map(maxiter, out=out[b0:b0 + n], select=None if select is None else select[b0:b0 + n],
+                        ignore_below=ignore_below)
             else:
                 obj.inference(maxiter, out=out[b0:b0 + n])
         finally:
@@ -194,7 +246,7 @@ def CRF_device_batch(images, unary, maxiter=10, scale_factor=1.0, color_factor=1
     return out
 
 
-def CRF_device_many(pairs, maxiter=10, scale_factor=1.0, color_factor=13, want="map", in_flight=4, batch=1):
+def CRF_device_many(pairs, maxiter=10, scale_factor=1.0, color_factor=13, want="map", in_flight=4, batch=1, ignore_below=None):
     """`CRF_device` over many images with `in_flight` of them overlapping on the GPU — the test-time loop of
     training/tools/test-ms.py:84-111 / generate_train_gt.py:78-106 (10 582 images, one CRF each).  The full-resolution CRF is
     ~170 short dependent launches per image (and one host read-back of the lattice sizes): one image at a time leaves most of
@@ -204,7 +256,10 @@ def CRF_device_many(pairs, maxiter=10, scale_factor=1.0, color_factor=13, want="
     yields the results in order: (H,W) int32 arg-max labels (want="map") or (H,W,M) float32 marginals.
     batch > 1: consecutive pairs of one shape (up to `batch`, at most MAX_BATCH) additionally share ONE batched object call —
     every launch of the build and of the mean-field loop then carries that many images (the loop is launch-bound: ~6 us
-    launches for 10 MB each at one image); results are the same bit for bit."""
+    launches for 10 MB each at one image); results are the same bit for bit.
+    An item may also be a triple (image, unary, select): with want="map" its labels are restricted to the ordered label list
+    `select` (DenseCRF.map; generate_train_gt.py:98-104, with ignore_below as there).  Consecutive same-shape triples share a
+    batched call, each with its own list; a pair never shares a call with a triple."""
     import threading
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
@@ -217,7 +272,7 @@ def CRF_device_many(pairs, maxiter=10, scale_factor=1.0, color_factor=13, want="
     batch = max(1, min(int(batch), MAX_BATCH))
 
     def work(group, ready):
-        """group: list of (image, unary) of one shape -> list of results"""
+        """group: list of (image, unary, select or None) of one shape, all with or all without a list -> list of results"""
         torch.cuda.set_device(device)
         if not hasattr(local, "stream"):
             local.stream, local.objs = torch.cuda.Stream(device=device), {}
@@ -230,13 +285,16 @@ def CRF_device_many(pairs, maxiter=10, scale_factor=1.0, color_factor=13, want="
             crf.set_stream(local.stream)
         local.stream.wait_event(ready)                      # the inputs were produced on the caller's stream
         with torch.cuda.stream(local.stream):
-            un = torch.stack([u for _, u in group]) if n > 1 else group[0][1]
-            im = torch.stack([i for i, _ in group]) if n > 1 else group[0][0]
+            un = torch.stack([g[1] for g in group]) if n > 1 else group[0][1]
+            im = torch.stack([g[0] for g in group]) if n > 1 else group[0][0]
+            select = None if group[0][2] is None else [g[2] for g in group]
             crf.set_unary_energy((-un.to(torch.float32)).contiguous())
             crf.add_pairwise_energy(_BILATERAL_W, sxy_b, sxy_b, color_factor, color_factor, color_factor, _GAUSS_W, sxy_g, sxy_g,
                                     im.reshape(-1).to(torch.uint8).contiguous())
             if want == "map":
-                out = crf.map(maxiter, out=torch.empty((n, H, W), dtype=torch.int32, device=un.device))
+                out = crf.map(maxiter, out=torch.empty((n, H, W), dtype=torch.int32, device=un.device),
+                              select=select if (select is None or batch > 1) else select[0],
+                              ignore_below=None if select is None else ignore_below)
             else:
                 out = crf.inference(maxiter, out=torch.empty((n, H, W, M), dtype=torch.float32, device=un.device))
         # allocated on this worker's stream, consumed on the caller's: keep the block out of this stream's pool until the
@@ -246,11 +304,16 @@ def CRF_device_many(pairs, maxiter=10, scale_factor=1.0, color_factor=13, want="
 
     def groups():
         run = []
-        for image, unary in pairs:
-            if run and (len(run) == batch or tuple(unary.shape) != tuple(run[0][1].shape)):
+        for item in pairs:
+            image, unary = item[0], item[1]
+            select = None if len(item) < 3 or item[2] is None else [int(l) for l in item[2]]
+            if select is not None and want != "map":
+                raise ValueError('a selection list goes with want="map"')
+            if run and (len(run) == batch or tuple(unary.shape) != tuple(run[0][1].shape)
+                        or (select is None) != (run[0][2] is None)):
                 yield run
                 run = []
-            run.append((image, unary))
+            run.append((image, unary, select))
         if run:
             yield run
 

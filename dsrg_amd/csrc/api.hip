@@ -501,6 +501,14 @@ extern "C" int dsrg_multiscale_unary_batch(int G, int K, int C, const float *con
     // every argument is checked before the first device call
     return launch_multiscale_unary_batch(G, K, C, scores, h, w, H, W, eps, unary, amax, sum, static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_train_gt_unary_batch(int G, int C, const float *scores, int h, int w, const int32_t *H, const int32_t *W, float eps,
+                                         const int32_t *select, const int32_t *nselect, int select_stride, float ignore_below,
+                                         float *workspace, float *const *unary, float *const *probs, int32_t *const *labels,
+                                         void *stream) {
+    // every argument is checked before the first device call
+    return launch_train_gt_unary_batch(G, C, scores, h, w, H, W, eps, select, nselect, select_stride, ignore_below, workspace, unary,
+                                       probs, labels, static_cast<hipStream_t>(stream));
+}
 extern "C" int dsrg_preprocess_ms_batch(int G, int capacity, int K, const unsigned char *const *images, const int32_t *H,
                                         const int32_t *W, const int32_t *sizes, const float *mean, float *const *out,
                                         void *stream) {
@@ -777,6 +785,7 @@ int large_crf_set_image(LargeCrf *c, const unsigned char *im_host);
 int large_crf_infer(LargeCrf *c, const dsrg_crf_params *prm, int n_iters);
 int large_crf_read_q(LargeCrf *c, float *out_host);
 int large_crf_read_map(LargeCrf *c, int32_t *labels_host);
+int large_crf_read_map_select(LargeCrf *c, const CrfSelArgs &sel, int32_t *labels_host);
 int large_crf_lattice_size(LargeCrf *c, int k);
 Profiler *large_crf_profiler(LargeCrf *c);
 void large_crf_set_stream(LargeCrf *c, hipStream_t s, bool async);
@@ -956,6 +965,37 @@ extern "C" int dsrg_crf_map(dsrg_crf_t h, int n_iters, int32_t *labels_host) {
     if (h->large) return large_crf_read_map(h->large, labels_host);
     const int N = h->W * h->H;
     rc = launch_argmax_planes(N, h->M, h->q, h->lab, h->stream);
+    if (rc) return rc;
+    DSRG_HIP_CHECK(hipMemcpyAsync(labels_host, h->lab, sizeof(int32_t) * (size_t)N, hipMemcpyDefault, h->stream));
+    if (!h->async) DSRG_HIP_CHECK(hipStreamSynchronize(h->stream));      // see dsrg_crf_inference
+    return DSRG_OK;
+}
+// dsrg_crf_map restricted to one ordered label list per image of the object (generate_train_gt.py:98-104): one more pass over the Q
+// that the last iteration wrote.  The lists travel to the kernel by value, so nothing of the caller's is read after the return.
+extern "C" int dsrg_crf_map_select(dsrg_crf_t h, int n_iters, const int32_t *select_host, const int32_t *nselect_host,
+                                   int select_stride, float ignore_below, int32_t *labels_host) {
+    static const char who[] = "crf map select";
+    if (!select_host || !nselect_host || !labels_host) return set_error(DSRG_ERR_INVALID, "%s: NULL argument", who);
+    // (every object holds at least one image and at most kMaxLabels labels: the first list is checked even without a handle)
+    int rc = check_select_list(who, 0, select_host, nselect_host[0], select_stride, kMaxLabels);
+    if (rc) return rc;
+    if (!h) return set_error(DSRG_ERR_INVALID, "%s: NULL handle", who);
+    if (h->nimg > kSelectImages) return set_error(DSRG_ERR_UNSUPPORTED, "%s: at most %d images per object", who, kSelectImages);
+    CrfSelArgs s;
+    memset(&s, 0, sizeof(s));
+    s.ignore_below = ignore_below;
+    for (int b = 0; b < h->nimg; ++b) {
+        const int32_t *sel = select_host + (size_t)b * select_stride;
+        rc = check_select_list(who, b, sel, nselect_host[b], select_stride, h->M);
+        if (rc) return rc;
+        s.n[b] = nselect_host[b];
+        for (int j = 0; j < s.n[b]; ++j) s.sel[b][j] = (unsigned char)sel[j];
+    }
+    rc = crf_infer(h, n_iters);
+    if (rc) return rc;
+    if (h->large) return large_crf_read_map_select(h->large, s, labels_host);
+    const int N = h->W * h->H;
+    rc = launch_select_planes(N, h->M, h->q, h->lab, s, h->stream);
     if (rc) return rc;
     DSRG_HIP_CHECK(hipMemcpyAsync(labels_host, h->lab, sizeof(int32_t) * (size_t)N, hipMemcpyDefault, h->stream));
     if (!h->async) DSRG_HIP_CHECK(hipStreamSynchronize(h->stream));      // see dsrg_crf_inference

@@ -103,6 +103,37 @@ constexpr int kMaxLabels = 96;     // per-pixel label loops keep at most this ma
                                    // 81-class blobs of AnnotationLayerCOCO, pylayers.py:389-512, fit)
 constexpr float kMinProb = 0.0001f;
 
+// ---- label-restricted selection (generate_train_gt.py:98-104) -----------------
+// The result over an ordered list sel[0..n) of label indices is sel[j*], j* the FIRST j that maximises v[sel[j]] (np.argmax on
+// probs[:, :, labels]: strict > while walking the list; duplicates and any order allowed).  Shared by the unary kernel's
+// smooth=False route (train_gt.hip) and the two kernels that read a CRF object's final marginals (layers.hip, lattice_large.hip).
+constexpr int kMaxSelect = 128;      // entries per list
+constexpr int kIgnoreLabel = 255;    // pixels whose maximum over ALL labels is below `ignore_below` (off at <= 0)
+constexpr int kSelectImages = 8;     // lists per CRF object: one per image of a batched object (kLargeBatchMax)
+struct CrfSelArgs {                  // passed to the kernels by value: correct for objects in asynchronous mode on any thread
+    int n[kSelectImages];
+    float ignore_below;
+    unsigned char sel[kSelectImages][kMaxSelect];
+};
+// v[c * stride]: the value of label c
+template <typename S>
+__device__ __forceinline__ int select_label(const float *__restrict__ v, size_t stride, const S *sel, int n) {
+    int best = (int)sel[0];
+    float bv = v[(size_t)best * stride];
+    for (int j = 1; j < n; ++j) {
+        const int c = (int)sel[j];
+        const float x = v[(size_t)c * stride];
+        if (x > bv) { bv = x; best = c; }
+    }
+    return best;
+}
+__device__ __forceinline__ float max_label_value(const float *__restrict__ v, size_t stride, int C) {
+    float m = v[0];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, v[(size_t)c * stride]);
+    return m;
+}
+int check_select_list(const char *who, int image, const int32_t *sel, int n, int stride, int C);
+
 // ---- permutohedral lattice, device-resident ----------------------------------
 // One lattice = one (image, kernel) pair.  All arrays are sized for the worst
 // case Mcap = Npad*(d+1) vertices so nothing depends on the data-dependent M.
@@ -216,6 +247,11 @@ int launch_sup_loss_backward(int B, int C, int HW, const float *logits, const fl
 int launch_lf_to_planes(int N, int M, const float *in, float *out, int negate, hipStream_t stream);
 int launch_planes_to_lf(int N, int M, const float *in, float *out, hipStream_t stream);
 int launch_argmax_planes(int N, int M, const float *q, int32_t *lab, hipStream_t stream);
+int launch_select_planes(int N, int M, const float *q, int32_t *lab, const CrfSelArgs &sel, hipStream_t stream);
+int launch_train_gt_unary_batch(int G, int C, const float *scores, int h, int w, const int32_t *H, const int32_t *W, float eps,
+                                const int32_t *select, const int32_t *nselect, int select_stride, float ignore_below,
+                                float *workspace, float *const *unary, float *const *probs, int32_t *const *labels,
+                                hipStream_t stream);
 int launch_seed_loss_plain(int B, int C, int HW, const float *p, const float *S, float *loss, float *grad, hipStream_t stream);
 int launch_expand_loss(int B, int C, int HW, const float *p, const float *stat, double q_fg, double q_bg, float *loss,
                        float *grad, double *terms, hipStream_t stream);

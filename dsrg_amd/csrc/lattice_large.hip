@@ -618,6 +618,20 @@ __global__ void lg_argmax_rows_kernel(int N, int C, int CP, const float *__restr
     for (int c = 1; c < C; c++) { const float v = q[(size_t)i * CP + c]; if (v > best) { best = v; m = c; } }
     lab[u] = m;
 }
+// the restricted MAP of generate_train_gt.py:98-104 from the padded rows of the final marginals; image b of a batched object
+// takes list b.  A pass of its own over Q (N * CP * 4 bytes) after the last iteration: lg_slice_update_kernel stays as it is.
+__global__ void lg_select_rows_kernel(int N, int C, int CP, const float *__restrict__ q, int32_t *__restrict__ lab, int Nimg, int Npimg,
+                                      CrfSelArgs s) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const long long u = lg_user_row((size_t)i, Nimg, Npimg);
+    if (u < 0) return;
+    const int b = Npimg ? i / Npimg : 0;
+    const float *row = q + (size_t)i * CP;
+    int m = select_label(row, 1, s.sel[b], s.n[b]);
+    if (s.ignore_below > 0.0f && max_label_value(row, 1, C) < s.ignore_below) m = kIgnoreLabel;
+    lab[u] = m;
+}
 
 // ---------------------------------------------------------------------------------------------
 // The two device-wide primitives of the build, written for its sizes (the full-resolution lattices have 0.1 - 1.5 M entries):
@@ -1055,6 +1069,16 @@ int large_crf_read_map(LargeCrf *c, int32_t *labels_host) {
     if (!c->lab_valid)                                       // (no iteration ran: Q is the softmax of the unaries, lg_update_kernel)
         hipLaunchKernelGGL(lg_argmax_rows_kernel, dim3(blocks_for(c->N, 256)), dim3(256), 0, c->stream, c->N, c->C, c->CP, c->q, c->lab,
                        c->Nimg, c->Npimg);
+    DSRG_LAUNCH_CHECK();
+    DSRG_HIP_CHECK(hipMemcpyAsync(labels_host, c->lab, sizeof(int32_t) * (size_t)c->nimg * c->Nimg, hipMemcpyDefault, c->stream));
+    if (!c->async) DSRG_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return DSRG_OK;
+}
+// `lab` then holds the restricted labels, no longer the arg-max the last slice launch wrote
+int large_crf_read_map_select(LargeCrf *c, const CrfSelArgs &sel, int32_t *labels_host) {
+    hipLaunchKernelGGL(lg_select_rows_kernel, dim3(blocks_for(c->N, 256)), dim3(256), 0, c->stream, c->N, c->C, c->CP, c->q, c->lab,
+                       c->Nimg, c->Npimg, sel);
+    c->lab_valid = false;
     DSRG_LAUNCH_CHECK();
     DSRG_HIP_CHECK(hipMemcpyAsync(labels_host, c->lab, sizeof(int32_t) * (size_t)c->nimg * c->Nimg, hipMemcpyDefault, c->stream));
     if (!c->async) DSRG_HIP_CHECK(hipStreamSynchronize(c->stream));

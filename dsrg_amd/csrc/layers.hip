@@ -506,6 +506,14 @@ __global__ void argmax_planes_kernel(int N, int M, const float *__restrict__ q, 
     }
     lab[i] = m;
 }
+// the restricted MAP of generate_train_gt.py:98-104 from the label planes of the final marginals (one image: list 0)
+__global__ void select_planes_kernel(int N, int M, const float *__restrict__ q, int32_t *__restrict__ lab, CrfSelArgs s) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    int m = select_label(q + i, (size_t)N, s.sel[0], s.n[0]);
+    if (s.ignore_below > 0.0f && max_label_value(q + i, (size_t)N, M) < s.ignore_below) m = kIgnoreLabel;
+    lab[i] = m;
+}
 int launch_lf_to_planes(int N, int M, const float *in, float *out, int negate, hipStream_t stream) {
     hipLaunchKernelGGL(lf_to_planes_kernel, dim3((N * M + 255) / 256), dim3(256), 0, stream, N, M, in, out, negate);
     DSRG_LAUNCH_CHECK();
@@ -518,6 +526,11 @@ int launch_planes_to_lf(int N, int M, const float *in, float *out, hipStream_t s
 }
 int launch_argmax_planes(int N, int M, const float *q, int32_t *lab, hipStream_t stream) {
     hipLaunchKernelGGL(argmax_planes_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, N, M, q, lab);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+int launch_select_planes(int N, int M, const float *q, int32_t *lab, const CrfSelArgs &sel, hipStream_t stream) {
+    hipLaunchKernelGGL(select_planes_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, N, M, q, lab, sel);
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
 }

@@ -6,6 +6,7 @@ full-resolution dense CRF on log-probabilities, pseudo-label generation, and the
   preprocess_relative   <-> training/tools/test-ms-f.py:100-112
   predict_mask_ms_f     <-> training/tools/test-ms-f.py:115-142     (run.sh step 4: the final test at relative scales)
   predict_train_gt      <-> training/tools/generate_train_gt.py:78-106
+  predict_train_gt_many <-> the loop of generate_train_gt.py:117-123 over train_aug (batched forwards, fused HIP tail)
   ConfusionMatrix       <-> training/tools/evaluate.py:17-68
 
 The network runs in PyTorch-ROCm; resampling uses align-corners bilinear interpolation, which is the
@@ -252,9 +253,10 @@ def predict_masks_ms_batched(net, images, smooth=True, sizes=(241, 321, 401), de
     return [lab.cpu().numpy().astype(np.int64) for lab in labels]
 
 
-def _crf_in_flight(pairs, device, in_flight, batch):
+def _crf_in_flight(pairs, device, in_flight, batch, ignore_below=None):
     """the CRF half of the *_many generators: (image, unary) pairs -> (H,W) int64 masks in order, CRFs on worker streams while the
-    pairs (the forwards) are produced on a forward stream of their own"""
+    pairs (the forwards) are produced on a forward stream of their own.  (image, unary, select) triples: the masks are restricted
+    to each image's label list (crf.CRF_device_many), with ignore_below as DenseCRF.map takes it"""
     from .crf import CRF_device_many
     # the CRF workers come back from the library three times per image and need the interpreter lock for a few lines each time; the
     # caller's thread, busy issuing torch ops, would keep it for Python's default 5 ms switch interval — longer than a whole CRF
@@ -264,13 +266,18 @@ def _crf_in_flight(pairs, device, in_flight, batch):
     # ... and the forwards go to a stream of their own: on the caller's (usually the null) stream they share a hardware queue with one of
     # the CRF workers' streams or not, depending on how many streams the process made before — 178 or 240 images/s from run to run
     fstream = torch.cuda.Stream(device=device)
+    caller = torch.cuda.current_stream(device)
     try:
-        fstream.wait_stream(torch.cuda.current_stream(device))
+        fstream.wait_stream(caller)
         with torch.cuda.stream(fstream):
-            for lab in CRF_device_many(pairs, scale_factor=1.0, want="map", in_flight=in_flight, batch=batch):
+            for lab in CRF_device_many(pairs, scale_factor=1.0, want="map", in_flight=in_flight, batch=batch,
+                                       ignore_below=ignore_below):
                 yield lab.cpu().numpy().astype(np.int64)
     finally:
         sys.setswitchinterval(interval)
+        # what the forward stream still holds (a forward issued ahead of a generator that was closed early, writes into a graph's
+        # static buffers) is ordered before whatever the caller enqueues next; every yielded mask was already final
+        caller.wait_stream(fstream)
 
 
 # ---- the final test at relative scales (test-ms-f.py, run.sh step 4) ----------------------------------------------------------------
@@ -369,6 +376,53 @@ def predict_train_gt(net, image, labels, smooth=True, device="cuda"):
         p = probs.permute(1, 2, 0)
     sel = torch.as_tensor([0] + [int(l) for l in labels], device=p.device)
     return sel[p[:, :, sel].argmax(2)].cpu().numpy()
+
+
+def train_gt_selection(labels):
+    """the label list of generate_train_gt.py:98-99 (`labels.insert(0, 0)`): background, then the image-level labels in the order
+    (and with the duplicates) given"""
+    return [0] + [int(l) for l in labels]
+
+
+@torch.no_grad()
+def predict_train_gt_many(net, items, smooth=True, size=321, device="cuda", forward=None, in_flight=3, batch=1, forward_batch=1,
+                          ignore_below=None):
+    """generate_train_gt.py:78-106 over many images (its loop over the 10 582 images of train_aug): items is an iterable of
+    (image (H,W,3) RGB, image-level labels); a generator of (H,W) int64 masks in order, each restricted to background + the
+    image's labels.  The images are taken forward_batch = G at a time (the tail group is padded with zero inputs): one
+    dsrg_preprocess_ms_batch launch at `size` (into the static input of `forward`'s graph where `forward` is a GraphedForward), ONE
+    batch-G forward and one dsrg_train_gt_unary_batch (softmax at map resolution, zoom of the probabilities, clamp, log).
+    smooth: the full-resolution CRFs run on `in_flight` worker streams under the next group's forward (batch > 1: consecutive
+    same-sized images share one batched CRF call) and end in the restricted MAP of dsrg_crf_map_select; otherwise the labels are
+    the kernel's own restricted arg-max of the clamped probabilities.  ignore_below: pixels whose largest probability / marginal
+    over all labels is below it get 255 (the reference's commented-out line 104); None: off.  forward_batch=1 is the per-image
+    route on the same kernels.  A batch-G forward need not round as a batch-1 forward does: the masks are predict_train_gt's
+    except where two labels all but tie."""
+    from . import ops
+    size = int(size)
+
+    def group_results():
+        for group in _forward_groups(items, forward_batch):
+            real = [it for it in group if it is not None]
+            dev_images, xs = _batched_inputs([None if it is None else it[0] for it in group], (size,), device, forward)
+            with _eval_mode(net):
+                scores = (forward or net)(xs[0]).float().contiguous()
+            shapes = [(im.shape[0], im.shape[1]) for im in dev_images]
+            select = [train_gt_selection(labels) for _, labels in real]
+            if smooth:
+                unaries = ops.train_gt_unary_batch(scores, shapes, eps=0.00001, want="unary")
+                for triple in zip(dev_images, unaries, select):
+                    yield triple
+            else:
+                for lab in ops.train_gt_unary_batch(scores, shapes, eps=0.00001, want="labels", select=select,
+                                                    ignore_below=ignore_below):
+                    yield lab
+
+    if smooth:
+        yield from _crf_in_flight(group_results(), device, in_flight, batch, ignore_below)
+        return
+    for lab in group_results():
+        yield lab.cpu().numpy().astype(np.int64)
 
 
 class ConfusionMatrix(object):

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import CrfParams, check
+from .crf import select_arrays
 
 
 def _stream():
@@ -456,6 +457,64 @@ def multiscale_unary_batch(scores, shapes, eps=1e-5, want=("unary",)):
     Ws = (ctypes.c_int32 * G)(*[W for _, W in shapes])
     check(_lib.lib().dsrg_multiscale_unary_batch(G, K, int(C), ptrs, hs, ws, Hs, Ws, float(eps), ptr_array("unary"),
                                                  ptr_array("argmax"), ptr_array("sum"), _stream()))
+    if single:
+        return out[names[0]]
+    return [tuple(out[n][g] for n in names) for g in range(G)]
+
+
+_TG_OUTPUTS = ("unary", "probs", "labels")
+
+
+def train_gt_unary_batch(scores, shapes, eps=1e-5, want=("unary",), select=None, ignore_below=None):
+    """generate_train_gt.py:85-104 after the forward, for the G images of a group (dsrg_train_gt_unary_batch): softmax over
+    labels at map resolution, the probabilities zoomed to each image's H x W, clamped at eps.  scores: ONE (Gcap, C, h, w) float32
+    CUDA tensor, image g reads slice g; shapes: the G <= min(Gcap, 16) output sizes (H_g, W_g).  want: names among "unary"
+    ((H, W, C) f32 log-probabilities, the layout CRF_device takes), "probs" ((H, W, C) f32, for parity checks) and "labels"
+    ((H, W) int32: per pixel the first maximum over the image's list select[g] — an ordered sequence of 1..128 labels, e.g.
+    inference.train_gt_selection(labels) — or 255 where the largest probability over all labels is below ignore_below; None or
+    <= 0: off).  A string returns the list of that one tensor per image, a sequence a list of tuples in its order.  Image g's
+    results equal those of a G = 1 call on slice g bit for bit.  Runs on torch's current stream; the workspace (G * C * h * w
+    floats) is a torch tensor."""
+    single = isinstance(want, str)
+    names = (want,) if single else tuple(want)
+    for n in names:
+        if n not in _TG_OUTPUTS:
+            raise ValueError("unknown output %r (choose from %s)" % (n, ", ".join(_TG_OUTPUTS)))
+    if not names:
+        raise ValueError("want names no output")
+    if not torch.is_tensor(scores):
+        raise ValueError("scores must be one (Gcap, C, h, w) tensor")
+    scores = _f32c(scores, "scores")
+    if scores.dim() != 4:
+        raise ValueError("score maps must be (Gcap, C, h, w); got %s" % (tuple(scores.shape),))
+    shapes = [(int(H), int(W)) for H, W in shapes]
+    Gcap, C, h, w = scores.shape
+    G, dev = len(shapes), scores.device
+    if not 1 <= G <= Gcap:
+        raise ValueError("%d output shapes for score maps of %d images" % (G, Gcap))
+    sel = nsel = None
+    stride = 0
+    if "labels" in names:
+        if select is None:
+            raise ValueError('want="labels" needs one selection list per image (select=...)')
+        sel, nsel, stride = select_arrays(select, G, C)
+    out = {}
+    if "unary" in names:
+        out["unary"] = [torch.empty((H, W, C), dtype=torch.float32, device=dev) for H, W in shapes]
+    if "probs" in names:
+        out["probs"] = [torch.empty((H, W, C), dtype=torch.float32, device=dev) for H, W in shapes]
+    if "labels" in names:
+        out["labels"] = [torch.empty((H, W), dtype=torch.int32, device=dev) for H, W in shapes]
+    workspace = torch.empty((G, C, h, w), dtype=torch.float32, device=dev)
+
+    def ptr_array(name):
+        return (ctypes.c_void_p * G)(*[t.data_ptr() for t in out[name]]) if name in out else None
+
+    Hs = (ctypes.c_int32 * G)(*[H for H, _ in shapes])
+    Ws = (ctypes.c_int32 * G)(*[W for _, W in shapes])
+    check(_lib.lib().dsrg_train_gt_unary_batch(G, int(C), _ptr(scores), int(h), int(w), Hs, Ws, float(eps), sel, nsel, int(stride),
+                                               float(ignore_below or 0.0), _ptr(workspace), ptr_array("unary"), ptr_array("probs"),
+                                               ptr_array("labels"), _stream()))
     if single:
         return out[names[0]]
     return [tuple(out[n][g] for n in names) for g in range(G)]

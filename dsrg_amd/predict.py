@@ -3,13 +3,16 @@
   --mode ms    <-> training/tools/test-ms.py    (absolute sizes, default 241,321,401; pseudo labels)
   --mode ms-f  <-> training/tools/test-ms-f.py  (sizes relative to each image, default 0.75,1,1.25; the final test)
   --mode ms --scales 481 --class 81  <-> training/tools/test-coco.py:108-135 (single-scale COCO test)
+  --mode gt --cues PICKLE  <-> training/tools/generate_train_gt.py (one size, default 321; labels restricted to background + the
+               image-level labels '<id>_labels' of the cue pickle; --images holds the reference's input_list.txt lines "name.jpg <id>")
 
 Reads DIR/JPEGImages/<id>.jpg for every id of --images, writes OUT/<id>.png: 8-bit grayscale class ids, what
 training/tools/evaluate.py reads (and `python -m dsrg_amd.evaluate`).  The network is VGG16-ASPP with the weights of --model
 (checkpoint.load_weights: .caffemodel, .npz or a torch file), run under bf16 autocast (--fp32: float32, the reference's
 precision); forwards replay from captured HIP graphs (inference.GraphedForward, bounded for the relative scales) while the
 CRFs of earlier images are in flight (inference.predict_masks_ms_many / predict_masks_ms_f_many).  --mode ms --forward-batch N
-takes the images N at a time through batch-N forwards (the absolute sizes are the same for every image).
+takes the images N at a time through batch-N forwards (the absolute sizes are the same for every image); so does --mode gt
+(inference.predict_train_gt_many).
 """
 import argparse
 import os
@@ -18,22 +21,32 @@ import sys
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="multi-scale test: label PNGs for a list of images")
-    p.add_argument("--mode", choices=("ms", "ms-f"), required=True,
-                   help="ms: absolute sizes (test-ms.py); ms-f: sizes relative to each image (test-ms-f.py)")
+    p.add_argument("--mode", choices=("ms", "ms-f", "gt"), required=True,
+                   help="ms: absolute sizes (test-ms.py); ms-f: sizes relative to each image (test-ms-f.py); "
+                        "gt: pseudo labels restricted to the image-level labels (generate_train_gt.py)")
     p.add_argument("--model", required=True, help="weights (.caffemodel, .npz or torch file)")
-    p.add_argument("--images", required=True, help="list of image ids, one per line")
+    p.add_argument("--images", required=True, help="list of image ids, one per line (gt: lines 'name.jpg <id>')")
+    p.add_argument("--cues", default=None, help="gt: the localisation-cue pickle holding '<id>_labels' for every image")
     p.add_argument("--dir", required=True, help="dataset root holding JPEGImages/")
     p.add_argument("--output", required=True, help="directory for the <id>.png label maps")
     p.add_argument("--smooth", action="store_true", help="dense-CRF post-processing (as the reference's --smooth)")
     p.add_argument("--scales", default=None,
-                   help="comma-separated: sizes in pixels (ms; default 241,321,401) or factors (ms-f; default 0.75,1,1.25)")
+                   help="comma-separated: sizes in pixels (ms; default 241,321,401) or factors (ms-f; default 0.75,1,1.25); "
+                        "gt: one size (default 321)")
     p.add_argument("--class", dest="num_classes", type=int, default=21, help="number of classes including background")
     p.add_argument("--fp32", action="store_true", help="float32 forwards instead of bf16 autocast")
     p.add_argument("--in-flight", type=int, default=3, help="CRFs in flight under the next image's forwards")
     p.add_argument("--max-graphs", type=int, default=12, help="ms-f: captured forward graphs kept (least recently used dropped)")
     p.add_argument("--forward-batch", type=int, default=1,
-                   help="ms: images per batched forward (1..16; default 1: one image per forward)")
+                   help="ms, gt: images per batched forward (1..16; default 1: one image per forward)")
     a = p.parse_args(argv)
+    if a.mode == "gt":
+        if not a.cues:
+            p.error("--mode gt needs --cues (the pickle with the image-level labels)")
+        if a.scales is not None and len(a.scales.split(",")) != 1:
+            p.error("--mode gt takes one size in --scales")
+    elif a.cues:
+        p.error("--cues is for --mode gt only")
     if a.mode == "ms-f" and a.forward_batch != 1:
         p.error("--forward-batch is for --mode ms only: the relative scales of ms-f give every image size its own input shapes")
     if not 1 <= a.forward_batch <= 16:
@@ -43,6 +56,18 @@ def parse_args(argv=None):
 
 def read_ids(path):
     return [l.strip() for l in open(path) if l.strip()]
+
+
+def read_gt_list(path):
+    """the lines of the reference's input_list.txt, 'name.jpg <id>' (generate_train_gt.py:117-122) -> [(name without extension, id)]"""
+    out = []
+    for line in open(path):
+        parts = line.strip().split()
+        if parts:
+            if len(parts) < 2:
+                raise ValueError("%s: expected 'name.jpg <id>', got %r" % (path, line.strip()))
+            out.append((os.path.splitext(parts[0])[0], int(parts[1])))
+    return out
 
 
 def read_image(path):
@@ -68,23 +93,35 @@ def main(argv=None):
     from ._lib import require_gpu
 
     require_gpu()
-    if a.mode == "ms":
+    if a.mode == "gt":
+        from .layers import _open_cue_file
+        scales = (int(a.scales),) if a.scales else (321,)
+        cues = _open_cue_file(os.path.abspath(a.cues))
+    elif a.mode == "ms":
         scales = tuple(int(s) for s in a.scales.split(",")) if a.scales else (241, 321, 401)
     else:
         scales = tuple(float(s) for s in a.scales.split(",")) if a.scales else (0.75, 1.0, 1.25)
     dev = torch.device("cuda", torch.cuda.current_device())
     net = VGG16ASPP(num_classes=a.num_classes).to(dev).to(memory_format=torch.channels_last).eval()
     load_weights(net, a.model)
-    ids = read_ids(a.images)
+    if a.mode == "gt":
+        entries = read_gt_list(a.images)
+        ids = [name for name, _ in entries]
+        gt_labels = [cues['%i_labels' % num] for _, num in entries]
+    else:
+        ids = read_ids(a.images)
     os.makedirs(a.output, exist_ok=True)
     images = (read_image(os.path.join(a.dir, "JPEGImages", i + ".jpg")) for i in ids)
 
-    if a.mode == "ms":
+    if a.mode in ("ms", "gt"):
         fwd = I.GraphedForward(net)                         # one graph per fixed size
     else:                                                   # every image size has its own shapes: keep the common ones
         fwd = I.GraphedForward(net, max_shapes=a.max_graphs, capture_after=2)
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=not a.fp32):
-        if a.smooth:
+        if a.mode == "gt":
+            masks = I.predict_train_gt_many(net, zip(images, gt_labels), smooth=a.smooth, size=scales[0], device=dev, forward=fwd,
+                                            in_flight=a.in_flight, forward_batch=a.forward_batch)
+        elif a.smooth:
             if a.mode == "ms":
                 masks = I.predict_masks_ms_many(net, images, sizes=scales, device=dev, forward=fwd, in_flight=a.in_flight,
                                                 forward_batch=a.forward_batch)

@@ -89,6 +89,16 @@ int dsrg_crf_add_pairwise_energy(dsrg_crf_t h, float w1, float theta_alpha_1, fl
 int dsrg_crf_inference(dsrg_crf_t h, int n_iters, float *out_host);
 /* DenseCRFWrapper::map(int, int*)                               densecrf_wrapper.cpp:39-43 */
 int dsrg_crf_map(dsrg_crf_t h, int n_iters, int32_t *labels_host);
+/* dsrg_crf_map restricted to the labels known to be in the image — the selection of training/tools/generate_train_gt.py:98-104
+ * (probs[:, :, [0] + labels], np.argmax, labels[...]) on the final marginals.  select_host: HOST array of one ordered list per
+ * image of the object (one for dsrg_crf_create objects, `nimages` for batched ones), list b at select_host + b * select_stride,
+ * nselect_host[b] entries (1..128, <= select_stride), each a label of [0, nlabels); duplicates and any order are allowed.  The
+ * label of a pixel is sel[j], j the FIRST index that maximises Q[sel[j]].  ignore_below > 0: pixels whose largest marginal over
+ * ALL labels is below it get 255 (the reference's commented-out line 104); <= 0: off.  The lists are copied before the call
+ * returns.  Every argument is checked before the first device call.  Stream, async and labels_host (host or device pointer,
+ * [npixels]) exactly as dsrg_crf_map. */
+int dsrg_crf_map_select(dsrg_crf_t h, int n_iters, const int32_t *select_host, const int32_t *nselect_host, int select_stride,
+                        float ignore_below, int32_t *labels_host);
 /* Where an object's copies and kernels run (default: the null stream, every call synchronous as the reference's).  With
  * async != 0 the entry points enqueue and return: buffers passed in must be device (or pinned host) memory that stays valid,
  * results are final after dsrg_crf_synchronize.  Objects on different streams overlap their launches — how a test-time loop
@@ -276,6 +286,23 @@ int dsrg_multiscale_unary(int K, int C, const float *const *scores_dev, const in
 int dsrg_multiscale_unary_batch(int G, int K, int C, const float *const *scores_dev, const int32_t *h_host, const int32_t *w_host,
                                 const int32_t *H_host, const int32_t *W_host, float eps, float *const *unary_dev,
                                 int32_t *const *argmax_dev, float *const *sum_dev, void *stream);
+/* The full-resolution tail of the weakly supervised pseudo-label pass (training/tools/generate_train_gt.py:85-104) for G images
+ * whose score maps are the slices of one batched forward: scores_dev (Gcap >= G, C, h, w) f32 NCHW, image g reads slice g.  First
+ * the softmax over labels per MAP pixel in f32 (s - max, expf, sum in label order, divide) into workspace_dev (G * C * h * w
+ * floats, the caller's: nothing is allocated here), then the order-1 zoom of those probabilities to (H_g, W_g) ((in-1)/(out-1)
+ * mapping, blended in double and rounded once to f32) and p = max(p, eps).  G = 1 is the single-image form.  Outputs: HOST arrays
+ * of G device pointers each, or NULL; a class is NULL (or all-NULL) or set for every image, at least one class is required:
+ *   unary_dev  (H, W, C) f32 label-fastest: logf(p), the unary CRF_device takes; 16-byte aligned
+ *   probs_dev  (H, W, C) f32 label-fastest: p itself (parity tests); 16-byte aligned
+ *   labels_dev (H, W) int32: the selection of dsrg_crf_map_select applied to p (the smooth=False result): select_host /
+ *              nselect_host / select_stride / ignore_below as there, one list per image; may be NULL when labels_dev is
+ * 1 <= G <= 16, 1 <= C <= 96, H_g, W_g, h, w >= 1, H_g*W_g*C < 2^31, h*w*C < 2^31; every argument is checked before the first
+ * device call.  Stream-ordered, no host synchronisation, no handle; bit-reproducible (no atomics), and image g's outputs do not
+ * depend on the group. */
+int dsrg_train_gt_unary_batch(int G, int C, const float *scores_dev, int h, int w, const int32_t *H_host, const int32_t *W_host,
+                              float eps, const int32_t *select_host, const int32_t *nselect_host, int select_stride,
+                              float ignore_below, float *workspace_dev, float *const *unary_dev, float *const *probs_dev,
+                              int32_t *const *labels_dev, void *stream);
 /* The network inputs of a group of test images in one launch (training/tools/test-ms.py:68-81 for G images at K sizes):
  * images_dev is a HOST array of G device pointers to (H_g, W_g, 3) RGB uint8 images (H_host / W_host: their sizes), sizes_host K
  * target sizes S_k, mean_host the 3 values subtracted from the B, G, R output channels, out_dev a HOST array of K device
