@@ -630,6 +630,10 @@ extern "C" int dsrg_sgd_pack_f32(int n, float *const *param_dev, const float *co
 extern "C" size_t dsrg_conv_igemm_wgrad_workspace(int ngroups, int B, int H, int W, int cin, int cout, int ksize) {
     return conv_igemm_wgrad_workspace(ngroups, B, H, W, cin, cout, ksize);
 }
+extern "C" int dsrg_conv_igemm_wgrad_splits(int ngroups, int B, int H, int W, int cin, int cout, int ksize, const int *dilation,
+                                            int *splits_out) {
+    return conv_igemm_wgrad_splits(ngroups, B, H, W, cin, cout, ksize, dilation, splits_out);
+}
 extern "C" int dsrg_conv_igemm_wgrad_bf16(const void *const *x_dev, const void *const *g_dev, void *const *gw_dev, const int *dilation,
                                           int ngroups, void *workspace_dev, size_t workspace_bytes, int B, int H, int W, int cin,
                                           int cout, int ksize, int out_bf16, void *stream) {

@@ -293,6 +293,7 @@ size_t conv_igemm_colsum_workspace(int ngroups, int B, int H, int W, int cout);
 size_t conv_igemm_workspace();
 int conv_igemm_workspace_status(const void *workspace, hipStream_t stream, int *status);
 size_t conv_igemm_wgrad_workspace(int ngroups, int B, int H, int W, int cin, int cout, int k);
+int conv_igemm_wgrad_splits(int ngroups, int B, int H, int W, int cin, int cout, int k, const int *dil, int *splits);
 int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *const *gw, const int *dil, int ngroups, void *workspace,
                             size_t workspace_bytes, int B, int H, int W, int cin, int cout, int k, int out_bf16, hipStream_t stream);
 int launch_pack_conv_weight(const float *w, void *fwd, void *dgrad, int cout, int cin, int k, hipStream_t stream, int plain = 0,

@@ -790,14 +790,24 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_sk_kernel(IgemmSkArgs k) {
 //     position p ^ (r & 3) so that the four pixel rows of a transposing read hit four different bank quarters;
 //   * the x rows are the g rows' pixels shifted by the tile's tap (zero outside the map, per lane, by the descriptor's range
 //     check); (row, column) of a lane's pixels advance incrementally by 64 pixels per step — no division in the loop;
-//   * 9 * cin * cout / 65536 tiles are far fewer than CUs, so the pixel range is split over `ksplit` workgroups per tile
+//   * 9 * cin * cout / 65536 tiles are far fewer than CUs, so the pixel range of a tile is split over several workgroups
 //     (chosen by the launcher to fill whole rounds of the chip); each writes its fp32 partial tile, and a second kernel sums
 //     the partials in a fixed order (deterministic) into the gradient, laid out [n][tap][c] = a channels_last (cout, cin, k, k)
 //     tensor, in fp32 (the master weights' gradient needs no further cast) or bf16.
+//   * the number of splits is one `ksplit` for the whole launch — or, for a launch of dilated 3x3 kernels in the compact pixel
+//     order, a property of the (group, tap): a tile's reduction length is the number of pixels its tap reaches (16 images of
+//     41 x 41: 421 K-steps for a centre tap, 73 for a corner tap of dilation 24), so a uniform split leaves workgroups of 18 to
+//     105 steps and writes four partial copies of a gradient of which many hold a handful of steps.  Such a launch takes a
+//     WORK LIST (`plan`, built by the host once per geometry: build_wgrad_plan) in device memory:
+//       plan[2 (9 grp + tap)], plan[.. + 1] = the tap's split count (0: its rectangle is empty) and the index of its first partial
+//                                             plane (planes of Cout x Cin floats, counted from g[0].part);
+//       plan[72 + e]                        = entry e: grp | tap << 2 | split << 6 | split count << 14, longest entry first.
+//     Entry e belongs to XCD e % 8; an XCD's blocks run through its entries in order, the tiles_n x (Cin / 256) tiles of an entry
+//     (same rows of g and x) side by side.  Splits of one tap still take equal shares of its live pixels.
 struct WgradGroup {
     const uint16_t *x;      // (B, H, W, Cin) bf16: the layer's input
     const uint16_t *g;      // (B, H, W, Cout) bf16: gradient of its output
-    float *part;            // (ksplit, Cout, taps, Cin) f32 partials
+    float *part;            // (ksplit, Cout, taps, Cin) f32 partials — with a work list: the planes (Cout, Cin) of all groups, the same pointer in every group
     int dil, pad_;
 };
 struct IgemmWgradArgs {
@@ -808,7 +818,10 @@ struct IgemmWgradArgs {
     int xcd_mix;            // 1: XCD-interleaved map of the (group, pixel chunk, tile) workgroups (see the kernel); needs 8 | ksplit
     int skip_rows;          // 1: a K-step (64 pixels) whose rows the tile's tap shifts out of the map entirely is not loaded and
                             // not multiplied (its x rows would all be padding zeros)
+    int nent;               // entries of the work list
+    const uint32_t *plan;   // nullptr: `ksplit` splits for every tile; else the work list (needs compact, taps = 9, Cin != 128)
 };
+constexpr int kPlanHdr = 2 * 4 * 9;                        // words in front of the work list's entries
 constexpr int kWRow = 512;                                 // bytes per LDS row: 256 channels
 constexpr int kWTile = 64 * kWRow;                         // 64 pixels
 constexpr int kWStage = 2 * kWTile;
@@ -833,8 +846,20 @@ __device__ __forceinline__ void conv_igemm_wgrad_body(const IgemmWgradArgs &a, c
     // steps, a dilation-6 one 7 %) and an XCD only runs the blocks with its id % 8 — XCD x takes the pixel chunks x, x + 8, ..
     // of EVERY group and tile (order: group, chunk, tile), which keeps a chunk's tiles on one XCD and gives all XCDs the same mix.
     const int tiles = a.tiles_n * a.tiles_c;
-    int grp, split, t;
-    if (a.xcd_mix) {
+    int grp, split, t, ksp = a.ksplit;
+    size_t plane = 0;                                       // work list: the tile's partial plane
+    if (a.plan) {
+        const int ncb_ = (a.Cin + 255) >> 8, tpe = a.tiles_n * ncb_;
+        const int xcd = bid & 7, k = bid >> 3, pos = k / tpe, te = k - pos * tpe, e = pos * 8 + xcd;
+        if (e >= a.nent) return;                            // (the grid is whole rows of 8 entries; workgroup-uniform)
+        const uint32_t w = a.plan[kPlanHdr + e];
+        grp = (int)(w & 3u);
+        const int ptap = (int)((w >> 2) & 15u), tn_ = te / ncb_;
+        split = (int)((w >> 6) & 255u);
+        ksp = (int)((w >> 14) & 255u);
+        t = tn_ * a.tiles_c + ptap * ncb_ + (te - tn_ * ncb_);
+        plane = (size_t)a.plan[2 * (grp * 9 + ptap) + 1] + (size_t)split;
+    } else if (a.xcd_mix) {
         const int id = bid, xcd = id & 7, k = id >> 3;
         if (a.ksplit >= 8) {                                // 8 | ksplit: XCD x owns the chunks x, x + 8, ..
             const int per_group = (a.ksplit >> 3) * tiles;
@@ -878,7 +903,7 @@ __device__ __forceinline__ void conv_igemm_wgrad_body(const IgemmWgradArgs &a, c
     const int rh = max(rh_, 1), rw = max(rw_, 1);                         // (an empty rectangle: no steps at all, see Kc)
     const int area = rh * rw;
     const int Kc = (rh_ > 0 && rw_ > 0) ? a.B * area : 0;
-    const int kchunk = compact ? (((Kc + a.ksplit - 1) / a.ksplit + 63) >> 6) << 6 : a.kchunk;
+    const int kchunk = compact ? (((Kc + ksp - 1) / ksp + 63) >> 6) << 6 : a.kchunk;
     const int mbeg = split * kchunk, mend = min(Kc, mbeg + kchunk);      // [mbeg, mend) of the reduction index
     const int nsteps = mend > mbeg ? (mend - mbeg + 63) >> 6 : 0;
 
@@ -1021,7 +1046,9 @@ __device__ __forceinline__ void conv_igemm_wgrad_body(const IgemmWgradArgs &a, c
         have = more;
     }
     // C[row = channel of g][col = channel of x]: lane holds column l31, rows (reg & 3) + 8 (reg >> 2) + 4 kgrp
-    float *pp = G.part + (size_t)split * ((size_t)Cout * taps * Cin);
+    // (work list: the tile's own plane [n][c]; else split `split` of the whole gradient [n][tap][c])
+    float *pp = a.plan ? G.part + plane * ((size_t)Cout * Cin) : G.part + (size_t)split * ((size_t)Cout * taps * Cin);
+    const size_t prow = a.plan ? (size_t)Cin : (size_t)taps * Cin;
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -1032,7 +1059,7 @@ __device__ __forceinline__ void conv_igemm_wgrad_body(const IgemmWgradArgs &a, c
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
                     const int n = n0 + wn * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kgrp;
-                    pp[((size_t)n * taps + etap) * Cin + c] = acc[i][j][r];
+                    pp[(size_t)n * prow + (a.plan ? 0 : etap * Cin) + c] = acc[i][j][r];
                 }
             }
         }
@@ -1071,11 +1098,17 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_bwd_kernel(IgemmBwdArgs a) 
 }
 
 // gw[e] = sum over the splits of part[s][e], e over [n][tap][c], in split order; float4 per thread; blockIdx.y = the group
-// (the four branches of a grouped launch share ONE reduction launch: 17 -> 11 reduction launches per train step)
+// (the four branches of a grouped launch share ONE reduction launch: 17 -> 11 reduction launches per train step).
+// With a work list (IgemmWgradArgs::plan) the element's own tap says how many partials there are and where: plan[2 (9 grp + tap)]
+// planes of (Cout, Cin) floats from plane plan[.. + 1] on, summed in split order; a tap without a split (its rectangle is
+// empty: no workgroup ran) gets exact zeros.
 struct WgradReduceArgs {
     const float *part[4];
     void *gw[4];
     int ksplit;
+    int cin4;               // work list: float4s per (output channel, tap) = Cin / 4
+    const uint32_t *plan;   // nullptr, or the work list's table
+    size_t plane4;          // work list: float4s per partial plane = Cout * Cin / 4
     size_t n4;
     const float *scale;     // nullptr, or (cout) f32: output channel o's gradient times scale[o] (a constant per-channel factor folded into
     size_t per_o4;          // the kernel the convolution ran with: d/dw = scale * d/d(w scale)); per_o4 = float4s per output channel
@@ -1086,17 +1119,27 @@ __global__ __launch_bounds__(256) void conv_igemm_wgrad_reduce_kernel(WgradReduc
     if (e >= a.n4) return;
     const float4 *p = reinterpret_cast<const float4 *>(a.part[blockIdx.y]) + e;
     void *gw = a.gw[blockIdx.y];
-    float4 s = p[0];
+    int ksplit = a.ksplit;
+    size_t stride = a.n4;
+    if (a.plan) {
+        const size_t n = e / a.per_o4, rem = e - n * a.per_o4;
+        const int tap = (int)(rem / (size_t)a.cin4), c4 = (int)(rem - (size_t)tap * a.cin4);
+        const uint32_t *row = a.plan + 2 * ((int)blockIdx.y * 9 + tap);
+        ksplit = (int)row[0];
+        stride = a.plane4;
+        p = reinterpret_cast<const float4 *>(a.part[0]) + (size_t)row[1] * a.plane4 + n * (size_t)a.cin4 + c4;
+    }
+    float4 s = ksplit > 0 ? p[0] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     int k = 1;
-    for (; k + 8 <= a.ksplit; k += 8) {                      // eight loads in flight, added in split order (the sum's bits do not change)
+    for (; k + 8 <= ksplit; k += 8) {                        // eight loads in flight, added in split order (the sum's bits do not change)
         float4 v[8];
 #pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = p[(size_t)(k + u) * a.n4];
+        for (int u = 0; u < 8; u++) v[u] = p[(size_t)(k + u) * stride];
 #pragma unroll
         for (int u = 0; u < 8; u++) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
     }
-    for (; k < a.ksplit; k++) {
-        const float4 v = p[(size_t)k * a.n4];
+    for (; k < ksplit; k++) {
+        const float4 v = p[(size_t)k * stride];
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
     if (a.scale) {
@@ -1488,7 +1531,9 @@ static bool conv_igemm_wgrad_launchable(int cin, int cout, int k) {
 }
 static int wgrad_col_tiles(int cin, int k) { return (cin == 128 && k == 3) ? (k * k + 1) / 2 : k * k * ((cin + 255) / 256); }
 
-// pixel split of the weight-gradient launch: the number of workgroups per output tile that minimises
+// the UNIFORM pixel split of a weight-gradient launch (every launch but the dilated 3x3 ones in the compact pixel order, whose splits
+// are per (group, tap): build_wgrad_plan; the debug variants 6 / 7 of those; the bound the workspace is sized by): the number of
+// workgroups per output tile that minimises
 // rounds of the chip x (K-steps per workgroup + a fixed cost per workgroup for prologue and the partial tile's write-out)
 // out_bytes: the gradient tensors of all groups — every split writes and the reduction reads that much again, ~2.3 us (one
 // K-step of a workgroup) per 9.2 MB at the rate the reduction kernel streams (the four fc6_k: 75 MB, 8 K-steps per split)
@@ -1517,21 +1562,178 @@ static int wgrad_ksplit_cap(long long M, int ks) {
     return (int)(c < ks ? ks : c);
 }
 
-size_t conv_igemm_wgrad_workspace(int ngroups, int B, int H, int W, int cin, int cout, int k) {
-    if (!conv_igemm_wgrad_launchable(cin, cout, k) || ngroups < 1 || ngroups > 4) return 0;
+// the most partial copies of the gradient any launch of this geometry writes, whatever its dilations
+static int wgrad_ksplit_bound(int ngroups, int B, int H, int W, int cin, int cout, int k) {
     const long long M = (long long)B * H * W;
     const int tiles = ngroups * ((cout + 255) / 256) * wgrad_col_tiles(cin, k);
     int ks = wgrad_ksplit(M, tiles, 256, (double)ngroups * cout * k * k * cin * 4.0);
     const int ks_mix = wgrad_ksplit(M, tiles, 256, (double)ngroups * cout * k * k * cin * 4.0, true);      // (a launch of dilated kernels picks among these)
     if (ks_mix > ks) ks = ks_mix;
     if (ngroups == 1) ks = wgrad_ksplit_cap(M, ks);         // (the merged backward launch may cut a single layer's pixels finer)
-    return (size_t)ngroups * ks * cout * k * k * cin * sizeof(float);
+    return ks;
+}
+// room for the work list of a dilated launch behind the partials: its table and one word per partial plane (a plan never holds
+// more planes than the uniform bound: build_wgrad_plan)
+static size_t wgrad_plan_room(int ngroups, int ks_bound, int cin, int k) {
+    if (k != 3 || cin == 128) return 0;
+    return ((size_t)(kPlanHdr + ngroups * 9 * ks_bound) * sizeof(uint32_t) + 255) / 256 * 256;
+}
+
+size_t conv_igemm_wgrad_workspace(int ngroups, int B, int H, int W, int cin, int cout, int k) {
+    if (!conv_igemm_wgrad_launchable(cin, cout, k) || ngroups < 1 || ngroups > 4) return 0;
+    const int ks = wgrad_ksplit_bound(ngroups, B, H, W, cin, cout, k);
+    return (size_t)ngroups * ks * cout * k * k * cin * sizeof(float) + wgrad_plan_room(ngroups, ks, cin, k);
+}
+
+// ---- the work list of a dilated launch (IgemmWgradArgs::plan).  Split counts per (group, tap) from the tap's live pixels
+// B (H - |dy|) (W - |dx|): for every target length L (K-steps per workgroup) the counts round(steps / L) — at least one, none for an
+// empty rectangle, never so many that a split is empty — give a list of entries that is sorted longest first, dealt to the
+// XCDs in turn and run through the dispatch model merged_makespan uses (an XCD's CUs take its blocks in id order as they free up; a
+// workgroup costs its K-steps + 8); every partial plane is priced as wgrad_ksplit prices it (one K-step per 9.2 MB written and
+// read back).  The cheapest L wins; the planes never outnumber the uniform bound the workspace was sized for.
+struct WgradPlanKey {
+    int B, H, W, cin, cout, ngroups, dil[4], cus;
+    bool operator<(const WgradPlanKey &o) const { return memcmp(this, &o, sizeof(WgradPlanKey)) < 0; }
+};
+struct WgradPlan {
+    std::vector<uint32_t> words;      // table + entries, as the kernels read them
+    int nent = 0, planes = 0;
+};
+static std::mutex g_plan_mutex;
+
+static const WgradPlan *build_wgrad_plan(int ngroups, int B, int H, int W, int cin, int cout, const int *dil) {
+    static std::map<WgradPlanKey, WgradPlan *> memo;      // (entries live as long as the process: launches hold pointers to them)
+    WgradPlanKey key;
+    memset(&key, 0, sizeof(key));
+    key.B = B; key.H = H; key.W = W; key.cin = cin; key.cout = cout; key.ngroups = ngroups; key.cus = igemm_cus();
+    for (int q = 0; q < ngroups; q++) key.dil[q] = dil[q];
+    std::lock_guard<std::mutex> lock(g_plan_mutex);
+    auto it = memo.find(key);
+    if (it != memo.end()) return it->second;
+
+    const int ntap = ngroups * 9, tpe = ((cout + 255) / 256) * ((cin + 255) / 256);
+    const int cap = ntap * wgrad_ksplit_bound(ngroups, B, H, W, cin, cout, 3);
+    const int per_xcd = igemm_cus() / 8 > 0 ? igemm_cus() / 8 : 32;
+    const double plane_price = (double)cout * cin * 4.0 / 9.2e6;
+    std::vector<long long> Kc(ntap);
+    long long max_steps = 1;
+    for (int q = 0; q < ngroups; q++)
+        for (int tap = 0; tap < 9; tap++) {
+            const int rh = H - abs((tap / 3 - 1) * dil[q]), rw = W - abs((tap % 3 - 1) * dil[q]);
+            Kc[q * 9 + tap] = (rh > 0 && rw > 0) ? (long long)B * rh * rw : 0;
+            max_steps = std::max(max_steps, (Kc[q * 9 + tap] + 63) / 64);
+        }
+    struct Entry { int steps, grp, tap, split, count; };
+    auto chunk_of = [&](int i, long long c) { return ((Kc[i] + c - 1) / c + 63) / 64 * 64; };
+    auto count_for = [&](int i, long long L) -> int {                                       // tap i (not empty) at target length L
+        const long long steps = (Kc[i] + 63) / 64;
+        long long c = std::min<long long>(std::max<long long>((steps + L / 2) / L, 1), 128);
+        while (c > 1 && (c - 1) * chunk_of(i, c) >= Kc[i]) c--;                             // (an empty last split)
+        return (int)c;
+    };
+    auto entries_for = [&](std::vector<Entry> &out, const int *cnt) {
+        out.clear();
+        for (int i = 0; i < ntap; i++)
+            for (int s = 0; s < cnt[i]; s++) {
+                const long long ch = chunk_of(i, cnt[i]), beg = s * ch, end = std::min(Kc[i], beg + ch);
+                out.push_back({(int)((end - beg + 63) / 64), i / 9, i % 9, s, cnt[i]});
+            }
+        std::stable_sort(out.begin(), out.end(), [](const Entry &x, const Entry &y) { return x.steps > y.steps; });
+    };
+    auto makespan = [&](const std::vector<Entry> &es) -> double {
+        double worst = 0.0;
+        for (int x = 0; x < 8; x++) {
+            std::priority_queue<double, std::vector<double>, std::greater<double>> cu;
+            for (int c = 0; c < per_xcd; c++) cu.push(0.0);
+            for (size_t e = x; e < es.size(); e += 8)
+                for (int t = 0; t < tpe; t++) {
+                    const double end = cu.top() + es[e].steps + 8;
+                    cu.pop();
+                    cu.push(end);
+                    worst = std::max(worst, end);
+                }
+        }
+        return worst;
+    };
+    std::vector<Entry> es, best_es;
+    int counts[36], prev_counts[36], best_counts[36] = {0};
+    double best = -1.0;
+    auto counts_for = [&](long long L) -> int {                                             // -> planes, without the entries
+        int planes = 0;
+        for (int i = 0; i < ntap; i++) planes += (counts[i] = Kc[i] ? count_for(i, L) : 0);
+        return planes;
+    };
+    // (from the longest workgroups down; ties: the longer workgroups.  An L that cuts every tap as the one before it did is the same
+    // list and is not priced again; the counts grow as L falls, so the search ends at the first L whose planes outgrow the workspace)
+    for (long long L = max_steps; L >= 1; L--) {
+        const int planes = counts_for(L);
+        if (planes > cap) break;
+        if (L < max_steps && !memcmp(counts, prev_counts, sizeof(counts))) continue;
+        memcpy(prev_counts, counts, sizeof(counts));
+        entries_for(es, counts);
+        const double cost = makespan(es) + planes * plane_price;
+        if (best < 0.0 || cost < best) { best = cost; best_es = es; memcpy(best_counts, counts, sizeof(counts)); }
+    }
+    WgradPlan *p = new WgradPlan;
+    p->words.assign(kPlanHdr, 0u);
+    for (int i = 0, plane = 0; i < ntap; i++) {
+        p->words[2 * i] = (uint32_t)best_counts[i];
+        p->words[2 * i + 1] = (uint32_t)plane;
+        plane += best_counts[i];
+        p->planes = plane;
+    }
+    for (const Entry &e : best_es)
+        p->words.push_back((uint32_t)e.grp | (uint32_t)e.tap << 2 | (uint32_t)e.split << 6 | (uint32_t)e.count << 14);
+    p->nent = (int)best_es.size();
+    memo[key] = p;
+    return p;
+}
+
+// does a launch of these kernels take a work list?  3x3 kernels of which one has dilation >= 3, in the compact pixel order (not
+// the variants 6 / 7, not a 128-channel x), and not the weight-gradient half of a merged backward launch
+static bool wgrad_wants_plan(const int *dil, int ngroups, int cin, int k) {
+    if (k != 3 || cin == 128 || !dil || t_force_ksplit > 0 || t_prep_w) return false;
+    if (igemm_variant() == 6 || igemm_variant() == 7) return false;
+    for (int q = 0; q < ngroups; q++)
+        if (dil[q] < 1) return false;
+    for (int q = 0; q < ngroups; q++)
+        if (dil[q] >= 3) return true;
+    return false;
+}
+
+int conv_igemm_wgrad_splits(int ngroups, int B, int H, int W, int cin, int cout, int k, const int *dil, int *splits) {
+    if (ngroups < 1 || ngroups > 4 || !splits || !conv_igemm_wgrad_launchable(cin, cout, k) || (long long)B * H * W <= 0)
+        return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad_splits: 1..4 groups of a geometry conv_igemm_wgrad takes");
+    if (wgrad_wants_plan(dil, ngroups, cin, k)) {
+        const WgradPlan *p = build_wgrad_plan(ngroups, B, H, W, cin, cout, dil);
+        for (int i = 0; i < ngroups * 9; i++) splits[i] = (int)p->words[2 * i];
+        return DSRG_OK;
+    }
+    bool wants_mix = false;
+    for (int q = 0; q < ngroups; q++) wants_mix = wants_mix || (k == 3 && dil && dil[q] >= 3);
+    const int ks = wgrad_ksplit((long long)B * H * W, ngroups * ((cout + 255) / 256) * wgrad_col_tiles(cin, k), 256,
+                                (double)ngroups * cout * k * k * cin * 4.0, wants_mix);
+    for (int i = 0; i < ngroups * k * k; i++) splits[i] = ks;
+    return DSRG_OK;
+}
+
+// The work list reaches its place behind the partials as kernel arguments, in front of EVERY launch that reads it: a store kernel
+// in the launch's own stream (an ordinary kernel node under stream capture), kPlanChunk words per launch (fc6 x4 at batch 16: 132
+// words, one launch of one workgroup).  The host keeps no record of what a workspace holds, so nothing the caller does to it
+// between two calls matters.
+constexpr int kPlanChunk = 960;                            // (a kernel's arguments hold 4 KB)
+struct PlanChunkArgs { uint32_t *dst; int n, pad_; uint32_t w[kPlanChunk]; };
+__global__ void __launch_bounds__(256) conv_igemm_wgrad_plan_kernel(const PlanChunkArgs c) {
+    for (int i = threadIdx.x; i < c.n; i += 256) c.dst[i] = c.w[i];
 }
 
 static int launch_wgrad_reduce(const IgemmWgradArgs &a, void *const *gw, int ngroups, int cin, int cout, int k, int out_bf16, hipStream_t stream) {
     WgradReduceArgs r;
     memset(&r, 0, sizeof(r));
     r.ksplit = a.ksplit;
+    r.plan = a.plan;
+    r.cin4 = cin / 4;
+    r.plane4 = (size_t)cout * cin / 4;
     r.n4 = (size_t)cout * k * k * cin / 4;
     r.scale = t_wgrad_scale;
     r.per_o4 = (size_t)k * k * cin / 4;
@@ -1560,6 +1762,7 @@ int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *co
     a.tiles_c = wgrad_col_tiles(cin, k);
     bool wants_mix = false;                                  // dilated kernels: workgroups of unequal length, see xcd_mix
     for (int q = 0; q < ngroups; q++) wants_mix = wants_mix || (k == 3 && dil && dil[q] >= 3);      // (whatever the variant: tests compare them bit for bit)
+    const WgradPlan *plan = wgrad_wants_plan(dil, ngroups, cin, k) ? build_wgrad_plan(ngroups, B, H, W, cin, cout, dil) : nullptr;
     a.ksplit = t_force_ksplit > 0 ? t_force_ksplit
                                   : wgrad_ksplit(M, ngroups * a.tiles_n * a.tiles_c, 256, (double)ngroups * cout * k * k * cin * 4.0, wants_mix);
     a.kchunk = (int)(((M + a.ksplit - 1) / a.ksplit + 63) / 64 * 64);
@@ -1570,7 +1773,7 @@ int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *co
     for (int q = 0; q < ngroups; q++) {
         a.g[q].x = static_cast<const uint16_t *>(x[q]);
         a.g[q].g = static_cast<const uint16_t *>(g[q]);
-        a.g[q].part = static_cast<float *>(workspace) + (size_t)q * per_group;
+        a.g[q].part = static_cast<float *>(workspace) + (plan ? 0 : (size_t)q * per_group);
         a.g[q].dil = dil ? dil[q] : 1;
         if (!a.g[q].x || !a.g[q].g || !gw[q]) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: null pointer");
     }
@@ -1580,9 +1783,34 @@ int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *co
             (a.ksplit % 8 == 0 || (8 % a.ksplit == 0 && (a.tiles_n * a.tiles_c) % (8 / a.ksplit) == 0))) a.xcd_mix = 1;
         if (a.skip_rows && igemm_variant() != 7 && k == 3 && cin != 128 && a.g[q].dil >= 1) a.compact = 1;      // 7: tests — dead steps skipped in the flat pixel order
     }
+    if (plan) {
+        // the work list lies behind the partials any launch of this geometry may write
+        const size_t room = wgrad_plan_room(ngroups, wgrad_ksplit_bound(ngroups, B, H, W, cin, cout, k), cin, k);
+        if (plan->words.size() * sizeof(uint32_t) > room || (size_t)plan->planes * cout * cin * sizeof(float) > need - room)
+            return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: work list larger than its workspace");
+        uint32_t *dst = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + (need - room));
+        for (size_t at = 0; at < plan->words.size(); at += kPlanChunk) {
+            PlanChunkArgs c;
+            c.dst = dst + at;
+            c.n = (int)std::min<size_t>(kPlanChunk, plan->words.size() - at);
+            c.pad_ = 0;
+            memcpy(c.w, plan->words.data() + at, (size_t)c.n * sizeof(uint32_t));
+            hipLaunchKernelGGL(conv_igemm_wgrad_plan_kernel, dim3(1), dim3(256), 0, stream, c);
+            DSRG_LAUNCH_CHECK();
+        }
+        a.plan = dst;
+        a.nent = plan->nent;
+    }
     if (t_prep_w) {
         *t_prep_w = a;
         *t_prep_grid = a.tiles_per_group * ngroups;
+    } else if (a.plan) {
+        static LdsGrant grant;
+        constexpr size_t lds = 2 * kWStage;
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_wgrad_kernel), lds, grant)) return rc;
+        const int tpe = a.tiles_n * ((cin + 255) / 256);
+        hipLaunchKernelGGL(conv_igemm_wgrad_kernel, dim3((unsigned)((a.nent + 7) / 8 * 8 * tpe)), dim3(512), lds, stream, a);
+        DSRG_LAUNCH_CHECK();
     } else {
         static LdsGrant grant;
         constexpr size_t lds = 2 * kWStage;

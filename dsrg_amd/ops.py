@@ -1299,6 +1299,16 @@ def conv_igemm_wgrad(xs, gs, dilations, ksize, out_dtype=torch.float32, outs=Non
     return gws
 
 
+def conv_igemm_wgrad_splits(n, B, H, W, cin, cout, ksize, dilations):
+    """the pixel splits conv_igemm_wgrad runs for this launch, per (group, tap): a list of n lists of ksize * ksize counts (0: the
+    tap reaches no pixel).  Host only: nothing is launched"""
+    taps = int(ksize) * int(ksize)
+    out = (ctypes.c_int * (n * taps))()
+    check(_lib.lib().dsrg_conv_igemm_wgrad_splits(int(n), int(B), int(H), int(W), int(cin), int(cout), int(ksize),
+                                                   (ctypes.c_int * n)(*[int(d) for d in dilations]), out))
+    return [list(out[g * taps:(g + 1) * taps]) for g in range(n)]
+
+
 def heads_forward(xs, weight, bias):
     """fc8-SEC_k + Eltwise SUM in float32: xs = list of <= 4 (B,K,H,W) bf16 channels_last activations, weight (n,O,K) f32,
     bias (n,O) f32 or None -> (B,O,H,W) float32, NCHW-contiguous (what the supervision path reads)."""

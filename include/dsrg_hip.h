@@ -475,8 +475,16 @@ int dsrg_sgd_pack_f32(int n, float *const *param_dev, const float *const *grad_d
  * (cout, cin, ksize, ksize) tensor, float32 (out_bf16 = 0: the master weights' gradient, no cast behind it) or bf16; fp32
  * accumulation; the pixel range is split over workgroups whose partial tiles are summed in a fixed order (deterministic).
  * x_dev, g_dev, gw_dev, dilation: HOST arrays of ngroups (1..4) entries (the four ASPP branches in one launch).
- * workspace_dev: dsrg_conv_igemm_wgrad_workspace(ngroups, B, H, W, cin, cout, ksize) bytes of device scratch (0 = unsupported). */
+ * A launch of 3x3 kernels of which one has dilation >= 3 splits the pixels per (group, tap), in proportion to the pixels the tap
+ * reaches (a tap that reaches none runs no workgroup, its rows of the gradient are exact zeros); every other launch splits all
+ * its tiles alike.
+ * workspace_dev: dsrg_conv_igemm_wgrad_workspace(ngroups, B, H, W, cin, cout, ksize) bytes of device scratch (0 = unsupported;
+ * the size holds for any dilations).  A launch with per-tap splits writes a small work list into the end of those bytes itself,
+ * in the same stream, every time: the buffer's contents between calls do not matter. */
 size_t dsrg_conv_igemm_wgrad_workspace(int ngroups, int B, int H, int W, int cin, int cout, int ksize);
+/* Read-only query (host only, no launch): the number of pixel splits dsrg_conv_igemm_wgrad_bf16 runs for each (group, tap) of this
+ * launch: splits_out[ksize*ksize * g + tap], 0 for a tap that reaches no pixel. */
+int dsrg_conv_igemm_wgrad_splits(int ngroups, int B, int H, int W, int cin, int cout, int ksize, const int *dilation, int *splits_out);
 int dsrg_conv_igemm_wgrad_bf16(const void *const *x_dev, const void *const *g_dev, void *const *gw_dev, const int *dilation,
                                int ngroups, void *workspace_dev, size_t workspace_bytes, int B, int H, int W, int cin, int cout,
                                int ksize, int out_bf16, void *stream);

@@ -4,8 +4,9 @@ hipBLASLt GEMM with fused bias / ReLU, solutions picked by TunableOp) for the wi
 Prints one line per layer: microseconds (median of the rounds; variants interleaved inside every round) and TFLOP/s.
 
   python tools/igemm_probe.py [--rounds 5] [--iters 10] [--batch 16]
-  python tools/igemm_probe.py --ab A B [--rounds 7]     two debug variants (ops.set_igemm_variant; -1 = the default) of the layer table,
-                                                        interleaved in every round (after --warm seconds of both): every round's time, each arm's spread, the summed table
+  python tools/igemm_probe.py --ab A B [--rounds 7]     two debug variants (ops.set_igemm_variant; -1 = the default) of the layer table and
+                                                        then of the weight-gradient table, interleaved in every round (after --warm seconds of
+                                                        both): every round's time, each arm's spread, each table summed
 """
 import argparse
 import os
@@ -44,6 +45,7 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--ab", type=int, nargs=2, metavar=("A", "B"), default=None)
     ap.add_argument("--warm", type=float, default=1.0, help="--ab: seconds of alternating launches per layer before the timed rounds")
+    ap.add_argument("--wgrad-only", action="store_true", help="--ab: the weight-gradient table alone")
     args = ap.parse_args()
     B = args.batch
     layers = [  # name, H, W, cin, cout, k, dilations (len = groups)
@@ -61,7 +63,9 @@ def main():
         ("conv3_1 128->256 81x81", 81, 81, 128, 256, 3, [1]),
     ]
     if args.ab:
-        return variant_ab(layers, B, args.ab, args.rounds, args.iters, args.warm)
+        if not args.wgrad_only:
+            variant_ab(layers, B, args.ab, args.rounds, args.iters, args.warm)
+        return variant_ab(WGRAD_LAYERS, B, args.ab, args.rounds, args.iters, args.warm, wgrad=True)
     print("%-28s %9s %9s %9s %9s | %8s %8s | %s" % ("layer", "variant", "default", "im2col+mm", "mm only", "TF/s ig", "TF/s old", "max err"))
     for name, H, W, cin, cout, k, dils in layers:
         n = len(dils)
@@ -117,13 +121,15 @@ def main():
     absorb_probe(B, args.rounds, args.iters)
 
 
-def variant_ab(layers, B, ab, rounds, iters, warm_s):
+def variant_ab(layers, B, ab, rounds, iters, warm_s, wgrad=False):
     """two variants of every layer of the table on random operands, alternating inside every round (A B A B ..), stream-K where the
-    launcher picks it (as the train step runs them).  Per layer: every round of both arms, medians, max - min of each arm; then the
+    launcher picks it (as the train step runs them); wgrad: the weight gradient (ops.conv_igemm_wgrad, float32) of the table
+    instead of the forward.  Per layer: every round of both arms, medians, max - min of each arm; then the
     table summed per round — the figure a decision between the two is taken on: the gain of the summed medians against twice the
     spread of arm A's own rounds"""
     arms = ("A = variant %d" % ab[0], "B = variant %d" % ab[1])
-    print("%s, %s; batch %d, %.1f s of warm-up per layer, %d rounds of %d launches each; microseconds per launch" % (arms + (B, warm_s, rounds, iters)))
+    print("%s%s, %s; batch %d, %.1f s of warm-up per layer, %d rounds of %d launches each; microseconds per launch" % (
+        ("weight gradients: " if wgrad else "",) + arms + (B, warm_s, rounds, iters)))
     tot = np.zeros((2, rounds))
     for name, H, W, cin, cout, k, dils in layers:
         n = len(dils)
@@ -132,7 +138,11 @@ def variant_ab(layers, B, ab, rounds, iters, warm_s):
         packed = [ops.pack_conv_weight((torch.randn(cout, cin, k, k, device="cuda") * (2.0 / (cin * k * k)) ** 0.5).bfloat16()) for _ in range(n)]
         bs = [torch.randn(cout, device="cuda") for _ in range(n)]
 
+        gs = [torch.randn(B, cout, H, W, device="cuda").bfloat16().contiguous(memory_format=CL) for _ in range(n)] if wgrad else None
+
         def run():
+            if wgrad:
+                return ops.conv_igemm_wgrad(xs, gs, dils, k)
             return ops.conv_igemm(xs, packed, bs, dils, k, True, stream_k=True)
         t = np.zeros((2, rounds))
         try:
@@ -196,12 +206,15 @@ def absorb_probe(B, rounds, iters):
         print("%-28s %9.1f %9.1f %9.1f" % (name, np.median(t["f"]), np.median(t["s"]), np.median(t["p"])), flush=True)
 
 
+WGRAD_LAYERS = [("conv4_2 512->512", 41, 41, 512, 512, 3, [1]), ("conv4_1 256->512", 41, 41, 256, 512, 3, [1]),
+                ("fc6 512->1024 d12", 41, 41, 512, 1024, 3, [12]), ("fc6 x4 (one launch)", 41, 41, 512, 1024, 3, [6, 12, 18, 24]),
+                ("fc7 1024->1024 1x1", 41, 41, 1024, 1024, 1, [1]), ("fc7 x4 (one launch)", 41, 41, 1024, 1024, 1, [1] * 4),
+                ("conv3_2 256->256 81x81", 81, 81, 256, 256, 3, [1])]
+
+
 def wgrad_probe(B, rounds, iters):
     """the implicit weight gradient against im2col + g^T @ cols (what backbone._ConvFn.backward runs today)"""
-    layers = [("conv4_2 512->512", 41, 41, 512, 512, 3, [1]), ("conv4_1 256->512", 41, 41, 256, 512, 3, [1]),
-              ("fc6 512->1024 d12", 41, 41, 512, 1024, 3, [12]), ("fc6 x4 (one launch)", 41, 41, 512, 1024, 3, [6, 12, 18, 24]),
-              ("fc7 1024->1024 1x1", 41, 41, 1024, 1024, 1, [1]), ("fc7 x4 (one launch)", 41, 41, 1024, 1024, 1, [1] * 4),
-              ("conv3_2 256->256 81x81", 81, 81, 256, 256, 3, [1])]
+    layers = WGRAD_LAYERS
     print("%-28s %9s %9s %9s | %8s %8s | %s" % ("weight gradient", "igemm", "im2col+mm", "mm only", "TF/s ig", "TF/s old", "max err"))
     for name, H, W, cin, cout, k, dils in layers:
         n = len(dils)
