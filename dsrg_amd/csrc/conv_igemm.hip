@@ -30,14 +30,16 @@
 //   * up to four independent problems (the four ASPP branches: same geometry, own input / weights / dilation / output) share
 //     a launch, so that the 424 tiles of one fc6 become 1696 and fill 256 CUs to 95 % instead of 83 %;
 //   * epilogue: bias (+ ReLU) on the fp32 accumulators, bf16 pack, through LDS for 16-byte coalesced NHWC stores.
+//
+// Host side (behind the kernels): every launch is PREPARED (prepare_igemm / prepare_wgrad: validate, fill the argument block,
+// state the grid and the form; nothing is enqueued) and then RUN (run_igemm / run_wgrad, or the merged backward grid over both
+// prepared halves); what a launch depends on is in those functions' parameters.  The decisions themselves — tile maps, class
+// order, pixel splits, work lists, the merged grid's split and order, the debug variants — are plain C++ in igemm_plan.h (which
+// also holds kBM, kBN, kMaxClasses and kPlanHdr), checked on the CPU by tests/test_igemm_plan.py.
 #include "common.h"
+#include "igemm_plan.h"
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <map>
-#include <mutex>
-#include <queue>
 #include <vector>
 
 namespace dsrg {
@@ -49,7 +51,6 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((address_space(3))) void lds_void;
 
-constexpr int kBM = 256, kBN = 256;
 constexpr int kOutRow = 128 * 2 + 16;                      // epilogue: a wave's 64 pixels x 128 channels, padded rows
 constexpr int kOutWave = 64 * kOutRow;
 constexpr uint32_t kOob = 0x80000000u;                     // beyond any descriptor of this kernel: the load returns zeros
@@ -79,7 +80,6 @@ struct IgemmClass {
     uint32_t rect;          // y0 | h << 8 | x0 << 16 | w << 24
     int q0;
 };
-constexpr int kMaxClasses = 9;
 struct IgemmGroup {
     const uint16_t *x;      // (B, H, W, Cin) bf16
     const uint16_t *w;      // (Cout, Cin / 64, taps, 64) bf16
@@ -798,7 +798,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_sk_kernel(IgemmSkArgs k) {
 //     order, a property of the (group, tap): a tile's reduction length is the number of pixels its tap reaches (16 images of
 //     41 x 41: 421 K-steps for a centre tap, 73 for a corner tap of dilation 24), so a uniform split leaves workgroups of 18 to
 //     105 steps and writes four partial copies of a gradient of which many hold a handful of steps.  Such a launch takes a
-//     WORK LIST (`plan`, built by the host once per geometry: build_wgrad_plan) in device memory:
+//     WORK LIST (`plan`, built by the host once per geometry: build_wgrad_plan, igemm_plan.h) in device memory:
 //       plan[2 (9 grp + tap)], plan[.. + 1] = the tap's split count (0: its rectangle is empty) and the index of its first partial
 //                                             plane (planes of Cout x Cin floats, counted from g[0].part);
 //       plan[72 + e]                        = entry e: grp | tap << 2 | split << 6 | split count << 14, longest entry first.
@@ -821,7 +821,6 @@ struct IgemmWgradArgs {
     int nent;               // entries of the work list
     const uint32_t *plan;   // nullptr: `ksplit` splits for every tile; else the work list (needs compact, taps = 9, Cin != 128)
 };
-constexpr int kPlanHdr = 2 * 4 * 9;                        // words in front of the work list's entries
 constexpr int kWRow = 512;                                 // bytes per LDS row: 256 channels
 constexpr int kWTile = 64 * kWRow;                         // 64 pixels
 constexpr int kWStage = 2 * kWTile;
@@ -1194,18 +1193,10 @@ __global__ __launch_bounds__(256) void pack_conv_weight_kernel(const float *w, u
 bool conv_igemm_supported(int cin, int cout, int k) {
     return (k == 1 || k == 3) && cin >= 64 && cin % 64 == 0 && cout >= 128 && cout % 128 == 0;
 }
-// what the launch takes: also a 64-channel output (a wave's 128 output columns half empty: rows of w past cout read zeros through the
-// descriptor, the store skips them) — not the recommended route for a 3x3 layer (conv_direct.hip), but a 1x1 layer over many pixels
-// is bandwidth-bound either way (ResNet res2: 256 -> 64 at 129 x 129 x 10 pixels)
-static bool conv_igemm_launchable(int cin, int cout, int k) {
-    return (k == 1 || k == 3) && cin >= 64 && cin % 64 == 0 && (cout == 64 || (cout >= 128 && cout % 128 == 0));
-}
 
 std::atomic<int> g_igemm_variant{-1};      // dsrg_debug_set_igemm_variant (tests / tools); -1 = the default, 3
-static int igemm_variant() {
-    const int v = g_igemm_variant.load(std::memory_order_relaxed);
-    return (v < 0 || v == 2 || v == 5) ? 3 : v;      // (2, 5: retired experiments — a ring of four 32-deep stages, an early barrier — now the default)
-}
+// read ONCE per public launch; the decoded struct is handed down (igemm_plan.h)
+static IgemmVariant igemm_variant() { return decode_igemm_variant(g_igemm_variant.load(std::memory_order_relaxed)); }
 
 static int igemm_cus() {
     static const int n = [] {
@@ -1247,106 +1238,25 @@ int launch_igemm_colsum(const float *const *parts, float *const *outs, int ngrou
     return DSRG_OK;
 }
 
-// row-aligned pixel tiles (IgemmArgs::row_tiles) when at least two rows fit a tile and the rows a band leaves empty cost less
-// than a tenth of the tiles
-static bool conv_igemm_row_tiles(int H, int W) {
-    if (W > kBM / 2) return false;
-    const int r = kBM / W, bands = (H + r - 1) / r;
-    return (long long)bands * kBM * 10 <= (long long)H * W * 11 + 10LL * kBM;
-}
-// most pixel tiles a launch over B maps of H x W can have per group (flattened or row-aligned): sizes the column-sum scratch
-static size_t conv_igemm_pixel_tiles(int B, int H, int W) {
-    const long long M = (long long)B * H * W;
-    size_t t = (size_t)((M + kBM - 1) / kBM);
-    if (W <= kBM && conv_igemm_row_tiles(H, W)) {
-        const int r = kBM / W;
-        const size_t tr = (size_t)B * ((H + r - 1) / r);
-        if (tr > t) t = tr;
-    }
-    return t;
-}
 size_t conv_igemm_colsum_workspace(int ngroups, int B, int H, int W, int cout) {
     return (size_t)ngroups * conv_igemm_pixel_tiles(B, H, W) * (size_t)cout * sizeof(float);
 }
 
-// ---- class order of a dilated launch's pixels (IgemmArgs::cls_tiles)
-static uint32_t tap_mask_rect(int H, int W, int d, int y0, int y1, int x0, int x1) {      // the taps that reach a pixel of [y0, y1) x [x0, x1)
-    uint32_t m = 0;
-    for (int tap = 0; tap < 9; tap++) {
-        const int dy = (tap / 3 - 1) * d, dx = (tap % 3 - 1) * d;
-        if (std::max(y0, -dy) < std::min(y1, H - dy) && std::max(x0, -dx) < std::min(x1, W - dx)) m |= 1u << tap;
-    }
-    return m;
-}
-// the bands of an axis of n pixels inside each of which the taps -d / +d are either valid for every pixel or for none
-static int axis_bands(int n, int d, int (*out)[2]) {
-    if (d >= n) { out[0][0] = 0; out[0][1] = n; return 1; }
-    const int lo = std::min(d, n - d), hi = std::max(d, n - d), cut[4] = {0, lo, hi, n};
-    int k = 0;
-    for (int i = 0; i < 3; i++)
-        if (cut[i + 1] > cut[i]) { out[k][0] = cut[i]; out[k][1] = cut[i + 1]; k++; }
-    return k;
-}
-struct HostClass { int y0, y1, x0, x1; uint32_t mask; };
-static int build_classes(int H, int W, int d, HostClass *c) {      // most live taps first (ties: map order)
-    int yb[3][2], xb[3][2];
-    const int ny = axis_bands(H, d, yb), nx = axis_bands(W, d, xb);
-    int n = 0;
-    for (int i = 0; i < ny; i++)
-        for (int j = 0; j < nx; j++) c[n++] = HostClass{yb[i][0], yb[i][1], xb[j][0], xb[j][1], tap_mask_rect(H, W, d, yb[i][0], yb[i][1], xb[j][0], xb[j][1])};
-    std::stable_sort(c, c + n, [](const HostClass &a, const HostClass &b) { return __builtin_popcount(a.mask) > __builtin_popcount(b.mask); });
-    return n;
-}
-// K-steps per 64-channel chunk (= live taps summed over the pixel tiles) of one group: class order / row-aligned / flattened tiles
-static long long tile_taps(int B, int H, int W, int d, int mode) {
-    const long long M = (long long)B * H * W;
-    long long tot = 0;
-    if (mode == 2) {                                         // class order
-        HostClass c[kMaxClasses];
-        const int n = build_classes(H, W, d, c);
-        long long q0[kMaxClasses + 1];
-        q0[0] = 0;
-        for (int k = 0; k < n; k++) q0[k + 1] = q0[k] + (long long)B * (c[k].y1 - c[k].y0) * (c[k].x1 - c[k].x0);
-        for (long long t0 = 0; t0 < M; t0 += kBM) {
-            const long long t1 = std::min(M, t0 + kBM);
-            uint32_t m = 0;
-            for (int k = 0; k < n; k++)
-                if (q0[k] < t1 && q0[k + 1] > t0) m |= c[k].mask;
-            tot += __builtin_popcount(m);
-        }
-    } else if (mode == 1) {                                  // whole rows of one image
-        const int r = kBM / W;
-        for (int y0 = 0; y0 < H; y0 += r) tot += (long long)B * __builtin_popcount(tap_mask_rect(H, W, d, y0, std::min(H, y0 + r), 0, W));
-    } else {                                                 // 256 consecutive pixels
-        for (long long t0 = 0; t0 < M; t0 += kBM) {
-            const long long t1 = std::min(M, t0 + kBM);
-            uint32_t m = 0;
-            for (long long p = t0; p < t1;) {                // row by row (a row piece is a rectangle)
-                const int rem = (int)(p % ((long long)H * W)), y = rem / W, x = rem % W;
-                const int x1 = (int)std::min<long long>(W, x + (t1 - p));
-                m |= tap_mask_rect(H, W, d, y, y + 1, x, x1);
-                p += x1 - x;
-            }
-            tot += __builtin_popcount(m);
-        }
-    }
-    return tot;
-}
+// ---- forward / data gradient: prepare_igemm validates and decides, run_igemm launches what was prepared
+namespace {
+struct IgemmLaunch {
+    IgemmSkArgs sk;         // sk.base: the argument block of either form; the rest is filled when stream_k
+    int grid;
+    bool stream_k;          // conv_igemm_sk_kernel instead of conv_igemm_kernel_64x2
+};
 
-// set by launch_conv_igemm_backward around its calls of the two launchers below: they then validate, fill the argument block
-// and return it instead of launching
-static thread_local IgemmArgs *t_prep_d = nullptr;
-static thread_local IgemmWgradArgs *t_prep_w = nullptr;
-static thread_local int *t_prep_grid = nullptr;
-static thread_local int t_force_ksplit = 0;              // launch_conv_igemm_backward: the pixel split it picked for its merged grid
-static thread_local const float *t_wgrad_scale = nullptr; // launch_conv_igemm_backward_residual: per-output factor of the weight gradient (nullptr: none)
-static thread_local const void *t_res = nullptr;         // launch_conv_igemm_residual: the residual of its single group (nullptr: none)
-static thread_local int t_split_cin = 0;                 // launch_conv_igemm_split: the real input channel count (0: ordinary launch)
-
-int launch_conv_igemm(const void *const *x, const void *const *w, const float *const *bias, void *const *y, const int *dil,
-                      int ngroups, int B, int H, int W, int cin, int cout, int k, int relu, float drop_p, unsigned long long seed,
-                      void *workspace, size_t workspace_bytes, hipStream_t stream, const void *const *mask, float out_scale,
-                      float *const *colsum, void *colsum_ws, size_t colsum_ws_bytes) {
+// Besides launch_conv_igemm's public arguments: res — the residual of the single group (IgemmGroup::res) or nullptr; split_cin — split
+// mode: the real input channel count (cin is then the VIRTUAL count 6 * real), 0: an ordinary launch; may_stream_k — false: whole
+// tiles whatever the shape (the halves of a backward).  Launches nothing, enqueues nothing
+int prepare_igemm(const void *const *x, const void *const *w, const float *const *bias, void *const *y, const int *dil, int ngroups, int B, int H,
+                  int W, int cin, int cout, int k, int relu, float drop_p, unsigned long long seed, void *workspace, size_t workspace_bytes,
+                  const void *const *mask, float out_scale, float *const *colsum, void *colsum_ws, size_t colsum_ws_bytes, const void *res,
+                  int split_cin, bool may_stream_k, const IgemmVariant &v, IgemmLaunch &L) {
     if (ngroups < 1 || ngroups > 4) return set_error(DSRG_ERR_INVALID, "conv_igemm: 1..4 groups");
     if (colsum && (!colsum_ws || colsum_ws_bytes < conv_igemm_colsum_workspace(ngroups, B, H, W, cout)))
         return set_error(DSRG_ERR_INVALID, "conv_igemm: column-sum scratch missing or too small");
@@ -1356,8 +1266,8 @@ int launch_conv_igemm(const void *const *x, const void *const *w, const float *c
     const long long M = (long long)B * H * W;
     if (M <= 0 || M * cin * 2 >= 0x7fffffffLL || (long long)cout * k * k * cin * 2 >= 0x7fffffffLL || M * cout * 2 >= 0x7fffffff00LL)
         return set_error(DSRG_ERR_UNSUPPORTED, "conv_igemm: tensor too large for 32-bit buffer offsets");
-    IgemmArgs a;
-    memset(&a, 0, sizeof(a));
+    memset(&L, 0, sizeof(L));
+    IgemmArgs &a = L.sk.base;
     for (int g = 0; g < ngroups; g++) {
         a.g[g].x = static_cast<const uint16_t *>(x[g]);
         a.g[g].w = static_cast<const uint16_t *>(w[g]);
@@ -1366,20 +1276,20 @@ int launch_conv_igemm(const void *const *x, const void *const *w, const float *c
         a.g[g].dil = dil ? dil[g] : 1;
         a.g[g].mask = mask ? static_cast<const uint16_t *>(mask[g]) : nullptr;
         a.g[g].colsum = colsum ? static_cast<float *>(colsum_ws) + (size_t)g * conv_igemm_pixel_tiles(B, H, W) * cout : nullptr;
-        a.g[g].res = static_cast<const uint16_t *>(t_res);
+        a.g[g].res = static_cast<const uint16_t *>(res);
         if (!a.g[g].x || !a.g[g].w || !a.g[g].y || (mask && !mask[g]) || (colsum && !colsum[g]))
             return set_error(DSRG_ERR_INVALID, "conv_igemm: null pointer");
     }
     a.out_scale = out_scale;
     a.xrow = cin * 2;
-    if (t_split_cin > 0) {                                   // launch_conv_igemm_split: cin here is the VIRTUAL channel count 6 * real
-        a.xrow = 3 * t_split_cin * 2;
-        a.cpp = t_split_cin / 64;
+    if (split_cin > 0) {
+        a.xrow = 3 * split_cin * 2;
+        a.cpp = split_cin / 64;
         a.out_f32 = 1;
     }
-    a.skip_taps = igemm_variant() != 6;                      // 6: tests / tools — every tap of every tile, as before round 5
-    const bool fused_bwd = mask || colsum || t_res;
-    if (t_res && (colsum || ngroups != 1 || drop_p != 0.0f || t_split_cin))
+    a.skip_taps = v.skip_dead_steps;
+    const bool fused_bwd = mask || colsum || res;
+    if (res && (colsum || ngroups != 1 || drop_p != 0.0f || split_cin))
         return set_error(DSRG_ERR_UNSUPPORTED, "conv_igemm: a residual goes with one group, no column sums, no dropout");
     a.ngroups = ngroups; a.B = B; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.taps = k * k; a.relu = relu; a.M = (int)M;
     a.tiles_m = (int)((M + kBM - 1) / kBM);
@@ -1390,71 +1300,44 @@ int launch_conv_igemm(const void *const *x, const void *const *w, const float *c
     if (a.drop_thresh > 255) a.drop_thresh = 255;
     a.drop_scale = 256.0f / (float)(256 - (int)a.drop_thresh);
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
-    static LdsGrant grant[2];
-    a.stagger = igemm_variant() >= 3;
-    const bool default_form = igemm_variant() == 3 || igemm_variant() == 8 || igemm_variant() == 9;      // (8 / 9: 3 with one tiling forced)
-    const dim3 block(512);
+    a.stagger = v.stagger;
     // stream-K only where it was measured to win (profiles/r04_igemm_stream_k.txt): a single round that fills at most 60 % of
     // the chip (conv4_1's data gradient: 106 tiles, 115 -> 88 us).  A cut tile costs its workgroups ~25 us (256 KB of
     // accumulators written through, read back, one acquire), which eats the sixth of the chip that 212 tiles leave idle (131 ->
     // 136 us), and launches of several rounds lose less to their last round than the round count suggests (workgroups of
     // different rounds overlap: fc6 x 4, 6.6 rounds, 810 us whole against 902 us dealt out).
     const int units = igemm_cus(), tiles_total = a.tiles_per_group * ngroups, nsteps = (cin / 64) * k * k;
-    const bool sk_wins = tiles_total * 100 <= units * 60, sk_forced = igemm_variant() == 4;      // 4: tests / tools, wherever legal
-    if (!fused_bwd && t_split_cin == 0 && cout % 128 == 0 && workspace && workspace_bytes >= conv_igemm_workspace() && ((default_form && sk_wins) || sk_forced) &&
-        (long long)tiles_total * nsteps >= (long long)units * 8 && tiles_total * 3 >= units) {
-        IgemmSkArgs sk;
-        sk.base = a;
-        sk.base.stagger = 1;
-        sk.ws = static_cast<float *>(workspace);
-        sk.flags = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(workspace) + (size_t)units * (32 * 512 * 16));
-        sk.units = units;
-        sk.tiles_total = tiles_total;
-        constexpr size_t lds = ICfg<64, 2>::LDS;
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_sk_kernel), lds, grant[1])) return rc;
-        DSRG_HIP_CHECK(hipMemsetAsync(sk.flags, 0, sizeof(uint32_t) * ((size_t)units + 1), stream));      // every launch (a graph replays it)
-        hipLaunchKernelGGL(conv_igemm_sk_kernel, dim3(units), block, lds, stream, sk);
-        DSRG_LAUNCH_CHECK();
+    const bool sk_wins = tiles_total * 100 <= units * 60;
+    if (may_stream_k && !fused_bwd && split_cin == 0 && cout % 128 == 0 && workspace && workspace_bytes >= conv_igemm_workspace() &&
+        ((v.stream_k_where_it_wins && sk_wins) || v.stream_k_forced) && (long long)tiles_total * nsteps >= (long long)units * 8 &&
+        tiles_total * 3 >= units) {
+        L.stream_k = true; L.grid = units;
+        a.stagger = 1;
+        L.sk.ws = static_cast<float *>(workspace);
+        L.sk.flags = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(workspace) + (size_t)units * (32 * 512 * 16));
+        L.sk.units = units; L.sk.tiles_total = tiles_total;
         return DSRG_OK;
     }
     // tap skipping makes tiles unequal: spread every group's tiles over all XCDs (conv_igemm_body).  Only then: the layers
     // whose tiles all run the same steps keep the map they were tuned with (neighbouring pixel tiles share rows in one L2)
-    for (int g = 0; g < ngroups; g++)
-        if (a.skip_taps && k == 3 && a.g[g].dil >= 3) a.xcd_mix = 1;
+    int dils[4];
+    for (int g = 0; g < ngroups; g++) {
+        dils[g] = a.g[g].dil;
+        if (a.skip_taps && k == 3 && dils[g] >= 3) a.xcd_mix = 1;
+    }
     const bool rows_ok = a.xcd_mix && W <= kBM && conv_igemm_row_tiles(H, W);
-    if (a.xcd_mix && igemm_variant() != 8 && H <= 255 && W <= 255) {       // 8: tests — round 5's row-aligned tiles
-        // the class order pays where its tiles run fewer K-steps than the tiling it replaces (a map of few tiles has most of them
-        // straddle classes); decided once per geometry
-        struct Key { int B, H, W, d[4], n, rows; bool operator<(const Key &o) const { return memcmp(this, &o, sizeof(Key)) < 0; } };
-        static std::map<Key, bool> memo;
-        static std::mutex memo_mutex;
-        Key key;
-        memset(&key, 0, sizeof(key));
-        key.B = B; key.H = H; key.W = W; key.n = ngroups; key.rows = rows_ok;
-        for (int g = 0; g < ngroups; g++) key.d[g] = a.g[g].dil;
-        bool pays;
-        {
-            std::lock_guard<std::mutex> lock(memo_mutex);
-            auto it = memo.find(key);
-            if (it == memo.end()) {
-                long long now = 0, then = 0;
-                for (int g = 0; g < ngroups; g++) { now += tile_taps(B, H, W, a.g[g].dil, 2); then += tile_taps(B, H, W, a.g[g].dil, rows_ok ? 1 : 0); }
-                it = memo.emplace(key, now * 100 < then * 97).first;
-            }
-            pays = it->second;
-        }
-        if (pays || igemm_variant() == 9) {                  // 9: tests — the class order wherever it is legal
-            a.cls_tiles = 1;
-            for (int g = 0; g < ngroups; g++) {
-                HostClass c[kMaxClasses];
-                const int n = build_classes(H, W, a.g[g].dil, c);
-                long long q0 = 0;
-                a.g[g].ncls = n;
-                for (int k = 0; k < n; k++) {
-                    a.g[g].cls[k].rect = (uint32_t)c[k].y0 | (uint32_t)(c[k].y1 - c[k].y0) << 8 | (uint32_t)c[k].x0 << 16 | (uint32_t)(c[k].x1 - c[k].x0) << 24;
-                    a.g[g].cls[k].q0 = (int)q0;
-                    q0 += (long long)B * (c[k].y1 - c[k].y0) * (c[k].x1 - c[k].x0);
-                }
+    // the class order where it pays, or wherever it is legal when forced (a rectangle encodes coordinates below 256)
+    if (a.xcd_mix && v.class_tiles_allowed && H <= 255 && W <= 255 && (class_order_pays(B, H, W, dils, ngroups, rows_ok) || v.class_tiles_forced)) {
+        a.cls_tiles = 1;
+        for (int g = 0; g < ngroups; g++) {
+            HostClass c[kMaxClasses];
+            const int n = build_classes(H, W, dils[g], c);
+            long long q0 = 0;
+            a.g[g].ncls = n;
+            for (int i = 0; i < n; i++) {
+                a.g[g].cls[i].rect = (uint32_t)c[i].y0 | (uint32_t)(c[i].y1 - c[i].y0) << 8 | (uint32_t)c[i].x0 << 16 | (uint32_t)(c[i].x1 - c[i].x0) << 24;
+                a.g[g].cls[i].q0 = (int)q0;
+                q0 += (long long)B * (c[i].y1 - c[i].y0) * (c[i].x1 - c[i].x0);
             }
         }
     }
@@ -1467,24 +1350,43 @@ int launch_conv_igemm(const void *const *x, const void *const *w, const float *c
         a.tiles_m = B * a.bands;
         a.tiles_per_group = a.tiles_m * a.tiles_n;
     }
-    const dim3 grid(a.xcd_mix ? 8 * ngroups * ((a.tiles_m + 7) / 8) * a.tiles_n : a.tiles_per_group * ngroups);
-    if (t_prep_d) {                                          // launch_conv_igemm_backward: arguments only, it launches the merged kernel
-        *t_prep_d = a;
-        *t_prep_grid = (int)grid.x;
-        return DSRG_OK;
-    }
-    constexpr size_t lds = ICfg<64, 2>::LDS;
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_kernel_64x2), lds, grant[0])) return rc;
-    hipLaunchKernelGGL(conv_igemm_kernel_64x2, grid, block, lds, stream, a);
-    DSRG_LAUNCH_CHECK();
-    if (colsum) {
-        const float *parts[4];
-        for (int g = 0; g < ngroups; g++) parts[g] = a.g[g].colsum;
-        if (int rc = launch_igemm_colsum(parts, colsum, ngroups, a.tiles_m, cout, stream)) return rc;
-    }
+    L.grid = a.xcd_mix ? 8 * ngroups * ((a.tiles_m + 7) / 8) * a.tiles_n : a.tiles_per_group * ngroups;
     return DSRG_OK;
 }
 
+// the prepared launch, then the column-sum pass into colsum (nullptr: the launch kept no column sums)
+int run_igemm(const IgemmLaunch &L, float *const *colsum, hipStream_t stream) {
+    static LdsGrant grant[2];
+    constexpr size_t lds = ICfg<64, 2>::LDS;
+    const IgemmArgs &a = L.sk.base;
+    if (L.stream_k) {
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_sk_kernel), lds, grant[1])) return rc;
+        DSRG_HIP_CHECK(hipMemsetAsync(L.sk.flags, 0, sizeof(uint32_t) * ((size_t)L.sk.units + 1), stream));      // every launch (a graph replays it)
+        hipLaunchKernelGGL(conv_igemm_sk_kernel, dim3(L.grid), dim3(512), lds, stream, L.sk);
+        DSRG_LAUNCH_CHECK();
+        return DSRG_OK;
+    }
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_kernel_64x2), lds, grant[0])) return rc;
+    hipLaunchKernelGGL(conv_igemm_kernel_64x2, dim3(L.grid), dim3(512), lds, stream, a);
+    DSRG_LAUNCH_CHECK();
+    if (colsum) {
+        const float *parts[4];
+        for (int g = 0; g < a.ngroups; g++) parts[g] = a.g[g].colsum;
+        if (int rc = launch_igemm_colsum(parts, colsum, a.ngroups, a.tiles_m, a.Cout, stream)) return rc;
+    }
+    return DSRG_OK;
+}
+}  // namespace
+
+int launch_conv_igemm(const void *const *x, const void *const *w, const float *const *bias, void *const *y, const int *dil,
+                      int ngroups, int B, int H, int W, int cin, int cout, int k, int relu, float drop_p, unsigned long long seed,
+                      void *workspace, size_t workspace_bytes, hipStream_t stream, const void *const *mask, float out_scale,
+                      float *const *colsum, void *colsum_ws, size_t colsum_ws_bytes) {
+    IgemmLaunch L;
+    if (int rc = prepare_igemm(x, w, bias, y, dil, ngroups, B, H, W, cin, cout, k, relu, drop_p, seed, workspace, workspace_bytes, mask, out_scale,
+                               colsum, colsum_ws, colsum_ws_bytes, nullptr, 0, true, igemm_variant(), L)) return rc;
+    return run_igemm(L, colsum, stream);
+}
 
 // A float32 convolution on the bf16 MFMA (forward, one group; layer-level prototype of round 6): x3 = the three bf16 planes of the
 // float32 activation, (B, H, W, 3 cin) with channel index plane * cin + c; w = the packed kernel over 6 cin VIRTUAL channels,
@@ -1496,12 +1398,10 @@ int launch_conv_igemm_split(const void *x3, const void *w, const float *bias, fl
     const void *xp[1] = {x3}, *wp[1] = {w};
     const float *bp[1] = {bias};
     void *yp[1] = {y};
-    const int dils[1] = {dil};
-    t_split_cin = cin;
-    const int rc = launch_conv_igemm(xp, wp, bias ? bp : nullptr, yp, dils, 1, B, H, W, 6 * cin, cout, k, relu, 0.0f, 0ull, nullptr, 0, stream,
-                                     nullptr, 1.0f, nullptr, nullptr, 0);
-    t_split_cin = 0;
-    return rc;
+    IgemmLaunch L;
+    if (int rc = prepare_igemm(xp, wp, bias ? bp : nullptr, yp, &dil, 1, B, H, W, 6 * cin, cout, k, relu, 0.0f, 0ull, nullptr, 0, nullptr, 1.0f,
+                               nullptr, nullptr, 0, nullptr, cin, true, igemm_variant(), L)) return rc;
+    return run_igemm(L, nullptr, stream);
 }
 
 // One group with a residual in the store (IgemmGroup::res): y = post(bf16(conv(x, w) + bias) + res), post = ReLU (relu) and / or
@@ -1512,207 +1412,29 @@ int launch_conv_igemm_residual(const void *x, const void *w, const float *bias, 
     const void *xp[1] = {x}, *wp[1] = {w}, *mp[1] = {mask};
     const float *bp[1] = {bias};
     void *yp[1] = {y};
-    const int dils[1] = {dil};
-    t_res = res;
-    const int rc = launch_conv_igemm(xp, wp, bias ? bp : nullptr, yp, dils, 1, B, H, W, cin, cout, k, relu, 0.0f, 0ull, nullptr, 0, stream,
-                                     mask ? mp : nullptr, 1.0f, nullptr, nullptr, 0);
-    t_res = nullptr;
-    return rc;
+    IgemmLaunch L;
+    if (int rc = prepare_igemm(xp, wp, bias ? bp : nullptr, yp, &dil, 1, B, H, W, cin, cout, k, relu, 0.0f, 0ull, nullptr, 0, mask ? mp : nullptr,
+                               1.0f, nullptr, nullptr, 0, res, 0, true, igemm_variant(), L)) return rc;
+    return run_igemm(L, nullptr, stream);
 }
 
 bool conv_igemm_wgrad_supported(int cin, int cout, int k) {
     return (k == 1 || k == 3) && ((cin >= 256 && cin % 256 == 0) || (cin == 128 && k == 3)) && cout >= 256 && cout % 256 == 0;
 }
-// what the launch takes (conv_igemm_wgrad_supported: where it is the recommended route): any multiples of 64 channels — a tile is 256 outputs
-// x (one tap x 256 inputs), narrower tensors leave part of it empty (ResNet res2 / res3: 64 / 128 channels over 42 - 166 thousand pixels,
-// bandwidth-bound either way)
-static bool conv_igemm_wgrad_launchable(int cin, int cout, int k) {
-    return (k == 1 || k == 3) && cin >= 64 && cin % 64 == 0 && cout >= 64 && cout % 64 == 0;
-}
-static int wgrad_col_tiles(int cin, int k) { return (cin == 128 && k == 3) ? (k * k + 1) / 2 : k * k * ((cin + 255) / 256); }
-
-// the UNIFORM pixel split of a weight-gradient launch (every launch but the dilated 3x3 ones in the compact pixel order, whose splits
-// are per (group, tap): build_wgrad_plan; the debug variants 6 / 7 of those; the bound the workspace is sized by): the number of
-// workgroups per output tile that minimises
-// rounds of the chip x (K-steps per workgroup + a fixed cost per workgroup for prologue and the partial tile's write-out)
-// out_bytes: the gradient tensors of all groups — every split writes and the reduction reads that much again, ~2.3 us (one
-// K-step of a workgroup) per 9.2 MB at the rate the reduction kernel streams (the four fc6_k: 75 MB, 8 K-steps per split)
-// xcd_mix_only: only the splits the XCD-interleaved workgroup map takes (a divisor or a multiple of 8)
-static int wgrad_ksplit(long long M, int tiles, int cus, double out_bytes = 0.0, bool xcd_mix_only = false) {
-    long long best_cost = -1;
-    int best = 1;
-    for (int ks = 1; ks <= 128; ks++) {
-        const long long chunk = ((M + ks - 1) / ks + 63) / 64 * 64;
-        if ((long long)(ks - 1) * chunk >= M) continue;                 // an empty last split
-        if (xcd_mix_only && ks % 8 != 0 && 8 % ks != 0) continue;
-        const long long steps = chunk / 64, rounds = ((long long)tiles * ks + cus - 1) / cus;
-        const long long cost = rounds * (steps + 8) + (long long)(ks * out_bytes / 9.2e6);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = ks; }
-    }
-    return best;
-}
-
-// the finest pixel split launch_conv_igemm_backward may pick for a layer whose stand-alone split is ks: twice as fine, never beyond
-// one 64-pixel step per split
-static int wgrad_ksplit_cap(long long M, int ks) {
-    const long long most = (M + 63) / 64;
-    long long c = 2LL * ks;
-    if (c > most) c = most;
-    if (c > 128) c = 128;
-    return (int)(c < ks ? ks : c);
-}
-
-// the most partial copies of the gradient any launch of this geometry writes, whatever its dilations
-static int wgrad_ksplit_bound(int ngroups, int B, int H, int W, int cin, int cout, int k) {
-    const long long M = (long long)B * H * W;
-    const int tiles = ngroups * ((cout + 255) / 256) * wgrad_col_tiles(cin, k);
-    int ks = wgrad_ksplit(M, tiles, 256, (double)ngroups * cout * k * k * cin * 4.0);
-    const int ks_mix = wgrad_ksplit(M, tiles, 256, (double)ngroups * cout * k * k * cin * 4.0, true);      // (a launch of dilated kernels picks among these)
-    if (ks_mix > ks) ks = ks_mix;
-    if (ngroups == 1) ks = wgrad_ksplit_cap(M, ks);         // (the merged backward launch may cut a single layer's pixels finer)
-    return ks;
-}
-// room for the work list of a dilated launch behind the partials: its table and one word per partial plane (a plan never holds
-// more planes than the uniform bound: build_wgrad_plan)
-static size_t wgrad_plan_room(int ngroups, int ks_bound, int cin, int k) {
-    if (k != 3 || cin == 128) return 0;
-    return ((size_t)(kPlanHdr + ngroups * 9 * ks_bound) * sizeof(uint32_t) + 255) / 256 * 256;
-}
 
 size_t conv_igemm_wgrad_workspace(int ngroups, int B, int H, int W, int cin, int cout, int k) {
-    if (!conv_igemm_wgrad_launchable(cin, cout, k) || ngroups < 1 || ngroups > 4) return 0;
-    const int ks = wgrad_ksplit_bound(ngroups, B, H, W, cin, cout, k);
-    return (size_t)ngroups * ks * cout * k * k * cin * sizeof(float) + wgrad_plan_room(ngroups, ks, cin, k);
-}
-
-// ---- the work list of a dilated launch (IgemmWgradArgs::plan).  Split counts per (group, tap) from the tap's live pixels
-// B (H - |dy|) (W - |dx|): for every target length L (K-steps per workgroup) the counts round(steps / L) — at least one, none for an
-// empty rectangle, never so many that a split is empty — give a list of entries that is sorted longest first, dealt to the
-// XCDs in turn and run through the dispatch model merged_makespan uses (an XCD's CUs take its blocks in id order as they free up; a
-// workgroup costs its K-steps + 8); every partial plane is priced as wgrad_ksplit prices it (one K-step per 9.2 MB written and
-// read back).  The cheapest L wins; the planes never outnumber the uniform bound the workspace was sized for.
-struct WgradPlanKey {
-    int B, H, W, cin, cout, ngroups, dil[4], cus;
-    bool operator<(const WgradPlanKey &o) const { return memcmp(this, &o, sizeof(WgradPlanKey)) < 0; }
-};
-struct WgradPlan {
-    std::vector<uint32_t> words;      // table + entries, as the kernels read them
-    int nent = 0, planes = 0;
-};
-static std::mutex g_plan_mutex;
-
-static const WgradPlan *build_wgrad_plan(int ngroups, int B, int H, int W, int cin, int cout, const int *dil) {
-    static std::map<WgradPlanKey, WgradPlan *> memo;      // (entries live as long as the process: launches hold pointers to them)
-    WgradPlanKey key;
-    memset(&key, 0, sizeof(key));
-    key.B = B; key.H = H; key.W = W; key.cin = cin; key.cout = cout; key.ngroups = ngroups; key.cus = igemm_cus();
-    for (int q = 0; q < ngroups; q++) key.dil[q] = dil[q];
-    std::lock_guard<std::mutex> lock(g_plan_mutex);
-    auto it = memo.find(key);
-    if (it != memo.end()) return it->second;
-
-    const int ntap = ngroups * 9, tpe = ((cout + 255) / 256) * ((cin + 255) / 256);
-    const int cap = ntap * wgrad_ksplit_bound(ngroups, B, H, W, cin, cout, 3);
-    const int per_xcd = igemm_cus() / 8 > 0 ? igemm_cus() / 8 : 32;
-    const double plane_price = (double)cout * cin * 4.0 / 9.2e6;
-    std::vector<long long> Kc(ntap);
-    long long max_steps = 1;
-    for (int q = 0; q < ngroups; q++)
-        for (int tap = 0; tap < 9; tap++) {
-            const int rh = H - abs((tap / 3 - 1) * dil[q]), rw = W - abs((tap % 3 - 1) * dil[q]);
-            Kc[q * 9 + tap] = (rh > 0 && rw > 0) ? (long long)B * rh * rw : 0;
-            max_steps = std::max(max_steps, (Kc[q * 9 + tap] + 63) / 64);
-        }
-    struct Entry { int steps, grp, tap, split, count; };
-    auto chunk_of = [&](int i, long long c) { return ((Kc[i] + c - 1) / c + 63) / 64 * 64; };
-    auto count_for = [&](int i, long long L) -> int {                                       // tap i (not empty) at target length L
-        const long long steps = (Kc[i] + 63) / 64;
-        long long c = std::min<long long>(std::max<long long>((steps + L / 2) / L, 1), 128);
-        while (c > 1 && (c - 1) * chunk_of(i, c) >= Kc[i]) c--;                             // (an empty last split)
-        return (int)c;
-    };
-    auto entries_for = [&](std::vector<Entry> &out, const int *cnt) {
-        out.clear();
-        for (int i = 0; i < ntap; i++)
-            for (int s = 0; s < cnt[i]; s++) {
-                const long long ch = chunk_of(i, cnt[i]), beg = s * ch, end = std::min(Kc[i], beg + ch);
-                out.push_back({(int)((end - beg + 63) / 64), i / 9, i % 9, s, cnt[i]});
-            }
-        std::stable_sort(out.begin(), out.end(), [](const Entry &x, const Entry &y) { return x.steps > y.steps; });
-    };
-    auto makespan = [&](const std::vector<Entry> &es) -> double {
-        double worst = 0.0;
-        for (int x = 0; x < 8; x++) {
-            std::priority_queue<double, std::vector<double>, std::greater<double>> cu;
-            for (int c = 0; c < per_xcd; c++) cu.push(0.0);
-            for (size_t e = x; e < es.size(); e += 8)
-                for (int t = 0; t < tpe; t++) {
-                    const double end = cu.top() + es[e].steps + 8;
-                    cu.pop();
-                    cu.push(end);
-                    worst = std::max(worst, end);
-                }
-        }
-        return worst;
-    };
-    std::vector<Entry> es, best_es;
-    int counts[36], prev_counts[36], best_counts[36] = {0};
-    double best = -1.0;
-    auto counts_for = [&](long long L) -> int {                                             // -> planes, without the entries
-        int planes = 0;
-        for (int i = 0; i < ntap; i++) planes += (counts[i] = Kc[i] ? count_for(i, L) : 0);
-        return planes;
-    };
-    // (from the longest workgroups down; ties: the longer workgroups.  An L that cuts every tap as the one before it did is the same
-    // list and is not priced again; the counts grow as L falls, so the search ends at the first L whose planes outgrow the workspace)
-    for (long long L = max_steps; L >= 1; L--) {
-        const int planes = counts_for(L);
-        if (planes > cap) break;
-        if (L < max_steps && !memcmp(counts, prev_counts, sizeof(counts))) continue;
-        memcpy(prev_counts, counts, sizeof(counts));
-        entries_for(es, counts);
-        const double cost = makespan(es) + planes * plane_price;
-        if (best < 0.0 || cost < best) { best = cost; best_es = es; memcpy(best_counts, counts, sizeof(counts)); }
-    }
-    WgradPlan *p = new WgradPlan;
-    p->words.assign(kPlanHdr, 0u);
-    for (int i = 0, plane = 0; i < ntap; i++) {
-        p->words[2 * i] = (uint32_t)best_counts[i];
-        p->words[2 * i + 1] = (uint32_t)plane;
-        plane += best_counts[i];
-        p->planes = plane;
-    }
-    for (const Entry &e : best_es)
-        p->words.push_back((uint32_t)e.grp | (uint32_t)e.tap << 2 | (uint32_t)e.split << 6 | (uint32_t)e.count << 14);
-    p->nent = (int)best_es.size();
-    memo[key] = p;
-    return p;
-}
-
-// does a launch of these kernels take a work list?  3x3 kernels of which one has dilation >= 3, in the compact pixel order (not
-// the variants 6 / 7, not a 128-channel x), and not the weight-gradient half of a merged backward launch
-static bool wgrad_wants_plan(const int *dil, int ngroups, int cin, int k) {
-    if (k != 3 || cin == 128 || !dil || t_force_ksplit > 0 || t_prep_w) return false;
-    if (igemm_variant() == 6 || igemm_variant() == 7) return false;
-    for (int q = 0; q < ngroups; q++)
-        if (dil[q] < 1) return false;
-    for (int q = 0; q < ngroups; q++)
-        if (dil[q] >= 3) return true;
-    return false;
+    return wgrad_workspace_bytes(ngroups, B, H, W, cin, cout, k);
 }
 
 int conv_igemm_wgrad_splits(int ngroups, int B, int H, int W, int cin, int cout, int k, const int *dil, int *splits) {
     if (ngroups < 1 || ngroups > 4 || !splits || !conv_igemm_wgrad_launchable(cin, cout, k) || (long long)B * H * W <= 0)
         return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad_splits: 1..4 groups of a geometry conv_igemm_wgrad takes");
-    if (wgrad_wants_plan(dil, ngroups, cin, k)) {
-        const WgradPlan *p = build_wgrad_plan(ngroups, B, H, W, cin, cout, dil);
-        for (int i = 0; i < ngroups * 9; i++) splits[i] = (int)p->words[2 * i];
+    if (wgrad_wants_plan(igemm_variant(), dil, ngroups, cin, k)) {
+        const WgradPlan &p = build_wgrad_plan(ngroups, B, H, W, cin, cout, dil, igemm_cus());
+        for (int i = 0; i < ngroups * 9; i++) splits[i] = (int)p.words[2 * i];
         return DSRG_OK;
     }
-    bool wants_mix = false;
-    for (int q = 0; q < ngroups; q++) wants_mix = wants_mix || (k == 3 && dil && dil[q] >= 3);
-    const int ks = wgrad_ksplit((long long)B * H * W, ngroups * ((cout + 255) / 256) * wgrad_col_tiles(cin, k), 256,
-                                (double)ngroups * cout * k * k * cin * 4.0, wants_mix);
+    const int ks = wgrad_uniform_ksplit(ngroups, (long long)B * H * W, cin, cout, k, wgrad_wants_mix(dil, ngroups, k));
     for (int i = 0; i < ngroups * k * k; i++) splits[i] = ks;
     return DSRG_OK;
 }
@@ -1727,53 +1449,42 @@ __global__ void __launch_bounds__(256) conv_igemm_wgrad_plan_kernel(const PlanCh
     for (int i = threadIdx.x; i < c.n; i += 256) c.dst[i] = c.w[i];
 }
 
-static int launch_wgrad_reduce(const IgemmWgradArgs &a, void *const *gw, int ngroups, int cin, int cout, int k, int out_bf16, hipStream_t stream) {
-    WgradReduceArgs r;
-    memset(&r, 0, sizeof(r));
-    r.ksplit = a.ksplit;
-    r.plan = a.plan;
-    r.cin4 = cin / 4;
-    r.plane4 = (size_t)cout * cin / 4;
-    r.n4 = (size_t)cout * k * k * cin / 4;
-    r.scale = t_wgrad_scale;
-    r.per_o4 = (size_t)k * k * cin / 4;
-    for (int q = 0; q < ngroups; q++) { r.part[q] = a.g[q].part; r.gw[q] = gw[q]; }
-    const dim3 rgrid((unsigned)((r.n4 + 255) / 256), (unsigned)ngroups);
-    if (out_bf16) hipLaunchKernelGGL(conv_igemm_wgrad_reduce_kernel<true>, rgrid, dim3(256), 0, stream, r);
-    else hipLaunchKernelGGL(conv_igemm_wgrad_reduce_kernel<false>, rgrid, dim3(256), 0, stream, r);
-    DSRG_LAUNCH_CHECK();
-    return DSRG_OK;
-}
+// ---- weight gradient: prepare_wgrad validates and decides; upload_wgrad_plan, launch_wgrad and reduce_wgrad are the launch's steps
+namespace {
+struct WgradLaunch {
+    IgemmWgradArgs a;
+    const WgradPlan *plan;  // the work list a.plan will hold once uploaded (nullptr: a uniform split)
+    int grid;
+};
 
-int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *const *gw, const int *dil, int ngroups, void *workspace,
-                            size_t workspace_bytes, int B, int H, int W, int cin, int cout, int k, int out_bf16, hipStream_t stream) {
+// forced_ksplit > 0: the weight-gradient half of a merged backward grid, with the pixel split picked for that grid (a uniform split:
+// such a launch takes no work list).  Launches nothing, enqueues nothing
+int prepare_wgrad(const void *const *x, const void *const *g, void *const *gw, const int *dil, int ngroups, void *workspace, size_t workspace_bytes,
+                  int B, int H, int W, int cin, int cout, int k, const IgemmVariant &v, int forced_ksplit, WgradLaunch &L) {
     if (ngroups < 1 || ngroups > 4) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: 1..4 groups");
     if (!conv_igemm_wgrad_launchable(cin, cout, k))
         return set_error(DSRG_ERR_UNSUPPORTED, "conv_igemm_wgrad: cin %% 64 == 0, cout %% 64 == 0, k in (1, 3) required (got %d, %d, %d)", cin, cout, k);
     const long long M = (long long)B * H * W;
     if (M <= 0 || M * cin * 2 >= 0x7fffffffLL || M * cout * 2 >= 0x7fffffffLL)
         return set_error(DSRG_ERR_UNSUPPORTED, "conv_igemm_wgrad: tensor too large for 32-bit buffer offsets");
-    const size_t need = conv_igemm_wgrad_workspace(ngroups, B, H, W, cin, cout, k);
+    const size_t need = wgrad_workspace_bytes(ngroups, B, H, W, cin, cout, k);
     if (!workspace || workspace_bytes < need) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: workspace of %zu bytes needed", need);
-    IgemmWgradArgs a;
-    memset(&a, 0, sizeof(a));
+    memset(&L, 0, sizeof(L));
+    IgemmWgradArgs &a = L.a;
     a.ngroups = ngroups; a.B = B; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.taps = k * k; a.M = (int)M;
     a.tiles_n = (cout + 255) / 256;
     a.tiles_c = wgrad_col_tiles(cin, k);
-    bool wants_mix = false;                                  // dilated kernels: workgroups of unequal length, see xcd_mix
-    for (int q = 0; q < ngroups; q++) wants_mix = wants_mix || (k == 3 && dil && dil[q] >= 3);      // (whatever the variant: tests compare them bit for bit)
-    const WgradPlan *plan = wgrad_wants_plan(dil, ngroups, cin, k) ? build_wgrad_plan(ngroups, B, H, W, cin, cout, dil) : nullptr;
-    a.ksplit = t_force_ksplit > 0 ? t_force_ksplit
-                                  : wgrad_ksplit(M, ngroups * a.tiles_n * a.tiles_c, 256, (double)ngroups * cout * k * k * cin * 4.0, wants_mix);
+    if (forced_ksplit <= 0 && wgrad_wants_plan(v, dil, ngroups, cin, k)) L.plan = &build_wgrad_plan(ngroups, B, H, W, cin, cout, dil, igemm_cus());
+    a.ksplit = forced_ksplit > 0 ? forced_ksplit : wgrad_uniform_ksplit(ngroups, M, cin, cout, k, wgrad_wants_mix(dil, ngroups, k));
     a.kchunk = (int)(((M + a.ksplit - 1) / a.ksplit + 63) / 64 * 64);
     a.tiles_per_group = a.tiles_n * a.tiles_c * a.ksplit;
-    a.stagger = igemm_variant() >= 3;
-    a.skip_rows = igemm_variant() != 6;
+    a.stagger = v.stagger;
+    a.skip_rows = v.skip_dead_steps;
     const size_t per_group = (size_t)a.ksplit * cout * k * k * cin;
     for (int q = 0; q < ngroups; q++) {
         a.g[q].x = static_cast<const uint16_t *>(x[q]);
         a.g[q].g = static_cast<const uint16_t *>(g[q]);
-        a.g[q].part = static_cast<float *>(workspace) + (plan ? 0 : (size_t)q * per_group);
+        a.g[q].part = static_cast<float *>(workspace) + (L.plan ? 0 : (size_t)q * per_group);
         a.g[q].dil = dil ? dil[q] : 1;
         if (!a.g[q].x || !a.g[q].g || !gw[q]) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: null pointer");
     }
@@ -1781,162 +1492,137 @@ int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *co
     for (int q = 0; q < ngroups; q++) {
         if (a.skip_rows && k == 3 && a.g[q].dil >= 3 &&
             (a.ksplit % 8 == 0 || (8 % a.ksplit == 0 && (a.tiles_n * a.tiles_c) % (8 / a.ksplit) == 0))) a.xcd_mix = 1;
-        if (a.skip_rows && igemm_variant() != 7 && k == 3 && cin != 128 && a.g[q].dil >= 1) a.compact = 1;      // 7: tests — dead steps skipped in the flat pixel order
+        if (a.skip_rows && v.wgrad_compact && k == 3 && cin != 128 && a.g[q].dil >= 1) a.compact = 1;
     }
-    if (plan) {
+    L.grid = a.tiles_per_group * ngroups;
+    if (L.plan) {
         // the work list lies behind the partials any launch of this geometry may write
         const size_t room = wgrad_plan_room(ngroups, wgrad_ksplit_bound(ngroups, B, H, W, cin, cout, k), cin, k);
-        if (plan->words.size() * sizeof(uint32_t) > room || (size_t)plan->planes * cout * cin * sizeof(float) > need - room)
+        if (L.plan->words.size() * sizeof(uint32_t) > room || (size_t)L.plan->planes * cout * cin * sizeof(float) > need - room)
             return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: work list larger than its workspace");
-        uint32_t *dst = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + (need - room));
-        for (size_t at = 0; at < plan->words.size(); at += kPlanChunk) {
-            PlanChunkArgs c;
-            c.dst = dst + at;
-            c.n = (int)std::min<size_t>(kPlanChunk, plan->words.size() - at);
-            c.pad_ = 0;
-            memcpy(c.w, plan->words.data() + at, (size_t)c.n * sizeof(uint32_t));
-            hipLaunchKernelGGL(conv_igemm_wgrad_plan_kernel, dim3(1), dim3(256), 0, stream, c);
-            DSRG_LAUNCH_CHECK();
-        }
-        a.plan = dst;
-        a.nent = plan->nent;
+        a.plan = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + (need - room));
+        a.nent = L.plan->nent;
+        L.grid = (a.nent + 7) / 8 * 8 * (a.tiles_n * ((cin + 255) / 256));      // whole rows of 8 entries, an entry's tiles side by side
     }
-    if (t_prep_w) {
-        *t_prep_w = a;
-        *t_prep_grid = a.tiles_per_group * ngroups;
-    } else if (a.plan) {
-        static LdsGrant grant;
-        constexpr size_t lds = 2 * kWStage;
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_wgrad_kernel), lds, grant)) return rc;
-        const int tpe = a.tiles_n * ((cin + 255) / 256);
-        hipLaunchKernelGGL(conv_igemm_wgrad_kernel, dim3((unsigned)((a.nent + 7) / 8 * 8 * tpe)), dim3(512), lds, stream, a);
-        DSRG_LAUNCH_CHECK();
-    } else {
-        static LdsGrant grant;
-        constexpr size_t lds = 2 * kWStage;
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_wgrad_kernel), lds, grant)) return rc;
-        hipLaunchKernelGGL(conv_igemm_wgrad_kernel, dim3(a.tiles_per_group * ngroups), dim3(512), lds, stream, a);
-        DSRG_LAUNCH_CHECK();
-    }
-    if (t_prep_w) return DSRG_OK;                            // (the caller runs the reduction below itself, after its merged launch)
-    return launch_wgrad_reduce(a, gw, ngroups, cin, cout, k, out_bf16, stream);
+    return DSRG_OK;
 }
 
-
-// when the last block of a merged backward grid ends (us): blocks go to the 8 XCDs round-robin by id, an XCD's CUs take its
-// blocks in id order as they free up — nd data-gradient tiles of td us first, then (from the next multiple of 8) nw weight-gradient
-// workgroups of tw us
-static double merged_makespan(int nd, double td, int nw, double tw) {
-    const int per_xcd = igemm_cus() / 8 > 0 ? igemm_cus() / 8 : 32;
-    double worst = 0.0;
-    for (int x = 0; x < 8; x++) {
-        std::priority_queue<double, std::vector<double>, std::greater<double>> cu;
-        for (int c = 0; c < per_xcd; c++) cu.push(0.0);
-        const int ndx = (nd - x + 7) / 8 > 0 ? (nd - x + 7) / 8 : 0, nwx = (nw - x + 7) / 8 > 0 ? (nw - x + 7) / 8 : 0;
-        double end = 0.0;
-        for (int b = 0; b < ndx + nwx; b++) {
-            const double t = cu.top() + (b < ndx ? td : tw);
-            cu.pop();
-            cu.push(t);
-            if (t > end) end = t;
-        }
-        if (end > worst) worst = end;
+int upload_wgrad_plan(const WgradLaunch &L, hipStream_t stream) {
+    if (!L.plan) return DSRG_OK;
+    for (size_t at = 0, n = L.plan->words.size(); at < n; at += kPlanChunk) {
+        PlanChunkArgs c;
+        c.dst = const_cast<uint32_t *>(L.a.plan) + at;
+        c.n = (int)std::min<size_t>(kPlanChunk, n - at);
+        c.pad_ = 0;
+        memcpy(c.w, L.plan->words.data() + at, (size_t)c.n * sizeof(uint32_t));
+        hipLaunchKernelGGL(conv_igemm_wgrad_plan_kernel, dim3(1), dim3(256), 0, stream, c);
+        DSRG_LAUNCH_CHECK();
     }
-    return worst;
+    return DSRG_OK;
 }
 
-// The backward of ONE 3x3 convolution as one launch (conv_igemm_bwd_kernel): data gradient of g with the flipped kernel `wd` (+ the
-// ReLU / Dropout backward and bias gradient of the layer below when `mask` is given, as launch_conv_igemm's fused form) and the
-// weight gradient from (x, g).  Falls back to the two launches where the merged kernel does not apply (grouped launches, the
-// XCD-interleaved or stream-K forms, a 128-channel x): same results either way — the two halves run the very code of the
-// separate kernels on the very argument blocks.
-int launch_conv_igemm_backward(const void *g, const void *wd, const void *x, const void *mask, void *gx, void *gw, int dil, float *bias_grad,
-                               float mask_scale, void *colsum_ws, size_t colsum_ws_bytes, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H,
-                               int W, int cin, int cout, int k, hipStream_t stream) {
+int launch_wgrad(const WgradLaunch &L, hipStream_t stream) {
+    static LdsGrant grant;
+    constexpr size_t lds = 2 * kWStage;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_wgrad_kernel), lds, grant)) return rc;
+    hipLaunchKernelGGL(conv_igemm_wgrad_kernel, dim3((unsigned)L.grid), dim3(512), lds, stream, L.a);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
+// scale: nullptr, or the per-output factor of the gradient (WgradReduceArgs::scale)
+int reduce_wgrad(const IgemmWgradArgs &a, void *const *gw, const float *scale, int out_bf16, hipStream_t stream) {
+    WgradReduceArgs r;
+    memset(&r, 0, sizeof(r));
+    r.ksplit = a.ksplit;
+    r.plan = a.plan;
+    r.cin4 = a.Cin / 4;
+    r.plane4 = (size_t)a.Cout * a.Cin / 4;
+    r.n4 = (size_t)a.Cout * a.taps * a.Cin / 4;
+    r.scale = scale;
+    r.per_o4 = (size_t)a.taps * a.Cin / 4;
+    for (int q = 0; q < a.ngroups; q++) { r.part[q] = a.g[q].part; r.gw[q] = gw[q]; }
+    const dim3 rgrid((unsigned)((r.n4 + 255) / 256), (unsigned)a.ngroups);
+    if (out_bf16) hipLaunchKernelGGL(conv_igemm_wgrad_reduce_kernel<true>, rgrid, dim3(256), 0, stream, r);
+    else hipLaunchKernelGGL(conv_igemm_wgrad_reduce_kernel<false>, rgrid, dim3(256), 0, stream, r);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
+int run_wgrad(const WgradLaunch &L, void *const *gw, const float *scale, int out_bf16, hipStream_t stream) {
+    if (int rc = upload_wgrad_plan(L, stream)) return rc;
+    if (int rc = launch_wgrad(L, stream)) return rc;
+    return reduce_wgrad(L.a, gw, scale, out_bf16, stream);
+}
+}  // namespace
+
+int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *const *gw, const int *dil, int ngroups, void *workspace,
+                            size_t workspace_bytes, int B, int H, int W, int cin, int cout, int k, int out_bf16, hipStream_t stream) {
+    WgradLaunch L;
+    if (int rc = prepare_wgrad(x, g, gw, dil, ngroups, workspace, workspace_bytes, B, H, W, cin, cout, k, igemm_variant(), 0, L)) return rc;
+    return run_wgrad(L, gw, nullptr, out_bf16, stream);
+}
+
+// The backward of ONE convolution as one launch (conv_igemm_bwd_kernel): data gradient of g with the flipped kernel `wd` (+ the
+// ReLU / Dropout backward and bias gradient of the layer below when `mask` is given, as launch_conv_igemm's fused form; + a residual in
+// its store, IgemmGroup::res, when `res` is given) and the weight gradient from (x, g), times gw_scale per output when that is given.
+// Both halves are prepared — whole tiles, no stream-K — and the split and block order of the merged grid come from
+// merged_backward_split (igemm_plan.h).  Where the merged kernel does not apply (a dilation >= 3: the XCD-interleaved forms; the
+// variants without it) the two prepared halves run as two launches: same results either way — the two halves of the merged kernel
+// run the very code of the separate kernels on the very argument blocks.
+static int conv_igemm_backward(const void *g, const void *wd, const void *x, const void *mask, const void *res, void *gx, void *gw,
+                               const float *gw_scale, int dil, float *bias_grad, float mask_scale, void *colsum_ws, size_t colsum_ws_bytes,
+                               void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W, int cin, int cout, int k, hipStream_t stream) {
     // (forward convolution: cin -> cout; g has cout channels, gx and x have cin, gw is (cout, cin, k, k) in float32)
     const void *gp[1] = {g}, *wp[1] = {wd}, *xp[1] = {x}, *mp[1] = {mask};
     void *gxp[1] = {gx}, *gwp[1] = {gw};
     float *bgp[1] = {bias_grad};
-    const int dils[1] = {dil};
-    const bool can_merge = ((k == 3 && dil < 3) || k == 1) && (igemm_variant() == 3 || igemm_variant() == 1 || igemm_variant() == 8 || igemm_variant() == 9);
+    float *const *colsum = bias_grad ? bgp : nullptr;
+    const IgemmVariant v = igemm_variant();
+    IgemmLaunch d;
+    if (int rc = prepare_igemm(gp, wp, nullptr, gxp, &dil, 1, B, H, W, cout, cin, k, 0, 0.0f, 0ull, nullptr, 0, mask ? mp : nullptr, mask_scale,
+                               colsum, colsum_ws, colsum_ws_bytes, res, 0, false, v, d)) return rc;
+    const bool merge = ((k == 3 && dil < 3) || k == 1) && v.merged_backward && !d.sk.base.xcd_mix && d.grid >= 1;
+    const std::pair<int, int> pick = merge ? merged_backward_split(B, H, W, cin, cout, k, d.grid, igemm_cus()) : std::make_pair(0, 0);
+    WgradLaunch w;
+    if (int rc = prepare_wgrad(xp, gp, gwp, &dil, 1, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout, k, v, pick.first, w)) return rc;
+    if (!merge || w.grid < 1) {
+        if (int rc = run_igemm(d, colsum, stream)) return rc;
+        return run_wgrad(w, gwp, gw_scale, 0, stream);
+    }
     IgemmBwdArgs a;
     memset(&a, 0, sizeof(a));
-    int nd = 0, nw = 0, rc = DSRG_OK;
-    if (can_merge) {
-        t_prep_d = &a.d; t_prep_grid = &nd;
-        rc = launch_conv_igemm(gp, wp, nullptr, gxp, dils, 1, B, H, W, cout, cin, k, 0, 0.0f, 0ull, nullptr, 0, stream, mask ? mp : nullptr,
-                               mask_scale, bias_grad ? bgp : nullptr, colsum_ws, colsum_ws_bytes);
-        t_prep_d = nullptr;
-        if (!rc && !a.d.xcd_mix && nd > 0) {
-            // the pixel split of the weight gradient half, chosen for THIS grid: its workgroups fill the CUs the data gradient's
-            // tiles leave idle and then the whole chip; what counts is when the last of them ends (merged_makespan)
-            const long long M = (long long)B * H * W;
-            const int tiles = ((cout + 255) / 256) * wgrad_col_tiles(cin, k), ks0 = wgrad_ksplit(M, tiles, 256, (double)cout * k * k * cin * 4.0), cap = wgrad_ksplit_cap(M, ks0);
-            const double td = ((cout / 64) * k * k + 6) * 1.85;                  // us per data-gradient tile: K-steps + prologue / epilogue
-            double best = -1.0;
-            int best_ks = ks0;
-            // the search simulates up to 2 x 128 grids of ~1 000 blocks — 0.25 - 0.5 ms of host time, as much as the launch runs on the
-            // GPU: decided once per geometry (a ResNet-101 step has 77 of these launches)
-            struct Key { int B, H, W, cin, cout, k, nd; bool operator<(const Key &o) const { return memcmp(this, &o, sizeof(Key)) < 0; } };
-            static std::map<Key, std::pair<int, int>> memo;
-            static std::mutex memo_mutex;
-            Key key;
-            memset(&key, 0, sizeof(key));
-            key.B = B; key.H = H; key.W = W; key.cin = cin; key.cout = cout; key.k = k; key.nd = nd;
-            bool known = false;
-            {
-                std::lock_guard<std::mutex> lock(memo_mutex);
-                auto it = memo.find(key);
-                if (it != memo.end()) { best_ks = it->second.first; a.w_first = it->second.second; known = true; }
-            }
-            // (the block order is searched too for the shapes round 6 added — 1x1 layers, channel counts below 256: their data-gradient
-            // tiles are a few K-steps long, and long weight-gradient workgroups dispatched LAST would run on alone; the 3x3 layers of
-            // the VGG path keep the order they were tuned with)
-            const bool order_free = k == 1 || cin < 256 || cout < 256;
-            for (int ks = 1; ks <= cap && !known; ks++) {
-                const long long chunk = ((M + ks - 1) / ks + 63) / 64 * 64;
-                if ((long long)(ks - 1) * chunk >= M) continue;                  // an empty last split
-                const double tw = (chunk / 64 + 8) * 2.3;                        // us per weight-gradient workgroup: steps + partial tile out
-                const double tail = 3.0 + 2.4 * ks * ((double)cout * k * k * cin / (512.0 * 4608.0));
-                const double t = merged_makespan(nd, td, tiles * ks, tw) + tail;
-                if (best < 0.0 || t < best) { best = t; best_ks = ks; a.w_first = 0; }
-                if (order_free) {
-                    const double t2 = merged_makespan(tiles * ks, tw, nd, td) + tail;
-                    if (t2 < best) { best = t2; best_ks = ks; a.w_first = 1; }
-                }
-            }
-            if (!known) {
-                std::lock_guard<std::mutex> lock(memo_mutex);
-                memo[key] = std::make_pair(best_ks, a.w_first);
-            }
-            t_force_ksplit = best_ks;
-            t_prep_w = &a.w; t_prep_grid = &nw;
-            rc = launch_conv_igemm_wgrad(xp, gp, gwp, dils, 1, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout, k, 0, stream);
-            t_prep_w = nullptr;
-            t_force_ksplit = 0;
-        }
-        t_prep_grid = nullptr;
-        if (rc) return rc;
-    }
-    if (!can_merge || a.d.xcd_mix || nd < 1 || nw < 1) {
-        rc = launch_conv_igemm(gp, wp, nullptr, gxp, dils, 1, B, H, W, cout, cin, k, 0, 0.0f, 0ull, nullptr, 0, stream, mask ? mp : nullptr,
-                               mask_scale, bias_grad ? bgp : nullptr, colsum_ws, colsum_ws_bytes);
-        if (rc) return rc;
-        return launch_conv_igemm_wgrad(xp, gp, gwp, dils, 1, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout, k, 0, stream);
-    }
-    a.nd = nd; a.nd_pad = (nd + 7) & ~7; a.nw = nw; a.nw_pad = (nw + 7) & ~7;
+    a.d = d.sk.base;
+    a.w = w.a;
+    a.nd = d.grid; a.nd_pad = (a.nd + 7) & ~7; a.nw = w.grid; a.nw_pad = (a.nw + 7) & ~7;
+    a.w_first = pick.second;
     static LdsGrant grant;
     constexpr size_t lds = ICfg<64, 2>::LDS > (size_t)(2 * kWStage) ? ICfg<64, 2>::LDS : (size_t)(2 * kWStage);
-    if (int rc2 = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_bwd_kernel), lds, grant)) return rc2;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_bwd_kernel), lds, grant)) return rc;
     hipLaunchKernelGGL(conv_igemm_bwd_kernel, dim3(a.w_first ? a.nw_pad + a.nd : a.nd_pad + a.nw), dim3(512), lds, stream, a);
     DSRG_LAUNCH_CHECK();
     if (bias_grad) {
         const float *parts[1] = {a.d.g[0].colsum};
-        if (int rc2 = launch_igemm_colsum(parts, bgp, 1, a.d.tiles_m, cin, stream)) return rc2;
+        if (int rc = launch_igemm_colsum(parts, bgp, 1, a.d.tiles_m, cin, stream)) return rc;
     }
-    return launch_wgrad_reduce(a.w, gwp, 1, cin, cout, k, 0, stream);
+    return reduce_wgrad(a.w, gwp, gw_scale, 0, stream);
 }
 
+int launch_conv_igemm_backward(const void *g, const void *wd, const void *x, const void *mask, void *gx, void *gw, int dil, float *bias_grad,
+                               float mask_scale, void *colsum_ws, size_t colsum_ws_bytes, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H,
+                               int W, int cin, int cout, int k, hipStream_t stream) {
+    return conv_igemm_backward(g, wd, x, mask, nullptr, gx, gw, nullptr, dil, bias_grad, mask_scale, colsum_ws, colsum_ws_bytes, wgrad_ws,
+                               wgrad_ws_bytes, B, H, W, cin, cout, k, stream);
+}
+
+// launch_conv_igemm_backward with a residual in the data gradient's store (res may be nullptr) and a per-output-channel factor on the
+// weight gradient (gw_scale may be nullptr); no bias gradient.  A ResNet bottleneck convolution's whole backward.
+int launch_conv_igemm_backward_residual(const void *g, const void *wd, const void *x, const void *mask, const void *res, void *gx, void *gw,
+                                        const float *gw_scale, int dil, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W, int cin,
+                                        int cout, int k, hipStream_t stream) {
+    return conv_igemm_backward(g, wd, x, mask, res, gx, gw, gw_scale, dil, nullptr, 1.0f, nullptr, 0, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout,
+                               k, stream);
+}
 
 int launch_pack_conv_weight(const float *w, void *fwd, void *dgrad, int cout, int cin, int k, hipStream_t stream, int plain, const float *scale) {
     if (!w || cout < 64 || cout % 64 || cin < 64 || cin % 64 || (k != 1 && k != 3))
@@ -1946,20 +1632,6 @@ int launch_pack_conv_weight(const float *w, void *fwd, void *dgrad, int cout, in
                        static_cast<uint16_t *>(dgrad), cout, cin, k * k, plain, scale);
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
-}
-
-// launch_conv_igemm_backward with a residual in the data gradient's store (IgemmGroup::res; res may be nullptr) and a per-output-channel
-// factor on the weight gradient (gw_scale may be nullptr); no bias gradient.  A ResNet bottleneck convolution's whole backward.
-int launch_conv_igemm_backward_residual(const void *g, const void *wd, const void *x, const void *mask, const void *res, void *gx, void *gw,
-                                        const float *gw_scale, int dil, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W, int cin,
-                                        int cout, int k, hipStream_t stream) {
-    t_res = res;
-    t_wgrad_scale = gw_scale;
-    const int rc = launch_conv_igemm_backward(g, wd, x, mask, gx, gw, dil, nullptr, 1.0f, nullptr, 0, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout,
-                                              k, stream);
-    t_res = nullptr;
-    t_wgrad_scale = nullptr;
-    return rc;
 }
 
 // tests: the error word of the last stream-K launch that used this workspace (1 = a workgroup gave up waiting); synchronises
