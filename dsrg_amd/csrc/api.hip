@@ -515,6 +515,22 @@ extern "C" int dsrg_preprocess_ms_batch(int G, int capacity, int K, const unsign
     // every argument is checked before the first device call
     return launch_preprocess_ms_batch(G, capacity, K, images, H, W, sizes, mean, out, static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_train_s_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off,
+                                        const int32_t *H, const int32_t *W, const int32_t *cue_off, const int32_t *ncues,
+                                        const int32_t *label_off, const int32_t *nlabels, const int32_t *mirror, int S, int C, int Hm,
+                                        int Wm, const float *mean, float *images, float *cues, float *labels, void *stream) {
+    // every argument is checked before the first device call
+    return launch_train_s_input_batch(B, stage, stage_bytes, image_off, H, W, cue_off, ncues, label_off, nlabels, mirror, S, C, Hm, Wm,
+                                      mean, images, cues, labels, static_cast<hipStream_t>(stream));
+}
+extern "C" int dsrg_train_f_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off,
+                                        const int32_t *label_off, const int32_t *H, const int32_t *W, const int32_t *top,
+                                        const int32_t *left, const int32_t *mirror, int ch, int cw, const float *mean, float scale,
+                                        float ignore_label, float *data, float *label, void *stream) {
+    // every argument is checked before the first device call
+    return launch_train_f_input_batch(B, stage, stage_bytes, image_off, label_off, H, W, top, left, mirror, ch, cw, mean, scale,
+                                      ignore_label, data, label, static_cast<hipStream_t>(stream));
+}
 extern "C" int dsrg_im2col3x3_nhwc16(const void *in, void *out, int B, int H, int W, int C, int dilation, void *stream) {
     if (!in || !out || B < 1 || H < 1 || W < 1 || C < 1 || dilation < 1) return set_error(DSRG_ERR_INVALID, "bad argument");
     return launch_im2col3x3(in, out, B, H, W, C, dilation, static_cast<hipStream_t>(stream));

@@ -264,6 +264,14 @@ int launch_multiscale_unary_batch(int G, int K, int C, const float *const *score
                                   float *const *sum_out, hipStream_t stream);
 int launch_preprocess_ms_batch(int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H, const int32_t *W,
                                const int32_t *sizes, const float *mean, float *const *out, hipStream_t stream);
+int launch_train_s_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *H,
+                               const int32_t *W, const int32_t *cue_off, const int32_t *ncues, const int32_t *label_off,
+                               const int32_t *nlabels, const int32_t *mirror, int S, int C, int Hm, int Wm, const float *mean,
+                               float *images, float *cues, float *labels, hipStream_t stream);
+int launch_train_f_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *label_off,
+                               const int32_t *H, const int32_t *W, const int32_t *top, const int32_t *left, const int32_t *mirror,
+                               int ch, int cw, const float *mean, float scale, float ignore_label, float *data, float *label,
+                               hipStream_t stream);
 int launch_im2col3x3(const void *in, void *out, int B, int H, int W, int C, int dil, hipStream_t stream);
 int launch_col2im3x3(const void *cols, void *out, int B, int H, int W, int C, int dil, hipStream_t stream);
 int launch_relu_bwd_bias(const void *g, const void *y, void *gm, float *bias_grad, float *part, int part_blocks,

@@ -1,0 +1,234 @@
+// The training batches of both stages, assembled on the device from ONE staging buffer of raw bytes that the host fills and
+// uploads with a single copy per batch: the training-side sibling of preprocess_ms_batch_kernel.  Per-image descriptors (byte
+// offsets into the staging buffer, sizes, counts) ride by value in the argument block, at most 32 images (~1 KB).
+//
+// train_s_input_kernel (stage 1): Caffe's ImageData layer (train-s.prototxt:3-22: read, cv::resize to S x S, mean) followed by
+// AnnotationLayer (pylayers.py:346-387).  One launch, two block ranges:
+//   blocks [0, cue0): one thread owns one output pixel of one image (its three channels).  The resize is the 8-bit bilinear
+//     resize stated in DESIGN.md (a restatement of OpenCV's INTER_LINEAR path for 8-bit images: coordinates through double, the
+//     fraction in float, weights rounded half-even to 11 bits, horizontal pass in int32, vertical pass with the >> 4, >> 16, + 2,
+//     >> 2 sequence), then RGB -> BGR, then float(pixel) - mean[c].  All of it is integer arithmetic up to the last subtraction,
+//     so the result is exact or wrong.  KNOWN, ACCEPTED DEVIATION: OpenCV runs an exact 2x shrink (source = 2S on both axes) as
+//     area averaging; this kernel blends bilinearly there as everywhere else.
+//   blocks [cue0, cue0 + B*C): one workgroup owns one (image, class) plane of the cues: it zeroes the plane, passes a barrier,
+//     then walks the image's K (class, row, column) int32 triplets and writes 1.0 for those of its class; thread 0 writes the
+//     image-level label of the class (1.0 for class 0 and for the listed ids).  A triplet outside the planes writes nothing.
+//   One flag per image reverses the last axis of its pixels and cue planes (pylayers.py:384-387) by writing to the mirrored column.
+//
+// train_f_input_kernel (stage 2): data.SimpleTransformer.preprocess (layer.py:169-236) for B images: one thread owns one pixel of
+// one crop: (float(px) - mean[c]) * scale in BGR order (two separately rounded f32 operations) where the crop lies on the image and
+// 0.0 off it; the label byte as float, ignore_label off the image; the mirror reverses both along x.
+//
+// Both: loads are issued unconditionally on clamped indices and selected afterwards; no atomics, no scratch, no LDS, no dependence on
+// the order of workgroups (every output element has exactly one owner; duplicate cue triplets write the same value behind the
+// owner's barrier); -ffp-contract=off (Makefile).  Results are bit-reproducible.
+#include <string.h>
+#include "common.h"
+
+namespace dsrg {
+
+constexpr int kTiThreads = 256;
+constexpr int kTiMaxBatch = 32;
+
+struct TsArgs {
+    int img_off[kTiMaxBatch], H[kTiMaxBatch], W[kTiMaxBatch];       // (H, W, 3) RGB uint8 at stage + img_off
+    int cue_off[kTiMaxBatch], ncue[kTiMaxBatch];                    // (3, K) int32 at stage + cue_off: classes, rows, columns
+    int lab_off[kTiMaxBatch], nlab[kTiMaxBatch];                    // L int32 class ids at stage + lab_off
+    unsigned mirror;                                                // bit b: image b is mirrored
+    float mean[3];                                                  // of the OUTPUT channels (B, G, R)
+};
+
+struct TfArgs {
+    int img_off[kTiMaxBatch], lab_off[kTiMaxBatch];                 // (H, W, 3) RGB uint8 / (H, W) uint8
+    int H[kTiMaxBatch], W[kTiMaxBatch], top[kTiMaxBatch], left[kTiMaxBatch];
+    unsigned mirror;
+    float mean[3], scale, ignore_label;
+};
+
+// source index and the two 11-bit weights of output coordinate d on an axis of n source and S output samples; `zero_at_border`:
+// the x axis' rule (fraction zeroed where the index is clamped), the y axis keeps its fraction and clamps the two rows instead
+__device__ __forceinline__ void resize_tap(int d, int n, int S, bool zero_at_border, int &s, int &w0, int &w1) {
+    const double scale = 1.0 / ((double)S / (double)n);
+    float f = (float)(((double)d + 0.5) * scale - 0.5);
+    s = (int)floorf(f);
+    f -= (float)s;
+    if (zero_at_border) {
+        if (s < 0) { s = 0; f = 0.0f; }
+        if (s >= n - 1) { s = n - 1; f = 0.0f; }
+    }
+    const int r1 = (int)rintf(f * 2048.0f), r0 = (int)rintf((1.0f - f) * 2048.0f);        // round half even; saturate to int16
+    w1 = min(max(r1, -32768), 32767);
+    w0 = min(max(r0, -32768), 32767);
+}
+
+__global__ __launch_bounds__(kTiThreads) void train_s_input_kernel(const unsigned char *__restrict__ stage, TsArgs a, int B, int S, int C,
+                                                                   int Hm, int Wm, int cue0, float *__restrict__ images,
+                                                                   float *__restrict__ cues, float *__restrict__ labels) {
+    const int blk = (int)blockIdx.x;
+    if (blk < cue0) {                                                                       // (uniform over the block)
+        const int SS = S * S;
+        const int idx = blk * kTiThreads + (int)threadIdx.x;                                // (image, y, x) flattened: < B * S * S < 2^31 / 3
+        if (idx >= B * SS) return;
+        const int b = idx / SS, r = idx - b * SS;
+        const int y = r / S, x = r - y * S;
+        const int H = a.H[b], W = a.W[b];
+        int sx, a0, a1, sy, b0, b1;
+        resize_tap(x, W, S, true, sx, a0, a1);
+        resize_tap(y, H, S, false, sy, b0, b1);
+        const int x0 = sx, x1 = min(sx + 1, W - 1);
+        const int y0 = min(max(sy, 0), H - 1), y1 = min(max(sy + 1, 0), H - 1);
+        const unsigned char *im = stage + a.img_off[b];
+        const unsigned char *p00 = im + ((size_t)y0 * W + x0) * 3, *p01 = im + ((size_t)y0 * W + x1) * 3;
+        const unsigned char *p10 = im + ((size_t)y1 * W + x0) * 3, *p11 = im + ((size_t)y1 * W + x1) * 3;
+        const int xo = ((a.mirror >> b) & 1u) ? S - 1 - x : x;
+        float *o = images + (size_t)b * 3 * SS + (size_t)y * S + xo;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {                                                       // output channel c = input channel 2 - c (BGR)
+            const int D0 = (int)p00[2 - c] * a0 + (int)p01[2 - c] * a1;
+            const int D1 = (int)p10[2 - c] * a0 + (int)p11[2 - c] * a1;
+            const int v = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2;
+            o[c * SS] = (float)v - a.mean[c];
+        }
+        return;
+    }
+    const int plane = blk - cue0;                                                           // < B * C
+    const int b = plane / C, c = plane - b * C;
+    const int HW = Hm * Wm, tid = (int)threadIdx.x;
+    float *p = cues + (size_t)plane * HW;
+    for (int i = tid; i < HW; i += kTiThreads) p[i] = 0.0f;
+    __syncthreads();                                                                        // the plane's zeros are complete before its ones
+    const int K = a.ncue[b];
+    const int *t = reinterpret_cast<const int *>(stage + a.cue_off[b]);
+    const bool mir = (a.mirror >> b) & 1u;
+    for (int k = tid; k < K; k += kTiThreads) {
+        const int cls = t[k], yy = t[K + k], xx = t[2 * K + k];
+        if (cls == c && yy >= 0 && yy < Hm && xx >= 0 && xx < Wm) p[yy * Wm + (mir ? Wm - 1 - xx : xx)] = 1.0f;
+    }
+    if (tid == 0) {
+        const int L = a.nlab[b];
+        const int *l = reinterpret_cast<const int *>(stage + a.lab_off[b]);
+        bool present = c == 0;
+        for (int k = 0; k < L; ++k) present = present || l[k] == c;
+        labels[plane] = present ? 1.0f : 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(kTiThreads) void train_f_input_kernel(const unsigned char *__restrict__ stage, TfArgs a, int B, int ch, int cw,
+                                                                   float *__restrict__ data, float *__restrict__ label) {
+    const int P = ch * cw;
+    const int idx = (int)blockIdx.x * kTiThreads + (int)threadIdx.x;                        // (image, y, x) flattened: < B * ch * cw < 2^31 / 3
+    if (idx >= B * P) return;
+    const int b = idx / P, r = idx - b * P;
+    const int y = r / cw, x = r - y * cw;
+    const int H = a.H[b], W = a.W[b];
+    const int sy = a.top[b] + y, sx = a.left[b] + x;                                       // on the extended image (top, left >= 0)
+    const bool on = sy < H && sx < W;
+    const size_t src = (size_t)min(sy, H - 1) * W + min(sx, W - 1);                        // clamped: the loads below are unconditional
+    const unsigned char *px = stage + a.img_off[b] + src * 3;
+    const float lab = (float)stage[(size_t)a.lab_off[b] + src];
+    const int xo = ((a.mirror >> b) & 1u) ? cw - 1 - x : x;
+    const size_t at = (size_t)y * cw + xo;
+    float *o = data + (size_t)b * 3 * P + at;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {                                                           // output channel c = input channel 2 - c (BGR)
+        const float v = ((float)px[2 - c] - a.mean[c]) * a.scale;
+        o[c * P] = on ? v : 0.0f;
+    }
+    label[(size_t)b * P + at] = on ? lab : a.ignore_label;
+}
+
+// `n` bytes at byte offset `off` lie inside the staging buffer?
+static bool inside(long long off, long long n, size_t stage_bytes) {
+    return off >= 0 && n >= 0 && (unsigned long long)off + (unsigned long long)n <= (unsigned long long)stage_bytes;
+}
+
+int launch_train_s_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *H,
+                               const int32_t *W, const int32_t *cue_off, const int32_t *ncues, const int32_t *label_off,
+                               const int32_t *nlabels, const int32_t *mirror, int S, int C, int Hm, int Wm, const float *mean,
+                               float *images, float *cues, float *labels, hipStream_t stream) {
+    if (B < 1 || B > kTiMaxBatch) return set_error(DSRG_ERR_INVALID, "train-s input: 1..%d images, got %d", kTiMaxBatch, B);
+    if (!stage) return set_error(DSRG_ERR_INVALID, "train-s input: NULL staging buffer");
+    if (!image_off || !H || !W) return set_error(DSRG_ERR_INVALID, "train-s input: NULL image offset / image size array");
+    if (!cue_off || !ncues || !label_off || !nlabels) return set_error(DSRG_ERR_INVALID, "train-s input: NULL cue / label descriptor array");
+    if (!mirror || !mean) return set_error(DSRG_ERR_INVALID, "train-s input: NULL mirror / mean array");
+    if (!images || !cues || !labels) return set_error(DSRG_ERR_INVALID, "train-s input: NULL output");
+    if (((uintptr_t)images | (uintptr_t)cues | (uintptr_t)labels) & 3)
+        return set_error(DSRG_ERR_INVALID, "train-s input: an output is not aligned to a float");
+    if (S < 1 || C < 1 || Hm < 1 || Wm < 1) return set_error(DSRG_ERR_INVALID, "train-s input: size %d, %d classes, %dx%d planes", S, C, Hm, Wm);
+    if (stage_bytes >= ((size_t)1 << 31)) return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: staging buffer holds >= 2^31 bytes");
+    if ((long long)B * 3 * S * S >= (1LL << 31))
+        return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: images hold %lld >= 2^31 values", (long long)B * 3 * S * S);
+    if ((long long)B * C * Hm * Wm >= (1LL << 31))
+        return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: cues hold %lld >= 2^31 values", (long long)B * C * Hm * Wm);
+    TsArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int b = 0; b < B; ++b) {
+        if (H[b] < 1 || W[b] < 1) return set_error(DSRG_ERR_INVALID, "train-s input: image %d is %dx%d", b, H[b], W[b]);
+        if ((long long)H[b] * W[b] * 3 >= (1LL << 31)) return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: image %d holds >= 2^31 values", b);
+        if (!inside(image_off[b], (long long)H[b] * W[b] * 3, stage_bytes))
+            return set_error(DSRG_ERR_INVALID, "train-s input: image %d lies outside the staging buffer", b);
+        if (ncues[b] < 0 || nlabels[b] < 0) return set_error(DSRG_ERR_INVALID, "train-s input: image %d has a negative cue / label count", b);
+        if (((uintptr_t)stage + (uintptr_t)(uint32_t)cue_off[b]) & 3 || ((uintptr_t)stage + (uintptr_t)(uint32_t)label_off[b]) & 3)
+            return set_error(DSRG_ERR_INVALID, "train-s input: cues / labels of image %d are not aligned to an int32", b);
+        if (!inside(cue_off[b], 12LL * ncues[b], stage_bytes))
+            return set_error(DSRG_ERR_INVALID, "train-s input: cues of image %d lie outside the staging buffer", b);
+        if (!inside(label_off[b], 4LL * nlabels[b], stage_bytes))
+            return set_error(DSRG_ERR_INVALID, "train-s input: labels of image %d lie outside the staging buffer", b);
+        a.img_off[b] = image_off[b], a.H[b] = H[b], a.W[b] = W[b];
+        a.cue_off[b] = cue_off[b], a.ncue[b] = ncues[b];
+        a.lab_off[b] = label_off[b], a.nlab[b] = nlabels[b];
+        if (mirror[b]) a.mirror |= 1u << b;
+    }
+    for (int c = 0; c < 3; ++c) a.mean[c] = mean[c];
+    const long long n = (long long)B * S * S;
+    const int cue0 = (int)((n + kTiThreads - 1) / kTiThreads);                               // < 2^23
+    const long long blocks = (long long)cue0 + (long long)B * C;                             // B * C < 2^31 / (Hm * Wm)
+    if (blocks >= (1LL << 24))                                                               // a grid holds < 2^32 threads
+        return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: %lld workgroups >= 2^24 (pixel blocks + B * C planes)", blocks);
+    hipLaunchKernelGGL(train_s_input_kernel, dim3((unsigned)blocks), dim3(kTiThreads), 0, stream, stage, a, B, S, C, Hm, Wm, cue0, images,
+                       cues, labels);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
+int launch_train_f_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *label_off,
+                               const int32_t *H, const int32_t *W, const int32_t *top, const int32_t *left, const int32_t *mirror,
+                               int ch, int cw, const float *mean, float scale, float ignore_label, float *data, float *label,
+                               hipStream_t stream) {
+    if (B < 1 || B > kTiMaxBatch) return set_error(DSRG_ERR_INVALID, "train-f input: 1..%d images, got %d", kTiMaxBatch, B);
+    if (!stage) return set_error(DSRG_ERR_INVALID, "train-f input: NULL staging buffer");
+    if (!image_off || !label_off || !H || !W) return set_error(DSRG_ERR_INVALID, "train-f input: NULL offset / image size array");
+    if (!top || !left || !mirror || !mean) return set_error(DSRG_ERR_INVALID, "train-f input: NULL top / left / mirror / mean array");
+    if (!data || !label) return set_error(DSRG_ERR_INVALID, "train-f input: NULL output");
+    if (((uintptr_t)data | (uintptr_t)label) & 3) return set_error(DSRG_ERR_INVALID, "train-f input: an output is not aligned to a float");
+    if (ch < 1 || cw < 1) return set_error(DSRG_ERR_INVALID, "train-f input: crop %dx%d", ch, cw);
+    if (stage_bytes >= ((size_t)1 << 31)) return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: staging buffer holds >= 2^31 bytes");
+    if ((long long)B * 3 * ch * cw >= (1LL << 31))
+        return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: data holds %lld >= 2^31 values", (long long)B * 3 * ch * cw);
+    TfArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int b = 0; b < B; ++b) {
+        if (H[b] < 1 || W[b] < 1) return set_error(DSRG_ERR_INVALID, "train-f input: image %d is %dx%d", b, H[b], W[b]);
+        if ((long long)H[b] * W[b] * 3 >= (1LL << 31)) return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: image %d holds >= 2^31 values", b);
+        if (top[b] < 0 || left[b] < 0) return set_error(DSRG_ERR_INVALID, "train-f input: image %d has a negative offset (%d, %d)", b, top[b], left[b]);
+        if ((long long)top[b] + ch >= (1LL << 31) || (long long)left[b] + cw >= (1LL << 31))
+            return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: image %d has an offset + crop >= 2^31", b);
+        if (!inside(image_off[b], (long long)H[b] * W[b] * 3, stage_bytes))
+            return set_error(DSRG_ERR_INVALID, "train-f input: image %d lies outside the staging buffer", b);
+        if (!inside(label_off[b], (long long)H[b] * W[b], stage_bytes))
+            return set_error(DSRG_ERR_INVALID, "train-f input: label %d lies outside the staging buffer", b);
+        a.img_off[b] = image_off[b], a.lab_off[b] = label_off[b];
+        a.H[b] = H[b], a.W[b] = W[b], a.top[b] = top[b], a.left[b] = left[b];
+        if (mirror[b]) a.mirror |= 1u << b;
+    }
+    for (int c = 0; c < 3; ++c) a.mean[c] = mean[c];
+    a.scale = scale;
+    a.ignore_label = ignore_label;
+    const long long n = (long long)B * ch * cw;
+    hipLaunchKernelGGL(train_f_input_kernel, dim3((unsigned)((n + kTiThreads - 1) / kTiThreads)), dim3(kTiThreads), 0, stream, stage, a, B,
+                       ch, cw, data, label);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
+}  // namespace dsrg

@@ -1,0 +1,469 @@
+"""The training input pipelines of both stages: files -> device tensors ready for DSRGTrainer.step / RetrainTrainer.step.
+
+  TrainSInput  <-> Caffe's ImageData layer (train-s.prototxt:3-22) + AnnotationLayer (pylayers.py:346-387)
+  TrainFInput  <-> ImageSegDataLayer (layer.py:17-251; train-f.prototxt:3-14)
+
+The host decodes files (PIL, on a thread pool), packs the raw bytes of a batch — uint8 pixels, uint8 labels, int32 cue triplets
+and class ids — into ONE pinned staging buffer and uploads it with one copy; the batch itself (resize, BGR, mean, cue planes,
+image-level labels, crop, mirror) is assembled on the device by ops.train_s_input_batch / ops.train_f_input_batch.  Everything
+that decides WHAT a batch holds is plain host code that needs no device: the epoch order and its sharding over ranks
+(`epoch_items`), the random draws (`plan_batch`), the staging layout (`layout_train_s`, `layout_train_f`) and the packing
+(`pack_train_s`, `pack_train_f`).
+
+Random numbers.  Each loader owns its generators, the global ones are never touched.  TrainSInput: the epoch shuffle comes from a
+`random.Random(seed)` — NOT Caffe's RNG, so a run does not see the reference's image order — and the mirror draws from an
+`np.random.RandomState(seed)`, one `choice(2)` per image in batch order, 0 = mirror: AnnotationLayer's draws under
+`np.random.seed(seed)`.  TrainFInput: BatchLoader's and SimpleTransformer.preprocess's draws in their order — per image the row
+offset, the column offset (`random.Random(seed).randint`), the mirror (`RandomState(seed).choice(2)`), and `shuffle` from the same
+`random.Random` between the last image of an epoch and the first of the next — so a run seeded like `random.seed(seed);
+np.random.seed(seed)` sees the reference's crops.  With world_size > 1 the shuffle moves to a second `random.Random(seed)` that
+does nothing else (see TrainFInput.__init__), so that every rank shuffles alike.  All draws are made on the iterating thread, never
+in a worker.
+"""
+import os
+import random
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from .data import SimpleTransformer, _Window
+
+MAX_BATCH = 32                                   # images per launch (dsrg_train_s_input_batch / dsrg_train_f_input_batch)
+
+
+def _align(n):
+    return (n + 15) & ~15                        # every piece of a staging buffer starts on a 16-byte boundary
+
+
+def epoch_items(entries, shuffle, rng, rank=0, world_size=1):
+    """the endless item stream of one rank: the list in file order for the first epoch, reshuffled (rng.shuffle, identically on every
+    rank) before each later one when `shuffle`; a rank takes items rank, rank + world_size, ... of each epoch.  Batches are cut from
+    this stream, so the list wraps mid-batch (as Caffe's ImageData and layer.py's BatchLoader do)."""
+    entries = list(entries)
+    if not 0 <= rank < world_size:
+        raise ValueError("rank %d outside world size %d" % (rank, world_size))
+    if len(entries) <= rank:
+        raise ValueError("%d list entries leave rank %d of %d without an image" % (len(entries), rank, world_size))
+    while True:
+        for i in range(rank, len(entries), world_size):
+            yield entries[i]
+        if shuffle:
+            rng.shuffle(entries)
+
+
+def read_train_s_list(path):
+    """'name.jpg <id>' lines (the reference's list/input_list.txt) -> [(name, id)]"""
+    out = []
+    with open(path) as f:
+        for line in f:
+            parts = line.split()
+            if parts:
+                if len(parts) < 2:
+                    raise ValueError("%s: expected 'name.jpg <id>', got %r" % (path, line.strip()))
+                out.append((parts[0], int(parts[1])))
+    if not out:
+        raise ValueError("%s lists no image" % path)
+    return out
+
+
+def read_rgb(path):
+    """(H, W, 3) RGB uint8, contiguous"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8))
+
+
+def read_gray(path):
+    """(H, W) uint8, contiguous"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("L"), dtype=np.uint8))
+
+
+def image_size(path):
+    """(H, W) from the file's header (nothing is decoded)"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return im.size[1], im.size[0]
+
+
+def cue_arrays(cue_dict, image_id, num_classes=21, map_size=(41, 41)):
+    """-> ((3, K) int32 cue triplets, (L,) int32 class ids) of one image, checked: a triplet outside the (num_classes, *map_size)
+    planes or a class id outside [0, num_classes) raises ValueError (numpy's fancy indexing in AnnotationLayer would raise
+    IndexError or wrap a negative index; the kernel's own guard only keeps bad data from writing out of bounds)"""
+    cues = np.asarray(cue_dict['%i_cues' % image_id])
+    cues = np.ascontiguousarray(cues.reshape(3, -1), dtype=np.int32)
+    labels = np.ascontiguousarray(np.asarray(cue_dict['%i_labels' % image_id]).reshape(-1), dtype=np.int32)
+    for axis, bound in enumerate((num_classes, map_size[0], map_size[1])):
+        if cues.shape[1] and (cues[axis].min() < 0 or cues[axis].max() >= bound):
+            raise ValueError("image %d: a cue triplet lies outside the %d x %d x %d planes" % ((image_id, num_classes) + tuple(map_size)))
+    if labels.size and (labels.min() < 0 or labels.max() >= num_classes):
+        raise ValueError("image %d: a class id lies outside [0, %d)" % (image_id, num_classes))
+    return cues, labels
+
+
+def _check_batch(n, total):
+    if not 1 <= n <= MAX_BATCH:
+        raise ValueError("a batch holds 1..%d images, got %d" % (MAX_BATCH, n))
+    if total >= 1 << 31:
+        raise ValueError("the staging buffer of one batch would hold %d >= 2^31 bytes" % total)
+
+
+def layout_train_s(shapes, ncues, nlabels, mirror=None):
+    """where the pieces of a stage-1 batch lie in its staging buffer.  shapes: (H, W) per image; ncues / nlabels: triplets / class
+    ids per image -> (bytes, desc): desc is the dict of per-image lists ops.train_s_input_batch takes."""
+    n = len(shapes)
+    desc = dict(image_off=[], H=[], W=[], cue_off=[], ncues=[], label_off=[], nlabels=[],
+                mirror=[0] * n if mirror is None else [int(bool(m)) for m in mirror])
+    off = 0
+    for (H, W), K, L in zip(shapes, ncues, nlabels):
+        if H < 1 or W < 1:
+            raise ValueError("an image of %d x %d pixels" % (H, W))
+        desc["image_off"].append(off), desc["H"].append(int(H)), desc["W"].append(int(W))
+        off = _align(off + H * W * 3)
+        desc["cue_off"].append(off), desc["ncues"].append(int(K))
+        off = _align(off + 12 * K)
+        desc["label_off"].append(off), desc["nlabels"].append(int(L))
+        off = _align(off + 4 * L)
+    _check_batch(n, off)
+    return off, desc
+
+
+def pack_train_s(buf, desc, images, cues, labels):
+    """write the batch's raw bytes into buf (1-d uint8 numpy array, at least the layout's size): images (H, W, 3) uint8 RGB, cues
+    (3, K) int32, labels (L,) int32"""
+    for b, (im, cue, lab) in enumerate(zip(images, cues, labels)):
+        if im.dtype != np.uint8 or im.shape != (desc["H"][b], desc["W"][b], 3):
+            raise ValueError("image %d must be (%d, %d, 3) uint8" % (b, desc["H"][b], desc["W"][b]))
+        o = desc["image_off"][b]
+        buf[o:o + im.size] = im.reshape(-1)
+        o, K = desc["cue_off"][b], desc["ncues"][b]
+        buf[o:o + 12 * K].view(np.int32)[:] = np.asarray(cue, dtype=np.int32).reshape(-1)
+        o, L = desc["label_off"][b], desc["nlabels"][b]
+        buf[o:o + 4 * L].view(np.int32)[:] = np.asarray(lab, dtype=np.int32).reshape(-1)
+
+
+def layout_train_f(shapes, top, left, mirror):
+    """where the pieces of a stage-2 batch lie in its staging buffer.  shapes: (H, W) per image; top / left / mirror: the host's
+    draws -> (bytes, desc): desc is the dict of per-image lists ops.train_f_input_batch takes."""
+    n = len(shapes)
+    desc = dict(image_off=[], label_off=[], H=[], W=[], top=[int(t) for t in top], left=[int(v) for v in left],
+                mirror=[int(bool(m)) for m in mirror])
+    off = 0
+    for H, W in shapes:
+        if H < 1 or W < 1:
+            raise ValueError("an image of %d x %d pixels" % (H, W))
+        desc["image_off"].append(off), desc["H"].append(int(H)), desc["W"].append(int(W))
+        off = _align(off + H * W * 3)
+        desc["label_off"].append(off)
+        off = _align(off + H * W)
+    if min(desc["top"] + desc["left"]) < 0:
+        raise ValueError("negative crop offset")
+    _check_batch(n, off)
+    return off, desc
+
+
+def pack_train_f(buf, desc, images, labels):
+    """write the batch's raw bytes into buf: images (H, W, 3) uint8 RGB, labels (H, W) uint8"""
+    for b, (im, lab) in enumerate(zip(images, labels)):
+        H, W = desc["H"][b], desc["W"][b]
+        if im.dtype != np.uint8 or im.shape != (H, W, 3):
+            raise ValueError("image %d must be (%d, %d, 3) uint8" % (b, H, W))
+        if lab.dtype != np.uint8 or lab.shape != (H, W):
+            raise ValueError("label %d must be (%d, %d) uint8, the size of its image" % (b, H, W))
+        o = desc["image_off"][b]
+        buf[o:o + im.size] = im.reshape(-1)
+        o = desc["label_off"][b]
+        buf[o:o + lab.size] = lab.reshape(-1)
+
+
+class _Slot(object):
+    """one staging slot: a pinned host buffer and a device buffer of the same size (grown only when a batch needs more), the
+    slot's own output tensors, and the events that order its reuse"""
+
+    def __init__(self, torch, outputs):
+        self.pinned = self.host = self.dev = None
+        self.outputs = outputs
+        self.copied = torch.cuda.Event()          # side stream: the upload has left the pinned buffer
+        self.ready = torch.cuda.Event()           # side stream: the batch is assembled
+        self.free = torch.cuda.Event()            # caller's stream: the caller's work on the slot's previous batch is enqueued before it
+        self.in_flight = False
+        self.desc, self.nbytes = None, 0
+
+
+class _StagedLoader(object):
+    """The mechanics both loaders share.  Two staging slots; per __next__ call n (0-based), on the calling thread:
+      1. batch n — uploaded during call n-1 — is assembled by ONE launch on the loader's side stream, behind an event recorded
+         on the caller's current stream (the caller's work on batch n-2, this slot's previous tenant, is in front of it), and the
+         caller's stream is made to wait for the assembly;
+      2. batch n+1 — decoding on the pool since call n-1 — is collected in list order, packed into the OTHER slot's pinned
+         buffer and uploaded (non_blocking) on the side stream: it runs under the caller's step on batch n;
+      3. the files of batch n+2 are handed to the pool.
+    CONTRACT: the tensors of batch n are valid until the __next__ call after next (call n+2 hands their slot to batch n+2); a
+    caller that keeps a batch longer clones it.  A call that raises (a file that does not decode, say) closes the loader: later
+    calls raise RuntimeError.  No stream is left current across calls: every `with torch.cuda.stream` block
+    closes inside the call that opens it."""
+
+    def __init__(self, batch_size, workers, device):
+        self.batch_size = int(batch_size)
+        if not 1 <= self.batch_size <= MAX_BATCH:
+            raise ValueError("batch_size must be 1..%d, got %d" % (MAX_BATCH, self.batch_size))
+        self.workers = int(workers)
+        if self.workers < 1:
+            raise ValueError("workers must be >= 1")
+        self.device = device
+        self._pool = self._side = self._slots = self._decoding = None
+        self._count = 0
+        self._closed = False
+
+    # -- what a loader defines -------------------------------------------------------------------------------------------------
+    def plan_batch(self):                         # iterating thread: the next batch's items with every random draw made
+        raise NotImplementedError
+
+    def _decode(self, item):                      # worker thread: files -> arrays
+        raise NotImplementedError
+
+    def _layout(self, plan, arrays):              # -> (bytes, desc, pieces to pack)
+        raise NotImplementedError
+
+    def _pack(self, buf, desc, pieces):
+        raise NotImplementedError
+
+    def _outputs(self, torch):                    # a slot's output tensors
+        raise NotImplementedError
+
+    def _assemble(self, slot):                    # one launch on the current (side) stream -> the tuple __next__ returns
+        raise NotImplementedError
+
+    # -- mechanics -------------------------------------------------------------------------------------------------------------
+    def _submit(self):
+        plan = self.plan_batch()
+        return plan, [self._pool.submit(self._decode, item) for item in plan]
+
+    def _upload(self, pending, slot):
+        import torch
+        plan, futures = pending
+        arrays = [f.result() for f in futures]                          # in list order, whatever order the workers finished in
+        nbytes, desc, pieces = self._layout(plan, arrays)
+        if slot.in_flight:
+            slot.copied.synchronize()                                   # the slot's previous upload has left the pinned buffer
+        if slot.pinned is None or slot.pinned.numel() < nbytes:
+            cap = (nbytes + (1 << 20) - 1) & ~((1 << 20) - 1)
+            slot.pinned = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
+            slot.host = slot.pinned.numpy()
+            with torch.cuda.stream(self._side):                         # (allocated and freed in the side stream's order)
+                slot.dev = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        self._pack(slot.host, desc, pieces)
+        with torch.cuda.stream(self._side):
+            slot.dev[:nbytes].copy_(slot.pinned[:nbytes], non_blocking=True)
+            slot.copied.record(self._side)
+        slot.in_flight = True
+        slot.desc, slot.nbytes = desc, nbytes
+
+    def _start(self):
+        import torch
+        from . import _lib
+        _lib.require_gpu()
+        if self.device is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device(self.device)
+        self._pool = ThreadPoolExecutor(self.workers)
+        with torch.cuda.device(self.device):
+            self._side = torch.cuda.Stream(device=self.device)
+            self._slots = [_Slot(torch, self._outputs(torch)) for _ in range(2)]
+            self._upload(self._submit(), self._slots[0])
+        self._decoding = self._submit()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._closed:
+            raise RuntimeError("the loader is closed")
+        try:
+            return self._advance()
+        except BaseException:
+            # a file that does not decode, a bad cue, a failed launch: the batch this call was about to return may be assembled
+            # and the one behind it half staged — no retry could be told apart from a fresh call, so the loader ends here
+            self.close()
+            raise
+
+    def _advance(self):
+        import torch
+        if self._slots is None:
+            self._start()
+        n = self._count
+        slot = self._slots[n % 2]
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            slot.free.record(cur)
+            self._side.wait_event(slot.free)
+            with torch.cuda.stream(self._side):
+                out = self._assemble(slot)
+                slot.ready.record(self._side)
+            cur.wait_event(slot.ready)
+            self._upload(self._decoding, self._slots[(n + 1) % 2])
+        self._decoding = self._submit()
+        self._count = n + 1
+        return out
+
+    def close(self):
+        """join the pool, wait for the side stream; the tensors already returned stay valid (nothing overwrites them any more)"""
+        if self._closed:
+            return
+        self._closed = True
+        if self._pool is not None:
+            if self._decoding is not None:
+                for f in self._decoding[1]:
+                    f.cancel()
+            self._pool.shutdown(wait=True)
+        if self._side is not None:
+            self._side.synchronize()
+        self._pool = self._decoding = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class TrainSInput(_StagedLoader):
+    """Iterator of (images (B,3,size,size), labels (B,1,1,21), cues (B,21,41,41)) float32 device tensors for DSRGTrainer.step:
+    Caffe's ImageData layer (train-s.prototxt:3-22: read, resize to size x size, mean 104/117/123, shuffle) followed by
+    AnnotationLayer (pylayers.py:346-387), assembled on the device by ops.train_s_input_batch.
+
+    list_file: 'name.jpg <id>' lines, the image is root/name; cues: the localisation-cue pickle (layers._open_cue_file) or its
+    dictionary.  Epochs: file order first, reshuffled before each later epoch when `shuffle` (a random.Random(seed) of the loader's
+    own: not Caffe's RNG); the list wraps mid-batch; with world_size > 1 every rank shuffles identically and takes items rank,
+    rank + world_size, ... of the epoch.  Mirror: one RandomState(seed).choice(2) per image in batch order, 0 = mirror
+    (AnnotationLayer's draw).  The tensors of batch n are valid until the __next__ call after next (_StagedLoader)."""
+
+    num_classes, map_size, mean = 21, (41, 41), (104.0, 117.0, 123.0)
+
+    def __init__(self, list_file, root, cues, batch_size=20, size=321, mirror=True, shuffle=True, seed=0, workers=8, rank=0,
+                 world_size=1, device=None):
+        _StagedLoader.__init__(self, batch_size, workers, device)
+        self.size, self.mirror, self.root = int(size), bool(mirror), root
+        if isinstance(cues, dict):
+            self.cues = cues
+        else:
+            from .layers import _open_cue_file
+            self.cues = _open_cue_file(os.path.abspath(cues))
+        self.entries = read_train_s_list(list_file)
+        self._items = epoch_items(self.entries, shuffle, random.Random(seed), rank, world_size)
+        self._mirror_rng = np.random.RandomState(seed)
+        self._checked = {}
+
+    def _cues_of(self, image_id):
+        if image_id not in self._checked:
+            self._checked[image_id] = cue_arrays(self.cues, image_id, self.num_classes, self.map_size)
+        return self._checked[image_id]
+
+    def plan_batch(self):
+        plan = []
+        for _ in range(self.batch_size):
+            name, image_id = next(self._items)
+            self._cues_of(image_id)                                     # a bad triplet raises here, before any upload
+            plan.append(dict(name=name, id=image_id,
+                             mirror=bool(self.mirror) and int(self._mirror_rng.choice(2)) == 0))
+        return plan
+
+    def _decode(self, item):
+        return read_rgb(os.path.join(self.root, item["name"]))
+
+    def _layout(self, plan, arrays):
+        anno = [self._cues_of(item["id"]) for item in plan]
+        cues, labels = [a[0] for a in anno], [a[1] for a in anno]
+        nbytes, desc = layout_train_s([a.shape[:2] for a in arrays], [c.shape[1] for c in cues], [l.size for l in labels],
+                                      [item["mirror"] for item in plan])
+        return nbytes, desc, (arrays, cues, labels)
+
+    def _pack(self, buf, desc, pieces):
+        pack_train_s(buf, desc, *pieces)
+
+    def _outputs(self, torch):
+        B, C, (Hm, Wm) = self.batch_size, self.num_classes, self.map_size
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)      # noqa: E731
+        return mk(B, 3, self.size, self.size), mk(B, 1, 1, C), mk(B, C, Hm, Wm)
+
+    def _assemble(self, slot):
+        from . import ops
+        return ops.train_s_input_batch(slot.dev, slot.desc, self.size, self.num_classes, self.map_size, self.mean,
+                                       out=slot.outputs, nbytes=slot.nbytes)
+
+
+class TrainFInput(_StagedLoader):
+    """Iterator of (data (B,3,ch,cw), label (B,1,ch,cw)) float32 device tensors for RetrainTrainer.step: ImageSegDataLayer
+    (layer.py:17-251), assembled on the device by ops.train_f_input_batch.
+
+    params: the layer's param dict — source ('image_path label_path' lines), root_folder (prefixed to both as it stands),
+    batch_size, crop_size, mean, scale, mirror, phase, ignore_label; what is left out takes SimpleTransformer.check_params'
+    defaults.  List order and reshuffling are BatchLoader's, the draws SimpleTransformer.preprocess's, in its order per image: row
+    offset, column offset (phase 'Train' only), mirror choice (with `mirror` only) — from a random.Random(seed) and an
+    np.random.RandomState(seed) of the loader's own.  An image's size is read from its label file's header when the batch is
+    planned, so the draws never wait for a decode.  With world_size > 1 every rank shuffles identically — from a second
+    random.Random(seed) that only shuffles, since the offsets' generator advances by amounts that depend on each rank's own images —
+    and takes items rank, rank + world_size, ... of the epoch; the crops are then no longer the single-process run's.  The tensors of batch n are valid until the __next__ call after next (_StagedLoader)."""
+
+    def __init__(self, params, seed=0, workers=8, rank=0, world_size=1, device=None):
+        params = dict(params)
+        SimpleTransformer.check_params(params)
+        _StagedLoader.__init__(self, params['batch_size'], workers, device)
+        self.params = params
+        self.crop = (int(params['crop_size'][0]), int(params['crop_size'][1]))
+        if min(self.crop) < 1:
+            raise ValueError("crop_size %r" % (params['crop_size'],))
+        self.mean, self.scale = tuple(float(np.float32(m)) for m in params['mean']), float(np.float32(params['scale']))
+        self.is_mirror, self.phase, self.ignore_label = bool(params['mirror']), params['phase'], params['ignore_label']
+        self.root_folder = params['root_folder']
+        with open(params['source']) as f:
+            self.entries = [tuple(ln.split()[:2]) for ln in f if ln.strip()]
+        if not self.entries:
+            raise ValueError("%s lists no image / label pair" % params['source'])
+        self._rng = random.Random(seed)
+        self._np_rng = np.random.RandomState(seed)
+        # One process: BatchLoader's shuffle, from the generator the crop offsets come from.  Several ranks: `randint` takes a
+        # number of words from its generator that depends on the range, i.e. on the sizes of the images a rank draws for, so the
+        # ranks' offset generators drift apart within an epoch — the shuffle then has a generator of its own, which every rank
+        # advances alike: the shards stay disjoint and jointly the epoch.
+        shuffle_rng = self._rng if world_size == 1 else random.Random(seed)
+        self._items = epoch_items(self.entries, True, shuffle_rng, rank, world_size)
+
+    def plan_batch(self):
+        plan = []
+        for _ in range(self.batch_size):
+            image_path, label_path = next(self._items)                  # (reshuffles between two epochs, from the offsets' generator)
+            image_path, label_path = self.root_folder + image_path, self.root_folder + label_path
+            win = _Window(image_size(label_path), self.crop)
+            top, left = win.top, win.left                               # centred unless drawn
+            if self.phase == 'Train':
+                max_top, max_left = win.slack()
+                top = self._rng.randint(0, max_top)
+                left = self._rng.randint(0, max_left)
+            mirror = self.is_mirror and int(self._np_rng.choice(2)) == 0
+            plan.append(dict(image=image_path, label=label_path, top=top, left=left, mirror=mirror))
+        return plan
+
+    def _decode(self, item):
+        return read_rgb(item["image"]), read_gray(item["label"])
+
+    def _layout(self, plan, arrays):
+        images, labels = [a[0] for a in arrays], [a[1] for a in arrays]
+        nbytes, desc = layout_train_f([a.shape[:2] for a in images], [it["top"] for it in plan], [it["left"] for it in plan],
+                                      [it["mirror"] for it in plan])
+        return nbytes, desc, (images, labels)
+
+    def _pack(self, buf, desc, pieces):
+        pack_train_f(buf, desc, *pieces)
+
+    def _outputs(self, torch):
+        B, (ch, cw) = self.batch_size, self.crop
+        return (torch.empty((B, 3, ch, cw), dtype=torch.float32, device=self.device),
+                torch.empty((B, 1, ch, cw), dtype=torch.float32, device=self.device))
+
+    def _assemble(self, slot):
+        from . import ops
+        return ops.train_f_input_batch(slot.dev, slot.desc, self.crop, self.mean, self.scale, self.ignore_label, out=slot.outputs,
+                                       nbytes=slot.nbytes)

@@ -564,6 +564,76 @@ def preprocess_ms_batch(images, sizes, capacity=None, mean=MEAN_PIXEL, out=None)
     return out
 
 
+def _i32s(values):
+    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
+
+
+def _stage_arg(stage, nbytes):
+    if not (torch.is_tensor(stage) and stage.is_cuda and stage.dtype == torch.uint8 and stage.is_contiguous() and stage.dim() == 1):
+        raise ValueError("stage must be a contiguous 1-d uint8 CUDA tensor")
+    nbytes = stage.numel() if nbytes is None else int(nbytes)
+    if not 0 <= nbytes <= stage.numel():
+        raise ValueError("the staging buffer holds %d bytes, the batch states %d" % (stage.numel(), nbytes))
+    return nbytes
+
+
+def _out_arg(out, shape, name, dev):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    _f32c(out, name)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError("%s must be %s, got %s" % (name, tuple(shape), tuple(out.shape)))
+    return out
+
+
+def train_s_input_batch(stage, desc, size=321, num_classes=21, map_size=(41, 41), mean=MEAN_PIXEL, out=None, nbytes=None):
+    """The stage-1 training batch in one launch (dsrg_train_s_input_batch): Caffe's ImageData layer (train-s.prototxt:3-22) followed
+    by AnnotationLayer (pylayers.py:346-387).  stage: the batch's raw bytes as a 1-d uint8 CUDA tensor (input.pack_train_s makes
+    them on the host; one upload); desc: the dict of per-image lists input.layout_train_s returns — image_off, H, W, cue_off, ncues,
+    label_off, nlabels (byte offsets and counts) — and mirror (one flag per image).  Returns (images (B,3,S,S), labels (B,1,1,C),
+    cues (B,C,Hm,Wm)), float32: the arguments of DSRGTrainer.step.  out: three existing tensors of those shapes to write into.
+    Runs on torch's current stream."""
+    nbytes = _stage_arg(stage, nbytes)
+    B = len(desc["H"])
+    S, C, (Hm, Wm) = int(size), int(num_classes), (int(map_size[0]), int(map_size[1]))
+    if len(mean) != 3:
+        raise ValueError("mean must hold 3 values")
+    keys = ("image_off", "H", "W", "cue_off", "ncues", "label_off", "nlabels", "mirror")
+    if any(len(desc[k]) != B for k in keys):
+        raise ValueError("every descriptor list must hold one entry per image")
+    out = (None, None, None) if out is None else out
+    images = _out_arg(out[0], (B, 3, S, S), "out[0]", stage.device)
+    labels = _out_arg(out[1], (B, 1, 1, C), "out[1]", stage.device)
+    cues = _out_arg(out[2], (B, C, Hm, Wm), "out[2]", stage.device)
+    check(_lib.lib().dsrg_train_s_input_batch(B, _ptr(stage), nbytes, *[_i32s(desc[k]) for k in keys], S, C, Hm, Wm,
+                                              (ctypes.c_float * 3)(*[float(m) for m in mean]), _ptr(images), _ptr(cues), _ptr(labels),
+                                              _stream()))
+    return images, labels, cues
+
+
+def train_f_input_batch(stage, desc, crop_size, mean, scale=1.0, ignore_label=255, out=None, nbytes=None):
+    """The stage-2 training batch in one launch (dsrg_train_f_input_batch): data.SimpleTransformer.preprocess (layer.py:169-236) for
+    every image of the batch.  stage: the batch's raw bytes as a 1-d uint8 CUDA tensor (input.pack_train_f); desc: the dict of
+    per-image lists input.layout_train_f returns — image_off, label_off, H, W — and the host's draws top, left, mirror.  Returns
+    (data (B,3,ch,cw), label (B,1,ch,cw)), float32: the arguments of RetrainTrainer.step.  out: two existing tensors of those shapes
+    to write into.  Runs on torch's current stream."""
+    nbytes = _stage_arg(stage, nbytes)
+    B = len(desc["H"])
+    ch, cw = int(crop_size[0]), int(crop_size[1])
+    if len(mean) != 3:
+        raise ValueError("mean must hold 3 values")
+    keys = ("image_off", "label_off", "H", "W", "top", "left", "mirror")
+    if any(len(desc[k]) != B for k in keys):
+        raise ValueError("every descriptor list must hold one entry per image")
+    out = (None, None) if out is None else out
+    data = _out_arg(out[0], (B, 3, ch, cw), "out[0]", stage.device)
+    label = _out_arg(out[1], (B, 1, ch, cw), "out[1]", stage.device)
+    check(_lib.lib().dsrg_train_f_input_batch(B, _ptr(stage), nbytes, *[_i32s(desc[k]) for k in keys], ch, cw,
+                                              (ctypes.c_float * 3)(*[float(m) for m in mean]), float(scale), float(ignore_label),
+                                              _ptr(data), _ptr(label), _stream()))
+    return data, label
+
+
 def supervision_step(logits, images, labels, cues, th1=0.99, th2=0.85, scale_factor=12.0, maxiter=10,
                      ctx=None, want_blobs=False, prepared=False):
     """The five Python layers of train-s.prototxt:746-810, forward and backward, in one

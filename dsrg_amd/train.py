@@ -1,0 +1,140 @@
+"""`python -m dsrg_amd.train`: the two training runs of run.sh, fed from files.
+
+  --stage s  <-> training/tools/train.py --solver solver-s.prototxt   (DSRG training: train-s.prototxt; DSRGTrainer + TrainSInput)
+  --stage f  <-> training/tools/train.py --solver solver-f.prototxt   (retraining on the pseudo labels: train-f.prototxt;
+                                                                      RetrainTrainer + TrainFInput)
+
+Stage s reads --list ('name.jpg <id>' lines, the reference's list/input_list.txt), the images under --root and the localisation
+cues of --cues; stage f reads --list ('image_path label_path' lines, list/train.txt) with --root prefixed to both paths.  The
+defaults are the solver files' values (STAGE_DEFAULTS).  Batches are assembled on the GPU (dsrg_amd/input.py) while the step
+before runs.  Every --display steps the mean of the last --display losses is printed with the learning rate; snapshots
+(<prefix>_iter_N.caffemodel + .solverstate.pt) are written every --snapshot-every steps and at the end; --snapshot resumes at the
+snapshot's iteration count.  Under a launcher (torch.distributed.run: RANK / WORLD_SIZE set) every rank takes its shard of each
+epoch and --batch / WORLD_SIZE images per step.
+"""
+import argparse
+import os
+import sys
+
+# solver-s.prototxt / train-s.prototxt:14-21 and solver-f.prototxt / train-f.prototxt:11
+STAGE_DEFAULTS = {
+    "s": dict(iters=8000, snapshot_every=8000, display=10, prefix="models/model-s", batch=20),
+    "f": dict(iters=20000, snapshot_every=10000, display=20, prefix="models/model-f", batch=10),
+}
+F_DEFAULTS = dict(crop=321, mean=(104.0, 117.0, 123.0))
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(prog="python -m dsrg_amd.train", description="train stage s (DSRG) or stage f (retrain) from files")
+    p.add_argument("--stage", choices=("s", "f"), required=True, help="s: solver-s.prototxt (DSRG training); f: solver-f.prototxt (retrain)")
+    p.add_argument("--list", required=True, help="s: 'name.jpg <id>' lines; f: 'image_path label_path' lines")
+    p.add_argument("--root", required=True, help="s: directory of the images; f: prefix of both paths of a list line")
+    p.add_argument("--weights", default=None, help="initial weights (.caffemodel, .npz or torch file), copied by layer name")
+    p.add_argument("--snapshot", default=None, help="a .solverstate.pt written by an earlier run: resume there")
+    p.add_argument("--prefix", default=None, help="snapshot prefix (s: models/model-s, f: models/model-f)")
+    p.add_argument("--iters", type=int, default=None, help="last iteration (s: 8000, f: 20000)")
+    p.add_argument("--snapshot-every", type=int, default=None, help="snapshot interval (s: 8000, f: 10000)")
+    p.add_argument("--batch", type=int, default=None, help="images per step over all ranks (s: 20, f: 10)")
+    p.add_argument("--seed", type=int, default=0, help="weights, dropout, shuffle and augmentation draws (solver: random_seed 0)")
+    p.add_argument("--display", type=int, default=None, help="print the mean loss every N steps (s: 10, f: 20)")
+    p.add_argument("--workers", type=int, default=8, help="decoding threads")
+    p.add_argument("--cues", default=None, help="s: the localisation-cue pickle")
+    p.add_argument("--backbone", choices=("vgg16", "resnet101"), default=None, help="f: the network (default vgg16)")
+    p.add_argument("--crop", type=int, default=None, help="f: crop size (321)")
+    p.add_argument("--mean", default=None, help="f: B,G,R mean (104,117,123)")
+    p.add_argument("--no-mirror", action="store_true", help="f: no random mirror")
+    a = p.parse_args(argv)
+    for key, value in STAGE_DEFAULTS[a.stage].items():
+        if getattr(a, key) is None:
+            setattr(a, key, value)
+    if a.stage == "s":
+        if not a.cues:
+            p.error("--stage s needs --cues (the localisation-cue pickle)")
+        if a.backbone or a.crop is not None or a.mean is not None or a.no_mirror:
+            p.error("--backbone, --crop, --mean and --no-mirror are for --stage f")
+    else:
+        if a.cues:
+            p.error("--cues is for --stage s")
+        a.backbone = a.backbone or "vgg16"
+        a.crop = F_DEFAULTS["crop"] if a.crop is None else a.crop
+        a.mean = F_DEFAULTS["mean"] if a.mean is None else tuple(float(v) for v in a.mean.split(","))
+        if len(a.mean) != 3:
+            p.error("--mean takes three values: B,G,R")
+    if min(a.iters, a.snapshot_every, a.batch, a.display, a.workers) < 1:
+        p.error("--iters, --snapshot-every, --batch, --display and --workers must be >= 1")
+    return a
+
+
+def _process_group(torch):
+    """(rank, world size, local rank); under a launcher the group is initialised here, one GPU per rank"""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size(), int(os.environ.get("LOCAL_RANK", torch.cuda.current_device()))
+    if os.environ.get("RANK") is None:
+        return 0, 1, torch.cuda.current_device()
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local_rank)
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))        # nccl == RCCL on ROCm
+    return dist.get_rank(), dist.get_world_size(), local_rank
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    import torch
+    from ._lib import require_gpu
+    from .input import TrainFInput, TrainSInput
+    from .trainer import DSRGTrainer, params_checksum
+
+    require_gpu()
+    rank, world, local_rank = _process_group(torch)
+    torch.cuda.set_device(local_rank)
+    device = torch.device("cuda", local_rank)
+    if a.batch % world:
+        raise SystemExit("--batch %d is not a multiple of the %d ranks" % (a.batch, world))
+    batch = a.batch // world
+    say = print if rank == 0 else (lambda *args, **kw: None)
+
+    if a.stage == "s":
+        trainer = DSRGTrainer(device, world_size=world, seed=a.seed, weights=a.weights, snapshot=a.snapshot)
+        loader = TrainSInput(a.list, a.root, a.cues, batch_size=batch, seed=a.seed, workers=a.workers, rank=rank,
+                             world_size=world, device=device)
+        names = ("loss-Seed", "loss-Constrain")
+        rate = trainer.opt.lr
+    else:
+        from .retrain import RetrainTrainer, poly_lr
+        trainer = RetrainTrainer(device, world_size=world, backbone=a.backbone, max_iter=a.iters, seed=a.seed, weights=a.weights,
+                                 snapshot=a.snapshot)
+        loader = TrainFInput(dict(source=a.list, root_folder=a.root, batch_size=batch, crop_size=(a.crop, a.crop), mean=a.mean,
+                                  mirror=not a.no_mirror), seed=a.seed, workers=a.workers, rank=rank, world_size=world, device=device)
+        names = ("loss",)
+        rate = lambda: poly_lr(trainer.base_lr, trainer.opt.iter, trainer.max_iter)      # noqa: E731
+    if trainer.opt.iter:
+        say("resumed from %s at iteration %d" % (a.snapshot, trainer.opt.iter), flush=True)
+
+    window, saved_at = [], None
+    with loader:
+        while trainer.opt.iter < a.iters:
+            lr = rate()
+            window.append(trainer.step(*next(loader)).detach().reshape(-1))
+            it = trainer.opt.iter
+            if it % a.display == 0 or it == a.iters:
+                mean = DSRGTrainer.reduce_losses(trainer, torch.stack(window).mean(0)).tolist()
+                say("Iteration %d, lr = %g, %s" % (it, lr, ", ".join("%s = %.6f" % nv for nv in zip(names, mean))), flush=True)
+                window = []
+            if it % a.snapshot_every == 0 or it == a.iters:
+                paths = trainer.save(a.prefix)                           # (collective: every rank calls it)
+                saved_at = it
+                say("snapshot %s %s" % paths, flush=True)
+    if saved_at != trainer.opt.iter:                                     # (a run that had nothing left to do still leaves its model)
+        say("snapshot %s %s" % trainer.save(a.prefix), flush=True)
+    words = params_checksum(list(trainer.net.parameters()) + [b for g in trainer.opt.groups for b in g["bufs"]])
+    say("done: iteration %d weights_checksum %d %d" % ((trainer.opt.iter,) + tuple(int(v) for v in words.cpu())), flush=True)
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and os.environ.get("RANK") is not None:
+        dist.destroy_process_group()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -314,6 +314,40 @@ int dsrg_train_gt_unary_batch(int G, int C, const float *scores_dev, int h, int 
 int dsrg_preprocess_ms_batch(int G, int capacity, int K, const unsigned char *const *images_dev, const int32_t *H_host,
                              const int32_t *W_host, const int32_t *sizes_host, const float *mean_host, float *const *out_dev,
                              void *stream);
+/* The stage-1 training batch in one launch: Caffe's ImageData layer (training/experiment/seed_mc/train-s.prototxt:3-22: read,
+ * cv::resize to S x S, mean 104/117/123) followed by AnnotationLayer (pylayers/pylayers/pylayers.py:346-387), for B images.
+ * stage_dev: ONE device buffer of stage_bytes raw bytes (uploaded by the caller with one copy per batch); the HOST arrays
+ * describe image b in it by byte offsets: image_off (H_b, W_b, 3) RGB uint8; cue_off the (3, ncues_b) int32 array '<id>_cues'
+ * (classes, rows, columns; 4-byte aligned; ncues_b may be 0); label_off the nlabels_b int32 class ids '<id>_labels' (4-byte
+ * aligned); mirror_host[b] != 0 reverses the last axis of image b's pixels and cue planes (pylayers.py:384-387).  Outputs:
+ *   images_dev (B, 3, S, S) f32 NCHW: the 8-bit bilinear resize of the image (the integer arithmetic stated in DESIGN.md, a
+ *              restatement of OpenCV's INTER_LINEAR for 8-bit images; an exact 2x shrink is NOT switched to area averaging),
+ *              reordered to BGR, float(pixel) - mean_host[c]
+ *   cues_dev   (B, C, Hm, Wm) f32: zeros, 1.0 at every (class, row, column) triplet; a triplet outside the planes writes nothing
+ *   labels_dev (B, 1, 1, C) f32: 1.0 for class 0 and the listed ids, else 0
+ * 1 <= B <= 32, S, C, Hm, Wm >= 1, H_b, W_b >= 1, every offset + extent inside stage_bytes < 2^31, H_b*W_b*3, B*3*S*S and
+ * B*C*Hm*Wm < 2^31, ceil(B*S*S / 256) + B*C < 2^24 workgroups, outputs aligned to 4 bytes; every argument is checked before the first device call.  Nothing is allocated.
+ * Stream-ordered, no host synchronisation, no handle; bit-reproducible (no atomics). */
+int dsrg_train_s_input_batch(int B, const unsigned char *stage_dev, size_t stage_bytes, const int32_t *image_off_host,
+                             const int32_t *H_host, const int32_t *W_host, const int32_t *cue_off_host, const int32_t *ncues_host,
+                             const int32_t *label_off_host, const int32_t *nlabels_host, const int32_t *mirror_host, int S, int C,
+                             int Hm, int Wm, const float *mean_host, float *images_dev, float *cues_dev, float *labels_dev,
+                             void *stream);
+/* The stage-2 training batch in one launch: SimpleTransformer.preprocess of ImageSegDataLayer (pylayers/pylayers/layer.py:17-251,
+ * the arithmetic of layer.py:169-236; train-f.prototxt:3-14) for B images.  stage_dev / stage_bytes as above; image_off the
+ * (H_b, W_b, 3) RGB uint8 image, label_off its (H_b, W_b) uint8 label; top_host / left_host: the crop's offsets on the image
+ * extended to at least the crop size at its bottom / right edges (drawn or centred by the host, >= 0); mirror_host[b] != 0
+ * reverses both outputs along x.  Outputs:
+ *   data_dev  (B, 3, ch, cw) f32: (float(pixel) - mean_host[c]) * scale in BGR order (two separately rounded f32 operations)
+ *             where the crop lies on the image, 0.0 off it
+ *   label_dev (B, 1, ch, cw) f32: the label byte as float where the crop lies on the image, ignore_label off it
+ * 1 <= B <= 32, ch, cw >= 1, H_b, W_b >= 1, every offset + extent inside stage_bytes < 2^31, H_b*W_b*3 and B*3*ch*cw < 2^31,
+ * outputs aligned to 4 bytes; every argument is checked before the first device call.  Nothing is allocated.  Stream-ordered,
+ * no host synchronisation, no handle; bit-reproducible (no atomics). */
+int dsrg_train_f_input_batch(int B, const unsigned char *stage_dev, size_t stage_bytes, const int32_t *image_off_host,
+                             const int32_t *label_off_host, const int32_t *H_host, const int32_t *W_host, const int32_t *top_host,
+                             const int32_t *left_host, const int32_t *mirror_host, int ch, int cw, const float *mean_host, float scale,
+                             float ignore_label, float *data_dev, float *label_dev, void *stream);
 
 /* Backbone plumbing (no reference counterpart; Caffe's im2col lives in the external framework): NHWC im2col
  * of a 3x3, stride-1, "same"-padded, dilated convolution for 2-byte elements (bf16/fp16), C % 8 == 0:
