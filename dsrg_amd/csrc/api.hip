@@ -531,6 +531,16 @@ extern "C" int dsrg_train_f_input_batch(int B, const unsigned char *stage, size_
     return launch_train_f_input_batch(B, stage, stage_bytes, image_off, label_off, H, W, top, left, mirror, ch, cw, mean, scale,
                                       ignore_label, data, label, static_cast<hipStream_t>(stream));
 }
+extern "C" size_t dsrg_resnet_stem_packed_bytes(void) { return resnet_stem_packed_bytes(); }
+extern "C" int dsrg_pack_resnet_stem_f32(const float *w, const float *scale, void *packed, void *stream) {
+    if (!w || !scale || !packed) return set_error(DSRG_ERR_INVALID, "resnet stem pack: NULL argument");
+    return launch_pack_resnet_stem(w, scale, packed, static_cast<hipStream_t>(stream));      // (alignment: checked there, before the launch)
+}
+extern "C" int dsrg_resnet_stem_bf16(const float *x, const void *packed, const float *shift, void *y, int B, int H, int W, void *stream) {
+    if (!x || !packed || !shift || !y) return set_error(DSRG_ERR_INVALID, "resnet stem: NULL argument");
+    if (B < 1 || H < 1 || W < 1) return set_error(DSRG_ERR_INVALID, "resnet stem: %d images of %dx%d", B, H, W);
+    return launch_resnet_stem(x, packed, shift, y, B, H, W, static_cast<hipStream_t>(stream));   // (alignment and size limits: checked there, before the launch)
+}
 extern "C" int dsrg_im2col3x3_nhwc16(const void *in, void *out, int B, int H, int W, int C, int dilation, void *stream) {
     if (!in || !out || B < 1 || H < 1 || W < 1 || C < 1 || dilation < 1) return set_error(DSRG_ERR_INVALID, "bad argument");
     return launch_im2col3x3(in, out, B, H, W, C, dilation, static_cast<hipStream_t>(stream));

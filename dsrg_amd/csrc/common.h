@@ -272,6 +272,9 @@ int launch_train_f_input_batch(int B, const unsigned char *stage, size_t stage_b
                                const int32_t *H, const int32_t *W, const int32_t *top, const int32_t *left, const int32_t *mirror,
                                int ch, int cw, const float *mean, float scale, float ignore_label, float *data, float *label,
                                hipStream_t stream);
+size_t resnet_stem_packed_bytes();
+int launch_pack_resnet_stem(const float *w, const float *scale, void *packed, hipStream_t stream);
+int launch_resnet_stem(const float *x, const void *packed, const float *shift, void *y, int B, int H, int W, hipStream_t stream);
 int launch_im2col3x3(const void *in, void *out, int B, int H, int W, int C, int dil, hipStream_t stream);
 int launch_col2im3x3(const void *cols, void *out, int B, int H, int W, int C, int dil, hipStream_t stream);
 int launch_relu_bwd_bias(const void *g, const void *y, void *gm, float *bias_grad, float *part, int part_blocks,

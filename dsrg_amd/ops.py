@@ -1435,6 +1435,42 @@ def maxpool3x3_out_size(n, stride, ceil_mode):
     return o
 
 
+def resnet_stem_pack(weight, scale):
+    """the stem kernel of ResNet101DeepLab with its frozen BatchNorm scale folded in, packed once for resnet_stem
+    (dsrg_pack_resnet_stem_f32): weight (64,3,7,7) float32, scale (64) float32 -> (64,192) bf16,
+    packed[o][(ky * 3 + c) * 8 + kx] = bf16(weight[o,c,ky,kx] * scale[o]) (one float32 product, one rounding), zero where kx = 7 or
+    ky * 3 + c >= 21"""
+    if not (weight.is_cuda and weight.dtype == torch.float32 and tuple(weight.shape) == (64, 3, 7, 7)):
+        raise ValueError("resnet_stem_pack needs a (64,3,7,7) float32 CUDA kernel")
+    if tuple(scale.shape) != (64,):
+        raise ValueError("resnet_stem_pack needs 64 scales")
+    w = weight.detach().contiguous()
+    nbytes = _lib.lib().dsrg_resnet_stem_packed_bytes()
+    packed = torch.empty((64, nbytes // 128), dtype=torch.bfloat16, device=weight.device)
+    check(_lib.lib().dsrg_pack_resnet_stem_f32(_ptr(w), _ptr(_f32c(scale.detach(), "scale")), _ptr(packed), _stream()))
+    return packed
+
+
+def resnet_stem(x, packed, shift):
+    """the whole ResNet stem in one launch (dsrg_resnet_stem_bf16): x (B,3,H,W) float32 contiguous NCHW (rounded to bf16 as it is
+    read), packed = resnet_stem_pack(weight, scale), shift (64) float32 -> max_pool(3, 2, 1, ceil)(relu(conv7x7/2(x) + shift)),
+    (B,64,PH,PW) bf16 channels_last, rounded once; pool windows see only the real convolution map"""
+    if not (x.dim() == 4 and x.shape[1] == 3):
+        raise ValueError("resnet_stem needs a (B,3,H,W) input")
+    x = _f32c(x, "x")
+    B, _, H, W = x.shape
+    if not (packed.is_cuda and packed.dtype == torch.bfloat16 and packed.is_contiguous()
+            and packed.numel() * 2 == _lib.lib().dsrg_resnet_stem_packed_bytes()):
+        raise ValueError("resnet_stem needs a kernel packed by resnet_stem_pack")
+    if tuple(shift.shape) != (64,):
+        raise ValueError("resnet_stem needs 64 shifts")
+    OHc, OWc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    PH, PW = maxpool3x3_out_size(OHc, 2, True), maxpool3x3_out_size(OWc, 2, True)
+    y = torch.empty((B, 64, PH, PW), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    check(_lib.lib().dsrg_resnet_stem_bf16(_ptr(x), _ptr(packed), _ptr(_f32c(shift, "shift")), _ptr(y), B, H, W, _stream()))
+    return y
+
+
 def maxpool3x3_fwd(x, stride, ceil_mode, relu_input=False):
     """x (B,C,H,W) bf16 channels_last -> (pooled (B,C,OH,OW) channels_last, window codes (B,OH,OW,C) uint8).
     relu_input: x is a ReLU's output and maxpool3x3_bwd_relu will be given these codes WITHOUT x — windows whose maximum is

@@ -7,7 +7,8 @@
                image-level labels '<id>_labels' of the cue pickle; --images holds the reference's input_list.txt lines "name.jpg <id>")
 
 Reads DIR/JPEGImages/<id>.jpg for every id of --images, writes OUT/<id>.png: 8-bit grayscale class ids, what
-training/tools/evaluate.py reads (and `python -m dsrg_amd.evaluate`).  The network is VGG16-ASPP with the weights of --model
+training/tools/evaluate.py reads (and `python -m dsrg_amd.evaluate`).  The network is VGG16-ASPP (--backbone resnet101: the DeepLab-v2
+ResNet-101 of the stage-2 trainer, run through resnet_test.ResNetTestNet: fused HIP stem, weights packed once) with the weights of --model
 (checkpoint.load_weights: .caffemodel, .npz or a torch file), run under bf16 autocast (--fp32: float32, the reference's
 precision); forwards replay from captured HIP graphs (inference.GraphedForward, bounded for the relative scales) while the
 CRFs of earlier images are in flight (inference.predict_masks_ms_many / predict_masks_ms_f_many).  --mode ms --forward-batch N
@@ -35,6 +36,9 @@ def parse_args(argv=None):
                         "gt: one size (default 321)")
     p.add_argument("--class", dest="num_classes", type=int, default=21, help="number of classes including background")
     p.add_argument("--fp32", action="store_true", help="float32 forwards instead of bf16 autocast")
+    p.add_argument("--backbone", choices=("vgg16", "resnet101"), default="vgg16",
+                   help="the network of --model: vgg16 (VGG16-ASPP, the default) or resnet101 (DeepLab-v2 ResNet-101, the model of "
+                        "`python -m dsrg_amd.train --stage f --backbone resnet101`)")
     p.add_argument("--in-flight", type=int, default=3, help="CRFs in flight under the next image's forwards")
     p.add_argument("--max-graphs", type=int, default=12, help="ms-f: captured forward graphs kept (least recently used dropped)")
     p.add_argument("--forward-batch", type=int, default=1,
@@ -102,8 +106,16 @@ def main(argv=None):
     else:
         scales = tuple(float(s) for s in a.scales.split(",")) if a.scales else (0.75, 1.0, 1.25)
     dev = torch.device("cuda", torch.cuda.current_device())
-    net = VGG16ASPP(num_classes=a.num_classes).to(dev).to(memory_format=torch.channels_last).eval()
-    load_weights(net, a.model)
+    if a.backbone == "resnet101":
+        from .retrain import ResNet101DeepLab
+        net = ResNet101DeepLab(num_classes=a.num_classes).to(dev).to(memory_format=torch.channels_last).eval()
+        load_weights(net, a.model)
+        if not a.fp32:                                      # the packed test-time path is bf16 by contract; float32 runs the module itself
+            from .resnet_test import ResNetTestNet
+            net = ResNetTestNet(net)                        # packs the loaded weights once
+    else:
+        net = VGG16ASPP(num_classes=a.num_classes).to(dev).to(memory_format=torch.channels_last).eval()
+        load_weights(net, a.model)
     if a.mode == "gt":
         entries = read_gt_list(a.images)
         ids = [name for name, _ in entries]

@@ -284,6 +284,27 @@ class _Bottleneck(nn.Module):
         return F.relu(y + idn)
 
 
+def _aspp_stacked_kernel(dils, ws):
+    """the ASPP branches' 3x3 kernels as ONE 1x1 kernel (_AsppFn; ResNetTestNet keeps its packing) -> (offsets, the (CT, cin, 1, 1)
+    float32 channels_last kernel, CT): row j * O + o = w_branch[o, :, ky, kx], j = branch * 9 + ky * 3 + kx, which reads the map
+    at offsets[j] = ((ky - 1) * d, (kx - 1) * d); the 9 n O rows are padded with zeros to CT, a multiple of 128"""
+    O, cin = ws[0].shape[0], ws[0].shape[1]
+    J = 9 * len(dils)
+    CT = (J * O + 127) // 128 * 128
+    offsets = [((tap // 3 - 1) * d, (tap % 3 - 1) * d) for d in dils for tap in range(9)]
+    wcat = torch.cat([w.detach().float().permute(2, 3, 0, 1).reshape(9 * O, cin) for w in ws])
+    wcat = F.pad(wcat, (0, 0, 0, CT - J * O)).view(CT, cin, 1, 1).contiguous(memory_format=torch.channels_last)
+    return offsets, wcat, CT
+
+
+def _aspp_bias_sum(bs):
+    """the branches' biases summed in branch order (float32, contiguous)"""
+    bias = bs[0].detach().float()
+    for b in bs[1:]:
+        bias = bias + b.detach().float()
+    return bias.contiguous()
+
+
 class _AsppFn(torch.autograd.Function):
     """the DeepLab-v2 ASPP head, sum over four dilated 3x3 classifiers (2048 -> 21, dilation 6 / 12 / 18 / 24) of one feature map, as
     ONE 1x1 convolution on the implicit-GEMM kernels plus a shifted gather: out[p][o] = sum_j W_j[o] . f[p + off_j] over the 36
@@ -301,19 +322,11 @@ class _AsppFn(torch.autograd.Function):
         O, cin = ws[0].shape[0], ws[0].shape[1]
         f = f if f.dtype == torch.bfloat16 else f.bfloat16()
         f = f if f.is_contiguous(memory_format=torch.channels_last) else f.contiguous(memory_format=torch.channels_last)
-        J = 9 * n
-        CT = (J * O + 127) // 128 * 128
-        offsets = [((tap // 3 - 1) * d, (tap % 3 - 1) * d) for d in dils for tap in range(9)]
-        # row j * O + o of the stacked kernel = w_branch[o, :, ky, kx], j = branch * 9 + ky * 3 + kx
-        wcat = torch.cat([w.detach().float().permute(2, 3, 0, 1).reshape(9 * O, cin) for w in ws])
-        wcat = F.pad(wcat, (0, 0, 0, CT - J * O)).view(CT, cin, 1, 1).contiguous(memory_format=torch.channels_last)
+        offsets, wcat, CT = _aspp_stacked_kernel(dils, ws)
         need_d = ctx.needs_input_grad[1]
         pf, pd = pack_conv_weight_pair(wcat, True, need_d)
         (yp,) = conv_igemm([f], [pf], None, [1], 1, False)
-        bias = bs[0].detach().float()
-        for b in bs[1:]:
-            bias = bias + b.detach().float()
-        out = aspp_shift_sum(yp, offsets, O, bias.contiguous())
+        out = aspp_shift_sum(yp, offsets, O, _aspp_bias_sum(bs))
         ctx.save_for_backward(f)
         ctx.pd, ctx.offsets, ctx.O, ctx.CT, ctx.n, ctx.cin = pd, offsets, O, CT, n, cin
         return out

@@ -348,6 +348,25 @@ int dsrg_train_f_input_batch(int B, const unsigned char *stage_dev, size_t stage
                              const int32_t *label_off_host, const int32_t *H_host, const int32_t *W_host, const int32_t *top_host,
                              const int32_t *left_host, const int32_t *mirror_host, int ch, int cw, const float *mean_host, float scale,
                              float ignore_label, float *data_dev, float *label_dev, void *stream);
+/* The stem of the DeepLab-v2 ResNet-101 at test time in one launch (backbone plumbing; the reference's networks are Caffe
+ * prototxts): conv 7x7 / stride 2 / zero pad 3, 3 -> 64, with a frozen BatchNorm folded in -> ReLU -> max pool 3x3 / stride 2 /
+ * pad 1, ceil mode.  The convolution map never reaches memory.
+ *   dsrg_pack_resnet_stem_f32: w_dev (64, 3, 7, 7) f32 contiguous and scale_dev (64) f32 -> packed_dev,
+ *     dsrg_resnet_stem_packed_bytes() bytes, 16-byte aligned: (64, 192) bf16, packed[o][(ky * 3 + c) * 8 + kx] =
+ *     bf16(w[o][c][ky][kx] * scale[o]) — one f32 product, rounded once to nearest even — and 0 where kx = 7 or ky * 3 + c >= 21.
+ *   dsrg_resnet_stem_bf16: x_dev (B, 3, H, W) f32 contiguous NCHW, each value rounded to bf16 (nearest even) as it is read;
+ *     shift_dev (64) f32; y_dev (B, PH, PW, 64) bf16 (the memory of a channels_last (B, 64, PH, PW) tensor):
+ *       conv[b,o,i,j] = max(0, shift[o] + sum_{c,ky,kx} packed(o,c,ky,kx) * bf16(x[b, c, 2i - 3 + ky, 2j - 3 + kx]))   (zero outside x)
+ *     for i < OHc = (H - 1) / 2 + 1, j < OWc = (W - 1) / 2 + 1, products summed in f32, and
+ *       y[b,p,q,o] = bf16(max of conv[b,o,i,j] over 2p - 1 <= i <= 2p + 1, 2q - 1 <= j <= 2q + 1 ON the OHc x OWc map)
+ *     for p < PH = OHc / 2 + 1 less one if 2 (PH - 1) >= OHc + 1 (the 3x3 / 2 / pad 1 ceil-mode extent), PW likewise.  Window
+ *     positions off the map do not exist (they are not convolutions over zero padding).  shift_dev, packed_dev, y_dev 16-byte aligned.
+ * Both check every argument before the first device call (NULL pointers, B, H, W < 1: DSRG_ERR_INVALID).  Nothing is allocated.
+ * Stream-ordered, no host synchronisation, no handle; bit-reproducible (no atomics). */
+size_t dsrg_resnet_stem_packed_bytes(void);
+int dsrg_pack_resnet_stem_f32(const float *w_dev, const float *scale_dev, void *packed_dev, void *stream);
+int dsrg_resnet_stem_bf16(const float *x_dev, const void *packed_dev, const float *shift_dev, void *y_dev, int B, int H, int W,
+                          void *stream);
 
 /* Backbone plumbing (no reference counterpart; Caffe's im2col lives in the external framework): NHWC im2col
  * of a 3x3, stride-1, "same"-padded, dilated convolution for 2-byte elements (bf16/fp16), C % 8 == 0:
