@@ -69,9 +69,12 @@ __device__ __forceinline__ void bias_finalize_block(const float *__restrict__ pa
     }
 }
 // Deferred form (dsrg_defer_reductions / dsrg_flush_reductions): while deferral is on, a launch that would end with one of the two
-// passes above records it instead — true: recorded, the caller launches nothing; false: not deferring (or the list is full).
+// passes above records it instead — true: recorded, the caller launches nothing; false: not deferring (or the list has no room),
+// nothing was recorded and the caller runs the pass now.  A launch's n reductions of one shape (an igemm launch's groups) are
+// recorded under one lock, all or none.
 // kind 0: colsum_block over (rows, cols = cout); kind 1: bias_finalize_block over (rows = nblk, cols = C).
-bool defer_reduction(int kind, const float *part, float *out, int rows, int cols);
+bool defer_reduction(int kind, int n, const float *const *parts, float *const *outs, int rows, int cols);
+inline bool defer_reduction(int kind, const float *part, float *out, int rows, int cols) { return defer_reduction(kind, 1, &part, &out, rows, cols); }
 
 // raise a kernel's dynamic-LDS limit (default 64 KiB) to `bytes`; `granted` caches what was set.
 // The limit is requested per need, not as a flat 160 KiB: static LDS (e.g. the variable behind

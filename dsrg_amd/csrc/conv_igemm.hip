@@ -1223,12 +1223,7 @@ __global__ __launch_bounds__(1024) void igemm_colsum_kernel(ColsumArgs a) {
 
 int launch_igemm_colsum(const float *const *parts, float *const *outs, int ngroups, int rows, int cout, hipStream_t stream) {
     if (ngroups < 1 || ngroups > 4 || cout % 64 || rows < 1) return set_error(DSRG_ERR_INVALID, "column sums: 1..4 groups, 64 | channels");
-    {   // deferred (dsrg_defer_reductions): all groups or none
-        int g = 0;
-        while (g < ngroups && defer_reduction(0, parts[g], outs[g], rows, cout)) g++;
-        if (g == ngroups) return DSRG_OK;
-        if (g > 0) return set_error(DSRG_ERR_INVALID, "column sums: the deferred-reduction list filled up in the middle of a launch's groups");
-    }
+    if (defer_reduction(0, ngroups, parts, outs, rows, cout)) return DSRG_OK;      // all groups recorded; else none: sum now
     ColsumArgs c;
     memset(&c, 0, sizeof(c));
     for (int g = 0; g < ngroups; g++) { c.part[g] = parts[g]; c.out[g] = outs[g]; }

@@ -4,7 +4,8 @@
 // (igemm_colsum_kernel x 10, bias_finalize_kernel x 5: 96 us of an 8.2 ms step) and nothing reads a bias gradient before the
 // update.  While deferral is on those passes are recorded (common.h: defer_reduction) and dsrg_flush_reductions runs them all in
 // ONE launch — the same device bodies on the same partial rows in the same order: the gradients' bits do not change.  The caller
-// keeps every recorded launch's partial rows alive and unshared until the flush (dsrg_amd/ops.py does).
+// keeps every recorded launch's partial rows alive and unshared, and its bias gradient's memory allocated, until the flush
+// (dsrg_amd/ops.py does).  A launch's reductions are recorded all or none (defer_reduction's n).
 #include "common.h"
 #include <mutex>
 #include <cstring>
@@ -41,12 +42,14 @@ int g_blocks = 0;
 
 }  // namespace
 
-bool defer_reduction(int kind, const float *part, float *out, int rows, int cols) {
+bool defer_reduction(int kind, int n, const float *const *parts, float *const *outs, int rows, int cols) {
     std::lock_guard<std::mutex> lock(g_mutex);
-    if (!g_on || g_list.n >= kMaxDeferred || rows < 1 || cols < 1 || (kind == 0 && cols % 64)) return false;
-    DeferredReduction &d = g_list.e[g_list.n++];
-    d.part = part; d.out = out; d.rows = rows; d.cols = cols; d.kind = kind; d.first_block = g_blocks;
-    g_blocks += kind == 0 ? cols / 64 : (cols + 31) / 32;
+    if (!g_on || n < 1 || g_list.n + n > kMaxDeferred || rows < 1 || cols < 1 || (kind == 0 && cols % 64)) return false;
+    for (int i = 0; i < n; i++) {
+        DeferredReduction &d = g_list.e[g_list.n++];
+        d.part = parts[i]; d.out = outs[i]; d.rows = rows; d.cols = cols; d.kind = kind; d.first_block = g_blocks;
+        g_blocks += kind == 0 ? cols / 64 : (cols + 31) / 32;
+    }
     return true;
 }
 

@@ -4,8 +4,11 @@ PyTorch is plumbing here (HBM allocations, streams); all arithmetic happens in t
 HIP kernels behind the C ABI (include/dsrg_hip.h).  Every function below names the
 reference routine it replaces.
 """
+import contextlib
 import ctypes
+import os
 import threading
+import weakref as _weakref
 
 import torch
 
@@ -31,18 +34,62 @@ def _f32c(t, name):
 # ---- deferred bias-gradient reductions (dsrg_defer_reductions / dsrg_flush_reductions) -------------------------------------------
 # Inside `with deferred_reductions():` the 5-7 us passes that finish a bias gradient (column sums of a data gradient's partial rows,
 # the direct kernels' block partials: fifteen per train-s step) are recorded by the library and run in ONE launch when the block
-# ends.  This module's part of the contract: every recorded launch gets partial-row scratch of its own (`_partial_rows`: a fresh
-# tensor instead of the cached one) and all such scratch stays alive until the flush is enqueued (`_defer_keep`).
-_defer = [False]
-_defer_keep = []
+# ends.  This module's part of the contract is to keep alive, until the flush is enqueued, everything that launch touches: every
+# recording op takes the scratch its reduction reads from `_reduction_scratch` (inside a block a tensor of the launch's own) and
+# the bias gradient it writes from `_bias_grad_dest`; both park what they hand out in `_defer_keep`.
+_defer = [False]                       # [0]: inside deferred_reductions()
+_defer_keep = []                       # what the flush reads and writes, held until it is enqueued
 
 
-def _keep_until_flush(*tensors):
+_scratch = {}
+
+
+def _stream_scratch(kind, device, nbytes):
+    """launch scratch of at least nbytes (uint8), cached per (kind, device index, torch's current stream) and replaced only when it
+    is too small.  Launches are stream-ordered, so consecutive users of one buffer never overlap; replacing a buffer that earlier
+    launches on the stream still use is safe as well, because torch's allocator hands a freed block only to later work on the
+    stream that allocated it."""
+    key = (kind, device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _scratch.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _scratch[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _reduction_scratch(device, nbytes, kind=None):
+    """the scratch (uint8) a launch's bias-gradient reduction reads.  Inside deferred_reductions(): a tensor of the launch's own,
+    held until the flush.  Outside: the per-stream buffer of `kind`, or a fresh tensor when no kind is named."""
+    if kind is not None and not _defer[0]:
+        return _stream_scratch(kind, device, nbytes)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
     if _defer[0]:
-        _defer_keep.extend(t for t in tensors if t is not None)
+        _defer_keep.append(ws)
+    return ws
 
 
-@__import__("contextlib").contextmanager
+def _dest(out, shape, dtype, device, channels_last=False):
+    """`out` if it can take a kernel's result of this shape / dtype in place (a reducer's gradient slot: dense, the layout the
+    kernel writes), else a fresh tensor"""
+    if out is not None and out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.device == device and (
+            out.is_contiguous(memory_format=torch.channels_last) if channels_last else out.is_contiguous()):
+        return out
+    if channels_last:
+        return torch.empty(shape, dtype=dtype, device=device, memory_format=torch.channels_last)
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def _bias_grad_dest(out, shape, device):
+    """the float32 destination of a bias gradient: `out` if it can take it (_dest), else a fresh tensor.  Inside deferred_reductions()
+    the flush writes it, so its storage is held until then — through an alias, never the tensor itself: AccumulateGrad adopts a
+    gradient without copying only while nobody else holds the tensor object (backbone._landed), and a copy made before the flush
+    would be a copy of a gradient that is not final"""
+    gb = _dest(out, shape, torch.float32, device)
+    if _defer[0]:
+        _defer_keep.append(gb.detach())
+    return gb
+
+
+@contextlib.contextmanager
 def deferred_reductions(enabled=True):
     """inside: bias gradients returned by this module's launches are NOT final until the block ends (nothing may read them; autograd's
     AccumulateGrad adopting a gradient of a parameter whose .grad is None is no read); on exit one launch finishes them all"""
@@ -55,9 +102,9 @@ def deferred_reductions(enabled=True):
     try:
         yield
     finally:
-        _defer[0] = False
         rc = L.dsrg_flush_reductions(_stream())
         L.dsrg_defer_reductions(0)
+        _defer[0] = False
         del _defer_keep[:]
         check(rc)
 
@@ -220,7 +267,7 @@ def crf_refine(probs, images, scale_factor=12.0, maxiter=10, ctx=None, want_log=
     return refined, logq
 
 
-_MEAN_PIXEL = (104.0, 117.0, 123.0)
+MEAN_PIXEL = (104.0, 117.0, 123.0)      # B, G, R (test-ms.py:79; inference.MEAN_PIXEL)
 
 
 def _map_images_u8(images, H, W):
@@ -231,7 +278,7 @@ def _map_images_u8(images, H, W):
     x = images
     if x.shape[2] != H or x.shape[3] != W:
         x = F.interpolate(x.double(), size=(H, W), mode="bilinear", align_corners=True).float()
-    mean = torch.tensor(_MEAN_PIXEL, dtype=torch.float64, device=x.device).view(1, 3, 1, 1)
+    mean = torch.tensor(MEAN_PIXEL, dtype=torch.float64, device=x.device).view(1, 3, 1, 1)
     v = torch.round(x.double() + mean).to(torch.int64) & 0xff                    # half-even, then C's conversion to unsigned char
     return v.to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
@@ -374,6 +421,30 @@ def confusion_matrix(gt, pred, nclass, rule_lt=False, hist=None):
 
 
 _MS_OUTPUTS = ("unary", "argmax", "sum")
+_TG_OUTPUTS = ("unary", "probs", "labels")
+_INT_OUTPUTS = ("argmax", "labels")                  # (H, W) int32 maps; every other output is (H, W, C) float32
+
+
+def _want_names(want, allowed):
+    """a `want=` argument -> (names, single): a string names one output and asks for it bare, a sequence for tuples in its order"""
+    single = isinstance(want, str)
+    names = (want,) if single else tuple(want)
+    for n in names:
+        if n not in allowed:
+            raise ValueError("unknown output %r (choose from %s)" % (n, ", ".join(allowed)))
+    if not names:
+        raise ValueError("want names no output")
+    return names, single
+
+
+def _want_outputs(names, shapes, C, device):
+    """-> {name: [one output tensor per (H, W) of shapes]}"""
+    return {n: [torch.empty((H, W) if n in _INT_OUTPUTS else (H, W, C), dtype=torch.int32 if n in _INT_OUTPUTS else torch.float32,
+                            device=device) for H, W in shapes] for n in names}
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors]) if tensors is not None else None
 
 
 def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",)):
@@ -382,13 +453,7 @@ def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",)):
     tensors (sizes may differ).  want: names among "unary" ((H, W, C) f32 log-probabilities, the layout CRF_device takes),
     "argmax" ((H, W) int32, the first maximum) and "sum" ((H, W, C) f32 summed scores, for parity checks).  A string returns
     that one tensor, a sequence a tuple in its order.  Runs on torch's current stream."""
-    single = isinstance(want, str)
-    names = (want,) if single else tuple(want)
-    for n in names:
-        if n not in _MS_OUTPUTS:
-            raise ValueError("unknown output %r (choose from %s)" % (n, ", ".join(_MS_OUTPUTS)))
-    if not names:
-        raise ValueError("want names no output")
+    names, single = _want_names(want, _MS_OUTPUTS)
     scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
     if not scores:
         raise ValueError("no score maps")
@@ -396,14 +461,8 @@ def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",)):
     for s in scores:
         if s.dim() != 4 or s.shape[0] != 1 or s.shape[1] != C:
             raise ValueError("score maps must be (1, C, h, w) with one C; got %s" % (tuple(s.shape),))
-    K, dev = len(scores), scores[0].device
-    out = {}
-    if "unary" in names:
-        out["unary"] = torch.empty((H, W, C), dtype=torch.float32, device=dev)
-    if "argmax" in names:
-        out["argmax"] = torch.empty((H, W), dtype=torch.int32, device=dev)
-    if "sum" in names:
-        out["sum"] = torch.empty((H, W, C), dtype=torch.float32, device=dev)
+    K = len(scores)
+    out = {n: ts[0] for n, ts in _want_outputs(names, [(H, W)], C, scores[0].device).items()}
     ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scores])
     hs = (ctypes.c_int32 * K)(*[s.shape[2] for s in scores])
     ws = (ctypes.c_int32 * K)(*[s.shape[3] for s in scores])
@@ -419,18 +478,12 @@ def multiscale_unary_batch(scores, shapes, eps=1e-5, want=("unary",)):
     tensors, image g reads slice g; shapes: the G <= min(Gcap, 16) output sizes (H_g, W_g).  want: as multiscale_unary.  Returns a
     list of G entries, each what multiscale_unary(slices g, H_g, W_g, eps, want) returns, bit for bit.  Runs on torch's current
     stream."""
-    single = isinstance(want, str)
-    names = (want,) if single else tuple(want)
-    for n in names:
-        if n not in _MS_OUTPUTS:
-            raise ValueError("unknown output %r (choose from %s)" % (n, ", ".join(_MS_OUTPUTS)))
-    if not names:
-        raise ValueError("want names no output")
+    names, single = _want_names(want, _MS_OUTPUTS)
     scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
     if not scores:
         raise ValueError("no score maps")
     shapes = [(int(H), int(W)) for H, W in shapes]
-    G, K, dev = len(shapes), len(scores), scores[0].device
+    G, K = len(shapes), len(scores)
     if scores[0].dim() != 4:
         raise ValueError("score maps must be (Gcap, C, h, w); got %s" % (tuple(scores[0].shape),))
     Gcap, C = scores[0].shape[0], scores[0].shape[1]
@@ -439,30 +492,17 @@ def multiscale_unary_batch(scores, shapes, eps=1e-5, want=("unary",)):
             raise ValueError("score maps must be (Gcap, C, h, w) with one Gcap and one C; got %s" % (tuple(s.shape),))
     if not 1 <= G <= Gcap:
         raise ValueError("%d output shapes for score maps of %d images" % (G, Gcap))
-    out = {}
-    if "unary" in names:
-        out["unary"] = [torch.empty((H, W, C), dtype=torch.float32, device=dev) for H, W in shapes]
-    if "argmax" in names:
-        out["argmax"] = [torch.empty((H, W), dtype=torch.int32, device=dev) for H, W in shapes]
-    if "sum" in names:
-        out["sum"] = [torch.empty((H, W, C), dtype=torch.float32, device=dev) for H, W in shapes]
-
-    def ptr_array(name):
-        return (ctypes.c_void_p * G)(*[t.data_ptr() for t in out[name]]) if name in out else None
-
+    out = _want_outputs(names, shapes, C, scores[0].device)
     ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scores])
     hs = (ctypes.c_int32 * K)(*[s.shape[2] for s in scores])
     ws = (ctypes.c_int32 * K)(*[s.shape[3] for s in scores])
     Hs = (ctypes.c_int32 * G)(*[H for H, _ in shapes])
     Ws = (ctypes.c_int32 * G)(*[W for _, W in shapes])
-    check(_lib.lib().dsrg_multiscale_unary_batch(G, K, int(C), ptrs, hs, ws, Hs, Ws, float(eps), ptr_array("unary"),
-                                                 ptr_array("argmax"), ptr_array("sum"), _stream()))
+    check(_lib.lib().dsrg_multiscale_unary_batch(G, K, int(C), ptrs, hs, ws, Hs, Ws, float(eps), _ptr_array(out.get("unary")),
+                                                 _ptr_array(out.get("argmax")), _ptr_array(out.get("sum")), _stream()))
     if single:
         return out[names[0]]
     return [tuple(out[n][g] for n in names) for g in range(G)]
-
-
-_TG_OUTPUTS = ("unary", "probs", "labels")
 
 
 def train_gt_unary_batch(scores, shapes, eps=1e-5, want=("unary",), select=None, ignore_below=None):
@@ -475,13 +515,7 @@ def train_gt_unary_batch(scores, shapes, eps=1e-5, want=("unary",), select=None,
     <= 0: off).  A string returns the list of that one tensor per image, a sequence a list of tuples in its order.  Image g's
     results equal those of a G = 1 call on slice g bit for bit.  Runs on torch's current stream; the workspace (G * C * h * w
     floats) is a torch tensor."""
-    single = isinstance(want, str)
-    names = (want,) if single else tuple(want)
-    for n in names:
-        if n not in _TG_OUTPUTS:
-            raise ValueError("unknown output %r (choose from %s)" % (n, ", ".join(_TG_OUTPUTS)))
-    if not names:
-        raise ValueError("want names no output")
+    names, single = _want_names(want, _TG_OUTPUTS)
     if not torch.is_tensor(scores):
         raise ValueError("scores must be one (Gcap, C, h, w) tensor")
     scores = _f32c(scores, "scores")
@@ -498,29 +532,16 @@ def train_gt_unary_batch(scores, shapes, eps=1e-5, want=("unary",), select=None,
         if select is None:
             raise ValueError('want="labels" needs one selection list per image (select=...)')
         sel, nsel, stride = select_arrays(select, G, C)
-    out = {}
-    if "unary" in names:
-        out["unary"] = [torch.empty((H, W, C), dtype=torch.float32, device=dev) for H, W in shapes]
-    if "probs" in names:
-        out["probs"] = [torch.empty((H, W, C), dtype=torch.float32, device=dev) for H, W in shapes]
-    if "labels" in names:
-        out["labels"] = [torch.empty((H, W), dtype=torch.int32, device=dev) for H, W in shapes]
+    out = _want_outputs(names, shapes, C, dev)
     workspace = torch.empty((G, C, h, w), dtype=torch.float32, device=dev)
-
-    def ptr_array(name):
-        return (ctypes.c_void_p * G)(*[t.data_ptr() for t in out[name]]) if name in out else None
-
     Hs = (ctypes.c_int32 * G)(*[H for H, _ in shapes])
     Ws = (ctypes.c_int32 * G)(*[W for _, W in shapes])
     check(_lib.lib().dsrg_train_gt_unary_batch(G, int(C), _ptr(scores), int(h), int(w), Hs, Ws, float(eps), sel, nsel, int(stride),
-                                               float(ignore_below or 0.0), _ptr(workspace), ptr_array("unary"), ptr_array("probs"),
-                                               ptr_array("labels"), _stream()))
+                                               float(ignore_below or 0.0), _ptr(workspace), _ptr_array(out.get("unary")),
+                                               _ptr_array(out.get("probs")), _ptr_array(out.get("labels")), _stream()))
     if single:
         return out[names[0]]
     return [tuple(out[n][g] for n in names) for g in range(G)]
-
-
-MEAN_PIXEL = (104.0, 117.0, 123.0)      # B, G, R (test-ms.py:79; inference.MEAN_PIXEL)
 
 
 def preprocess_ms_batch(images, sizes, capacity=None, mean=MEAN_PIXEL, out=None):
@@ -695,35 +716,7 @@ def col2im3x3_nhwc(cols, B, H, W, C, dilation):
     return out
 
 
-_PARTIAL_BLOCKS = 512
-# scratch for the per-block partial column sums, one buffer per (device, channel count).  Calls are stream-ordered on
-# torch's current stream (autograd runs a backward pass on one stream), so consecutive users never overlap; code that
-# drives these ops from several streams at once must give each stream its own buffers.
-_partials = {}
-
-
-def _partial_rows(device, C):
-    """the partial-row scratch of a bias-gradient launch: the cached buffer of (device, C) — or, while the finishing passes are being
-    deferred (deferred_reductions), a buffer of the launch's own, kept until the flush"""
-    if _defer[0]:
-        part = torch.empty(_PARTIAL_BLOCKS * C, dtype=torch.float32, device=device)
-        _defer_keep.append(part)
-        return part
-    part = _partials.get((device, C))
-    if part is None:
-        part = _partials[(device, C)] = torch.empty(_PARTIAL_BLOCKS * C, dtype=torch.float32, device=device)
-    return part
-
-
-def _dest(out, shape, dtype, device, channels_last=False):
-    """`out` if it can take a kernel's result of this shape / dtype in place (a reducer's gradient slot: dense, the layout the
-    kernel writes), else a fresh tensor"""
-    if out is not None and out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.device == device and (
-            out.is_contiguous(memory_format=torch.channels_last) if channels_last else out.is_contiguous()):
-        return out
-    if channels_last:
-        return torch.empty(shape, dtype=dtype, device=device, memory_format=torch.channels_last)
-    return torch.empty(shape, dtype=dtype, device=device)
+_PARTIAL_BLOCKS = 512                  # rows of per-block partial column sums (relu_bwd_bias, bias_grad, maxpool3x3_bwd_relu)
 
 
 def relu_bwd_bias(g, y, scale=1.0, gb_out=None):
@@ -736,8 +729,8 @@ def relu_bwd_bias(g, y, scale=1.0, gb_out=None):
         raise ValueError("relu_bwd_bias needs bf16 channels_last CUDA tensors")
     g = g.contiguous(memory_format=cl)
     gm = torch.empty_like(y)
-    gb = _dest(gb_out, (C,), torch.float32, y.device)
-    part = _partial_rows(y.device, C)
+    gb = _bias_grad_dest(gb_out, (C,), y.device)
+    part = _reduction_scratch(y.device, 4 * _PARTIAL_BLOCKS * C, "rows").view(torch.float32)
     check(_lib.lib().dsrg_relu_bwd_bias_bf16(_ptr(g), _ptr(y), _ptr(gm), _ptr(gb), _ptr(part), _PARTIAL_BLOCKS,
                                              B * H * W, C, float(scale), _stream()))
     return gm, gb
@@ -749,8 +742,8 @@ def bias_grad(g):
     if not (g.is_cuda and g.dtype == torch.bfloat16):
         raise ValueError("bias_grad needs a bf16 CUDA tensor")
     g = g.contiguous(memory_format=torch.channels_last)
-    gb = torch.empty(C, dtype=torch.float32, device=g.device)
-    part = _partial_rows(g.device, C)
+    gb = _bias_grad_dest(None, (C,), g.device)
+    part = _reduction_scratch(g.device, 4 * _PARTIAL_BLOCKS * C, "rows").view(torch.float32)
     if C % 8 == 0:                                   # 16-byte lanes, no mask, nothing stored
         check(_lib.lib().dsrg_relu_bwd_bias_bf16(_ptr(g), None, None, _ptr(gb), _ptr(part), _PARTIAL_BLOCKS,
                                                  B * H * W, C, 1.0, _stream()))
@@ -810,8 +803,8 @@ def conv3x3_direct(x, weight, bias=None, relu=False):
     if not (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and tuple(weight.shape) == (cout, C, 3, 3)
             and ((C in DIRECT_CONV_CHANNELS and cout in DIRECT_CONV_CHANNELS) or (C, cout) == (3, 64))):
         raise ValueError("conv3x3_direct needs a bf16 CUDA input and a (cout,cin,3,3) bf16 kernel with cin, cout in (64, 128) or 3 -> 64")
-    x = x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl)
-    w = weight if weight.is_contiguous(memory_format=cl) else weight.contiguous(memory_format=cl)
+    x = x.contiguous(memory_format=cl)
+    w = weight.contiguous(memory_format=cl)
     if bias is not None:
         bias = bias.float().contiguous()
     y = torch.empty((B, cout, H, W), dtype=torch.bfloat16, device=x.device, memory_format=cl)
@@ -830,20 +823,18 @@ def conv3x3_direct_dgrad(g, weight_t, mask):
             and C in DIRECT_CONV_CHANNELS and cout in DIRECT_CONV_CHANNELS and mask.dtype == torch.bfloat16
             and tuple(mask.shape) == (B, cout, H, W) and mask.is_contiguous(memory_format=cl)):
         raise ValueError("conv3x3_direct_dgrad needs bf16 CUDA tensors, 64 / 128 channels, a channels_last mask of the output's shape")
-    g = g if g.is_contiguous(memory_format=cl) else g.contiguous(memory_format=cl)
-    w = weight_t if weight_t.is_contiguous(memory_format=cl) else weight_t.contiguous(memory_format=cl)
+    g = g.contiguous(memory_format=cl)
+    w = weight_t.contiguous(memory_format=cl)
     L = _lib.lib()
     gx = torch.empty((B, cout, H, W), dtype=torch.bfloat16, device=g.device, memory_format=cl)
-    gb = torch.empty(cout, dtype=torch.float32, device=g.device)
-    ws = torch.empty(L.dsrg_conv3x3_direct_dgrad_workspace(cout), dtype=torch.uint8, device=g.device)
-    _keep_until_flush(ws)
+    gb = _bias_grad_dest(None, (cout,), g.device)
+    ws = _reduction_scratch(g.device, L.dsrg_conv3x3_direct_dgrad_workspace(cout))
     check(L.dsrg_conv3x3_direct_dgrad_bf16(_ptr(g), _ptr(w), _ptr(mask), _ptr(gx), _ptr(gb), _ptr(ws), ws.numel(), B, H, W, C, cout,
                                            _stream()))
     return gx, gb
 
 
 WGRAD_CONV_SHAPES = ((3, 64), (64, 64), (64, 128), (128, 128))      # (cin, cout)
-_wgrad_ws = {}
 
 
 # ---- the packed bf16 kernels of the float32 master parameters, kept from step to step — only for parameters an optimizer that
@@ -856,9 +847,6 @@ _wgrad_ws = {}
 # parameter unless its optimizer says it plays along; unclaimed parameters are packed inside every forward as before.  Writes
 # through `param.data` (whose version counter is its own) or by foreign kernels are equally invisible: code that does that to a
 # claimed parameter calls forget_weight_packs afterwards.
-import weakref as _weakref
-
-
 class _WeightPacks(object):
     __slots__ = ("ref", "version", "fwd", "dg", "plain")
 
@@ -932,7 +920,7 @@ def _packs_for(weight, plain, want_fwd, want_dgrad, fwd_shape, dg_shape, fwd_cl=
 # DSRG_CHECK_PACKS=N (debugging aid): every N-th time a forward takes kept packs for good, the parameter is packed again into
 # scratch buffers and compared — a writer the version counter cannot see (`p.data.copy_`, an EMA through `.data`, a foreign
 # kernel, torch's private fused optimizer ops) then fails loudly instead of training on kernels one update behind.  0 = off.
-_CHECK_PACKS = int(__import__("os").environ.get("DSRG_CHECK_PACKS", "0") or 0)
+_CHECK_PACKS = int(os.environ.get("DSRG_CHECK_PACKS", "0") or 0)
 _check_packs_calls = [0]
 
 
@@ -1015,13 +1003,9 @@ def conv3x3_wgrad(x, g, out_dtype=torch.bfloat16, out=None):
     if not (x.is_cuda and x.dtype == torch.bfloat16 and g.dtype == torch.bfloat16 and tuple(g.shape) == (B, cout, H, W)
             and (cin, cout) in WGRAD_CONV_SHAPES):
         raise ValueError("conv3x3_wgrad needs bf16 CUDA tensors with (cin, cout) in %s" % (WGRAD_CONV_SHAPES,))
-    x = x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl)
-    g = g if g.is_contiguous(memory_format=cl) else g.contiguous(memory_format=cl)
-    need = _lib.lib().dsrg_conv3x3_wgrad_workspace(B, H, W, cin, cout)
-    key = (x.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _wgrad_ws.get(key)                                          # per-stream scratch, reused across layers and steps
-    if ws is None or ws.numel() < need:
-        ws = _wgrad_ws[key] = torch.empty(need, dtype=torch.uint8, device=x.device)
+    x = x.contiguous(memory_format=cl)
+    g = g.contiguous(memory_format=cl)
+    ws = _stream_scratch("wgrad3x3", x.device, _lib.lib().dsrg_conv3x3_wgrad_workspace(B, H, W, cin, cout))
     if out_dtype not in (torch.bfloat16, torch.float32):
         raise ValueError("conv3x3_wgrad: bf16 or float32 output")
     gw = _dest(out, (cout, cin, 3, 3), out_dtype, x.device, True)
@@ -1133,7 +1117,7 @@ def conv_igemm(xs, packed, biases, dilations, ksize, relu, dropout_p=0.0, seed=0
         if not (x.is_cuda and x.dtype == torch.bfloat16 and tuple(x.shape) == (B, cin, H, W) and p.dtype == torch.bfloat16
                 and tuple(p.shape) == (cout, cin // 64, ksize * ksize, 64) and p.is_contiguous()):
             raise ValueError("conv_igemm needs bf16 CUDA inputs of one shape and kernels packed by pack_conv_weight")
-    xs = [x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl) for x in xs]
+    xs = [x.contiguous(memory_format=cl) for x in xs]
     bs = [None if b is None else _f32c(b, "bias") for b in (biases or [None] * n)]
     ys = [torch.empty((B, cout, H, W), dtype=torch.bfloat16, device=xs[0].device, memory_format=cl) for _ in range(n)]
     vp = ctypes.c_void_p * n
@@ -1158,7 +1142,7 @@ def conv_igemm_residual(x, packed, bias, res, mask, dilation, ksize, relu):
     if not (x.is_cuda and x.dtype == torch.bfloat16 and packed.dtype == torch.bfloat16 and packed.is_contiguous()
             and tuple(packed.shape) == (cout, cin // 64, ksize * ksize, 64) and ok(res) and (mask is None or ok(mask))):
         raise ValueError("conv_igemm_residual needs bf16 channels_last tensors of matching shapes and a kernel packed by pack_conv_weight")
-    x = x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl)
+    x = x.contiguous(memory_format=cl)
     b = None if bias is None else _f32c(bias, "bias")
     y = torch.empty((B, cout, H, W), dtype=torch.bfloat16, device=x.device, memory_format=cl)
     check(_lib.lib().dsrg_conv_igemm_residual_bf16(_ptr(x), _ptr(packed), _ptr(b), _ptr(res), _ptr(mask), _ptr(y), int(dilation), B, H, W,
@@ -1212,15 +1196,14 @@ def conv_igemm_dgrad(gs, packed_t, masks, dilations, ksize, mask_scale=1.0, bias
                 and tuple(p.shape) == (cout, cin // 64, ksize * ksize, 64) and p.is_contiguous() and m.dtype == torch.bfloat16
                 and tuple(m.shape) == (B, cout, H, W) and m.is_contiguous(memory_format=cl)):
             raise ValueError("conv_igemm_dgrad needs bf16 channels_last gradients / masks of one shape and packed kernels")
-    gs = [g if g.is_contiguous(memory_format=cl) else g.contiguous(memory_format=cl) for g in gs]
+    gs = [g.contiguous(memory_format=cl) for g in gs]
     outs = [torch.empty((B, cout, H, W), dtype=torch.bfloat16, device=gs[0].device, memory_format=cl) for _ in range(n)]
     vp = ctypes.c_void_p * n
     L = _lib.lib()
     gb = ws = None
     if bias_grad:
-        gb = [_dest(gb_outs[i] if gb_outs is not None else None, (cout,), torch.float32, gs[0].device) for i in range(n)]
-        ws = torch.empty(L.dsrg_conv_igemm_dgrad_workspace(n, B, H, W, cout), dtype=torch.uint8, device=gs[0].device)
-        _keep_until_flush(ws)
+        gb = [_bias_grad_dest(gb_outs[i] if gb_outs is not None else None, (cout,), gs[0].device) for i in range(n)]
+        ws = _reduction_scratch(gs[0].device, L.dsrg_conv_igemm_dgrad_workspace(n, B, H, W, cout))
     check(L.dsrg_conv_igemm_dgrad_bf16(vp(*[g.data_ptr() for g in gs]), vp(*[p.data_ptr() for p in packed_t]),
                                        vp(*[m.data_ptr() for m in masks]), vp(*[o.data_ptr() for o in outs]),
                                        vp(*[b.data_ptr() for b in gb]) if gb else None,
@@ -1244,22 +1227,18 @@ def conv_igemm_backward(g, packed_d, x, dilation, mask=None, mask_scale=1.0, ksi
             and packed_d.is_contiguous() and x.is_contiguous(memory_format=cl)
             and (mask is None or (mask.dtype == torch.bfloat16 and tuple(mask.shape) == (B, cin, H, W) and mask.is_contiguous(memory_format=cl)))):
         raise ValueError("conv_igemm_backward needs bf16 channels_last g / x (/ mask) of one geometry and the data-gradient packing")
-    g = g if g.is_contiguous(memory_format=cl) else g.contiguous(memory_format=cl)
+    g = g.contiguous(memory_format=cl)
     L = _lib.lib()
     need = L.dsrg_conv_igemm_wgrad_workspace(1, B, H, W, cin, cout, ksize)
     if need == 0:
         raise ValueError("conv_igemm_backward: 256 | cin (or cin = 128), 256 | cout required (got %d, %d)" % (cin, cout))
-    key = (g.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _igemm_ws.get(key)                                          # per-stream scratch, shared with conv_igemm_wgrad
-    if ws is None or ws.numel() < need:
-        ws = _igemm_ws[key] = torch.empty(need, dtype=torch.uint8, device=g.device)
+    ws = _stream_scratch("igemm_wgrad", g.device, need)              # shared with conv_igemm_wgrad
     gx = torch.empty((B, cin, H, W), dtype=torch.bfloat16, device=g.device, memory_format=cl)
     gw = _dest(gw_out, (cout, cin, ksize, ksize), torch.float32, g.device, True)
     gb = cws = None
     if mask is not None:
-        gb = _dest(gb_out, (cin,), torch.float32, g.device)
-        cws = torch.empty(L.dsrg_conv_igemm_dgrad_workspace(1, B, H, W, cin), dtype=torch.uint8, device=g.device)
-        _keep_until_flush(cws)
+        gb = _bias_grad_dest(gb_out, (cin,), g.device)
+        cws = _reduction_scratch(g.device, L.dsrg_conv_igemm_dgrad_workspace(1, B, H, W, cin))
     check(L.dsrg_conv_igemm_backward_bf16(_ptr(g), _ptr(packed_d), _ptr(x), _ptr(mask), _ptr(gx), _ptr(gw), int(dilation), _ptr(gb),
                                           float(mask_scale), _ptr(cws), cws.numel() if cws is not None else 0, _ptr(ws), ws.numel(),
                                           B, H, W, cin, cout, ksize, _stream()))
@@ -1278,15 +1257,12 @@ def conv_igemm_backward_residual(g, packed_d, x, dilation, ksize, mask=None, res
     if not (g.is_cuda and g.dtype == torch.bfloat16 and ok(x) and packed_d.dtype == torch.bfloat16 and packed_d.is_contiguous()
             and tuple(packed_d.shape) == (cin, cout // 64, ksize * ksize, 64) and (mask is None or ok(mask)) and (res is None or ok(res))):
         raise ValueError("conv_igemm_backward_residual needs bf16 channels_last g / x (/ mask / res) of one geometry and the data-gradient packing")
-    g = g if g.is_contiguous(memory_format=cl) else g.contiguous(memory_format=cl)
+    g = g.contiguous(memory_format=cl)
     L = _lib.lib()
     need = L.dsrg_conv_igemm_wgrad_workspace(1, B, H, W, cin, cout, ksize)
     if need == 0:
         raise ValueError("conv_igemm_backward_residual: 256 | cin (or cin = 128 with a 3x3 kernel), 256 | cout required (got %d, %d)" % (cin, cout))
-    key = (g.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _igemm_ws.get(key)                                          # per-stream scratch, shared with conv_igemm_wgrad
-    if ws is None or ws.numel() < need:
-        ws = _igemm_ws[key] = torch.empty(need, dtype=torch.uint8, device=g.device)
+    ws = _stream_scratch("igemm_wgrad", g.device, need)              # shared with conv_igemm_wgrad
     gx = torch.empty((B, cin, H, W), dtype=torch.bfloat16, device=g.device, memory_format=cl)
     gw = _dest(gw_out, (cout, cin, ksize, ksize), torch.float32, g.device, True)
     sc = None if gw_scale is None else _f32c(gw_scale, "gw_scale")
@@ -1295,16 +1271,9 @@ def conv_igemm_backward_residual(g, packed_d, x, dilation, ksize, mask=None, res
     return gx, gw
 
 
-_igemm_sk_ws = {}
-
-
 def _igemm_sk_workspace(device):
-    """the stream-K scratch of (device, current stream): one accumulator tile per CU + flags, allocated once"""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _igemm_sk_ws.get(key)
-    if ws is None:
-        ws = _igemm_sk_ws[key] = torch.empty(_lib.lib().dsrg_conv_igemm_workspace(), dtype=torch.uint8, device=device)
-    return ws
+    """the stream-K scratch of (device, current stream): one accumulator tile per CU + flags — a fixed size, so never replaced"""
+    return _stream_scratch("igemm_stream_k", device, _lib.lib().dsrg_conv_igemm_workspace())
 
 
 def conv_igemm_stream_k_status(device=None):
@@ -1319,9 +1288,6 @@ def conv_igemm_stream_k_status(device=None):
 def dropout_seed():
     """a 63-bit seed for a fused dropout from torch's CPU generator (deterministic under torch.manual_seed, no device sync)"""
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-
-
-_igemm_ws = {}
 
 
 def conv_igemm_wgrad_supported(cin, cout, k):
@@ -1351,16 +1317,13 @@ def conv_igemm_wgrad(xs, gs, dilations, ksize, out_dtype=torch.float32, outs=Non
         if not (x.is_cuda and x.dtype == torch.bfloat16 and g.dtype == torch.bfloat16 and tuple(x.shape) == (B, cin, H, W)
                 and tuple(g.shape) == (B, cout, H, W)):
             raise ValueError("conv_igemm_wgrad needs bf16 CUDA tensors of one geometry")
-    xs = [x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl) for x in xs]
-    gs = [g if g.is_contiguous(memory_format=cl) else g.contiguous(memory_format=cl) for g in gs]
+    xs = [x.contiguous(memory_format=cl) for x in xs]
+    gs = [g.contiguous(memory_format=cl) for g in gs]
     L = _lib.lib()
     need = L.dsrg_conv_igemm_wgrad_workspace(n, B, H, W, cin, cout, ksize)
     if need == 0:
         raise ValueError("conv_igemm_wgrad: 64 | cin, 64 | cout, k in (1, 3) required (got %d, %d, %d)" % (cin, cout, ksize))
-    key = (xs[0].device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _igemm_ws.get(key)                                          # per-stream scratch, reused across layers and steps
-    if ws is None or ws.numel() < need:
-        ws = _igemm_ws[key] = torch.empty(need, dtype=torch.uint8, device=xs[0].device)
+    ws = _stream_scratch("igemm_wgrad", xs[0].device, need)          # reused across layers and steps
     gws = [_dest(outs[i] if outs is not None else None, (cout, cin, ksize, ksize), out_dtype, xs[0].device, True) for i in range(n)]
     vp = ctypes.c_void_p * n
     check(L.dsrg_conv_igemm_wgrad_bf16(vp(*[x.data_ptr() for x in xs]), vp(*[g.data_ptr() for g in gs]),
@@ -1385,7 +1348,7 @@ def heads_forward(xs, weight, bias):
     B, K, H, W = xs[0].shape
     n, O = weight.shape[0], weight.shape[1]
     cl = torch.channels_last
-    xs = [x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl) for x in xs]
+    xs = [x.contiguous(memory_format=cl) for x in xs]
     if not all(x.is_cuda and x.dtype == torch.bfloat16 and x.shape == xs[0].shape for x in xs) or len(xs) != n:
         raise ValueError("heads_forward needs n bf16 CUDA activations of one shape")
     _f32c(weight, "weight")
@@ -1404,7 +1367,7 @@ def heads_backward(xs, weight, g, need_gx=True, relu_scale=0.0):
     B, K, H, W = xs[0].shape
     n, O = weight.shape[0], weight.shape[1]
     cl = torch.channels_last
-    xs = [x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl) for x in xs]
+    xs = [x.contiguous(memory_format=cl) for x in xs]
     _f32c(weight, "weight")
     g = g.contiguous()
     _f32c(g, "g")
@@ -1415,9 +1378,8 @@ def heads_backward(xs, weight, g, need_gx=True, relu_scale=0.0):
     part = torch.empty(L.dsrg_heads_backward_chunks(M) * n * O * K, dtype=torch.float32, device=g.device)
     ptrs = (ctypes.c_void_p * 4)(*([x.data_ptr() for x in xs] + [None] * (4 - n)))
     if relu_scale > 0.0 and need_gx:
-        gb = torch.empty((n, K), dtype=torch.float32, device=g.device)
-        ws = torch.empty(L.dsrg_heads_backward_relu_workspace(n, M, K), dtype=torch.uint8, device=g.device)
-        _keep_until_flush(ws)
+        gb = _bias_grad_dest(None, (n, K), g.device)
+        ws = _reduction_scratch(g.device, L.dsrg_heads_backward_relu_workspace(n, M, K))
         check(L.dsrg_heads_backward_relu_bf16(ptrs, n, _ptr(weight), _ptr(g), _ptr(gx), M * K * 2, _ptr(gw), _ptr(part),
                                               float(relu_scale), _ptr(gb), _ptr(ws), ws.numel(), B, H * W, K, O, _stream()))
         return [gx[k].permute(0, 3, 1, 2) for k in range(n)], gw, gb
@@ -1508,8 +1470,8 @@ def maxpool3x3_bwd_relu(gout, code, relu_out, stride=2, gb_out=None):
         raise ValueError("maxpool3x3_bwd_relu: stride 2, bf16 channels_last, channels / 8 a divisor of 256")
     gout = gout.contiguous(memory_format=cl)
     gin = torch.empty((B, C, H, W), dtype=torch.bfloat16, device=gout.device, memory_format=cl)
-    gb = _dest(gb_out, (C,), torch.float32, gout.device)
-    part = _partial_rows(gout.device, C)                            # shared with relu_bwd_bias (same stream-ordering rule)
+    gb = _bias_grad_dest(gb_out, (C,), gout.device)
+    part = _reduction_scratch(gout.device, 4 * _PARTIAL_BLOCKS * C, "rows").view(torch.float32)
     check(_lib.lib().dsrg_maxpool3x3_bwd_relu_bf16(_ptr(gout), _ptr(code), _ptr(relu_out) if have_y else None, _ptr(gin), _ptr(gb), _ptr(part),
                                                    _PARTIAL_BLOCKS, B, H, W, OH, OW, C, _stream()))
     return gin, gb
