@@ -144,6 +144,13 @@ SIGNATURES = {
     "dsrg_maxpool3x3_bwd_relu_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dsrg_supervision_step": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _d, _d, ctypes.POINTER(CrfParams),
                                    _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsrg_supervision_step_total": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _d, _d, ctypes.POINTER(CrfParams),
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsrg_heads_forward_ptrs_bf16": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "dsrg_heads_backward_ptrs_bf16": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _vp, _vp, _f, _vp, _vp, _sz] + [_i] * 4 + [_vp]),
+    "dsrg_image_nchw_to_nhwc_bf16": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "dsrg_sum_bf16": (_i, [_vp, _i, _vp, _sz, _vp]),
+    "dsrg_sgd_pack_cast_f32": (_i, [_i] + [_vp] * 10 + [_f, _vp]),
 }
 
 _LIB = None

@@ -275,6 +275,12 @@ class _IgemmConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, k, dils, relu, drop_p, pool, n, links_in, links_out, *t):
         xs, ws, bs = t[:n], t[n:2 * n], t[2 * n:3 * n]
+        # one tensor fed n times (the four fc6_k read pool5a's output): backward returns the sum of its n data gradients, formed in
+        # one pass the way autograd's accumulation forms it, instead of leaving n - 1 pairwise adds to the engine
+        # (bf16 inputs only: a float32 input's gradients are cast up before the engine adds them)
+        ctx.same_x = n > 1 and xs[0].dtype == torch.bfloat16 and all(
+            x.data_ptr() == xs[0].data_ptr() and x.shape == xs[0].shape and x.stride() == xs[0].stride() and x.dtype == xs[0].dtype
+            and x._version == xs[0]._version for x in xs[1:])
         xs = [x if x.dtype == torch.bfloat16 else x.bfloat16() for x in xs]
         packs_d = [None] * n
         fb = [b.detach().float().contiguous() for b in bs]
@@ -379,7 +385,18 @@ class _IgemmConvFn(torch.autograd.Function):
                 d = ctx.dils[i]
                 gws.append(torch.ops.aten.convolution_backward(gms[i], xs[i], ws[i].to(torch.bfloat16), None, [1, 1], [d, d], [d, d],
                                                                False, [0, 0], 1, [False, True, False])[1].float())
+        if ctx.same_x and all(need_x) and _sum_takes(gxs):
+            # rne(rne(rne(g_1 + g_2) + g_3) + g_4): the bits the engine's accumulation of the n gradients of one tensor has
+            gxs = [ops.sum_bf16(list(gxs))] + [None] * (n - 1)
         return (None,) * 8 + tuple(gx if nx else None for gx, nx in zip(gxs, need_x)) + tuple(gws) + tuple(gbs)
+
+
+def _sum_takes(gs):
+    """does ops.sum_bf16 take these gradients: 2..4 bf16 CUDA tensors of one shape and one dense layout, 8 | elements"""
+    g0 = gs[0]
+    return 2 <= len(gs) <= 4 and all(g is not None and g.is_cuda and g.dtype == torch.bfloat16 and g.shape == g0.shape and
+                                     g.stride() == g0.stride() for g in gs) and g0.numel() > 0 and g0.numel() % 8 == 0 and \
+        (g0.is_contiguous() or (g0.dim() == 4 and g0.is_contiguous(memory_format=torch.channels_last)))
 
 
 class _DirectConvFn(torch.autograd.Function):
@@ -391,11 +408,13 @@ class _DirectConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu, pool, link_in, link_out):
-        x = x if x.dtype == torch.bfloat16 else x.bfloat16()
         cl = torch.channels_last
+        if ops.image_takes_fused_cast(x):
+            x = ops.image_to_bf16_nhwc(x)              # the float32 NCHW image: layout and cast in one pass, the same bits
+        x = x if x.dtype == torch.bfloat16 else x.bfloat16()
         x = x if x.is_contiguous(memory_format=cl) else x.contiguous(memory_format=cl)
         if weight.shape[1] == 3:
-            w16, wd = weight.detach().to(torch.bfloat16), None                            # the image needs no gradient
+            w16, wd = ops.cast_weight_kept(weight), None                                  # the image needs no gradient
         else:
             w16, wd = ops.pack_direct_weight_pair(weight, ctx.needs_input_grad[0])
         out = ops.conv3x3_direct(x, w16, bias.detach(), relu)
@@ -647,6 +666,40 @@ class _HeadsFn(torch.autograd.Function):
         return (None, gw, gb1.unsqueeze(0).expand(n, O).contiguous()) + (tuple(gxs) if gxs is not None else (None,) * n)
 
 
+class _HeadsPtrFn(torch.autograd.Function):
+    """_HeadsFn with the n classifier kernels and biases read where the parameters lie (ops.heads_forward_ptrs: no stacked copy
+    of either per step) and every kernel's gradient written to a tensor of its own with the parameter's strides — a reducer's slot
+    (`_dsrg_grad_out`) where the parameter names one.  apply(links, n, w_1..w_n, b_1..b_n, x_1..x_n); the same bits as _HeadsFn."""
+
+    @staticmethod
+    def forward(ctx, links, n, *t):
+        ws, bs, xs = t[:n], t[n:2 * n], t[2 * n:]
+        cl = torch.channels_last
+        ctx.links = links if (links is not None and all(lk is not None for lk in links) and
+                              all(x.is_contiguous(memory_format=cl) for x in xs)) else None
+        xs = [x.contiguous(memory_format=cl) for x in xs]
+        ctx.n = n
+        ctx.gw_out = [getattr(w, "_dsrg_grad_out", None) for w in ws]
+        ctx.save_for_backward(*ws, *xs)
+        return ops.heads_forward_ptrs(xs, [w.detach() for w in ws], [b.detach() for b in bs])
+
+    @staticmethod
+    def backward(ctx, g):
+        n = ctx.n
+        ws, xs = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        O = ws[0].shape[0]
+        need_x = ctx.needs_input_grad[2 + 2 * n:]
+        if _FUSE_CHAIN and ctx.links is not None and all(need_x):
+            gxs, gws, gb_below = ops.heads_backward_ptrs(xs, ws, g, True, ctx.links[0].scale, gw_outs=ctx.gw_out)
+            for i, lk in enumerate(ctx.links):
+                lk.leave(gxs[i], gb_below[i])
+        else:
+            gxs, gws = ops.heads_backward_ptrs(xs, ws, g, need_gx=any(need_x), gw_outs=ctx.gw_out)
+        gb = g.sum((0, 2, 3)).unsqueeze(0).expand(n, O).contiguous()      # fp32, the same for every branch (torch's sum, as _HeadsFn)
+        gws = [_landed(gw, o) for gw, o in zip(gws, ctx.gw_out)]
+        return (None, None) + tuple(gws) + tuple(gb[i] for i in range(n)) + (tuple(gxs) if gxs is not None else (None,) * n)
+
+
 class _StackKernels(torch.autograd.Function):
     """the (cout, cin, 1, 1) classifier kernels as one (n, cout, cin) tensor; backward hands every kernel its slice of the gradient
     in the PARAMETER's strides (a channels_last 1x1 kernel has strides (cin, 1, cin, cin); the plain reshape's gradient has
@@ -733,10 +786,13 @@ class VGG16ASPP(nn.Module):
         heads = [br[-1] for br in self.branches]
         if hs[0].is_cuda and hs[0].dtype == torch.bfloat16 and len(hs) <= 4 and heads[0].out_channels <= 32 \
                 and heads[0].in_channels % 256 == 0:
-            w = _StackKernels.apply(*[m.weight for m in heads])
-            b = torch.stack([m.bias for m in heads])
             # (on the grouped route the fc7_k outputs feed these classifiers and nothing else)
             links = [getattr(h, "_dsrg_grad_link", None) for h in hs]
+            if all(m.bias is not None for m in heads) and ops.heads_kernels_in_place([m.weight for m in heads], [m.bias for m in heads]):
+                # the kernels and biases read where they lie, every weight gradient written to its own tensor
+                return _HeadsPtrFn.apply(links, len(heads), *[m.weight for m in heads], *[m.bias for m in heads], *hs)
+            w = _StackKernels.apply(*[m.weight for m in heads])       # the fallback (another dtype / layout): stacked copies
+            b = torch.stack([m.bias for m in heads])
             return _HeadsFn.apply(links, w.float(), b.float(), *hs)
         out = None
         with torch.autocast(device_type=hs[0].device.type, enabled=False):

@@ -643,15 +643,22 @@ extern "C" int dsrg_pack_conv_weight_f32(const float *w_dev, void *fwd_dev, void
 }
 namespace dsrg {   // sgd_pack.hip
 int launch_sgd_pack(int n, float *const *p, const float *const *g, float *const *buf, void *const *fwd, void *const *dg, const int *shape,
-                    const long long *numel, const float *lr, const float *wd, float momentum, hipStream_t stream);
+                    const long long *numel, const float *lr, const float *wd, float momentum, hipStream_t stream,
+                    void *const *cast = nullptr);
 }
 extern "C" int dsrg_sgd_pack_f32(int n, float *const *param_dev, const float *const *grad_dev, float *const *momentum_dev, void *const *fwd_dev,
                                  void *const *dgrad_dev, const int *shape, const long long *numel, const float *lr, const float *weight_decay,
                                  float momentum, void *stream) {
+    return dsrg_sgd_pack_cast_f32(n, param_dev, grad_dev, momentum_dev, fwd_dev, dgrad_dev, nullptr, shape, numel, lr, weight_decay,
+                                  momentum, stream);
+}
+extern "C" int dsrg_sgd_pack_cast_f32(int n, float *const *param_dev, const float *const *grad_dev, float *const *momentum_dev,
+                                      void *const *fwd_dev, void *const *dgrad_dev, void *const *cast_dev, const int *shape,
+                                      const long long *numel, const float *lr, const float *weight_decay, float momentum, void *stream) {
     if (n > 0 && (!param_dev || !numel || ((fwd_dev || dgrad_dev) && !shape)))
         return set_error(DSRG_ERR_INVALID, "sgd_pack: null argument");
     return launch_sgd_pack(n, param_dev, grad_dev, momentum_dev, fwd_dev, dgrad_dev, shape, numel, lr, weight_decay, momentum,
-                           static_cast<hipStream_t>(stream));
+                           static_cast<hipStream_t>(stream), cast_dev);
 }
 extern "C" size_t dsrg_conv_igemm_wgrad_workspace(int ngroups, int B, int H, int W, int cin, int cout, int ksize) {
     return conv_igemm_wgrad_workspace(ngroups, B, H, W, cin, cout, ksize);
@@ -739,6 +746,34 @@ extern "C" int dsrg_heads_backward_relu_bf16(const void *const *x_dev, int n_bra
     return launch_heads_bwd(x_dev, n_branches, w_dev, g_dev, gx_dev, gx_branch_stride_bytes, gw_dev, partial_dev, B, HW, K, O,
                             static_cast<hipStream_t>(stream), relu_scale, bias_grad_dev, workspace_dev, workspace_bytes);
 }
+extern "C" int dsrg_heads_forward_ptrs_bf16(const void *const *x_dev, int n_branches, const float *const *w_dev,
+                                            const float *const *bias_dev, float *out_dev, int B, int HW, int K, int O, void *stream) {
+    if (!x_dev || !w_dev || !out_dev || B < 1 || HW < 1 || n_branches < 1 || n_branches > 4) return set_error(DSRG_ERR_INVALID, "bad argument");
+    for (int k = 0; k < n_branches; k++)
+        if (!x_dev[k] || !w_dev[k]) return set_error(DSRG_ERR_INVALID, "NULL branch input or kernel");
+    return launch_heads_fwd_ptrs(x_dev, n_branches, w_dev, bias_dev, out_dev, B, HW, K, O, static_cast<hipStream_t>(stream));
+}
+extern "C" int dsrg_heads_backward_ptrs_bf16(const void *const *x_dev, int n_branches, const float *const *w_dev, const float *g_dev,
+                                             void *gx_dev, size_t gx_branch_stride_bytes, float *const *gw_dev, float *partial_dev,
+                                             float relu_scale, float *bias_grad_dev, void *workspace_dev, size_t workspace_bytes,
+                                             int B, int HW, int K, int O, void *stream) {
+    if (!x_dev || !w_dev || !g_dev || (!gx_dev && !gw_dev) || (gw_dev && !partial_dev) || B < 1 || HW < 1 || n_branches < 1 ||
+        n_branches > 4 || (relu_scale > 0.0f && (!gx_dev || !bias_grad_dev)))
+        return set_error(DSRG_ERR_INVALID, "bad argument");
+    for (int k = 0; k < n_branches; k++)
+        if (!x_dev[k] || !w_dev[k] || (gw_dev && !gw_dev[k])) return set_error(DSRG_ERR_INVALID, "NULL branch input, kernel or gradient");
+    return launch_heads_bwd_ptrs(x_dev, n_branches, w_dev, g_dev, gx_dev, gx_branch_stride_bytes, gw_dev, partial_dev, B, HW, K, O,
+                                 static_cast<hipStream_t>(stream), relu_scale > 0.0f ? relu_scale : 0.0f, bias_grad_dev, workspace_dev,
+                                 workspace_bytes);
+}
+extern "C" int dsrg_image_nchw_to_nhwc_bf16(const float *x_dev, void *y_dev, int B, int H, int W, void *stream) {
+    if (!x_dev || !y_dev) return set_error(DSRG_ERR_INVALID, "NULL argument");
+    return launch_image_nhwc_bf16(x_dev, y_dev, B, H, W, static_cast<hipStream_t>(stream));
+}
+extern "C" int dsrg_sum_bf16(const void *const *g_dev, int n, void *out_dev, size_t numel, void *stream) {
+    if (!g_dev) return set_error(DSRG_ERR_INVALID, "NULL argument");
+    return launch_sum_bf16(g_dev, n, out_dev, numel, static_cast<hipStream_t>(stream));
+}
 extern "C" int dsrg_maxpool3x3_fwd_bf16(const void *in, void *out, void *code, int B, int H, int W, int OH, int OW, int C,
                                         int stride, void *stream) {
     if (!in || !out || !code) return set_error(DSRG_ERR_INVALID, "NULL argument");
@@ -767,6 +802,13 @@ extern "C" int dsrg_supervision_step(dsrg_ctx_t c, int B, const float *logits, c
                                      int img_w, const float *labels, const float *cues, double th1, double th2,
                                      const dsrg_crf_params *prm, float *losses, float *grad_logits,
                                      float *probs_out, float *seeds_out, float *logq_out, void *stream) {
+    return dsrg_supervision_step_total(c, B, logits, images, img_h, img_w, labels, cues, th1, th2, prm, losses, nullptr, grad_logits,
+                                       probs_out, seeds_out, logq_out, stream);
+}
+extern "C" int dsrg_supervision_step_total(dsrg_ctx_t c, int B, const float *logits, const float *images, int img_h,
+                                           int img_w, const float *labels, const float *cues, double th1, double th2,
+                                           const dsrg_crf_params *prm, float *losses, float *total, float *grad_logits,
+                                           float *probs_out, float *seeds_out, float *logq_out, void *stream) {
     if (!c || !logits || !labels || !cues || !losses || !grad_logits)
         return set_error(DSRG_ERR_INVALID, "NULL argument");
     if (B < 1 || B > c->maxB) return set_error(DSRG_ERR_INVALID, "batch %d outside 1..%d", B, c->maxB);
@@ -797,7 +839,7 @@ extern "C" int dsrg_supervision_step(dsrg_ctx_t c, int B, const float *logits, c
     rc = launch_srg(B, C, c->H, c->W, labels, cues, c->refined, th1, th2, c->seeds, c->srg_code, s);    // DSRG
     if (rc) return rc;
     rc = launch_sup_loss_backward(B, C, N, logits, c->probs, c->seeds, c->logq, c->refined, c->stats, grad_logits,
-                                  losses, s);                                        // losses + backward
+                                  losses, s, total);                                 // losses (+ their sum) + backward
     if (rc) return rc;
     if (probs_out) DSRG_HIP_CHECK(hipMemcpyAsync(probs_out, c->probs, nb, hipMemcpyDeviceToDevice, s));
     if (seeds_out) DSRG_HIP_CHECK(hipMemcpyAsync(seeds_out, c->seeds, nb, hipMemcpyDeviceToDevice, s));

@@ -642,8 +642,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kHeadOutPad = 32;          // MFMA tile width; outputs beyond O are computed on clamped rows and never stored
 struct HeadArgs {
     const uint16_t *x[4];      // NBR activations, (M, K) bf16 row-major (NHWC)
-    const float *w;            // (NBR, O, K)
-    const float *bias;         // (NBR, O) or nullptr
+    const float *w[4];         // NBR kernels, (O, K) each (the stacked (NBR, O, K) form: w[k] = w + k O K)
+    const float *bias[4];      // NBR biases, (O) each, or nullptr
     float *out;                // (B, O, HW)
     int nbr, M, K, O, HW;
 };
@@ -658,13 +658,14 @@ __device__ __forceinline__ void bf16x8_to_f32(const uint4 &v, float (&f)[8]) {
 // MASK: the backward of the ReLU (+ Dropout) that produced x_k rides in the store — values kept where x_k > 0 (times
 // `scale`), and the column sums of what was stored (that layer's bias gradient) go out as one partial row per workgroup.
 struct HeadMask {
+    const float *w[4];      // the branches' kernels, (O, K) each
     const uint16_t *y[4];
     float *part;            // (nbr, gridDim.x, K)
     float scale;
     int tiles;              // 16-row tiles per workgroup
 };
 template <bool MASK>
-__global__ __launch_bounds__(256) void heads_bwd_dx_kernel(const float *__restrict__ g, const float *__restrict__ w,
+__global__ __launch_bounds__(256) void heads_bwd_dx_kernel(const float *__restrict__ g,
                                                            uint4 *__restrict__ gx, int M, int K, int O, int HW, size_t branch_stride,
                                                            HeadMask hm) {
     __shared__ __attribute__((aligned(16))) float gs[32][16];        // [o][row]
@@ -693,7 +694,7 @@ __global__ __launch_bounds__(256) void heads_bwd_dx_kernel(const float *__restri
             for (int r = 0; r < 8; r++)
 #pragma unroll
                 for (int c = 0; c < 8; c++) acc[r][c] = 0.0f;
-            const float *wk = w + (size_t)k * O * K + (size_t)cg * 8;
+            const float *__restrict__ wk = hm.w[k] + (size_t)cg * 8;
 #pragma unroll 7
             for (int o = 0; o < O; o++) {
                 const float4 w0 = *reinterpret_cast<const float4 *>(wk + (size_t)o * K), w1 = *reinterpret_cast<const float4 *>(wk + (size_t)o * K + 4);
@@ -759,7 +760,7 @@ __global__ __launch_bounds__(256) void heads_bwd_dx_kernel(const float *__restri
 // writes 512 contiguous bytes, a workgroup the row's whole 2 KB.  Four rows per iteration are in flight.  Same fma order over the
 // outputs as heads_bwd_dx_kernel: identical bits.  Column sums: a thread adds up what it stored, one partial row per workgroup.
 template <int O, bool MASK>
-__global__ __launch_bounds__(256) void heads_bwd_dx_rows_kernel(const float *__restrict__ g, const float *__restrict__ w,
+__global__ __launch_bounds__(256) void heads_bwd_dx_rows_kernel(const float *__restrict__ g,
                                                                 unsigned char *__restrict__ gx, int M, int K, int HW, size_t branch_stride,
                                                                 HeadMask hm, int rows_per_wg) {
     constexpr int OP = (O + 3) & ~3;                                 // a row of the strip's gradient in LDS: O floats padded to 16 bytes
@@ -774,9 +775,10 @@ __global__ __launch_bounds__(256) void heads_bwd_dx_rows_kernel(const float *__r
         gs_rows[r * OP + o] = v;
     }
     float wr[O][4];
+    const float *__restrict__ wk = hm.w[k];
 #pragma unroll
     for (int o = 0; o < O; o++) {
-        const float4 v = *reinterpret_cast<const float4 *>(w + ((size_t)k * O + o) * K + c);
+        const float4 v = *reinterpret_cast<const float4 *>(wk + (size_t)o * K + c);
         wr[o][0] = v.x; wr[o][1] = v.y; wr[o][2] = v.z; wr[o][3] = v.w;
     }
     __syncthreads();
@@ -910,13 +912,37 @@ __global__ __launch_bounds__(256) void heads_bwd_dw_kernel(HeadArgs a, const flo
             for (int r = 0; r < 16; r++) acc[t][r] = 0.0f;
     }
 }
-// stage 2: fixed-order sum over the row chunks
-__global__ void heads_bwd_dw_reduce_kernel(const float *__restrict__ partial, float *__restrict__ gw, int nchunks, size_t n) {
+// stage 2: fixed-order sum over the row chunks, chunk 0 first.  A thread owns one element and its nchunks addends lie a whole
+// plane apart, so one load per add is a chain of memory latencies (106 of them at the net's shape, on 1.3 waves per SIMD): the
+// loads go out kHeadReduceBatch at a time and the adds follow in chunk order — the same sum, bit for bit.  Branch k's (O, K)
+// gradient goes to its own destination gw.p[k] (a parameter's gradient or a reducer's slot).
+constexpr int kHeadReduceBatch = 16;
+struct HeadGw { float *p[4]; };
+__global__ __launch_bounds__(256) void heads_bwd_dw_reduce_kernel(const float *__restrict__ partial, HeadGw gw, int nchunks, size_t n,
+                                                                  size_t per_branch) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const float *__restrict__ p = partial + i;
     float s = 0.0f;
-    for (int c = 0; c < nchunks; c++) s += partial[(size_t)c * n + i];
-    gw[i] = s;
+    int c = 0;
+    for (; c + kHeadReduceBatch <= nchunks; c += kHeadReduceBatch) {
+        float v[kHeadReduceBatch];
+#pragma unroll
+        for (int u = 0; u < kHeadReduceBatch; u++) v[u] = p[(size_t)(c + u) * n];
+#pragma unroll
+        for (int u = 0; u < kHeadReduceBatch; u++) s += v[u];
+    }
+    if (c < nchunks) {
+        float v[kHeadReduceBatch];
+#pragma unroll
+        for (int u = 0; u < kHeadReduceBatch; u++) v[u] = c + u < nchunks ? p[(size_t)(c + u) * n] : 0.0f;
+#pragma unroll
+        for (int u = 0; u < kHeadReduceBatch; u++)
+            if (c + u < nchunks) s += v[u];
+    }
+    const size_t k = i / per_branch;
+    float *dst = k == 0 ? gw.p[0] : k == 1 ? gw.p[1] : k == 2 ? gw.p[2] : gw.p[3];
+    dst[i - k * per_branch] = s;
 }
 
 // ---- the same two GEMMs on the bf16 MFMA with the float32 operand split into three bf16 terms -------------------------------
@@ -977,7 +1003,7 @@ __global__ __launch_bounds__(256) void heads_fwd_split_kernel(HeadArgs a) {
         const uint16_t *xp[R];
 #pragma unroll
         for (int t = 0; t < R; t++) xp[t] = a.x[wave] + (size_t)min(m0 + 32 * t + row, a.M - 1) * a.K + half * 8;      // clamped rows are never stored
-        const float *wp = a.w + ((size_t)wave * a.O + min(row, a.O - 1)) * a.K + half * 8;
+        const float *wp = a.w[wave] + (size_t)min(row, a.O - 1) * a.K + half * 8;
         constexpr int G = 4;                                        // 16-channel steps in flight (K % 256 == 0)
         uint4 xv[G][R];
         float4 wv[G][2];
@@ -1029,7 +1055,7 @@ __global__ __launch_bounds__(256) void heads_fwd_split_kernel(HeadArgs a) {
                 const int hf = (rr >> 2) & 1, reg = (rr & 3) + 4 * (rr >> 3), ln = col + 32 * hf;
                 float s = 0.0f;
                 for (int k = 0; k < a.nbr; k++) {
-                    const float sk = part[t][k][reg][ln] + (a.bias ? a.bias[k * a.O + col] : 0.0f);
+                    const float sk = part[t][k][reg][ln] + (a.bias[k] ? a.bias[k][col] : 0.0f);
                     s = k == 0 ? sk : s + sk;
                 }
                 const int b = m / a.HW, hw = m - b * a.HW;
@@ -1116,16 +1142,31 @@ static int heads_check(int nbr, int K, int O) {
     return DSRG_OK;
 }
 
+// the kernels (and biases, if any) of the branches where they lie: w[k] (O, K), bias[k] (O); bias == nullptr: none
+int launch_heads_fwd_ptrs(const void *const *x, int nbr, const float *const *w, const float *const *bias, float *out, int B, int HW,
+                          int K, int O, hipStream_t stream) {
+    int rc = heads_check(nbr, K, O);
+    if (rc) return rc;
+    HeadArgs a;
+    for (int k = 0; k < 4; k++) {
+        a.x[k] = static_cast<const uint16_t *>(x[k < nbr ? k : 0]);
+        a.w[k] = w[k < nbr ? k : 0];
+        a.bias[k] = bias ? bias[k < nbr ? k : 0] : nullptr;
+    }
+    a.out = out; a.nbr = nbr; a.M = B * HW; a.K = K; a.O = O; a.HW = HW;
+    hipLaunchKernelGGL(heads_fwd_split_kernel<2>, dim3((a.M + 63) / 64), dim3(256), 0, stream, a);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
+// the stacked form: w (nbr, O, K), bias (nbr, O) or nullptr
 int launch_heads_fwd(const void *const *x, int nbr, const float *w, const float *bias, float *out, int B, int HW, int K, int O,
                      hipStream_t stream) {
     int rc = heads_check(nbr, K, O);
     if (rc) return rc;
-    HeadArgs a;
-    for (int k = 0; k < 4; k++) a.x[k] = static_cast<const uint16_t *>(x[k < nbr ? k : 0]);
-    a.w = w; a.bias = bias; a.out = out; a.nbr = nbr; a.M = B * HW; a.K = K; a.O = O; a.HW = HW;
-    hipLaunchKernelGGL(heads_fwd_split_kernel<2>, dim3((a.M + 63) / 64), dim3(256), 0, stream, a);
-    DSRG_LAUNCH_CHECK();
-    return DSRG_OK;
+    const float *wk[4], *bk[4];
+    for (int k = 0; k < nbr; k++) { wk[k] = w + (size_t)k * O * K; bk[k] = bias ? bias + (size_t)k * O : nullptr; }
+    return launch_heads_fwd_ptrs(x, nbr, wk, bias ? bk : nullptr, out, B, HW, K, O, stream);
 }
 
 // row chunks of the weight gradient: ~256 rows each so that two workgroups share a CU (one wave per SIMD each) and one's
@@ -1144,14 +1185,17 @@ size_t heads_bwd_relu_workspace(int nbr, int M, int K) {
     return (size_t)nbr * rows * (size_t)K * sizeof(float);
 }
 
-int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float *g, void *gx, size_t gx_branch_stride,
-                     float *gw, float *partial, int B, int HW, int K, int O, hipStream_t stream, float relu_scale, float *bias_grad,
-                     void *colsum_ws, size_t colsum_ws_bytes) {
+// w[k]: branch k's (O, K) kernel; gw: nullptr (no weight gradient) or nbr destinations of (O, K) floats each
+int launch_heads_bwd_ptrs(const void *const *x, int nbr, const float *const *w, const float *g, void *gx, size_t gx_branch_stride,
+                          float *const *gw, float *partial, int B, int HW, int K, int O, hipStream_t stream, float relu_scale,
+                          float *bias_grad, void *colsum_ws, size_t colsum_ws_bytes) {
     int rc = heads_check(nbr, K, O);
     if (rc) return rc;
     const int M = B * HW;
+    HeadMask hm;
+    memset(&hm, 0, sizeof(hm));
+    for (int k = 0; k < 4; k++) hm.w[k] = w[k < nbr ? k : 0];
     if (gx && relu_scale > 0.0f) {
-        HeadMask hm;
         for (int k = 0; k < 4; k++) hm.y[k] = static_cast<const uint16_t *>(x[k < nbr ? k : 0]);
         hm.tiles = kHeadMaskTiles; hm.scale = relu_scale;
         const int nblk = (M + 16 * kHeadMaskTiles - 1) / (16 * kHeadMaskTiles);
@@ -1162,10 +1206,10 @@ int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float 
         if (head_strips(K, O)) {
             nblk_s = (M + kHeadStripRows - 1) / kHeadStripRows;
             hipLaunchKernelGGL((heads_bwd_dx_rows_kernel<21, true>), dim3(nblk_s, nbr, K / 1024), dim3(256),
-                               (size_t)kHeadStripRows * 24 * sizeof(float), stream, g, w, static_cast<unsigned char *>(gx), M, K, HW,
+                               (size_t)kHeadStripRows * 24 * sizeof(float), stream, g, static_cast<unsigned char *>(gx), M, K, HW,
                                gx_branch_stride, hm, kHeadStripRows);
         } else {
-            hipLaunchKernelGGL(heads_bwd_dx_kernel<true>, dim3(nblk, nbr), dim3(256), 0, stream, g, w, static_cast<uint4 *>(gx), M, K, O, HW,
+            hipLaunchKernelGGL(heads_bwd_dx_kernel<true>, dim3(nblk, nbr), dim3(256), 0, stream, g, static_cast<uint4 *>(gx), M, K, O, HW,
                                gx_branch_stride, hm);
         }
         DSRG_LAUNCH_CHECK();
@@ -1174,21 +1218,20 @@ int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float 
         for (int k = 0; k < nbr; k++) { parts[k] = hm.part + (size_t)k * nblk_s * K; outs[k] = bias_grad + (size_t)k * K; }
         if (int rc2 = launch_igemm_colsum(parts, outs, nbr, nblk_s, K, stream)) return rc2;
     } else if (gx) {
-        HeadMask hm;
-        memset(&hm, 0, sizeof(hm));
         if (head_strips(K, O))
             hipLaunchKernelGGL((heads_bwd_dx_rows_kernel<21, false>), dim3((M + kHeadStripRows - 1) / kHeadStripRows, nbr, K / 1024),
-                               dim3(256), (size_t)kHeadStripRows * 24 * sizeof(float), stream, g, w, static_cast<unsigned char *>(gx), M, K, HW,
+                               dim3(256), (size_t)kHeadStripRows * 24 * sizeof(float), stream, g, static_cast<unsigned char *>(gx), M, K, HW,
                                gx_branch_stride, hm, kHeadStripRows);
         else
-            hipLaunchKernelGGL(heads_bwd_dx_kernel<false>, dim3((M + 15) / 16, nbr), dim3(256), 0, stream, g, w, static_cast<uint4 *>(gx), M,
+            hipLaunchKernelGGL(heads_bwd_dx_kernel<false>, dim3((M + 15) / 16, nbr), dim3(256), 0, stream, g, static_cast<uint4 *>(gx), M,
                                K, O, HW, gx_branch_stride, hm);
         DSRG_LAUNCH_CHECK();
     }
     if (gw) {
         HeadArgs a;
+        memset(&a, 0, sizeof(a));
         for (int k = 0; k < 4; k++) a.x[k] = static_cast<const uint16_t *>(x[k < nbr ? k : 0]);
-        a.w = w; a.bias = nullptr; a.out = nullptr; a.nbr = nbr; a.M = M; a.K = K; a.O = O; a.HW = HW;
+        a.nbr = nbr; a.M = M; a.K = K; a.O = O; a.HW = HW;
         const int nch = heads_bwd_chunks(M), rows = ((M + nch - 1) / nch + 1) & ~1;
         const size_t lds = (size_t)kDwRows2 * (K * 2 + 64) + 32 * kDwGPitch * sizeof(float);
         if (lds > 160 * 1024) {
@@ -1200,9 +1243,100 @@ int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float 
         }
         DSRG_LAUNCH_CHECK();
         const size_t n = (size_t)nbr * O * K;
-        hipLaunchKernelGGL(heads_bwd_dw_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, partial, gw, nch, n);
+        HeadGw dst;
+        for (int k = 0; k < 4; k++) dst.p[k] = gw[k < nbr ? k : 0];
+        hipLaunchKernelGGL(heads_bwd_dw_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, partial, dst, nch, n,
+                           (size_t)O * K);
         DSRG_LAUNCH_CHECK();
     }
+    return DSRG_OK;
+}
+
+// the stacked form: w and gw (nbr, O, K)
+int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float *g, void *gx, size_t gx_branch_stride,
+                     float *gw, float *partial, int B, int HW, int K, int O, hipStream_t stream, float relu_scale, float *bias_grad,
+                     void *colsum_ws, size_t colsum_ws_bytes) {
+    int rc = heads_check(nbr, K, O);
+    if (rc) return rc;
+    const float *wk[4];
+    float *gwk[4];
+    for (int k = 0; k < nbr; k++) { wk[k] = w + (size_t)k * O * K; gwk[k] = gw ? gw + (size_t)k * O * K : nullptr; }
+    return launch_heads_bwd_ptrs(x, nbr, wk, g, gx, gx_branch_stride, gw ? gwk : nullptr, partial, B, HW, K, O, stream, relu_scale,
+                                 bias_grad, colsum_ws, colsum_ws_bytes);
+}
+
+// ---------------------------------------------------------------------------------
+// Two small passes at the ends of the train step that torch ran as two and three kernels.
+namespace {
+// float32 -> bf16 as torch's cast rounds: nearest even, every NaN becomes the quiet NaN 0x7fc0
+__device__ __forceinline__ uint32_t f32_to_bf16_torch(float f) {
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+struct SumArgs { const uint4 *g[4]; int n; };
+}  // namespace
+
+// the image: (B, 3, HW) float32 planes -> (B, HW, 3) bf16.  One thread = two consecutive pixels of the flattened (B, HW) range:
+// six plane loads (consecutive lanes read consecutive floats of a plane), three dword stores (a wave writes 768 contiguous bytes).
+__global__ __launch_bounds__(256) void image_nhwc_bf16_kernel(const float *__restrict__ x, uint16_t *__restrict__ y, size_t npix, int HW) {
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x, p0 = 2 * q;
+    if (p0 >= npix) return;
+    const size_t b0 = p0 / HW, i0 = p0 - b0 * HW;
+    const float *x0 = x + b0 * 3 * HW + i0;
+    const uint32_t r0 = f32_to_bf16_torch(x0[0]), g0 = f32_to_bf16_torch(x0[HW]), c0 = f32_to_bf16_torch(x0[2 * (size_t)HW]);
+    if (p0 + 1 >= npix) {                                   // an odd pixel count: the last pixel alone
+        y[3 * p0] = (uint16_t)r0; y[3 * p0 + 1] = (uint16_t)g0; y[3 * p0 + 2] = (uint16_t)c0;
+        return;
+    }
+    const size_t p1 = p0 + 1, b1 = p1 / HW, i1 = p1 - b1 * HW;
+    const float *x1 = x + b1 * 3 * HW + i1;
+    const uint32_t r1 = f32_to_bf16_torch(x1[0]), g1 = f32_to_bf16_torch(x1[HW]), c1 = f32_to_bf16_torch(x1[2 * (size_t)HW]);
+    uint32_t *d = reinterpret_cast<uint32_t *>(y + 3 * p0);  // 12 q bytes: dword-aligned
+    d[0] = r0 | (g0 << 16); d[1] = c0 | (r1 << 16); d[2] = g1 | (c1 << 16);
+}
+
+int launch_image_nhwc_bf16(const float *x, void *y, int B, int H, int W, hipStream_t stream) {
+    if (B < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return set_error(DSRG_ERR_INVALID, "image cast: bad shape");
+    const size_t npix = (size_t)B * H * W, threads = (npix + 1) / 2;
+    hipLaunchKernelGGL(image_nhwc_bf16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, x, static_cast<uint16_t *>(y),
+                       npix, H * W);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
+// out = rne(.. rne(rne(g0 + g1) + g2) ..): float32 adds, a bf16 rounding after each, input order; 8 elements per thread
+__global__ __launch_bounds__(256) void sum_bf16_kernel(SumArgs a, uint4 *__restrict__ out, size_t n8) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n8) return;
+    uint4 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (k < a.n) v[k] = a.g[k][i];
+    uint32_t s[4] = {v[0].x, v[0].y, v[0].z, v[0].w};
+#pragma unroll
+    for (int k = 1; k < 4; k++) {
+        if (k >= a.n) break;
+        const uint32_t t[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            s[e] = f32_to_bf16_torch(bf16_lo(s[e]) + bf16_lo(t[e])) | (f32_to_bf16_torch(bf16_hi(s[e]) + bf16_hi(t[e])) << 16);
+    }
+    out[i] = make_uint4(s[0], s[1], s[2], s[3]);
+}
+
+int launch_sum_bf16(const void *const *g, int n, void *out, size_t numel, hipStream_t stream) {
+    if (n < 2 || n > 4 || numel < 8 || numel % 8) return set_error(DSRG_ERR_INVALID, "sum_bf16: 2..4 tensors, a multiple of 8 elements");
+    SumArgs a;
+    a.n = n;
+    for (int k = 0; k < 4; k++) {
+        a.g[k] = static_cast<const uint4 *>(g[k < n ? k : 0]);
+        if (!a.g[k] || (reinterpret_cast<uintptr_t>(a.g[k]) & 15)) return set_error(DSRG_ERR_INVALID, "sum_bf16: tensor %d is null or not 16-byte aligned", k);
+    }
+    if (!out || (reinterpret_cast<uintptr_t>(out) & 15)) return set_error(DSRG_ERR_INVALID, "sum_bf16: output is null or not 16-byte aligned");
+    const size_t n8 = numel / 8;
+    hipLaunchKernelGGL(sum_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, a, static_cast<uint4 *>(out), n8);
+    DSRG_LAUNCH_CHECK();
     return DSRG_OK;
 }
 

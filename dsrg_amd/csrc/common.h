@@ -246,7 +246,7 @@ int launch_constrain_loss(int B, int C, int HW, const float *p, const float *lq,
                           float *glq, hipStream_t stream);
 int launch_sup_loss_backward(int B, int C, int HW, const float *logits, const float *probs, const float *seeds,
                              const float *logq, const double *refined, double *stats, float *grad_logits,
-                             float *losses, hipStream_t stream);
+                             float *losses, hipStream_t stream, float *total = nullptr);
 int launch_lf_to_planes(int N, int M, const float *in, float *out, int negate, hipStream_t stream);
 int launch_planes_to_lf(int N, int M, const float *in, float *out, hipStream_t stream);
 int launch_argmax_planes(int N, int M, const float *q, int32_t *lab, hipStream_t stream);
@@ -320,6 +320,13 @@ int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float 
                      float *gw, float *partial, int B, int HW, int K, int O, hipStream_t stream, float relu_scale = 0.0f,
                      float *bias_grad = nullptr, void *colsum_ws = nullptr, size_t colsum_ws_bytes = 0);
 size_t heads_bwd_relu_workspace(int nbr, int M, int K);
+int launch_heads_fwd_ptrs(const void *const *x, int nbr, const float *const *w, const float *const *bias, float *out, int B, int HW,
+                          int K, int O, hipStream_t stream);
+int launch_heads_bwd_ptrs(const void *const *x, int nbr, const float *const *w, const float *g, void *gx, size_t gx_branch_stride,
+                          float *const *gw, float *partial, int B, int HW, int K, int O, hipStream_t stream, float relu_scale = 0.0f,
+                          float *bias_grad = nullptr, void *colsum_ws = nullptr, size_t colsum_ws_bytes = 0);
+int launch_image_nhwc_bf16(const float *x, void *y, int B, int H, int W, hipStream_t stream);
+int launch_sum_bf16(const void *const *g, int n, void *out, size_t numel, hipStream_t stream);
 int launch_add_relu(const void *a, const void *b, void *y, size_t n, hipStream_t stream);
 int launch_aspp_shift_sum(const void *yp, const float *bias, float *out, const int *offsets, int J, int O, int CT, int B, int H, int W,
                           hipStream_t stream);

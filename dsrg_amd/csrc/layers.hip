@@ -376,7 +376,7 @@ __global__ __launch_bounds__(kGradParts * kGradPix) void sup_grad_kernel(int B, 
                                                        const double *__restrict__ refined,
                                                        const double *__restrict__ stats,
                                                        float *__restrict__ grad_logits,
-                                                       float *__restrict__ losses) {
+                                                       float *__restrict__ losses, float *__restrict__ total) {
     constexpr int P = kGradParts, LPP = (CT + P - 1) / P;       // labels per part
     const int lane = threadIdx.x & 63, part = threadIdx.x & (P - 1), lane0 = lane & ~(P - 1);
     const int idx = blockIdx.x * kGradPix + (int)(threadIdx.x / P);
@@ -415,8 +415,10 @@ __global__ __launch_bounds__(kGradParts * kGradPix) void sup_grad_kernel(int B, 
             __syncthreads();
         }
         if (threadIdx.x == 0) {
-            losses[0] = (float)ls;
-            losses[1] = (float)(lc / ((double)B * (double)HW));
+            const float l0 = (float)ls, l1 = (float)(lc / ((double)B * (double)HW));
+            losses[0] = l0;
+            losses[1] = l1;
+            if (total) *total = (0.0f + l0) + l1;            // the float32 sum of the two, as a reduction from +0 forms it
         }
     }
     const float dbg = (float)(cnt_bg > 1e-4 ? cnt_bg : 1e-4), dfg = (float)(cnt_fg > 1e-4 ? cnt_fg : 1e-4);
@@ -465,17 +467,17 @@ __global__ __launch_bounds__(kGradParts * kGradPix) void sup_grad_kernel(int B, 
 }
 int launch_sup_loss_backward(int B, int C, int HW, const float *logits, const float *probs, const float *seeds,
                              const float *logq, const double *refined, double *stats, float *grad_logits,
-                             float *losses, hipStream_t stream) {
+                             float *losses, hipStream_t stream, float *total) {
     if (C < 1 || C > kMaxLabels) return set_error(DSRG_ERR_UNSUPPORTED, "1 <= C <= %d required", kMaxLabels);
     hipLaunchKernelGGL(sup_stats_kernel, dim3(B * kStatSplit), dim3(1024), 0, stream, C, HW, probs, seeds, logq, stats);
     DSRG_LAUNCH_CHECK();
     const int threads = kGradParts * kGradPix, blocks = (B * HW + kGradPix - 1) / kGradPix;
     if (C <= 21)
         hipLaunchKernelGGL(sup_grad_kernel<21>, dim3(blocks), dim3(threads), 0, stream, B, C, HW, logits, probs, seeds,
-                           logq, refined, stats, grad_logits, losses);
+                           logq, refined, stats, grad_logits, losses, total);
     else
         hipLaunchKernelGGL(sup_grad_kernel<kMaxLabels>, dim3(blocks), dim3(threads), 0, stream, B, C, HW, logits,
-                           probs, seeds, logq, refined, stats, grad_logits, losses);
+                           probs, seeds, logq, refined, stats, grad_logits, losses, total);
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
 }

@@ -32,6 +32,7 @@ struct SgdTensor {
     const float *g;         // gradient, or null: no update (pack only)
     float *buf;             // momentum buffer B, updated in place (null with g)
     uint16_t *fwd, *dg;     // packed bf16 forms or null
+    uint16_t *cast;         // plain tensors: a bf16 copy of the new values in the parameter's own order, or null
     uint32_t n;             // elements
     uint32_t cout, cin, taps;   // of a packed kernel
     uint32_t first_block;   // this tensor's first block in the launch
@@ -69,31 +70,46 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(SgdArgs a) {
     const float m = a.momentum, lr = T.lr, wd = T.wd;
     if (!T.fwd && !T.dg) {
         // ---- a plain tensor (bias, classifier, first layer): 4096 elements per block, float4 per thread and pass
-        if (!T.g) return;
+        // (cast: the bf16 form of the values this thread holds anyway — conv1_1's kernel, which its route reads unpacked; the
+        // rounding of pack2_bf16, i.e. of the parameter's cast to bf16)
+        if (!T.g && !T.cast) return;
         const size_t base = (size_t)blk * 4096;
-        if (T.plain) {                                       // a slice of a larger buffer that is not 16-byte aligned: one float at a time
-            for (size_t q = base + t; q < T.n && q < base + 4096; q += 256) {
-                const float d = T.g[q] + wd * T.p[q], b = m * T.buf[q] + d;
+        auto scalar = [&](size_t q) {
+            float w = T.p[q];
+            if (T.g) {
+                const float d = T.g[q] + wd * w, b = m * T.buf[q] + d;
                 T.buf[q] = b;
-                T.p[q] = T.p[q] - lr * b;
+                w = w - lr * b;
+                T.p[q] = w;
             }
+            if (T.cast) T.cast[q] = (uint16_t)pack2_bf16(w, 0.0f);
+        };
+        if (T.plain) {                                       // a slice of a larger buffer that is not 16-byte aligned: one float at a time
+            for (size_t q = base + t; q < T.n && q < base + 4096; q += 256) scalar(q);
             return;
         }
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const size_t e = base + (size_t)(i * 256 + t) * 4;
             if (e + 3 < T.n) {
-                const float4 w = *reinterpret_cast<const float4 *>(T.p + e), g = load_grad4(T.g + e, T.g_split);
-                float4 b = *reinterpret_cast<const float4 *>(T.buf + e);
-                const float4 nw = sgd4(w, g, b, m, lr, wd);
-                *reinterpret_cast<float4 *>(T.buf + e) = b;
-                *reinterpret_cast<float4 *>(T.p + e) = nw;
-            } else {
-                for (size_t q = e; q < T.n && q < e + 4; q++) {
-                    const float d = T.g[q] + wd * T.p[q], b = m * T.buf[q] + d;
-                    T.buf[q] = b;
-                    T.p[q] = T.p[q] - lr * b;
+                float4 w = *reinterpret_cast<const float4 *>(T.p + e);
+                if (T.g) {
+                    const float4 g = load_grad4(T.g + e, T.g_split);
+                    float4 b = *reinterpret_cast<const float4 *>(T.buf + e);
+                    w = sgd4(w, g, b, m, lr, wd);
+                    *reinterpret_cast<float4 *>(T.buf + e) = b;
+                    *reinterpret_cast<float4 *>(T.p + e) = w;
                 }
+                if (T.cast) {
+                    if (reinterpret_cast<uintptr_t>(T.cast) & 7) {
+                        T.cast[e] = (uint16_t)pack2_bf16(w.x, 0.0f); T.cast[e + 1] = (uint16_t)pack2_bf16(w.y, 0.0f);
+                        T.cast[e + 2] = (uint16_t)pack2_bf16(w.z, 0.0f); T.cast[e + 3] = (uint16_t)pack2_bf16(w.w, 0.0f);
+                    } else {
+                        *reinterpret_cast<uint2 *>(T.cast + e) = make_uint2(pack2_bf16(w.x, w.y), pack2_bf16(w.z, w.w));
+                    }
+                }
+            } else {
+                for (size_t q = e; q < T.n && q < e + 4; q++) scalar(q);
             }
         }
         return;
@@ -135,10 +151,11 @@ __global__ __launch_bounds__(256) void sgd_pack_kernel(SgdArgs a) {
 }  // namespace
 
 // n tensors (any number: sixteen per launch).  p / g / buf: n pointers each (g[i] = buf[i] = null: pack only); fwd / dg: the packed
-// forms or null; shape[i] = {cout, cin, taps, plain} for packed tensors (64 | cout, 64 | cin), ignored otherwise; numel[i]
+// forms or null; cast (the array or an entry may be null): a plain bf16 copy, for tensors without packed forms; shape[i] = {cout, cin, taps, plain} for packed tensors (64 | cout, 64 | cin), ignored otherwise; numel[i]
 // elements; lr[i], wd[i] the tensor's rates.
 int launch_sgd_pack(int n, float *const *p, const float *const *g, float *const *buf, void *const *fwd, void *const *dg,
-                    const int *shape, const long long *numel, const float *lr, const float *wd, float momentum, hipStream_t stream) {
+                    const int *shape, const long long *numel, const float *lr, const float *wd, float momentum, hipStream_t stream,
+                    void *const *cast) {
     if (n < 0) return set_error(DSRG_ERR_INVALID, "sgd_pack: bad count");
     for (int i0 = 0; i0 < n; i0 += kSgdTensors) {
         SgdArgs a;
@@ -149,12 +166,15 @@ int launch_sgd_pack(int n, float *const *p, const float *const *g, float *const 
             SgdTensor &T = a.t[a.n++];
             T.p = p[i]; T.g = g ? g[i] : nullptr; T.buf = buf ? buf[i] : nullptr;
             T.fwd = fwd ? static_cast<uint16_t *>(fwd[i]) : nullptr; T.dg = dg ? static_cast<uint16_t *>(dg[i]) : nullptr;
+            T.cast = cast ? static_cast<uint16_t *>(cast[i]) : nullptr;
             T.lr = lr ? lr[i] : 0.0f; T.wd = wd ? wd[i] : 0.0f;
             if (!T.p || numel[i] < 1 || numel[i] > 0x7fffffffLL || (T.g && !T.buf))
                 return set_error(DSRG_ERR_INVALID, "sgd_pack: tensor %d: null parameter, bad size or a gradient without a momentum buffer", i);
             const uintptr_t low = reinterpret_cast<uintptr_t>(T.p) | reinterpret_cast<uintptr_t>(T.buf);
             if (((low | reinterpret_cast<uintptr_t>(T.g)) & 3) || ((low & 15) && (T.fwd || T.dg)))
                 return set_error(DSRG_ERR_INVALID, "sgd_pack: tensor %d is not aligned (4 bytes; parameter and momentum of a packed kernel: 16)", i);
+            if (T.cast && (T.fwd || T.dg || (reinterpret_cast<uintptr_t>(T.cast) & 1)))
+                return set_error(DSRG_ERR_INVALID, "sgd_pack: tensor %d: a bf16 copy goes with a tensor without packed forms, 2-byte aligned", i);
             T.g_split = (reinterpret_cast<uintptr_t>(T.g) & 15) != 0;
             T.n = (uint32_t)numel[i];
             T.first_block = blocks;

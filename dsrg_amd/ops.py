@@ -656,11 +656,12 @@ def train_f_input_batch(stage, desc, crop_size, mean, scale=1.0, ignore_label=25
 
 
 def supervision_step(logits, images, labels, cues, th1=0.99, th2=0.85, scale_factor=12.0, maxiter=10,
-                     ctx=None, want_blobs=False, prepared=False):
+                     ctx=None, want_blobs=False, prepared=False, want_total=False):
     """The five Python layers of train-s.prototxt:746-810, forward and backward, in one
     stream-ordered launch sequence (CRF computed once).
 
-    Returns (losses[2] = {loss-Seed, loss-Constrain}, d(sum)/d logits, blobs or None)."""
+    Returns (losses[2] = {loss-Seed, loss-Constrain}, d(sum)/d logits, blobs or None); want_total: a fourth result, the 0-d float32
+    losses[0] + losses[1], stored by the kernel that finishes the two losses (the bits of losses.sum())."""
     _f32c(logits, "logits"), _f32c(images, "images"), _f32c(labels, "labels"), _f32c(cues, "cues")
     B, C, H, W = logits.shape
     if images.dim() != 4 or images.shape[0] != B or images.shape[1] != 3:
@@ -678,21 +679,23 @@ def supervision_step(logits, images, labels, cues, th1=0.99, th2=0.85, scale_fac
         l_con, g_p, g_q = constrain_loss(probs, logq)
         grad = softmax_backward(logits, g_seed + g_p + crf_layer_backward(refined, g_q))
         losses = torch.stack([l_seed.reshape(()), l_con.reshape(())]).float()
-        return losses, grad, (dict(probs=probs, seeds=seeds, logq=logq, refined=refined) if want_blobs else None)
+        blobs = dict(probs=probs, seeds=seeds, logq=logq, refined=refined) if want_blobs else None
+        return (losses, grad, blobs, losses.sum()) if want_total else (losses, grad, blobs)
     ctx = ctx or get_context(B, C, H, W)
-    losses = torch.empty(2, dtype=torch.float32, device=logits.device)
+    out3 = torch.empty(3, dtype=torch.float32, device=logits.device)      # the two losses and their sum
+    losses = out3[:2]
     grad = torch.empty_like(logits)
     blobs = None
     if want_blobs:
         blobs = dict(probs=torch.empty_like(logits), seeds=torch.empty_like(logits), logq=torch.empty_like(logits))
     prm = CrfParams.from_crf_args(maxiter, scale_factor)
-    check(_lib.lib().dsrg_supervision_step(
+    check(_lib.lib().dsrg_supervision_step_total(
         ctx._h, B, _ptr(logits), None if prepared else _ptr(images), images.shape[2], images.shape[3],
         _ptr(labels), _ptr(cues),
-        float(th1), float(th2), ctypes.byref(prm), _ptr(losses), _ptr(grad),
+        float(th1), float(th2), ctypes.byref(prm), _ptr(losses), _ptr(out3[2]) if want_total else None, _ptr(grad),
         _ptr(blobs["probs"]) if blobs else None, _ptr(blobs["seeds"]) if blobs else None,
         _ptr(blobs["logq"]) if blobs else None, _stream()))
-    return losses, grad, blobs
+    return (losses, grad, blobs, out3[2]) if want_total else (losses, grad, blobs)
 
 
 def im2col3x3_nhwc(x_nhwc, dilation):
@@ -942,26 +945,31 @@ def _check_kept_packs(weight, fwd, dg, pack):
 
 def sgd_pack_step(params, grads, bufs, lrs, wds, momentum):
     """Caffe's SGD update B <- momentum B + (g + wd W); W <- W - lr B of float32 CUDA parameters in one launch per sixteen
-    tensors (dsrg_sgd_pack_f32), rewriting the packed bf16 kernels the convolution nodes keep for them in the same pass.
+    tensors (dsrg_sgd_pack_cast_f32), rewriting the packed bf16 kernels the convolution nodes keep for them (and conv1_1's plain
+    bf16 copy, cast_weight_kept) in the same pass.
     params / grads / bufs: dense tensors of one memory layout each; lrs / wds: per-tensor rates."""
     import numpy as np
     n = len(params)
     if n == 0:
         return
     ptr = lambda ts: np.array([0 if t is None else t.data_ptr() for t in ts], dtype=np.uint64)
-    fwd, dg, shape, entries = [None] * n, [None] * n, np.zeros((n, 4), dtype=np.int32), []
+    fwd, dg, cast, shape, entries = [None] * n, [None] * n, [None] * n, np.zeros((n, 4), dtype=np.int32), []
     for i, p in enumerate(params):
         e = _weight_packs.get(p.data_ptr())
         if e is None or e.ref() is None or e.ref().data_ptr() != p.data_ptr() or e.ref().shape != p.shape:
             continue
-        fwd[i], dg[i] = e.fwd, e.dg
-        shape[i] = (p.shape[0], p.shape[1], p.shape[2] * p.shape[3], e.plain)
+        if e.plain == _PLAIN_CAST:                                    # conv1_1: a bf16 copy in the parameter's own order
+            cast[i] = e.fwd
+        else:
+            fwd[i], dg[i] = e.fwd, e.dg
+            shape[i] = (p.shape[0], p.shape[1], p.shape[2] * p.shape[3], e.plain)
         entries.append((e, p))
-    pp, gp, bp, fp, dp = ptr(params), ptr(grads), ptr(bufs), ptr(fwd), ptr(dg)
+    pp, gp, bp, fp, dp, cp = ptr(params), ptr(grads), ptr(bufs), ptr(fwd), ptr(dg), ptr(cast)
     numel = np.array([p.numel() for p in params], dtype=np.int64)
     lr, wd = np.asarray(lrs, dtype=np.float32), np.asarray(wds, dtype=np.float32)
     a = lambda x: x.ctypes.data
-    check(_lib.lib().dsrg_sgd_pack_f32(n, a(pp), a(gp), a(bp), a(fp), a(dp), a(shape), a(numel), a(lr), a(wd), float(momentum), _stream()))
+    check(_lib.lib().dsrg_sgd_pack_cast_f32(n, a(pp), a(gp), a(bp), a(fp), a(dp), a(cp), a(shape), a(numel), a(lr), a(wd),
+                                            float(momentum), _stream()))
     torch.autograd.graph.increment_version(list(params))              # an in-place write autograd has not seen
     for e, p in entries:
         e.version = p._version
@@ -973,6 +981,26 @@ def sgd_pack_eligible(p, g, b):
         g.shape == p.shape and all(n == 1 or (sg == sp and sb == sp) for n, sp, sg, sb in zip(p.shape, p.stride(), g.stride(), b.stride())) and \
         (p.is_contiguous() or (p.dim() == 4 and p.is_contiguous(memory_format=torch.channels_last))) and \
         ((p.data_ptr() | b.data_ptr()) % 16 == 0 or p.data_ptr() not in _weight_packs)
+
+
+_PLAIN_CAST = 2                           # _WeightPacks.plain of an entry whose `fwd` is the parameter cast to bf16 as it lies
+
+
+def cast_weight_kept(weight):
+    """weight.to(bfloat16) of a float32 parameter whose convolution reads its kernel unpacked (conv1_1: conv3x3_direct with three
+    input channels), kept from step to step like the packed kernels: taken fresh the first time, after forget_weight_packs and
+    whenever the version counter says the kept copy is stale; otherwise the copy sgd_pack_step wrote with the update"""
+    w = weight.detach()
+    dense = w.is_contiguous() or (w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last))
+    if not (_packs_kept(weight) and w.dtype == torch.float32 and dense):
+        return w.to(torch.bfloat16)
+    e = _packs_entry(weight, _PLAIN_CAST)
+    if e is not None and e.version == weight._version and e.fwd is not None:
+        _check_kept_packs(weight, e.fwd, None, lambda f, d: f.copy_(w))
+        return e.fwd
+    w16 = w.to(torch.bfloat16)                                        # (the parameter's own strides: sgd_pack_step writes it in that order)
+    _packs_keep(weight, _PLAIN_CAST, w16, None)
+    return w16
 
 
 def pack_direct_weight_pair(weight, want_dgrad=True):
@@ -1388,6 +1416,105 @@ def heads_backward(xs, weight, g, need_gx=True, relu_scale=0.0):
     return ([gx[k].permute(0, 3, 1, 2) for k in range(n)] if need_gx else None), gw
 
 
+def _vp4(ts):
+    """host array of four device pointers (the library reads the first len(ts))"""
+    return (ctypes.c_void_p * 4)(*([t.data_ptr() for t in ts] + [None] * (4 - len(ts))))
+
+
+def heads_kernels_in_place(weights, biases=None):
+    """can heads_forward_ptrs / heads_backward_ptrs read these classifier parameters where they lie: <= 4 float32 CUDA kernels
+    (O,K,1,1) or (O,K) of one shape whose memory is (O,K) row-major (a channels_last 1x1 kernel is), biases (O) alike"""
+    if not 1 <= len(weights) <= 4 or weights[0].dim() < 2:
+        return False
+    O, K = weights[0].shape[0], weights[0].shape[1]
+    if not all(w.is_cuda and w.dtype == torch.float32 and w.shape == weights[0].shape and w.numel() == O * K and w.is_contiguous()
+               for w in weights):
+        return False
+    return biases is None or (len(biases) == len(weights) and all(
+        b.is_cuda and b.dtype == torch.float32 and tuple(b.shape) == (O,) and b.is_contiguous() for b in biases))
+
+
+def heads_forward_ptrs(xs, weights, biases):
+    """heads_forward with the n kernels (heads_kernels_in_place) and biases (a list, or None) read where they lie — no stacked
+    copy of either; the same bits"""
+    B, K, H, W = xs[0].shape
+    n, O = len(weights), weights[0].shape[0]
+    cl = torch.channels_last
+    xs = [x.contiguous(memory_format=cl) for x in xs]
+    if not all(x.is_cuda and x.dtype == torch.bfloat16 and x.shape == xs[0].shape for x in xs) or len(xs) != n:
+        raise ValueError("heads_forward_ptrs needs n bf16 CUDA activations of one shape")
+    if not heads_kernels_in_place(weights, biases) or weights[0].shape[1] != K:
+        raise ValueError("heads_forward_ptrs needs n float32 CUDA kernels whose memory is (O,K) row-major, and (O) biases")
+    out = torch.empty((B, O, H, W), dtype=torch.float32, device=xs[0].device)
+    check(_lib.lib().dsrg_heads_forward_ptrs_bf16(_vp4(xs), n, _vp4(weights), _vp4(biases) if biases is not None else None, _ptr(out),
+                                                  B, H * W, K, O, _stream()))
+    return out
+
+
+def heads_backward_ptrs(xs, weights, g, need_gx=True, relu_scale=0.0, gw_outs=None):
+    """heads_backward with the kernels read where they lie and every branch's weight gradient written to a tensor of its own, of
+    its kernel's shape and strides: gw_outs[k] if that can take it (a reducer's slot), else a fresh one -> (gx list or None, list of
+    gw_k[, (n,K) bias gradient of the layer below when relu_scale > 0]); the same bits as the stacked form"""
+    B, K, H, W = xs[0].shape
+    n, O = len(weights), weights[0].shape[0]
+    cl = torch.channels_last
+    xs = [x.contiguous(memory_format=cl) for x in xs]
+    if not heads_kernels_in_place(weights) or weights[0].shape[1] != K:
+        raise ValueError("heads_backward_ptrs needs n float32 CUDA kernels whose memory is (O,K) row-major")
+    g = g.contiguous()
+    _f32c(g, "g")
+    L = _lib.lib()
+    M = B * H * W
+    gx = torch.empty((n, B, H, W, K), dtype=torch.bfloat16, device=g.device) if need_gx else None
+    gws = []
+    for k, w in enumerate(weights):
+        out = gw_outs[k] if gw_outs is not None else None
+        if out is not None and out.dtype == torch.float32 and out.shape == w.shape and out.device == w.device and out.is_contiguous():
+            gws.append(out)
+        else:
+            gws.append(torch.empty_strided(tuple(w.shape), tuple(w.stride()), dtype=torch.float32, device=g.device))
+    part = torch.empty(L.dsrg_heads_backward_chunks(M) * n * O * K, dtype=torch.float32, device=g.device)
+    masked = relu_scale > 0.0 and need_gx
+    gb = _bias_grad_dest(None, (n, K), g.device) if masked else None
+    ws = _reduction_scratch(g.device, L.dsrg_heads_backward_relu_workspace(n, M, K)) if masked else None
+    check(L.dsrg_heads_backward_ptrs_bf16(_vp4(xs), n, _vp4(weights), _ptr(g), _ptr(gx), M * K * 2, _vp4(gws), _ptr(part),
+                                          float(relu_scale) if masked else 0.0, _ptr(gb), _ptr(ws), ws.numel() if masked else 0,
+                                          B, H * W, K, O, _stream()))
+    gxs = [gx[k].permute(0, 3, 1, 2) for k in range(n)] if need_gx else None
+    return (gxs, gws, gb) if masked else (gxs, gws)
+
+
+def image_to_bf16_nhwc(x):
+    """the network's input in one pass (dsrg_image_nchw_to_nhwc_bf16): x (B,3,H,W) float32 NCHW-contiguous -> (B,3,H,W) bf16
+    channels_last, the bits of x.contiguous(memory_format=channels_last).bfloat16()"""
+    if not (x.dim() == 4 and x.shape[1] == 3):
+        raise ValueError("image_to_bf16_nhwc needs a (B,3,H,W) image")
+    _f32c(x, "x")
+    B, _, H, W = x.shape
+    y = torch.empty((B, 3, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    check(_lib.lib().dsrg_image_nchw_to_nhwc_bf16(_ptr(x), _ptr(y), B, H, W, _stream()))
+    return y
+
+
+def image_takes_fused_cast(x):
+    """is x an image image_to_bf16_nhwc takes: float32, three channels, NCHW-contiguous, on the GPU"""
+    return x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and x.is_contiguous() and x.numel() > 0
+
+
+def sum_bf16(ts):
+    """rne(rne(rne(t0 + t1) + t2) + t3) of 2..4 bf16 CUDA tensors of one shape and one dense memory order (dsrg_sum_bf16): float32
+    adds, one bf16 rounding after each, in list order — what autograd's pairwise accumulation of these gradients gives, in one
+    pass.  -> a tensor of t0's shape and strides"""
+    t0 = ts[0]
+    if not (2 <= len(ts) <= 4 and all(t.is_cuda and t.dtype == torch.bfloat16 and t.shape == t0.shape and t.stride() == t0.stride()
+                                      for t in ts) and t0.numel() % 8 == 0 and t0.numel() > 0 and
+            (t0.is_contiguous() or (t0.dim() == 4 and t0.is_contiguous(memory_format=torch.channels_last)))):
+        raise ValueError("sum_bf16 needs 2..4 dense bf16 CUDA tensors of one shape and layout, 8 | elements")
+    out = torch.empty_like(t0)
+    check(_lib.lib().dsrg_sum_bf16(_vp4(ts), len(ts), _ptr(out), t0.numel(), _stream()))
+    return out
+
+
 def maxpool3x3_out_size(n, stride, ceil_mode):
     """output extent of a 3x3 / pad 1 pooling window walk over n pixels (Caffe's ceil rule, torch's with ceil_mode)"""
     num = n + 2 - 3
@@ -1482,16 +1609,17 @@ class DSRGSupervision(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, images, labels, cues, th1, th2, scale_factor, maxiter, prepared=False):
-        losses, grad, _ = supervision_step(logits.contiguous(), images, labels, cues, th1, th2, scale_factor, maxiter,
-                                           prepared=prepared)
+        losses, grad, _, total = supervision_step(logits.contiguous(), images, labels, cues, th1, th2, scale_factor, maxiter,
+                                                  prepared=prepared, want_total=True)
         ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(losses)
-        return losses.sum(), losses
+        ctx.set_materialize_grads(False)         # no zero-filled gradient made for `losses` (a launch per step nobody reads)
+        return total, losses
 
     @staticmethod
     def backward(ctx, g_total, _g_losses):
         (grad,) = ctx.saved_tensors
-        return grad * g_total, None, None, None, None, None, None, None, None
+        return (grad * g_total if g_total is not None else None), None, None, None, None, None, None, None, None
 
 
 def dsrg_supervision_loss(logits, images, labels, cues, th1=0.99, th2=0.85, scale_factor=12.0, maxiter=10,

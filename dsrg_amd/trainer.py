@@ -221,7 +221,12 @@ class DSRGTrainer(object):
             self.reducer.prepare()                          # gradients unset, every large parameter knows its bucket slot
         else:
             self.opt.zero_grad()
-        x = images.contiguous(memory_format=torch.channels_last) if self.channels_last else images
+        from .ops import image_takes_fused_cast, image_to_bf16_nhwc
+        if self.channels_last and self.amp_dtype == torch.bfloat16 and isinstance(self.net, VGG16ASPP) and image_takes_fused_cast(images):
+            # conv1_1 reads bf16 channels_last: one pass makes it from the float32 NCHW image (the CRF goes on reading `images`)
+            x = image_to_bf16_nhwc(images)
+        else:
+            x = images.contiguous(memory_format=torch.channels_last) if self.channels_last else images
         if self.overlap_build:
             from .ops import crf_prepare
             main = torch.cuda.current_stream()

@@ -625,6 +625,39 @@ int dsrg_supervision_step(dsrg_ctx_t ctx, int B, const float *logits_dev, const 
                           double th1, double th2, const dsrg_crf_params *params,
                           float *losses_dev, float *grad_logits_dev,
                           float *probs_dev, float *seeds_dev, float *logq_dev, void *stream);
+/* The same, and total_dev[0] (may be NULL) = losses_dev[0] + losses_dev[1], one float32 add in the kernel that finishes the two
+ * losses: what a two-element float32 sum of losses_dev gives, without its launch. */
+int dsrg_supervision_step_total(dsrg_ctx_t ctx, int B, const float *logits_dev, const float *images_dev,
+                                int img_h, int img_w, const float *labels_dev, const float *cues_dev,
+                                double th1, double th2, const dsrg_crf_params *params,
+                                float *losses_dev, float *total_dev, float *grad_logits_dev,
+                                float *probs_dev, float *seeds_dev, float *logq_dev, void *stream);
+
+/* dsrg_heads_forward_bf16 / dsrg_heads_backward_bf16 / dsrg_heads_backward_relu_bf16 with the branches' kernels, biases and
+ * weight gradients where they lie instead of stacked: w_dev / bias_dev / gw_dev are HOST arrays of n_branches device pointers
+ * to (O, K) f32 kernels (the memory of a channels_last (O, K, 1, 1) parameter), (O) f32 biases and (O, K) f32 gradient
+ * destinations (a parameter's gradient, a slot of a gradient bucket).  bias_dev may be NULL (no bias), gw_dev may be NULL (no
+ * weight gradient).  relu_scale > 0: the _relu form (bias_grad_dev and workspace_dev as there), else the plain one.  The same
+ * arithmetic in the same order as the stacked forms: identical bits. */
+int dsrg_heads_forward_ptrs_bf16(const void *const *x_dev, int n_branches, const float *const *w_dev, const float *const *bias_dev,
+                                 float *out_dev, int B, int HW, int K, int O, void *stream);
+int dsrg_heads_backward_ptrs_bf16(const void *const *x_dev, int n_branches, const float *const *w_dev, const float *g_dev,
+                                  void *gx_dev, size_t gx_branch_stride_bytes, float *const *gw_dev, float *partial_dev,
+                                  float relu_scale, float *bias_grad_dev, void *workspace_dev, size_t workspace_bytes, int B,
+                                  int HW, int K, int O, void *stream);
+/* The network's input in one pass: x_dev (B, 3, H, W) f32 NCHW -> y_dev (B, H, W, 3) bf16 (the memory of a channels_last
+ * (B, 3, H, W) tensor), round to nearest even, NaN -> 0x7fc0: the bits of a layout copy followed by a cast. */
+int dsrg_image_nchw_to_nhwc_bf16(const float *x_dev, void *y_dev, int B, int H, int W, void *stream);
+/* out = rne(rne(rne(g_0 + g_1) + g_2) + g_3) over n (2..4) bf16 tensors of numel elements (a multiple of 8, 16-byte aligned)
+ * in one memory order: float32 adds with one bf16 rounding after each, in input order (NaN -> 0x7fc0) — what accumulating n
+ * bf16 gradients of one tensor pairwise gives, in one pass.  g_dev: HOST array of n device pointers. */
+int dsrg_sum_bf16(const void *const *g_dev, int n, void *out_dev, size_t numel, void *stream);
+/* dsrg_sgd_pack_f32 with one more optional output per tensor: cast_dev[i] (may be NULL, as the array itself) receives the new
+ * values of parameter i rounded to bf16 (nearest even) in the parameter's own element order — the kernel of a convolution
+ * route that reads its weights unpacked (conv1_1).  Only for tensors without fwd_dev[i] / dgrad_dev[i]. */
+int dsrg_sgd_pack_cast_f32(int n, float *const *param_dev, const float *const *grad_dev, float *const *momentum_dev,
+                           void *const *fwd_dev, void *const *dgrad_dev, void *const *cast_dev, const int *shape,
+                           const long long *numel, const float *lr, const float *weight_decay, float momentum, void *stream);
 
 #pragma GCC visibility pop
 
