@@ -531,6 +531,15 @@ extern "C" int dsrg_train_f_input_batch(int B, const unsigned char *stage, size_
     return launch_train_f_input_batch(B, stage, stage_bytes, image_off, label_off, H, W, top, left, mirror, ch, cw, mean, scale,
                                       ignore_label, data, label, static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_train_f_input_scaled_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off,
+                                               const int32_t *label_off, const int32_t *H, const int32_t *W, const int32_t *Hs,
+                                               const int32_t *Ws, const int32_t *top, const int32_t *left, const int32_t *mirror, int ch,
+                                               int cw, const float *mean, float scale, float ignore_label, float *data, float *label,
+                                               void *stream) {
+    // every argument is checked before the first device call
+    return launch_train_f_input_scaled_batch(B, stage, stage_bytes, image_off, label_off, H, W, Hs, Ws, top, left, mirror, ch, cw, mean,
+                                             scale, ignore_label, data, label, static_cast<hipStream_t>(stream));
+}
 extern "C" size_t dsrg_resnet_stem_packed_bytes(void) { return resnet_stem_packed_bytes(); }
 extern "C" int dsrg_pack_resnet_stem_f32(const float *w, const float *scale, void *packed, void *stream) {
     if (!w || !scale || !packed) return set_error(DSRG_ERR_INVALID, "resnet stem pack: NULL argument");

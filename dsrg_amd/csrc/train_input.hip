@@ -19,7 +19,15 @@
 // one crop: (float(px) - mean[c]) * scale in BGR order (two separately rounded f32 operations) where the crop lies on the image and
 // 0.0 off it; the label byte as float, ignore_label off the image; the mirror reverses both along x.
 //
-// Both: loads are issued unconditionally on clamped indices and selected afterwards; no atomics, no scratch, no LDS, no dependence on
+// train_f_input_scaled_kernel (stage 2 with `scale_factors`): the same crop taken from image b rescaled to Hs_b x Ws_b, a size the
+// host computes (data.scaled_size); the rescaled image never exists in memory.  The thread of crop pixel (y, x) stands at
+// (top + y, left + x) on the SCALED image and computes its own taps: the pixel by the 8-bit bilinear resize above with (n, S) =
+// (W, Ws) on x and (H, Hs) on y — four clamped loads per channel — and the label by nearest neighbour, src = min((int)floor(d *
+// scale), n - 1) with the resize's own double `scale` per axis (cv::resize INTER_NEAREST).  Then mean, scale, border values and
+// mirror as in train_f_input_kernel.  Hs = H, Ws = W reproduces train_f_input_kernel bit for bit.  The two scales of an image ride
+// in the argument block beside Hs and Ws (the launcher divides once per image; the threads would each divide four times).
+//
+// All: loads are issued unconditionally on clamped indices and selected afterwards; no atomics, no scratch, no LDS, no dependence on
 // the order of workgroups (every output element has exactly one owner; duplicate cue triplets write the same value behind the
 // owner's barrier); -ffp-contract=off (Makefile).  Results are bit-reproducible.
 #include <string.h>
@@ -45,10 +53,20 @@ struct TfArgs {
     float mean[3], scale, ignore_label;
 };
 
-// source index and the two 11-bit weights of output coordinate d on an axis of n source and S output samples; `zero_at_border`:
-// the x axis' rule (fraction zeroed where the index is clamped), the y axis keeps its fraction and clamps the two rows instead
-__device__ __forceinline__ void resize_tap(int d, int n, int S, bool zero_at_border, int &s, int &w0, int &w1) {
-    const double scale = 1.0 / ((double)S / (double)n);
+struct TfScaledArgs {
+    TfArgs f;
+    int Hs[kTiMaxBatch], Ws[kTiMaxBatch];                           // the size image b is rescaled to before the crop
+    double ys[kTiMaxBatch], xs[kTiMaxBatch];                        // axis_scale(H, Hs), axis_scale(W, Ws): divided once, on the host
+};
+
+// source coordinates per output coordinate on an axis of n source and S output samples.  Two IEEE double divisions: the same bits
+// from the host and from the device
+__host__ __device__ __forceinline__ double axis_scale(int n, int S) { return 1.0 / ((double)S / (double)n); }
+
+// source index and the two 11-bit weights of output coordinate d on an axis of n source samples and scale axis_scale(n, S);
+// `zero_at_border`: the x axis' rule (fraction zeroed where the index is clamped), the y axis keeps its fraction and clamps the
+// two rows instead
+__device__ __forceinline__ void resize_tap(int d, int n, double scale, bool zero_at_border, int &s, int &w0, int &w1) {
     float f = (float)(((double)d + 0.5) * scale - 0.5);
     s = (int)floorf(f);
     f -= (float)s;
@@ -60,6 +78,9 @@ __device__ __forceinline__ void resize_tap(int d, int n, int S, bool zero_at_bor
     w1 = min(max(r1, -32768), 32767);
     w0 = min(max(r0, -32768), 32767);
 }
+
+// nearest-neighbour source index of output coordinate d on the same axis, from the same scale (d >= 0, so the index is >= 0)
+__device__ __forceinline__ int nearest_tap(int d, int n, double scale) { return min((int)floor((double)d * scale), n - 1); }
 
 __global__ __launch_bounds__(kTiThreads) void train_s_input_kernel(const unsigned char *__restrict__ stage, TsArgs a, int B, int S, int C,
                                                                    int Hm, int Wm, int cue0, float *__restrict__ images,
@@ -73,8 +94,8 @@ __global__ __launch_bounds__(kTiThreads) void train_s_input_kernel(const unsigne
         const int y = r / S, x = r - y * S;
         const int H = a.H[b], W = a.W[b];
         int sx, a0, a1, sy, b0, b1;
-        resize_tap(x, W, S, true, sx, a0, a1);
-        resize_tap(y, H, S, false, sy, b0, b1);
+        resize_tap(x, W, axis_scale(W, S), true, sx, a0, a1);
+        resize_tap(y, H, axis_scale(H, S), false, sy, b0, b1);
         const int x0 = sx, x1 = min(sx + 1, W - 1);
         const int y0 = min(max(sy, 0), H - 1), y1 = min(max(sy + 1, 0), H - 1);
         const unsigned char *im = stage + a.img_off[b];
@@ -137,6 +158,43 @@ __global__ __launch_bounds__(kTiThreads) void train_f_input_kernel(const unsigne
     label[(size_t)b * P + at] = on ? lab : a.ignore_label;
 }
 
+__global__ __launch_bounds__(kTiThreads) void train_f_input_scaled_kernel(const unsigned char *__restrict__ stage, TfScaledArgs sa, int B,
+                                                                          int ch, int cw, float *__restrict__ data,
+                                                                          float *__restrict__ label) {
+    const TfArgs &a = sa.f;
+    const int P = ch * cw;
+    const int idx = (int)blockIdx.x * kTiThreads + (int)threadIdx.x;                        // (image, y, x) flattened: < B * ch * cw < 2^31 / 3
+    if (idx >= B * P) return;
+    const int b = idx / P, r = idx - b * P;
+    const int y = r / cw, x = r - y * cw;
+    const int H = a.H[b], W = a.W[b], Hs = sa.Hs[b], Ws = sa.Ws[b];
+    const int sy = a.top[b] + y, sx = a.left[b] + x;                                       // on the extended SCALED image (top, left >= 0)
+    const bool on = sy < Hs && sx < Ws;
+    const int dy = min(sy, Hs - 1), dx = min(sx, Ws - 1);                                  // clamped: taps and loads below are unconditional
+    const double ys = sa.ys[b], xs = sa.xs[b];
+    int tx, a0, a1, ty, b0, b1;
+    resize_tap(dx, W, xs, true, tx, a0, a1);
+    resize_tap(dy, H, ys, false, ty, b0, b1);
+    const int x0 = tx, x1 = min(tx + 1, W - 1);                                            // all four inside [0, W) x [0, H)
+    const int y0 = min(max(ty, 0), H - 1), y1 = min(max(ty + 1, 0), H - 1);
+    const unsigned char *im = stage + a.img_off[b];
+    const unsigned char *p00 = im + ((size_t)y0 * W + x0) * 3, *p01 = im + ((size_t)y0 * W + x1) * 3;
+    const unsigned char *p10 = im + ((size_t)y1 * W + x0) * 3, *p11 = im + ((size_t)y1 * W + x1) * 3;
+    const float lab = (float)stage[(size_t)a.lab_off[b] + (size_t)nearest_tap(dy, H, ys) * W + nearest_tap(dx, W, xs)];
+    const int xo = ((a.mirror >> b) & 1u) ? cw - 1 - x : x;
+    const size_t at = (size_t)y * cw + xo;
+    float *o = data + (size_t)b * 3 * P + at;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {                                                           // output channel c = input channel 2 - c (BGR)
+        const int D0 = (int)p00[2 - c] * a0 + (int)p01[2 - c] * a1;
+        const int D1 = (int)p10[2 - c] * a0 + (int)p11[2 - c] * a1;
+        const int px = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2;
+        const float v = ((float)px - a.mean[c]) * a.scale;
+        o[c * P] = on ? v : 0.0f;
+    }
+    label[(size_t)b * P + at] = on ? lab : a.ignore_label;
+}
+
 // `n` bytes at byte offset `off` lie inside the staging buffer?
 static bool inside(long long off, long long n, size_t stage_bytes) {
     return off >= 0 && n >= 0 && (unsigned long long)off + (unsigned long long)n <= (unsigned long long)stage_bytes;
@@ -191,10 +249,10 @@ int launch_train_s_input_batch(int B, const unsigned char *stage, size_t stage_b
     return DSRG_OK;
 }
 
-int launch_train_f_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *label_off,
+// every check the two stage-2 entries share, and their common argument block
+static int check_train_f_input(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *label_off,
                                const int32_t *H, const int32_t *W, const int32_t *top, const int32_t *left, const int32_t *mirror,
-                               int ch, int cw, const float *mean, float scale, float ignore_label, float *data, float *label,
-                               hipStream_t stream) {
+                               int ch, int cw, const float *mean, float scale, float ignore_label, float *data, float *label, TfArgs &a) {
     if (B < 1 || B > kTiMaxBatch) return set_error(DSRG_ERR_INVALID, "train-f input: 1..%d images, got %d", kTiMaxBatch, B);
     if (!stage) return set_error(DSRG_ERR_INVALID, "train-f input: NULL staging buffer");
     if (!image_off || !label_off || !H || !W) return set_error(DSRG_ERR_INVALID, "train-f input: NULL offset / image size array");
@@ -205,7 +263,6 @@ int launch_train_f_input_batch(int B, const unsigned char *stage, size_t stage_b
     if (stage_bytes >= ((size_t)1 << 31)) return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: staging buffer holds >= 2^31 bytes");
     if ((long long)B * 3 * ch * cw >= (1LL << 31))
         return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: data holds %lld >= 2^31 values", (long long)B * 3 * ch * cw);
-    TfArgs a;
     memset(&a, 0, sizeof(a));
     for (int b = 0; b < B; ++b) {
         if (H[b] < 1 || W[b] < 1) return set_error(DSRG_ERR_INVALID, "train-f input: image %d is %dx%d", b, H[b], W[b]);
@@ -224,9 +281,44 @@ int launch_train_f_input_batch(int B, const unsigned char *stage, size_t stage_b
     for (int c = 0; c < 3; ++c) a.mean[c] = mean[c];
     a.scale = scale;
     a.ignore_label = ignore_label;
+    return DSRG_OK;
+}
+
+int launch_train_f_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *label_off,
+                               const int32_t *H, const int32_t *W, const int32_t *top, const int32_t *left, const int32_t *mirror,
+                               int ch, int cw, const float *mean, float scale, float ignore_label, float *data, float *label,
+                               hipStream_t stream) {
+    TfArgs a;
+    const int rc = check_train_f_input(B, stage, stage_bytes, image_off, label_off, H, W, top, left, mirror, ch, cw, mean, scale,
+                                       ignore_label, data, label, a);
+    if (rc != DSRG_OK) return rc;
     const long long n = (long long)B * ch * cw;
     hipLaunchKernelGGL(train_f_input_kernel, dim3((unsigned)((n + kTiThreads - 1) / kTiThreads)), dim3(kTiThreads), 0, stream, stage, a, B,
                        ch, cw, data, label);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
+int launch_train_f_input_scaled_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off,
+                                      const int32_t *label_off, const int32_t *H, const int32_t *W, const int32_t *Hs, const int32_t *Ws,
+                                      const int32_t *top, const int32_t *left, const int32_t *mirror, int ch, int cw, const float *mean,
+                                      float scale, float ignore_label, float *data, float *label, hipStream_t stream) {
+    TfScaledArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    const int rc = check_train_f_input(B, stage, stage_bytes, image_off, label_off, H, W, top, left, mirror, ch, cw, mean, scale,
+                                       ignore_label, data, label, sa.f);
+    if (rc != DSRG_OK) return rc;
+    if (!Hs || !Ws) return set_error(DSRG_ERR_INVALID, "train-f input: NULL scaled size array");
+    for (int b = 0; b < B; ++b) {
+        if (Hs[b] < 1 || Ws[b] < 1) return set_error(DSRG_ERR_INVALID, "train-f input: image %d is rescaled to %dx%d", b, Hs[b], Ws[b]);
+        if ((long long)Hs[b] * Ws[b] >= (1LL << 31))
+            return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: image %d rescaled to %dx%d holds >= 2^31 pixels", b, Hs[b], Ws[b]);
+        sa.Hs[b] = Hs[b], sa.Ws[b] = Ws[b];                                                 // (top + ch, left + cw < 2^31: checked above)
+        sa.ys[b] = axis_scale(H[b], Hs[b]), sa.xs[b] = axis_scale(W[b], Ws[b]);
+    }
+    const long long n = (long long)B * ch * cw;
+    hipLaunchKernelGGL(train_f_input_scaled_kernel, dim3((unsigned)((n + kTiThreads - 1) / kTiThreads)), dim3(kTiThreads), 0, stream, stage,
+                       sa, B, ch, cw, data, label);
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
 }

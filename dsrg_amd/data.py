@@ -26,7 +26,68 @@ except ImportError:
 
 # layer.py:238-251: the keys a param_str may leave out
 _DEFAULTS = (('crop_size', (505, 505)), ('mean', [128, 128, 128]), ('scale', 1.0), ('mirror', False), ('phase', 'Train'),
-             ('ignore_label', 255))
+             ('ignore_label', 255), ('scale_factors', ()))
+
+
+def scaled_size(H, W, s):
+    """the size an H x W image is rescaled to by the factor s: max(1, round half even of the double product) per axis (Python's
+    round, cvRound)"""
+    return max(1, int(round(float(H) * float(s)))), max(1, int(round(float(W) * float(s))))
+
+
+def check_scale_factors(factors):
+    """the `scale_factors` parameter as a tuple of floats: every factor finite and > 0 (empty: no rescaling)"""
+    factors = tuple(float(s) for s in factors)
+    if not all(np.isfinite(s) and s > 0 for s in factors):
+        raise ValueError("scale_factors must be finite and > 0, got %r" % (factors,))
+    return factors
+
+
+def _bilinear_taps(n, S, zero_at_border):
+    """DESIGN.md, "The resize contract", for every output coordinate of an axis of n source and S output samples: the two source
+    indices and their 11-bit weights"""
+    f = ((np.arange(S, dtype=np.float64) + 0.5) * (1.0 / (float(S) / float(n))) - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int64)
+    f = (f - s.astype(np.float32)).astype(np.float32)
+    if zero_at_border:                                                       # x: the fraction goes where the index is clamped
+        f = np.where((s < 0) | (s >= n - 1), np.float32(0.0), f).astype(np.float32)
+    w1 = np.clip(np.rint(f * np.float32(2048.0)), -32768, 32767).astype(np.int32)
+    w0 = np.clip(np.rint((np.float32(1.0) - f) * np.float32(2048.0)), -32768, 32767).astype(np.int32)
+    return np.clip(s, 0, n - 1), np.clip(s + 1, 0, n - 1), w0, w1
+
+
+def resize_bilinear_u8(img_u8, Hs, Ws):
+    """(H, W) or (H, W, C) uint8 -> (Hs, Ws[, C]) uint8: the 8-bit bilinear resize of DESIGN.md ("The resize contract", a
+    restatement of cv::resize INTER_LINEAR for 8-bit images) with its own output size per axis.  The identity when (Hs, Ws) is
+    the image's size.  An exact 2x shrink is not switched to area averaging."""
+    img = np.asarray(img_u8)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise TypeError("resize_bilinear_u8 takes an (H, W[, C]) uint8 image, got %s %s" % (img.dtype, img.shape))
+    if Hs < 1 or Ws < 1:
+        raise ValueError("resize to %d x %d" % (Hs, Ws))
+    H, W = img.shape[:2]
+    x0, x1, a0, a1 = _bilinear_taps(W, int(Ws), True)
+    y0, y1, b0, b1 = _bilinear_taps(H, int(Hs), False)
+    tail = (1,) * (img.ndim - 2)
+    p = img.astype(np.int32)
+    D = p[:, x0] * a0.reshape((1, -1) + tail) + p[:, x1] * a1.reshape((1, -1) + tail)              # (H, Ws[, C]) int32
+    b0, b1 = b0.reshape((-1, 1) + tail), b1.reshape((-1, 1) + tail)
+    out = (((b0 * (D[y0] >> 4)) >> 16) + ((b1 * (D[y1] >> 4)) >> 16) + 2) >> 2
+    return np.clip(out, 0, 255).astype(np.uint8)                            # (cv's saturate_cast; the weights sum to 2048: never hit)
+
+
+def _nearest_taps(n, S):
+    return np.minimum(np.floor(np.arange(S, dtype=np.float64) * (1.0 / (float(S) / float(n)))).astype(np.int64), n - 1)
+
+
+def resize_nearest(label, Hs, Ws):
+    """(H, W[, C]) of any dtype -> (Hs, Ws[, C]): cv::resize INTER_NEAREST, src = min(floor(d * scale), n - 1) per axis with the
+    bilinear resize's double scale = 1.0 / (S / n)"""
+    label = np.asarray(label)
+    if label.ndim < 2 or Hs < 1 or Ws < 1:
+        raise ValueError("resize_nearest of %s to %d x %d" % (label.shape, Hs, Ws))
+    H, W = label.shape[:2]
+    return label[_nearest_taps(H, int(Hs))[:, None], _nearest_taps(W, int(Ws))[None, :]]
 
 
 class _Window(object):
@@ -62,6 +123,7 @@ class SimpleTransformer:
         self.crop_h, self.crop_w = params['crop_size']
         self.mean, self.scale = params['mean'], params['scale']
         self.is_mirror, self.phase, self.ignore_label = params['mirror'], params['phase'], params['ignore_label']
+        self.scale_factors = check_scale_factors(params['scale_factors'])
 
     def set_mean(self, mean):
         self.mean = mean
@@ -82,7 +144,16 @@ class SimpleTransformer:
         """layer.py:171-236: image is BGR (cv2.imread order) -> CHW float32 crop (and the label crop, float32).
         Random draws, as the reference makes them: `random.randint` for the row offset, then for the column offset, both over
         the slack of the EXTENDED image and only in phase 'Train'; then, only with `mirror`, ONE `np.random.choice(2)` whose
-        value 0 means "mirror" (the reference's stride 2*0-1 = -1)."""
+        value 0 means "mirror" (the reference's stride 2*0-1 = -1).
+        With `scale_factors` (not the reference's: Caffe-DeepLab's parameter of that name), in phase 'Train' and with a label,
+        one `random.randrange(len(scale_factors))` comes first; the uint8 image (resize_bilinear_u8) and the label
+        (resize_nearest) are rescaled to scaled_size before the mean, and everything after works on the rescaled pair."""
+        if label is not None and self.scale_factors and np.asarray(image).dtype != np.uint8:
+            raise TypeError("scale_factors need the uint8 image as it was read, got %s" % np.asarray(image).dtype)
+        if label is not None and self.scale_factors and self.phase == 'Train':
+            label = np.asarray(label)
+            Hs, Ws = scaled_size(label.shape[0], label.shape[1], self.scale_factors[random.randrange(len(self.scale_factors))])
+            image, label = resize_bilinear_u8(image, Hs, Ws), resize_nearest(label, Hs, Ws)
         x = (np.asarray(image, np.float32) - np.asarray(self.mean, np.float32)) * np.float32(self.scale)
         if label is None:
             return self._centred(x)

@@ -13,8 +13,8 @@ that decides WHAT a batch holds is plain host code that needs no device: the epo
 Random numbers.  Each loader owns its generators, the global ones are never touched.  TrainSInput: the epoch shuffle comes from a
 `random.Random(seed)` — NOT Caffe's RNG, so a run does not see the reference's image order — and the mirror draws from an
 `np.random.RandomState(seed)`, one `choice(2)` per image in batch order, 0 = mirror: AnnotationLayer's draws under
-`np.random.seed(seed)`.  TrainFInput: BatchLoader's and SimpleTransformer.preprocess's draws in their order — per image the row
-offset, the column offset (`random.Random(seed).randint`), the mirror (`RandomState(seed).choice(2)`), and `shuffle` from the same
+`np.random.seed(seed)`.  TrainFInput: BatchLoader's and SimpleTransformer.preprocess's draws in their order — per image (only with `scale_factors`: the
+factor's index, `randrange`, first,) the row offset, the column offset (`random.Random(seed).randint`), the mirror (`RandomState(seed).choice(2)`), and `shuffle` from the same
 `random.Random` between the last image of an epoch and the first of the next — so a run seeded like `random.seed(seed);
 np.random.seed(seed)` sees the reference's crops.  With world_size > 1 the shuffle moves to a second `random.Random(seed)` that
 does nothing else (see TrainFInput.__init__), so that every rank shuffles alike.  All draws are made on the iterating thread, never
@@ -26,7 +26,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from .data import SimpleTransformer, _Window
+from .data import SimpleTransformer, _Window, check_scale_factors, scaled_size
 
 MAX_BATCH = 32                                   # images per launch (dsrg_train_s_input_batch / dsrg_train_f_input_batch)
 
@@ -143,12 +143,18 @@ def pack_train_s(buf, desc, images, cues, labels):
         buf[o:o + 4 * L].view(np.int32)[:] = np.asarray(lab, dtype=np.int32).reshape(-1)
 
 
-def layout_train_f(shapes, top, left, mirror):
+def layout_train_f(shapes, top, left, mirror, scaled=None):
     """where the pieces of a stage-2 batch lie in its staging buffer.  shapes: (H, W) per image; top / left / mirror: the host's
-    draws -> (bytes, desc): desc is the dict of per-image lists ops.train_f_input_batch takes."""
+    draws; scaled: (Hs, Ws) per image, the size each is rescaled to before the crop (top / left are then offsets on the rescaled
+    image), or None -> (bytes, desc): desc is the dict of per-image lists ops.train_f_input_batch takes; with `scaled` it holds
+    Hs and Ws too.  The bytes are the same either way: the source image is what is staged."""
     n = len(shapes)
     desc = dict(image_off=[], label_off=[], H=[], W=[], top=[int(t) for t in top], left=[int(v) for v in left],
                 mirror=[int(bool(m)) for m in mirror])
+    if scaled is not None:
+        if len(scaled) != n or min([1] + [min(s) for s in scaled]) < 1:
+            raise ValueError("one rescaled size >= 1 x 1 per image, got %r" % (list(scaled),))
+        desc["Hs"], desc["Ws"] = [int(s[0]) for s in scaled], [int(s[1]) for s in scaled]
     off = 0
     for H, W in shapes:
         if H < 1 or W < 1:
@@ -402,7 +408,10 @@ class TrainFInput(_StagedLoader):
     batch_size, crop_size, mean, scale, mirror, phase, ignore_label; what is left out takes SimpleTransformer.check_params'
     defaults.  List order and reshuffling are BatchLoader's, the draws SimpleTransformer.preprocess's, in its order per image: row
     offset, column offset (phase 'Train' only), mirror choice (with `mirror` only) — from a random.Random(seed) and an
-    np.random.RandomState(seed) of the loader's own.  An image's size is read from its label file's header when the batch is
+    np.random.RandomState(seed) of the loader's own.  `scale_factors` (default (): none; finite, > 0): in phase 'Train' each image
+    is first rescaled by one of them — `randrange(len(scale_factors))` from the offsets' generator, drawn before the row offset —
+    to data.scaled_size of its size, bilinearly (8 bit) for the image and by nearest neighbour for the label, and the window is
+    the rescaled image's; the device does the rescaling inside the same launch, the staged bytes are the source image's.  An image's size is read from its label file's header when the batch is
     planned, so the draws never wait for a decode.  With world_size > 1 every rank shuffles identically — from a second
     random.Random(seed) that only shuffles, since the offsets' generator advances by amounts that depend on each rank's own images —
     and takes items rank, rank + world_size, ... of the epoch; the crops are then no longer the single-process run's.  The tensors of batch n are valid until the __next__ call after next (_StagedLoader)."""
@@ -418,6 +427,7 @@ class TrainFInput(_StagedLoader):
         self.mean, self.scale = tuple(float(np.float32(m)) for m in params['mean']), float(np.float32(params['scale']))
         self.is_mirror, self.phase, self.ignore_label = bool(params['mirror']), params['phase'], params['ignore_label']
         self.root_folder = params['root_folder']
+        self.scale_factors = check_scale_factors(params['scale_factors'])
         with open(params['source']) as f:
             self.entries = [tuple(ln.split()[:2]) for ln in f if ln.strip()]
         if not self.entries:
@@ -436,14 +446,19 @@ class TrainFInput(_StagedLoader):
         for _ in range(self.batch_size):
             image_path, label_path = next(self._items)                  # (reshuffles between two epochs, from the offsets' generator)
             image_path, label_path = self.root_folder + image_path, self.root_folder + label_path
-            win = _Window(image_size(label_path), self.crop)
+            size, rescaled = image_size(label_path), {}
+            if self.scale_factors and self.phase == 'Train':             # first draw of the image; the window is the rescaled image's
+                k = self._rng.randrange(len(self.scale_factors))
+                size = scaled_size(size[0], size[1], self.scale_factors[k])
+                rescaled = dict(factor=k, Hs=size[0], Ws=size[1])
+            win = _Window(size, self.crop)
             top, left = win.top, win.left                               # centred unless drawn
             if self.phase == 'Train':
                 max_top, max_left = win.slack()
                 top = self._rng.randint(0, max_top)
                 left = self._rng.randint(0, max_left)
             mirror = self.is_mirror and int(self._np_rng.choice(2)) == 0
-            plan.append(dict(image=image_path, label=label_path, top=top, left=left, mirror=mirror))
+            plan.append(dict(image=image_path, label=label_path, top=top, left=left, mirror=mirror, **rescaled))
         return plan
 
     def _decode(self, item):
@@ -451,8 +466,9 @@ class TrainFInput(_StagedLoader):
 
     def _layout(self, plan, arrays):
         images, labels = [a[0] for a in arrays], [a[1] for a in arrays]
+        scaled = [(it["Hs"], it["Ws"]) for it in plan] if plan and "Hs" in plan[0] else None
         nbytes, desc = layout_train_f([a.shape[:2] for a in images], [it["top"] for it in plan], [it["left"] for it in plan],
-                                      [it["mirror"] for it in plan])
+                                      [it["mirror"] for it in plan], scaled)
         return nbytes, desc, (images, labels)
 
     def _pack(self, buf, desc, pieces):

@@ -637,21 +637,24 @@ def train_f_input_batch(stage, desc, crop_size, mean, scale=1.0, ignore_label=25
     every image of the batch.  stage: the batch's raw bytes as a 1-d uint8 CUDA tensor (input.pack_train_f); desc: the dict of
     per-image lists input.layout_train_f returns — image_off, label_off, H, W — and the host's draws top, left, mirror.  Returns
     (data (B,3,ch,cw), label (B,1,ch,cw)), float32: the arguments of RetrainTrainer.step.  out: two existing tensors of those shapes
-    to write into.  Runs on torch's current stream."""
+    to write into.  A desc that carries Hs and Ws (layout_train_f's `scaled`) goes to dsrg_train_f_input_scaled_batch: every image
+    is rescaled to (Hs, Ws) inside the same launch — 8-bit bilinear for the image, nearest neighbour for the label — and top /
+    left are offsets on the rescaled image.  Runs on torch's current stream."""
     nbytes = _stage_arg(stage, nbytes)
     B = len(desc["H"])
     ch, cw = int(crop_size[0]), int(crop_size[1])
     if len(mean) != 3:
         raise ValueError("mean must hold 3 values")
-    keys = ("image_off", "label_off", "H", "W", "top", "left", "mirror")
+    scaled = "Hs" in desc or "Ws" in desc
+    keys = ("image_off", "label_off", "H", "W") + (("Hs", "Ws") if scaled else ()) + ("top", "left", "mirror")
     if any(len(desc[k]) != B for k in keys):
         raise ValueError("every descriptor list must hold one entry per image")
     out = (None, None) if out is None else out
     data = _out_arg(out[0], (B, 3, ch, cw), "out[0]", stage.device)
     label = _out_arg(out[1], (B, 1, ch, cw), "out[1]", stage.device)
-    check(_lib.lib().dsrg_train_f_input_batch(B, _ptr(stage), nbytes, *[_i32s(desc[k]) for k in keys], ch, cw,
-                                              (ctypes.c_float * 3)(*[float(m) for m in mean]), float(scale), float(ignore_label),
-                                              _ptr(data), _ptr(label), _stream()))
+    entry = _lib.lib().dsrg_train_f_input_scaled_batch if scaled else _lib.lib().dsrg_train_f_input_batch
+    check(entry(B, _ptr(stage), nbytes, *[_i32s(desc[k]) for k in keys], ch, cw, (ctypes.c_float * 3)(*[float(m) for m in mean]),
+                float(scale), float(ignore_label), _ptr(data), _ptr(label), _stream()))
     return data, label
 
 

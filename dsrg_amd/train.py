@@ -6,7 +6,8 @@
 
 Stage s reads --list ('name.jpg <id>' lines, the reference's list/input_list.txt), the images under --root and the localisation
 cues of --cues; stage f reads --list ('image_path label_path' lines, list/train.txt) with --root prefixed to both paths.  The
-defaults are the solver files' values (STAGE_DEFAULTS).  Batches are assembled on the GPU (dsrg_amd/input.py) while the step
+defaults are the solver files' values (STAGE_DEFAULTS).  Stage f's --scale-factors (not the reference's; DeepLab's augmentation for
+--backbone resnet101 --crop 513, where no VOC image leaves the crop any slack) rescales each image by a drawn factor before the crop.  Batches are assembled on the GPU (dsrg_amd/input.py) while the step
 before runs.  Every --display steps the mean of the last --display losses is printed with the learning rate; snapshots
 (<prefix>_iter_N.caffemodel + .solverstate.pt) are written every --snapshot-every steps and at the end; --snapshot resumes at the
 snapshot's iteration count.  Under a launcher (torch.distributed.run: RANK / WORLD_SIZE set) every rank takes its shard of each
@@ -43,6 +44,9 @@ def parse_args(argv=None):
     p.add_argument("--crop", type=int, default=None, help="f: crop size (321)")
     p.add_argument("--mean", default=None, help="f: B,G,R mean (104,117,123)")
     p.add_argument("--no-mirror", action="store_true", help="f: no random mirror")
+    p.add_argument("--scale-factors", default=None,
+                   help="f: rescale every image by one of these factors, drawn per image, before the crop, e.g. 0.5,0.75,1,1.25,1.5 "
+                        "(bilinear for the image, nearest neighbour for the label, done on the GPU; default: none)")
     a = p.parse_args(argv)
     for key, value in STAGE_DEFAULTS[a.stage].items():
         if getattr(a, key) is None:
@@ -50,8 +54,8 @@ def parse_args(argv=None):
     if a.stage == "s":
         if not a.cues:
             p.error("--stage s needs --cues (the localisation-cue pickle)")
-        if a.backbone or a.crop is not None or a.mean is not None or a.no_mirror:
-            p.error("--backbone, --crop, --mean and --no-mirror are for --stage f")
+        if a.backbone or a.crop is not None or a.mean is not None or a.no_mirror or a.scale_factors is not None:
+            p.error("--backbone, --crop, --mean, --no-mirror and --scale-factors are for --stage f")
     else:
         if a.cues:
             p.error("--cues is for --stage s")
@@ -60,6 +64,15 @@ def parse_args(argv=None):
         a.mean = F_DEFAULTS["mean"] if a.mean is None else tuple(float(v) for v in a.mean.split(","))
         if len(a.mean) != 3:
             p.error("--mean takes three values: B,G,R")
+        if a.scale_factors is None:
+            a.scale_factors = ()
+        else:
+            try:
+                a.scale_factors = tuple(float(v) for v in a.scale_factors.split(","))
+            except ValueError:
+                p.error("--scale-factors takes numbers separated by commas, got %r" % a.scale_factors)
+            if not all(0.0 < s < float("inf") for s in a.scale_factors):
+                p.error("--scale-factors must be finite and > 0, got %r" % (a.scale_factors,))
     if min(a.iters, a.snapshot_every, a.batch, a.display, a.workers) < 1:
         p.error("--iters, --snapshot-every, --batch, --display and --workers must be >= 1")
     return a
@@ -106,7 +119,7 @@ def main(argv=None):
         trainer = RetrainTrainer(device, world_size=world, backbone=a.backbone, max_iter=a.iters, seed=a.seed, weights=a.weights,
                                  snapshot=a.snapshot)
         loader = TrainFInput(dict(source=a.list, root_folder=a.root, batch_size=batch, crop_size=(a.crop, a.crop), mean=a.mean,
-                                  mirror=not a.no_mirror), seed=a.seed, workers=a.workers, rank=rank, world_size=world, device=device)
+                                  mirror=not a.no_mirror, scale_factors=a.scale_factors), seed=a.seed, workers=a.workers, rank=rank, world_size=world, device=device)
         names = ("loss",)
         rate = lambda: poly_lr(trainer.base_lr, trainer.opt.iter, trainer.max_iter)      # noqa: E731
     if trainer.opt.iter:

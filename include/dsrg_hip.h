@@ -348,6 +348,25 @@ int dsrg_train_f_input_batch(int B, const unsigned char *stage_dev, size_t stage
                              const int32_t *label_off_host, const int32_t *H_host, const int32_t *W_host, const int32_t *top_host,
                              const int32_t *left_host, const int32_t *mirror_host, int ch, int cw, const float *mean_host, float scale,
                              float ignore_label, float *data_dev, float *label_dev, void *stream);
+/* dsrg_train_f_input_batch with a per-image rescaling in front of the crop (Caffe-DeepLab's `scale_factors`: cv::resize
+ * INTER_LINEAR for the image, INTER_NEAREST for the label), in one launch; the rescaled image is never stored.  Arguments as
+ * above, plus Hs_host / Ws_host: the size image b is rescaled to (the host's max(1, round_half_even(H_b * s)); the factor itself
+ * does not cross this boundary).  top_host / left_host are offsets on the RESCALED image extended to at least the crop size.  The
+ * pixel at (r, c) of the rescaled image is, per axis with n source and S output samples (n, S) = (H_b, Hs_b) and (W_b, Ws_b):
+ *   image: the 8-bit bilinear resize stated in DESIGN.md ("The resize contract": scale = 1.0 / ((double)S / (double)n), fraction
+ *          in float, 11-bit weights rounded half-even; x zeroes the fraction at clamped indices, y clamps its two rows; vertical
+ *          pass >> 4, >> 16, + 2, >> 2); an exact 2x shrink is NOT switched to area averaging
+ *   label: the byte at src = min((int)floor((double)d * scale), n - 1) on each axis, with the same double `scale`
+ * and the outputs are those of dsrg_train_f_input_batch on that image: (float(pixel) - mean_host[c]) * scale in BGR order / the
+ * label byte as float where the crop lies on the rescaled image, 0.0 / ignore_label off it, mirrored along x where
+ * mirror_host[b] != 0.  With Hs_b = H_b and Ws_b = W_b the outputs equal dsrg_train_f_input_batch's bit for bit.
+ * Limits as above, and Hs_b, Ws_b >= 1, Hs_b*Ws_b < 2^31; every argument is checked before the first device call.  Nothing is
+ * allocated.  Stream-ordered, no host synchronisation, no handle; bit-reproducible (no atomics). */
+int dsrg_train_f_input_scaled_batch(int B, const unsigned char *stage_dev, size_t stage_bytes, const int32_t *image_off_host,
+                                    const int32_t *label_off_host, const int32_t *H_host, const int32_t *W_host,
+                                    const int32_t *Hs_host, const int32_t *Ws_host, const int32_t *top_host, const int32_t *left_host,
+                                    const int32_t *mirror_host, int ch, int cw, const float *mean_host, float scale,
+                                    float ignore_label, float *data_dev, float *label_dev, void *stream);
 /* The stem of the DeepLab-v2 ResNet-101 at test time in one launch (backbone plumbing; the reference's networks are Caffe
  * prototxts): conv 7x7 / stride 2 / zero pad 3, 3 -> 64, with a frozen BatchNorm folded in -> ReLU -> max pool 3x3 / stride 2 /
  * pad 1, ceil mode.  The convolution map never reaches memory.

@@ -11,10 +11,15 @@ alternating.
   (d) the host composition the stage-1 kernel replaces: numpy restatement of the resize -> AnnotationLayer -> float32 upload, per
       batch of 20 (host clock, ends in a device synchronise).
 
+  (e) as (b) for the stage-2 launch at batch 10 / crop 513 without and with rescaling (train_f_input_scaled_kernel, factors 0.5 ...
+      1.5 over the 10 images), the sides alternating.
+  (f) images/s of TrainFInput at batch 10 / crop 513 without and with scale_factors = 0.5 ... 1.5, alternating windows.
+
   (k) the two launches alone, 200 times each, for `rocprofv3 --kernel-trace --stats` in a run of its own (tools/rocpd_stats.py
       summarises its database).
+  (j) the same for the two stage-2 launches of (e).
 
-usage: python tools/train_input_probe.py [a|b|c|d|k ...]     (default: a b c d; one JSON line at the end)
+usage: python tools/train_input_probe.py [a|b|c|d|e|f|j|k ...]     (default: a b c d; one JSON line at the end)
 """
 import json
 import os
@@ -159,6 +164,70 @@ def probe_k(p, launches=200):
     return dict(launches_each=launches, **sizes)
 
 
+SCALE_FACTORS = (0.5, 0.75, 1.0, 1.25, 1.5)
+
+
+def _scaled_calls(p, crop=513, n=10):
+    """-> (launch train_f_input_kernel, launch train_f_input_scaled_kernel, sizes): the same 10 staged images at crop 513, the scaled
+    launch with the factors 0.5 ... 1.5 twice over, offsets in the middle of each window's slack"""
+    from dsrg_amd import data as D, input as I, ops
+    images = [I.read_rgb(os.path.join(p["root"], "im%d.jpg" % k)) for k in range(n)]
+    labs = [I.read_gray(os.path.join(p["root"], "lab%d.png" % k)) for k in range(n)]
+    shapes = [l.shape for l in labs]
+    scaled = [D.scaled_size(H, W, SCALE_FACTORS[k % 5]) for k, (H, W) in enumerate(shapes)]
+    mid = lambda sizes: [[v // 2 for v in D._Window(s, (crop, crop)).slack()] for s in sizes]                  # noqa: E731
+    mirror = [k % 2 for k in range(n)]
+    nbytes, plain = I.layout_train_f(shapes, [m[0] for m in mid(shapes)], [m[1] for m in mid(shapes)], mirror)
+    sbytes, desc = I.layout_train_f(shapes, [m[0] for m in mid(scaled)], [m[1] for m in mid(scaled)], mirror, scaled)
+    assert sbytes == nbytes
+    buf = np.zeros(nbytes, np.uint8)
+    I.pack_train_f(buf, plain, images, labs)
+    stage = torch.from_numpy(buf).cuda()
+    out = ops.train_f_input_batch(stage, plain, (crop, crop), MEAN)
+    sout = ops.train_f_input_batch(stage, desc, (crop, crop), MEAN)
+    sizes = dict(crop=crop, images=n, staging_bytes=nbytes, output_bytes=sum(o.numel() * 4 for o in out), scaled_sizes=scaled)
+    return (lambda: ops.train_f_input_batch(stage, plain, (crop, crop), MEAN, out=out),
+            lambda: ops.train_f_input_batch(stage, desc, (crop, crop), MEAN, out=sout), sizes)
+
+
+def probe_e(p):
+    run_f, run_scaled, sizes = _scaled_calls(p)
+    us = [[], []]
+    for _ in range(3):                                                    # the sides alternating
+        us[0].append(round(_median_us(run_f, reps=200), 2))
+        us[1].append(round(_median_us(run_scaled, reps=200), 2))
+    print("(e) back-to-back calls at crop 513, 10 images, device events (an UPPER BOUND on kernel time): unscaled %s us, scaled "
+          "(factors %s) %s us; %d staging bytes -> %d output bytes either way"
+          % (us[0], list(SCALE_FACTORS), us[1], sizes["staging_bytes"], sizes["output_bytes"]), flush=True)
+    return dict(train_f_call_us=us[0], train_f_scaled_call_us=us[1], **sizes)
+
+
+def probe_j(p, launches=200):
+    """the unscaled and the scaled stage-2 launch at crop 513 alone, 200 times each, for a trace as in mode k"""
+    run_f, run_scaled, sizes = _scaled_calls(p)
+    for _ in range(launches):
+        run_f()
+        run_scaled()
+    torch.cuda.synchronize()
+    return dict(launches_each=launches, **sizes)
+
+
+def probe_f(p, workers=8, crop=513):
+    """TrainFInput at batch 10 / crop 513 without and with scale factors, alternating windows of 60 batches in one process"""
+    from dsrg_amd.input import TrainFInput
+    mk = lambda factors: TrainFInput(dict(source=p["f"], root_folder=p["root"], batch_size=10, crop_size=(crop, crop), mean=MEAN,      # noqa: E731
+                                          mirror=True, scale_factors=factors), workers=workers)
+    with mk(()) as plain, mk(SCALE_FACTORS) as scaled:
+        _window(plain, 3), _window(scaled, 3)
+        rp, rs = [], []
+        for _ in range(3):
+            rp.append(round(_window(plain, 60), 1))
+            rs.append(round(_window(scaled, 60), 1))
+    print("(f) TrainFInput at crop %d, batch 10, %d threads: %s images/s without factors, %s images/s with %s"
+          % (crop, workers, rp, rs, list(SCALE_FACTORS)), flush=True)
+    return dict(train_f_images_per_s=rp, train_f_scaled_images_per_s=rs, workers=workers, crop=crop)
+
+
 def probe_c(p, steps=50):
     from dsrg_amd.trainer import DSRGTrainer
     mk_s, _ = _loaders(p)
@@ -249,7 +318,8 @@ def main(which):
     out = {"device": torch.cuda.get_device_name(0), "files": N_FILES}
     with tempfile.TemporaryDirectory() as d:
         p = _files(d)
-        for key, fn in (("k", probe_k), ("b", probe_b), ("d", probe_d), ("a", probe_a), ("c", probe_c)):
+        for key, fn in (("k", probe_k), ("j", probe_j), ("b", probe_b), ("e", probe_e), ("d", probe_d), ("a", probe_a), ("f", probe_f),
+                        ("c", probe_c)):
             if key in which:
                 out[key] = fn(p)
     print(json.dumps(out))
