@@ -14,6 +14,7 @@ import torch.nn.functional as F
 import os as _os
 
 from . import ops
+from .streams import capture_stream
 
 # Which kernels a convolution runs is decided from what the call observes (device, dtype, layout, shape), by measured thresholds:
 # output channels from which the weight gradient of a 3x3 convolution at the 41x41 stages is the GEMM g^T @ im2col(x) (round 2, A/B
@@ -846,7 +847,8 @@ class GraphedForward(object):
         torch.cuda.current_stream().wait_stream(warm)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode=capture_error_mode):
+        # (on a stream no CRF worker of the test-time loops can hold: streams.py)
+        with torch.cuda.graph(self.graph, stream=capture_stream(example.device), capture_error_mode=capture_error_mode):
             self.out = self._fwd()
 
     def _fwd(self):

@@ -264,6 +264,7 @@ def CRF_device_many(pairs, maxiter=10, scale_factor=1.0, color_factor=13, want="
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
     import torch
+    from .streams import side_stream
     local = threading.local()
     device = torch.cuda.current_device()
     caller = torch.cuda.current_stream(device)
@@ -275,7 +276,7 @@ def CRF_device_many(pairs, maxiter=10, scale_factor=1.0, color_factor=13, want="
         """group: list of (image, unary, select or None) of one shape, all with or all without a list -> list of results"""
         torch.cuda.set_device(device)
         if not hasattr(local, "stream"):
-            local.stream, local.objs = torch.cuda.Stream(device=device), {}
+            local.stream, local.objs = side_stream(device), {}       # (never the stream a forward thread captures a graph on)
         H, W, M = group[0][1].shape
         n = len(group)
         key = (H, W, M, n if batch > 1 else None)

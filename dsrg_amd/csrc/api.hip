@@ -515,6 +515,12 @@ extern "C" int dsrg_preprocess_ms_batch(int G, int capacity, int K, const unsign
     // every argument is checked before the first device call
     return launch_preprocess_ms_batch(G, capacity, K, images, H, W, sizes, mean, out, static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_preprocess_rect_batch(int G, int capacity, int K, const unsigned char *const *images, const int32_t *H,
+                                          const int32_t *W, const int32_t *out_h, const int32_t *out_w, const float *mean,
+                                          float *const *out, void *stream) {
+    // every argument is checked before the first device call
+    return launch_preprocess_rect_batch(G, capacity, K, images, H, W, out_h, out_w, mean, out, static_cast<hipStream_t>(stream));
+}
 extern "C" int dsrg_train_s_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off,
                                         const int32_t *H, const int32_t *W, const int32_t *cue_off, const int32_t *ncues,
                                         const int32_t *label_off, const int32_t *nlabels, const int32_t *mirror, int S, int C, int Hm,

@@ -267,6 +267,8 @@ int launch_multiscale_unary_batch(int G, int K, int C, const float *const *score
                                   float *const *sum_out, hipStream_t stream);
 int launch_preprocess_ms_batch(int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H, const int32_t *W,
                                const int32_t *sizes, const float *mean, float *const *out, hipStream_t stream);
+int launch_preprocess_rect_batch(int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H, const int32_t *W,
+                                 const int32_t *oh, const int32_t *ow, const float *mean, float *const *out, hipStream_t stream);
 int launch_train_s_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *H,
                                const int32_t *W, const int32_t *cue_off, const int32_t *ncues, const int32_t *label_off,
                                const int32_t *nlabels, const int32_t *mirror, int S, int C, int Hm, int Wm, const float *mean,

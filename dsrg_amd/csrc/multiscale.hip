@@ -24,7 +24,7 @@ namespace dsrg {
 constexpr int kMsPix = 64;        // output pixels per workgroup
 constexpr int kMsThreads = 256;
 constexpr int kMsMaxScales = 8;
-constexpr int kMsMaxBatch = 16;   // images per batched launch (multiscale_unary_batch_kernel, preprocess_ms_batch_kernel)
+constexpr int kMsMaxBatch = 16;   // images per batched launch (multiscale_unary_batch_kernel, preprocess_rect_batch_kernel)
 
 struct MsArgs {
     const float *s[kMsMaxScales];  // (C, h_k, w_k) score maps

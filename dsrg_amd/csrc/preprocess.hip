@@ -1,12 +1,16 @@
-// Every network input of a group of test images in one launch: inference.preprocess (test-ms.py:68-81) for G images at K sizes.
-// Image g, (H_g, W_g, 3) RGB uint8, is zoomed to S_k x S_k for every k, reordered to BGR and has the mean subtracted; the results
-// are the slots g of K (Gcap, 3, S_k, S_k) f32 NCHW tensors: the batched inputs of the K forwards.  Slots g >= G are written as
-// zeros, so a padded tail group is deterministic.
+// Every network input of a group of test images in one launch: inference.preprocess (test-ms.py:68-81) for G images at K sizes, and
+// inference.preprocess_relative (test-ms-f.py:100-112) for G same-sized images at K relative scales.
+// Image g, (H_g, W_g, 3) RGB uint8, is zoomed to h_k x w_k for every k, reordered to BGR and has the mean subtracted; the results
+// are the slots g of K (Gcap, 3, h_k, w_k) f32 NCHW tensors: the batched inputs of the K forwards.  Slots g >= G are written as
+// zeros, so a padded tail group is deterministic.  dsrg_preprocess_ms_batch is the square case h_k = w_k = S_k of
+// dsrg_preprocess_rect_batch: one kernel and one launcher serve both.
 //
 // One thread owns one output pixel (its three channels) of one (scale, slot); blockIdx.x -> scale through per-scale block prefix
 // sums.  The zoom is the order-1 align-corners zoom stated at the top of multiscale.hip (torch's upsample_bilinear2d on float64
-// input, which is what inference._zoom runs): coordinate and two-tap blend in double, rounded once to f32; then the f32
-// subtraction of the mean.  At S_k == H_g == W_g the scale is 1, the weights are 1 and 0, and the pixel comes through exactly.
+// input, which is what inference._zoom runs): coordinate y * (H-1)/(h-1) (0 when h == 1; likewise x) and the two-tap blend
+// l0h * (l0w * v00 + l1w * v01) + l1h * (l0w * v10 + l1w * v11) in double, rounded once to f32; then the f32 subtraction of the
+// mean.  At h_k == H_g and w_k == W_g the scale is 1, the weights are 1 and 0, and the pixel comes through exactly.  The four
+// taps are loaded unconditionally from clamped indices.
 // -ffp-contract=off (Makefile) keeps every product and sum rounded on its own.  No atomics: results are bit-reproducible.
 #include <string.h>
 #include "common.h"
@@ -21,30 +25,30 @@ struct PpArgs {
     const unsigned char *im[kPpMaxBatch];
     int H[kPpMaxBatch], W[kPpMaxBatch];
     float *out[kPpMaxScales];
-    int S[kPpMaxScales];
+    int h[kPpMaxScales], w[kPpMaxScales];
     int blk0[kPpMaxScales + 1];       // first block of scale k (blk0[K] = the grid)
     float mean[3];                    // of the OUTPUT channels (B, G, R)
 };
 
-__global__ __launch_bounds__(kPpThreads) void preprocess_ms_batch_kernel(PpArgs a, int G, int Gcap, int K) {
+__global__ __launch_bounds__(kPpThreads) void preprocess_rect_batch_kernel(PpArgs a, int G, int Gcap, int K) {
     const int blk = (int)blockIdx.x;
     int k = 0;
     while (k + 1 < K && blk >= a.blk0[k + 1]) ++k;          // (uniform over the block)
-    const int S = a.S[k], SS = S * S;
-    const int idx = (blk - a.blk0[k]) * kPpThreads + (int)threadIdx.x;    // (slot, y, x) flattened: < Gcap * S * S < 2^31 / 3
-    if (idx >= Gcap * SS) return;
-    const int g = idx / SS, r = idx - g * SS;
-    const int y = r / S, x = r - y * S;
-    float *o = a.out[k] + (size_t)g * 3 * SS + r;
+    const int h = a.h[k], w = a.w[k], hw = h * w;
+    const int idx = (blk - a.blk0[k]) * kPpThreads + (int)threadIdx.x;    // (slot, y, x) flattened: < Gcap * h * w < 2^31 / 3
+    if (idx >= Gcap * hw) return;
+    const int g = idx / hw, r = idx - g * hw;
+    const int y = r / w, x = r - y * w;
+    float *o = a.out[k] + (size_t)g * 3 * hw + r;
     if (g >= G) {
         o[0] = 0.0f;
-        o[SS] = 0.0f;
-        o[2 * SS] = 0.0f;
+        o[hw] = 0.0f;
+        o[2 * hw] = 0.0f;
         return;
     }
     const int H = a.H[g], W = a.W[g];
-    const double sh = S > 1 ? (double)(H - 1) / (double)(S - 1) : 0.0;
-    const double sw = S > 1 ? (double)(W - 1) / (double)(S - 1) : 0.0;
+    const double sh = h > 1 ? (double)(H - 1) / (double)(h - 1) : 0.0;
+    const double sw = w > 1 ? (double)(W - 1) / (double)(w - 1) : 0.0;
     const double sy = sh * (double)y, sx = sw * (double)x;
     const int y0 = (int)sy, x0 = (int)sx;
     const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
@@ -57,46 +61,59 @@ __global__ __launch_bounds__(kPpThreads) void preprocess_ms_batch_kernel(PpArgs 
     for (int c = 0; c < 3; ++c) {                           // output channel c = input channel 2 - c (BGR)
         const double v00 = p00[2 - c], v01 = p01[2 - c], v10 = p10[2 - c], v11 = p11[2 - c];
         const float z = (float)(l0h * (l0w * v00 + l1w * v01) + l1h * (l0w * v10 + l1w * v11));
-        o[c * SS] = z - a.mean[c];
+        o[c * hw] = z - a.mean[c];
     }
 }
 
-int launch_preprocess_ms_batch(int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H, const int32_t *W,
-                               const int32_t *sizes, const float *mean, float *const *out, hipStream_t stream) {
-    if (G < 1 || G > kPpMaxBatch) return set_error(DSRG_ERR_INVALID, "preprocess batch: 1..%d images, got %d", kPpMaxBatch, G);
-    if (K < 1 || K > kPpMaxScales) return set_error(DSRG_ERR_INVALID, "preprocess batch: 1..%d sizes, got %d", kPpMaxScales, K);
-    if (Gcap < G) return set_error(DSRG_ERR_INVALID, "preprocess batch: capacity %d below the %d images", Gcap, G);
-    if (!images || !H || !W) return set_error(DSRG_ERR_INVALID, "preprocess batch: NULL image / image size array");
-    if (!sizes || !mean || !out) return set_error(DSRG_ERR_INVALID, "preprocess batch: NULL size / mean / output array");
+// `what` names the entry point in the messages; oh / ow: the K target heights / widths (the same array for the square case)
+static int launch_preprocess_batch(const char *what, int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H,
+                                   const int32_t *W, const int32_t *oh, const int32_t *ow, const float *mean, float *const *out,
+                                   hipStream_t stream) {
+    if (G < 1 || G > kPpMaxBatch) return set_error(DSRG_ERR_INVALID, "%s: 1..%d images, got %d", what, kPpMaxBatch, G);
+    if (K < 1 || K > kPpMaxScales) return set_error(DSRG_ERR_INVALID, "%s: 1..%d sizes, got %d", what, kPpMaxScales, K);
+    if (Gcap < G) return set_error(DSRG_ERR_INVALID, "%s: capacity %d below the %d images", what, Gcap, G);
+    if (!images || !H || !W) return set_error(DSRG_ERR_INVALID, "%s: NULL image / image size array", what);
+    if (!oh || !ow || !mean || !out) return set_error(DSRG_ERR_INVALID, "%s: NULL size / mean / output array", what);
     PpArgs a;
     memset(&a, 0, sizeof(a));
     for (int g = 0; g < G; ++g) {
-        if (!images[g]) return set_error(DSRG_ERR_INVALID, "preprocess batch: image %d is NULL", g);
-        if (H[g] < 1 || W[g] < 1) return set_error(DSRG_ERR_INVALID, "preprocess batch: image %d is %dx%d", g, H[g], W[g]);
+        if (!images[g]) return set_error(DSRG_ERR_INVALID, "%s: image %d is NULL", what, g);
+        if (H[g] < 1 || W[g] < 1) return set_error(DSRG_ERR_INVALID, "%s: image %d is %dx%d", what, g, H[g], W[g]);
         if ((long long)H[g] * W[g] * 3 >= (1LL << 31))
-            return set_error(DSRG_ERR_UNSUPPORTED, "preprocess batch: image %d holds >= 2^31 values", g);
+            return set_error(DSRG_ERR_UNSUPPORTED, "%s: image %d holds >= 2^31 values", what, g);
         a.im[g] = images[g];
         a.H[g] = H[g];
         a.W[g] = W[g];
     }
     long long blocks = 0;
     for (int k = 0; k < K; ++k) {
-        if (sizes[k] < 1) return set_error(DSRG_ERR_INVALID, "preprocess batch: size %d is %d", k, sizes[k]);
-        if (!out[k]) return set_error(DSRG_ERR_INVALID, "preprocess batch: output %d is NULL", k);
-        if ((uintptr_t)out[k] & 3) return set_error(DSRG_ERR_INVALID, "preprocess batch: output %d is not aligned to a float", k);
-        const long long n = (long long)Gcap * sizes[k] * sizes[k];
+        if (oh[k] < 1 || ow[k] < 1) return set_error(DSRG_ERR_INVALID, "%s: size %d is %dx%d", what, k, oh[k], ow[k]);
+        if (!out[k]) return set_error(DSRG_ERR_INVALID, "%s: output %d is NULL", what, k);
+        if ((uintptr_t)out[k] & 3) return set_error(DSRG_ERR_INVALID, "%s: output %d is not aligned to a float", what, k);
+        const long long n = (long long)Gcap * oh[k] * ow[k];
         if (n * 3 >= (1LL << 31))
-            return set_error(DSRG_ERR_UNSUPPORTED, "preprocess batch: output %d holds %lld >= 2^31 values", k, n * 3);
+            return set_error(DSRG_ERR_UNSUPPORTED, "%s: output %d holds %lld >= 2^31 values", what, k, n * 3);
         a.out[k] = out[k];
-        a.S[k] = sizes[k];
+        a.h[k] = oh[k];
+        a.w[k] = ow[k];
         a.blk0[k] = (int)blocks;
         blocks += (n + kPpThreads - 1) / kPpThreads;        // < 2^23 per scale
     }
     a.blk0[K] = (int)blocks;
     for (int c = 0; c < 3; ++c) a.mean[c] = mean[c];
-    hipLaunchKernelGGL(preprocess_ms_batch_kernel, dim3((unsigned)blocks), dim3(kPpThreads), 0, stream, a, G, Gcap, K);
+    hipLaunchKernelGGL(preprocess_rect_batch_kernel, dim3((unsigned)blocks), dim3(kPpThreads), 0, stream, a, G, Gcap, K);
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
+}
+
+int launch_preprocess_ms_batch(int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H, const int32_t *W,
+                               const int32_t *sizes, const float *mean, float *const *out, hipStream_t stream) {
+    return launch_preprocess_batch("preprocess batch", G, Gcap, K, images, H, W, sizes, sizes, mean, out, stream);
+}
+
+int launch_preprocess_rect_batch(int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H, const int32_t *W,
+                                 const int32_t *oh, const int32_t *ow, const float *mean, float *const *out, hipStream_t stream) {
+    return launch_preprocess_batch("preprocess rect batch", G, Gcap, K, images, H, W, oh, ow, mean, out, stream);
 }
 
 }  // namespace dsrg

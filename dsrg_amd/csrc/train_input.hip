@@ -1,5 +1,5 @@
 // The training batches of both stages, assembled on the device from ONE staging buffer of raw bytes that the host fills and
-// uploads with a single copy per batch: the training-side sibling of preprocess_ms_batch_kernel.  Per-image descriptors (byte
+// uploads with a single copy per batch: the training-side sibling of preprocess_rect_batch_kernel.  Per-image descriptors (byte
 // offsets into the staging buffer, sizes, counts) ride by value in the argument block, at most 32 images (~1 KB).
 //
 // train_s_input_kernel (stage 1): Caffe's ImageData layer (train-s.prototxt:3-22: read, cv::resize to S x S, mean) followed by

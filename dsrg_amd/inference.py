@@ -5,6 +5,7 @@ full-resolution dense CRF on log-probabilities, pseudo-label generation, and the
   predict_mask_ms       <-> training/tools/test-ms.py:84-111        (run.sh:6,10: pseudo labels / final test)
   preprocess_relative   <-> training/tools/test-ms-f.py:100-112
   predict_mask_ms_f     <-> training/tools/test-ms-f.py:115-142     (run.sh step 4: the final test at relative scales)
+  predict_masks_ms_f_many <-> the loop of test-ms-f.py:153-160 over the test list (same-sized images batched: plan_size_groups)
   predict_train_gt      <-> training/tools/generate_train_gt.py:78-106
   predict_train_gt_many <-> the loop of generate_train_gt.py:117-123 over train_aug (batched forwards, fused HIP tail)
   ConfusionMatrix       <-> training/tools/evaluate.py:17-68
@@ -258,6 +259,7 @@ def _crf_in_flight(pairs, device, in_flight, batch, ignore_below=None):
     pairs (the forwards) are produced on a forward stream of their own.  (image, unary, select) triples: the masks are restricted
     to each image's label list (crf.CRF_device_many), with ignore_below as DenseCRF.map takes it"""
     from .crf import CRF_device_many
+    from .streams import side_stream
     # the CRF workers come back from the library three times per image and need the interpreter lock for a few lines each time; the
     # caller's thread, busy issuing torch ops, would keep it for Python's default 5 ms switch interval — longer than a whole CRF
     import sys
@@ -265,7 +267,7 @@ def _crf_in_flight(pairs, device, in_flight, batch, ignore_below=None):
     sys.setswitchinterval(min(interval, 1e-4))
     # ... and the forwards go to a stream of their own: on the caller's (usually the null) stream they share a hardware queue with one of
     # the CRF workers' streams or not, depending on how many streams the process made before — 178 or 240 images/s from run to run
-    fstream = torch.cuda.Stream(device=device)
+    fstream = side_stream(device)
     caller = torch.cuda.current_stream(device)
     try:
         fstream.wait_stream(caller)
@@ -345,11 +347,131 @@ def predict_mask_ms_f(net, image, scales=(0.75, 1.0, 1.25), smooth=True, device=
     return out.cpu().numpy().astype(np.int64)
 
 
+def plan_size_groups(keys, G, window):
+    """the scheduler of the batched relative-scale test: collects same-keyed inputs (images keyed by their size) from a mixed
+    stream into groups of up to G.  keys: any iterable of hashable keys, consumed lazily one key at a time; a generator of lists
+    of input indices, ascending inside a list, every index in exactly one list.  For key i:
+      (a) i joins its key's bucket;
+      (b) a bucket that now holds G indices is emitted;
+      (c) while anything is pending and i + 1 - (the oldest pending index) >= window, the whole bucket that holds the oldest
+          pending index is emitted;
+      (d) at the end of the input the remaining buckets are emitted in the order of their oldest members.
+    So an input waits for at most window - 1 later inputs before its group is emitted, which bounds both the inputs held back
+    (fewer than `window`) and the results a consumer holds to restore the input order; key i + 1 is not pulled before the
+    groups due at key i were yielded.  window = 1 gives one input per group.  G outside 1..16 or window < 1: ValueError (at the
+    call, not at the first group)."""
+    G, window = int(G), int(window)
+    if not 1 <= G <= MAX_FORWARD_BATCH:
+        raise ValueError("groups hold 1..%d inputs, got %d" % (MAX_FORWARD_BATCH, G))
+    if window < 1:
+        raise ValueError("window must be at least 1, got %d" % window)
+
+    def groups():
+        buckets = {}                                        # key -> pending indices (fewer than `window` in all)
+        for i, key in enumerate(keys):
+            bucket = buckets.setdefault(key, [])
+            bucket.append(i)
+            if len(bucket) == G:
+                yield buckets.pop(key)
+            while buckets:
+                oldest = min(buckets, key=lambda k: buckets[k][0])
+                if i + 1 - buckets[oldest][0] < window:
+                    break
+                yield buckets.pop(oldest)
+        for bucket in sorted(buckets.values(), key=lambda b: b[0]):
+            yield bucket
+
+    return groups()
+
+
+def _relative_group_results(net, group, scales, device, forward, want):
+    """test-ms-f.py:121-134 for a group of n same-sized images (not padded): one dsrg_preprocess_rect_batch launch for all scales
+    (written straight into the static inputs of `forward`'s graphs where those exist; non-uint8 images take preprocess_relative
+    for their slot), len(scales) batch-n forwards and one dsrg_multiscale_unary_batch launch -> (the images on the device, the
+    `want` output of ops.multiscale_unary per image)"""
+    from . import ops
+    n = len(group)
+    H, W = group[0].shape[0], group[0].shape[1]
+    shapes = [(relative_size(H, s), relative_size(W, s)) for s in scales]
+    if any(h < 1 or w < 1 for h, w in shapes):
+        raise ValueError("a %d x %d image at the scales %s gives an input below one pixel: %s" % (H, W, tuple(scales), shapes))
+    arrays = [np.ascontiguousarray(np.asarray(im)) for im in group]
+    if all(a.dtype == np.uint8 for a in arrays):
+        dev_images = [torch.from_numpy(a).to(device) for a in arrays]
+        out = None
+        if isinstance(forward, GraphedForward):
+            out = [forward.static_input((n, 3, h, w)) for h, w in shapes]
+            if len(set(shapes)) != len(shapes) or any(o is None for o in out):
+                out = None                                  # (not captured yet: GraphedForward copies a fresh tensor in)
+        xs = ops.preprocess_rect_batch(dev_images, shapes, mean=MEAN_PIXEL, out=out)
+    else:
+        dev_images = [torch.as_tensor(a.astype('ubyte'), device=device) for a in arrays]
+        xs = [torch.cat([ops.preprocess_rect_batch([d], [hw], mean=MEAN_PIXEL)[0] if a.dtype == np.uint8
+                         else preprocess_relative(a, s, device) for a, d in zip(arrays, dev_images)])
+              for s, hw in zip(scales, shapes)]
+    scores = []
+    with _eval_mode(net):
+        for k, x in enumerate(xs):
+            sc = (forward or net)(x).float()
+            if forward is not None and shapes[k] in shapes[k + 1:]:
+                sc = sc.clone()                  # a graph's static output: the later replay of the same shape would overwrite it
+            scores.append(sc.contiguous())
+    return dev_images, ops.multiscale_unary_batch(scores, [(H, W)] * n, eps=0.00001, want=want)
+
+
 @torch.no_grad()
-def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda", forward=None, in_flight=3, batch=1, fused=True):
-    """predict_mask_ms_f (smooth) over many images, as predict_masks_ms_many does it for test-ms.py: a generator of (H,W) int64 masks
-    in order, the forwards of the next image running while the CRFs of the images before it are in flight.  Same masks as
-    predict_mask_ms_f image by image."""
+def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda", forward=None, in_flight=3, batch=1, fused=True,
+                            same_size_batch=1, window=64, smooth=True):
+    """predict_mask_ms_f over many images, as predict_masks_ms_many does it for test-ms.py: a generator of (H,W) int64 masks
+    in order, the forwards of the next image running while the CRFs of the images before it are in flight (smooth=False: the
+    arg-max, no CRF).  Same masks as predict_mask_ms_f image by image.
+
+    same_size_batch = G > 1 (2..16): the relative scales give every image SIZE its own input shapes, and a dataset holds few
+    sizes, so the images are keyed by (H, W) and collected by plan_size_groups(G, window) into groups of up to G same-sized
+    images.  A group of n images (never padded to G) is one dsrg_preprocess_rect_batch launch, len(scales) batch-n forwards (a
+    GraphedForward holds a graph per (n, size, scale) under its own capture_after / max_shapes policy) and one
+    dsrg_multiscale_unary_batch launch; its (image, unary) pairs reach the CRFs consecutively, so batch > 1 gives them one batched
+    CRF call.  Masks come back in input order through a reorder buffer: an image waits for at most window - 1 later images, so
+    fewer than `window` images and masks are held (window = 64 is a judgement, not a measurement).  A batch-n forward need not
+    round as a batch-1 forward does: the masks are predict_mask_ms_f's except where two labels all but tie, and there they
+    depend on the grouping (G, window and the order of the images).  A relative size below one pixel: ValueError before any
+    launch of that group.  These groups run the fused kernels only (fused=False: ValueError)."""
+    G = int(same_size_batch)
+    if G != 1:
+        if not fused:
+            raise ValueError("same_size_batch > 1 runs the fused kernels only")
+        held_images, order = {}, collections.deque()       # images waiting for their group; input indices in emission order
+
+        def keys():
+            for i, image in enumerate(images):
+                held_images[i] = image
+                yield (image.shape[0], image.shape[1])
+
+        groups = plan_size_groups(keys(), G, window)        # (G and window are checked here, before any stream or worker exists)
+
+        def results():
+            for idx in groups:
+                group = [held_images.pop(i) for i in idx]
+                dev_images, outs = _relative_group_results(net, group, scales, device, forward, "unary" if smooth else "argmax")
+                for i, im, out in zip(idx, dev_images, outs):
+                    order.append(i)
+                    yield (im, out) if smooth else out
+
+        if smooth:
+            masks = _crf_in_flight(results(), device, in_flight, batch)
+        else:
+            masks = (lab.cpu().numpy().astype(np.int64) for lab in results())
+        held_masks, nxt = {}, 0
+        for mask in masks:
+            held_masks[order.popleft()] = mask
+            while nxt in held_masks:
+                yield held_masks.pop(nxt)
+                nxt += 1
+        return
+    if not smooth:
+        for image in images:
+            yield predict_mask_ms_f(net, image, scales, False, device, forward, fused)
+        return
 
     def pairs():
         for image in images:

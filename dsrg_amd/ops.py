@@ -544,18 +544,15 @@ def train_gt_unary_batch(scores, shapes, eps=1e-5, want=("unary",), select=None,
     return [tuple(out[n][g] for n in names) for g in range(G)]
 
 
-def preprocess_ms_batch(images, sizes, capacity=None, mean=MEAN_PIXEL, out=None):
-    """inference.preprocess (test-ms.py:68-81) for a group of images at every size, in one launch (dsrg_preprocess_ms_batch).
-    images: G <= 16 contiguous (H_g, W_g, 3) RGB uint8 CUDA tensors (sizes may differ); sizes: the K <= 8 network input sizes S_k;
-    capacity >= G (default G): the batch size of the outputs, slots G.. are written as zeros.  Returns a list of K
-    (capacity, 3, S_k, S_k) float32 tensors, BGR, mean-subtracted: the inputs of K batched forwards.  out: K existing contiguous
-    float32 CUDA tensors of those shapes to write into (the static inputs of captured graphs, for one) and return.  Runs on
-    torch's current stream."""
+def _preprocess_group(images, out_shapes, capacity, mean, out):
+    """the shared front end of preprocess_ms_batch / preprocess_rect_batch: checks, output tensors and the launch's host arrays
+    -> (G, capacity, K, image pointers, H, W, mean, output pointers, outputs)"""
     images = list(images)
-    sizes = [int(s) for s in sizes]
-    G, K = len(images), len(sizes)
+    G, K = len(images), len(out_shapes)
     if G < 1 or K < 1:
         raise ValueError("no images / no sizes")
+    if any(h < 1 or w < 1 for h, w in out_shapes):
+        raise ValueError("every output size must be at least 1, got %s" % (out_shapes,))
     for g, im in enumerate(images):
         if not (torch.is_tensor(im) and im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous() and im.dim() == 3
                 and im.shape[2] == 3):
@@ -567,21 +564,46 @@ def preprocess_ms_batch(images, sizes, capacity=None, mean=MEAN_PIXEL, out=None)
         raise ValueError("mean must hold 3 values")
     dev = images[0].device
     if out is None:
-        out = [torch.empty((cap, 3, S, S), dtype=torch.float32, device=dev) for S in sizes]
+        out = [torch.empty((cap, 3, h, w), dtype=torch.float32, device=dev) for h, w in out_shapes]
     else:
         out = list(out)
         if len(out) != K:
             raise ValueError("out must hold one tensor per size")
-        for k, (o, S) in enumerate(zip(out, sizes)):
+        for k, (o, (h, w)) in enumerate(zip(out, out_shapes)):
             _f32c(o, "out[%d]" % k)
-            if tuple(o.shape) != (cap, 3, S, S):
-                raise ValueError("out[%d] must be %s, got %s" % (k, (cap, 3, S, S), tuple(o.shape)))
-    ims = (ctypes.c_void_p * G)(*[im.data_ptr() for im in images])
-    Hs = (ctypes.c_int32 * G)(*[im.shape[0] for im in images])
-    Ws = (ctypes.c_int32 * G)(*[im.shape[1] for im in images])
-    check(_lib.lib().dsrg_preprocess_ms_batch(G, cap, K, ims, Hs, Ws, (ctypes.c_int32 * K)(*sizes),
-                                              (ctypes.c_float * 3)(*[float(m) for m in mean]),
-                                              (ctypes.c_void_p * K)(*[o.data_ptr() for o in out]), _stream()))
+            if tuple(o.shape) != (cap, 3, h, w):
+                raise ValueError("out[%d] must be %s, got %s" % (k, (cap, 3, h, w), tuple(o.shape)))
+    return (G, cap, K, (ctypes.c_void_p * G)(*[im.data_ptr() for im in images]), (ctypes.c_int32 * G)(*[im.shape[0] for im in images]),
+            (ctypes.c_int32 * G)(*[im.shape[1] for im in images]), (ctypes.c_float * 3)(*[float(m) for m in mean]),
+            (ctypes.c_void_p * K)(*[o.data_ptr() for o in out]), out)
+
+
+def preprocess_ms_batch(images, sizes, capacity=None, mean=MEAN_PIXEL, out=None):
+    """inference.preprocess (test-ms.py:68-81) for a group of images at every size, in one launch (dsrg_preprocess_ms_batch).
+    images: G <= 16 contiguous (H_g, W_g, 3) RGB uint8 CUDA tensors (sizes may differ); sizes: the K <= 8 network input sizes S_k;
+    capacity >= G (default G): the batch size of the outputs, slots G.. are written as zeros.  Returns a list of K
+    (capacity, 3, S_k, S_k) float32 tensors, BGR, mean-subtracted: the inputs of K batched forwards.  out: K existing contiguous
+    float32 CUDA tensors of those shapes to write into (the static inputs of captured graphs, for one) and return.  Runs on
+    torch's current stream."""
+    sizes = [int(s) for s in sizes]
+    G, cap, K, ims, Hs, Ws, mean3, optrs, out = _preprocess_group(images, [(S, S) for S in sizes], capacity, mean, out)
+    check(_lib.lib().dsrg_preprocess_ms_batch(G, cap, K, ims, Hs, Ws, (ctypes.c_int32 * K)(*sizes), mean3, optrs, _stream()))
+    return out
+
+
+def preprocess_rect_batch(images, out_shapes, capacity=None, mean=MEAN_PIXEL, out=None):
+    """preprocess_ms_batch with a target (h_k, w_k) per scale, in one launch (dsrg_preprocess_rect_batch): what
+    inference.preprocess_relative (test-ms-f.py:100-112) makes of a group of same-sized images at every relative scale.  images: G
+    <= 16 contiguous (H_g, W_g, 3) RGB uint8 CUDA tensors; out_shapes: the K <= 8 targets (h_k, w_k); capacity, mean, out as
+    there.  Returns a list of K (capacity, 3, h_k, w_k) float32 tensors, BGR, mean-subtracted; with h_k = w_k they are
+    preprocess_ms_batch's bit for bit.  Runs on torch's current stream."""
+    try:
+        out_shapes = [(int(h), int(w)) for h, w in out_shapes]
+    except TypeError:
+        raise ValueError("out_shapes must hold (h, w) pairs")
+    G, cap, K, ims, Hs, Ws, mean3, optrs, out = _preprocess_group(images, out_shapes, capacity, mean, out)
+    check(_lib.lib().dsrg_preprocess_rect_batch(G, cap, K, ims, Hs, Ws, (ctypes.c_int32 * K)(*[h for h, _ in out_shapes]),
+                                                (ctypes.c_int32 * K)(*[w for _, w in out_shapes]), mean3, optrs, _stream()))
     return out
 
 

@@ -13,7 +13,8 @@ ResNet-101 of the stage-2 trainer, run through resnet_test.ResNetTestNet: fused 
 precision); forwards replay from captured HIP graphs (inference.GraphedForward, bounded for the relative scales) while the
 CRFs of earlier images are in flight (inference.predict_masks_ms_many / predict_masks_ms_f_many).  --mode ms --forward-batch N
 takes the images N at a time through batch-N forwards (the absolute sizes are the same for every image); so does --mode gt
-(inference.predict_train_gt_many).
+(inference.predict_train_gt_many).  --mode ms-f --same-size-batch N collects same-sized images (up to N, out of a window of
+--window images) into batch-n forwards (inference.plan_size_groups); the masks are still written per image, in input order.
 """
 import argparse
 import os
@@ -43,6 +44,10 @@ def parse_args(argv=None):
     p.add_argument("--max-graphs", type=int, default=12, help="ms-f: captured forward graphs kept (least recently used dropped)")
     p.add_argument("--forward-batch", type=int, default=1,
                    help="ms, gt: images per batched forward (1..16; default 1: one image per forward)")
+    p.add_argument("--same-size-batch", type=int, default=1,
+                   help="ms-f: same-sized images per batched forward (1..16; default 1: one image per forward)")
+    p.add_argument("--window", type=int, default=64,
+                   help="ms-f with --same-size-batch: an image waits for at most N - 1 later images for its group (default 64)")
     a = p.parse_args(argv)
     if a.mode == "gt":
         if not a.cues:
@@ -55,6 +60,12 @@ def parse_args(argv=None):
         p.error("--forward-batch is for --mode ms only: the relative scales of ms-f give every image size its own input shapes")
     if not 1 <= a.forward_batch <= 16:
         p.error("--forward-batch must be 1..16")
+    if a.mode != "ms-f" and (a.same_size_batch != 1 or a.window != 64):
+        p.error("--same-size-batch and --window are for --mode ms-f only")
+    if not 1 <= a.same_size_batch <= 16:
+        p.error("--same-size-batch must be 1..16")
+    if a.window < 1:
+        p.error("--window must be at least 1")
     return a
 
 
@@ -133,6 +144,11 @@ def main(argv=None):
         if a.mode == "gt":
             masks = I.predict_train_gt_many(net, zip(images, gt_labels), smooth=a.smooth, size=scales[0], device=dev, forward=fwd,
                                             in_flight=a.in_flight, forward_batch=a.forward_batch)
+        elif a.mode == "ms-f" and a.same_size_batch > 1:
+            from .crf import MAX_BATCH
+            masks = I.predict_masks_ms_f_many(net, images, scales=scales, device=dev, forward=fwd, in_flight=a.in_flight,
+                                              batch=min(a.same_size_batch, MAX_BATCH), same_size_batch=a.same_size_batch,
+                                              window=a.window, smooth=a.smooth)
         elif a.smooth:
             if a.mode == "ms":
                 masks = I.predict_masks_ms_many(net, images, sizes=scales, device=dev, forward=fwd, in_flight=a.in_flight,

@@ -314,6 +314,18 @@ int dsrg_train_gt_unary_batch(int G, int C, const float *scores_dev, int h, int 
 int dsrg_preprocess_ms_batch(int G, int capacity, int K, const unsigned char *const *images_dev, const int32_t *H_host,
                              const int32_t *W_host, const int32_t *sizes_host, const float *mean_host, float *const *out_dev,
                              void *stream);
+/* dsrg_preprocess_ms_batch with a target (h_k, w_k) per scale instead of S_k x S_k: the network inputs of a group of SAME-SIZED
+ * test images at K relative scales in one launch (training/tools/test-ms-f.py:100-112 for G images; the images' sizes may
+ * differ here too).  out_h_host / out_w_host: the K target heights / widths, out_dev a HOST array of K device pointers to
+ * (capacity, 3, h_k, w_k) f32 NCHW tensors.  Slot g < G of output k is image g zoomed to h_k x w_k: coordinate y*(H-1)/(h-1) (0
+ * when h == 1), likewise x; the two-tap blend l0h*(l0w*v00 + l1w*v01) + l1h*(l0w*v10 + l1w*v11) in double, rounded once to f32;
+ * BGR order; minus the mean (in f32).  Slots G..capacity-1 are written as zeros.  With h_k = w_k = S_k the results equal
+ * dsrg_preprocess_ms_batch's bit for bit (one kernel serves both).  1 <= G <= 16, G <= capacity, 1 <= K <= 8, all sizes >= 1,
+ * H_g*W_g*3 < 2^31, capacity*3*h_k*w_k < 2^31, outputs aligned to 4 bytes; every argument is checked before the first device
+ * call.  Nothing is allocated.  Stream-ordered, no host synchronisation, no handle; bit-reproducible (no atomics). */
+int dsrg_preprocess_rect_batch(int G, int capacity, int K, const unsigned char *const *images_dev, const int32_t *H_host,
+                               const int32_t *W_host, const int32_t *out_h_host, const int32_t *out_w_host, const float *mean_host,
+                               float *const *out_dev, void *stream);
 /* The stage-1 training batch in one launch: Caffe's ImageData layer (training/experiment/seed_mc/train-s.prototxt:3-22: read,
  * cv::resize to S x S, mean 104/117/123) followed by AnnotationLayer (pylayers/pylayers/pylayers.py:346-387), for B images.
  * stage_dev: ONE device buffer of stage_bytes raw bytes (uploaded by the caller with one copy per batch); the HOST arrays
