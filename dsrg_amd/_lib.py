@@ -58,6 +58,9 @@ SIGNATURES = {
     "dsrg_crf_npixels": (_i, [_vp]),
     "dsrg_crf_nlabels": (_i, [_vp]),
     "dsrg_crf_lattice_size": (_i, [_vp, _i]),
+    "dsrg_crf_lattice_dump": (_i, [_vp, _i, _i, ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _vp, _vp]),
+    "dsrg_crf_lattice_norm": (_i, [_vp, _i, _i, _vp]),
+    "dsrg_crf_filter_once": (_i, [_vp, _i, _i, _vp, _vp]),
     "dsrg_crf_profile_start": (_i, [_vp, _i]),
     "dsrg_crf_profile_stop": (_i, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]),
     "dsrg_ctx_create": (_i, [_i, _i, _i, _i, ctypes.POINTER(_vp)]),

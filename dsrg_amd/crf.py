@@ -141,6 +141,57 @@ class DenseCRF(object):
     def lattice_size(self, k):
         return _lib.lib().dsrg_crf_lattice_size(self._h, int(k))
 
+    # introspection (tests) of an object on the global-memory path; image b of a batched object
+
+    def _image_pixels(self):
+        return self.npixels() // (self._nimages or 1)
+
+    def lattice_dump(self, kind, b=0):
+        """One image's lattice in the reference's own form: kind 0 = Gaussian, 1 = bilateral.
+        -> dict(M, keys (M,d) int16, vid (N,d+1) int32, bary (N,d+1) f32, n1 / n2 (d+1,M) int32 with -1 = none); ids are local
+        to the image, in first-occurrence order."""
+        d, N = (2 if kind == 0 else 5), self._image_pixels()
+        m = ctypes.c_int32(0)
+        L = _lib.lib()
+        check(L.dsrg_crf_lattice_dump(self._h, int(kind), int(b), ctypes.byref(m), None, None, None, None, None))
+        M = m.value
+        keys = np.empty((M, d), np.int16)
+        vid = np.empty((N, d + 1), np.int32)
+        bary = np.empty((N, d + 1), np.float32)
+        n1 = np.empty((d + 1, M), np.int32)
+        n2 = np.empty((d + 1, M), np.int32)
+        check(L.dsrg_crf_lattice_dump(self._h, int(kind), int(b), ctypes.byref(m), keys.ctypes.data, vid.ctypes.data,
+                                      bary.ctypes.data, n1.ctypes.data, n2.ctypes.data))
+        return dict(M=M, keys=keys, vid=vid, bary=bary, n1=n1, n2=n2)
+
+    def lattice_norm(self, kind, b=0):
+        """norm = 1/sqrt(K 1 + 1e-20) of one image's lattice (pairwise.cpp:44,54-57), (N,) float32 numpy"""
+        out = np.empty(self._image_pixels(), np.float32)
+        check(_lib.lib().dsrg_crf_lattice_norm(self._h, int(kind), int(b), out.ctypes.data))
+        return out
+
+    def filter_once(self, kind, x, b=0):
+        """one application of the normalised kernel `kind` to image b's field x (N, nlabels), label-fastest: DenseKernel::filter
+        (pairwise.cpp:63-80) through the launches of one mean-field iteration.  numpy in, numpy out; a CUDA tensor in, a CUDA
+        tensor out."""
+        N, C = self._image_pixels(), self.nlabels()
+        if _is_cuda_tensor(x):
+            import torch
+            x = x.to(torch.float32).contiguous()
+            if x.numel() != N * C:
+                raise ValueError("x must hold npixels*nlabels floats of one image")
+            out = torch.empty_like(x)
+            torch.cuda.current_stream(x.device).synchronize()
+            check(_lib.lib().dsrg_crf_filter_once(self._h, int(kind), int(b), ctypes.c_void_p(x.data_ptr()),
+                                                  ctypes.c_void_p(out.data_ptr())))
+            return out
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.size != N * C:
+            raise ValueError("x must hold npixels*nlabels floats of one image")
+        out = np.empty_like(x)
+        check(_lib.lib().dsrg_crf_filter_once(self._h, int(kind), int(b), x.ctypes.data, out.ctypes.data))
+        return out
+
     def set_stream(self, stream, asynchronous=False):
         """run this object's copies and kernels on `stream` (a torch.cuda.Stream, a raw hipStream_t or None = the null
         stream); asynchronous: the calls enqueue and return (device tensors only), results are final after synchronize()"""

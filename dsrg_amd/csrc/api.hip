@@ -874,6 +874,10 @@ int large_crf_read_q(LargeCrf *c, float *out_host);
 int large_crf_read_map(LargeCrf *c, int32_t *labels_host);
 int large_crf_read_map_select(LargeCrf *c, const CrfSelArgs &sel, int32_t *labels_host);
 int large_crf_lattice_size(LargeCrf *c, int k);
+int large_crf_lattice_dump(LargeCrf *c, const dsrg_crf_params *prm, int kind, int b, int32_t *m_host, int16_t *keys_host,
+                           int32_t *vid_host, float *bary_host, int32_t *n1_host, int32_t *n2_host);
+int large_crf_lattice_norm(LargeCrf *c, const dsrg_crf_params *prm, int kind, int b, float *norm_host);
+int large_crf_filter_once(LargeCrf *c, const dsrg_crf_params *prm, int kind, int b, const float *x, float *out);
 Profiler *large_crf_profiler(LargeCrf *c);
 void large_crf_set_stream(LargeCrf *c, hipStream_t s, bool async);
 }  // namespace dsrg
@@ -1113,6 +1117,32 @@ extern "C" int dsrg_crf_profile_start(dsrg_crf_t h, int max_launches) {
 extern "C" int dsrg_crf_profile_stop(dsrg_crf_t h, double *total_ms, int32_t *launches) {
     if (!h || !total_ms || !launches) return set_error(DSRG_ERR_INVALID, "bad argument");
     return prof_stop(h->large ? *large_crf_profiler(h->large) : h->ctx->prof, total_ms, launches);
+}
+// introspection (tests) of an object on the global-memory path: dsrg_ctx_lattice_dump / _norm / _filter_once for image b of a
+// dsrg_crf_t.  The lattices are those of the last add_pairwise_energy (built here if no inference has run since).
+static int crf_large_introspect(dsrg_crf_t h, int kind, const char *who) {
+    if (!h || (kind != 0 && kind != 1)) return set_error(DSRG_ERR_INVALID, "%s: bad argument", who);
+    if (!h->large)
+        return set_error(DSRG_ERR_UNSUPPORTED, "%s: this object runs on the LDS-resident path (use the dsrg_ctx_* introspection, or "
+                         "dsrg_crf_create_batch for the global-memory path at this size)", who);
+    if (!h->have_pairwise) return set_error(DSRG_ERR_INVALID, "%s: add_pairwise_energy must be called first", who);
+    return DSRG_OK;
+}
+extern "C" int dsrg_crf_lattice_dump(dsrg_crf_t h, int kind, int b, int32_t *m_host, int16_t *keys_host, int32_t *vid_host,
+                                     float *bary_host, int32_t *n1_host, int32_t *n2_host) {
+    if (int rc = crf_large_introspect(h, kind, "crf lattice dump")) return rc;
+    if (!m_host) return set_error(DSRG_ERR_INVALID, "crf lattice dump: NULL argument");
+    return large_crf_lattice_dump(h->large, &h->prm, kind, b, m_host, keys_host, vid_host, bary_host, n1_host, n2_host);
+}
+extern "C" int dsrg_crf_lattice_norm(dsrg_crf_t h, int kind, int b, float *norm_host) {
+    if (int rc = crf_large_introspect(h, kind, "crf lattice norm")) return rc;
+    if (!norm_host) return set_error(DSRG_ERR_INVALID, "crf lattice norm: NULL argument");
+    return large_crf_lattice_norm(h->large, &h->prm, kind, b, norm_host);
+}
+extern "C" int dsrg_crf_filter_once(dsrg_crf_t h, int kind, int b, const float *x, float *out) {
+    if (int rc = crf_large_introspect(h, kind, "crf filter once")) return rc;
+    if (!x || !out) return set_error(DSRG_ERR_INVALID, "crf filter once: NULL argument");
+    return large_crf_filter_once(h->large, &h->prm, kind, b, x, out);
 }
 extern "C" int dsrg_crf_lattice_size(dsrg_crf_t h, int k) {
     if (h && h->large && k >= 0 && k <= 1) return large_crf_lattice_size(h->large, k);

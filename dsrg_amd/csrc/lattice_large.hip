@@ -385,20 +385,33 @@ __device__ __forceinline__ float lg_splat_segment(const LargeLattice &L, uint32_
 // unit `u` of a lattice's splat: segment u < T, or the zero row (u == T).  A vertex with ONE segment (rows of up to kSplatSeg
 // entries: the reference's accumulation order, exactly) writes its value; longer rows write per-segment partial sums that
 // lg_combine_kernel adds up in segment order (deterministic; differs from the strictly sequential sum by reassociation only).
+// WIDE: more than 64 padded labels.  A lane group is at most a wave, so lane l then also walks channels l + 64, ...; every channel's
+// sum keeps its order.  Up to 64 padded labels (WIDE = false) the loops below are gone and the code is the one-channel code.
+template <bool WIDE>
 __device__ __forceinline__ void lg_splat_unit(const LargeLattice &L, size_t u, int lane, int CP, const float *__restrict__ in,
                                               float *__restrict__ val, float *__restrict__ part) {
     const int M = L.M[0], T = L.M[1];
-    if (u == (size_t)T) { val[(size_t)M * CP + lane] = 0.0f; return; }
+    if (u == (size_t)T) {
+        int ch = lane;
+        do { val[(size_t)M * CP + ch] = 0.0f; ch += 64; } while (WIDE && ch < CP);
+        return;
+    }
     const uint32_t v = L.seg_v[u];
     const uint32_t s0 = L.seg_start[v], K = L.seg_start[v + 1] - s0;
     const uint32_t r0 = L.row_start[v], r1 = L.row_start[v + 1];
     const uint32_t p0 = r0 + ((uint32_t)u - s0) * (uint32_t)L.seg_len, p1 = min(p0 + (uint32_t)L.seg_len, r1);
-    const float sum = lg_splat_segment(L, p0, p1, lane, CP, in);
-    if (K == 1u) val[(size_t)v * CP + lane] = sum; else part[u * CP + lane] = sum;
+    int ch = lane;
+    do {
+        const float sum = lg_splat_segment(L, p0, p1, ch, CP, in);
+        if (K == 1u) val[(size_t)v * CP + ch] = sum; else part[u * CP + ch] = sum;
+        ch += 64;
+    } while (WIDE && ch < CP);
 }
 // One group of LPV lanes (the power of two >= CP, at most a wave) per vertex: with 21 labels padded to 24 a whole wave
 // per vertex would idle 40 of its 64 lanes.  No cross-lane traffic, so the groups of a wave are independent.
 // vertex groups [0, Mb] belong to the bilateral lattice (row Mb = its zero row), the following Mg+1 to the Gaussian one
+// (WIDE = false, up to 64 padded labels, is the kernel of every VOC-sized call; WIDE = true serves 65 .. 96 labels)
+template <bool WIDE>
 __global__ __launch_bounds__(256) void lg_splat2_kernel(LargeLattice Lb, LargeLattice Lg, int CP, int lpv_shift,
                                                          const float *__restrict__ in_b, const float *__restrict__ in_g,
                                                          float *__restrict__ val_b, float *__restrict__ val_g,
@@ -415,15 +428,16 @@ __global__ __launch_bounds__(256) void lg_splat2_kernel(LargeLattice Lb, LargeLa
         const long long f = xcd_strip_first(x | (sl << 3), (size_t)Tb + 1, upb, &end);
         const size_t u = (size_t)f + (threadIdx.x >> lpv_shift);
         if (f < 0 || u >= end) return;
-        lg_splat_unit(Lb, u, lane, CP, in_b, val_b, part_b);
+        lg_splat_unit<WIDE>(Lb, u, lane, CP, in_b, val_b, part_b);
     } else {
         const long long f = xcd_strip_first(x | ((sl - nb_b) << 3), (size_t)Tg + 1, upb, &end);
         const size_t u = (size_t)f + (threadIdx.x >> lpv_shift);
         if (f < 0 || u >= end) return;
-        lg_splat_unit(Lg, u, lane, CP, in_g, val_g, part_g);
+        lg_splat_unit<WIDE>(Lg, u, lane, CP, in_g, val_g, part_g);
     }
 }
 // the vertices whose row was cut into several segments: value = ((p_0 + p_1) + p_2) + ...
+template <bool WIDE>
 __global__ __launch_bounds__(256) void lg_combine_kernel(LargeLattice Lb, LargeLattice Lg, int CP, int lpv_shift,
                                                           float *__restrict__ val_b, float *__restrict__ val_g,
                                                           const float *__restrict__ part_b, const float *__restrict__ part_g) {
@@ -437,9 +451,13 @@ __global__ __launch_bounds__(256) void lg_combine_kernel(LargeLattice Lb, LargeL
     if (i >= (size_t)nb) { i -= nb; if (i >= (size_t)ng) return; L = &Lg; val = val_g; part = part_g; }
     const uint32_t v = L->multi_v[i];
     const uint32_t s0 = L->seg_start[v], s1 = L->seg_start[v + 1];
-    float acc = part[(size_t)s0 * CP + lane];
-    for (uint32_t q = s0 + 1; q < s1; q++) acc = acc + part[(size_t)q * CP + lane];
-    val[(size_t)v * CP + lane] = acc;
+    int ch = lane;                                           // (WIDE: channels beyond a wave's 64 lanes, as lg_splat_unit)
+    do {
+        float acc = part[(size_t)s0 * CP + ch];
+        for (uint32_t q = s0 + 1; q < s1; q++) acc = acc + part[(size_t)q * CP + ch];
+        val[(size_t)v * CP + ch] = acc;
+        ch += 64;
+    } while (WIDE && ch < CP);
 }
 // seq: <= 2 label planes take Permutohedral::seqCompute's arithmetic (permutohedral.cpp:476-527 via :600-601): the blur is
 // summed in double (the literal 0.5) and the slice multiplies (w * value) * alpha
@@ -978,8 +996,9 @@ int large_crf_set_image(LargeCrf *c, const unsigned char *im) {
     return DSRG_OK;
 }
 
-// DenseCRF::inference on the large path; q ends up in c->q ([N][CP])
-int large_crf_infer(LargeCrf *c, const dsrg_crf_params *prm, int n_iters) {
+// the lattices of the current image and kernel widths (built on the first call after add_pairwise_energy) and the value /
+// partial-sum buffers of their sizes
+static int large_prepare(LargeCrf *c, const dsrg_crf_params *prm) {
     hipStream_t s = c->stream;
     LatticeFeat Fg, Fb;
     lattice_feat_init(Fg, 2, c->W, c->H, prm->theta_gamma_x, prm->theta_gamma_y, 1.f, 1.f, 1.f);
@@ -997,7 +1016,7 @@ int large_crf_infer(LargeCrf *c, const dsrg_crf_params *prm, int n_iters) {
         c->built_for = *prm;
         c->lattices_valid = true;
     }
-    const int Mb = c->Lb.M_host, Mg = c->Lg.M_host, CP = c->CP, CP4 = CP / 4;
+    const int Mb = c->Lb.M_host, Mg = c->Lg.M_host, CP = c->CP;
     const size_t need = (size_t)Mb + 1 + (size_t)Mg + 1;
     if (need > c->val_rows) {
         if (c->val_a) (void)hipFree(c->val_a);
@@ -1009,7 +1028,7 @@ int large_crf_infer(LargeCrf *c, const dsrg_crf_params *prm, int n_iters) {
         if (e != hipSuccess) return set_error(DSRG_ERR_NOMEM, "hipMalloc of lattice values failed: %s", hipGetErrorString(e));
         c->val_rows = need;
     }
-    const int Tb = c->Lb.T_host, Tg = c->Lg.T_host, nmulti = c->Lb.nmulti_host + c->Lg.nmulti_host;
+    const int Tb = c->Lb.T_host, Tg = c->Lg.T_host;
     const size_t need_part = (size_t)Tb + (size_t)Tg + 1;
     if (need_part > c->part_rows) {
         if (c->part) (void)hipFree(c->part);
@@ -1018,33 +1037,58 @@ int large_crf_infer(LargeCrf *c, const dsrg_crf_params *prm, int n_iters) {
         if (e != hipSuccess) return set_error(DSRG_ERR_NOMEM, "hipMalloc of splat partials failed: %s", hipGetErrorString(e));
         c->part_rows = need_part;
     }
-    const int T = 256;
-    const size_t upd_lds = sizeof(float) * 256 * (size_t)(CP + 1);
-    hipLaunchKernelGGL(lg_update_kernel, dim3(blocks_for(c->N, T)), dim3(T), upd_lds, s, c->N, c->C, CP, c->neg_unary,
-                       nullptr, nullptr, 0, c->q, c->Lb.norm, c->Lg.norm, c->qn_b, c->qn_g);
+    return DSRG_OK;
+}
+
+// splat (with the combine of the rows cut into segments) and blur of both lattices from the splat inputs qn_b / qn_g: the
+// launches of one mean-field iteration up to its slice.  After 6 swaps the bilateral result is back in val_a; the Gaussian one
+// stopped after 3 swaps, in val_b (rows from g_off on).
+static int large_splat_blur(LargeCrf *c) {
+    hipStream_t s = c->stream;
+    const int Mb = c->Lb.M_host, Mg = c->Lg.M_host, CP = c->CP, CP4 = CP / 4;
+    const int Tb = c->Lb.T_host, Tg = c->Lg.T_host, nmulti = c->Lb.nmulti_host + c->Lg.nmulti_host;
     int lpv_shift = 3;
     while ((1 << lpv_shift) < CP && lpv_shift < 6) lpv_shift++;
     const size_t g_off = ((size_t)Mb + 1) * CP;                          // Gaussian rows follow the bilateral ones
+    const bool timed = c->prof.active && c->prof.used < c->prof.cap;      // the dominant kernel of this path (dsrg_crf_profile_*)
+    if (timed) DSRG_HIP_CHECK(hipEventRecord(c->prof.start[c->prof.used], s));
+    const bool wide = CP > 64;                                            // lane groups walk two channels each (lg_splat_unit)
+    hipLaunchKernelGGL(wide ? lg_splat2_kernel<true> : lg_splat2_kernel<false>,
+                       dim3(xcd_strip_blocks((size_t)Tb + 1, 256 >> lpv_shift) + xcd_strip_blocks((size_t)Tg + 1, 256 >> lpv_shift)),
+                       dim3(256), 0, s, c->Lb, c->Lg, CP, lpv_shift, c->qn_b, c->qn_g, c->val_a, c->val_a + g_off, c->part,
+                       c->part + (size_t)Tb * CP);
+    if (nmulti > 0)
+        hipLaunchKernelGGL(wide ? lg_combine_kernel<true> : lg_combine_kernel<false>, dim3(blocks_for((size_t)nmulti, 256 >> lpv_shift)),
+                           dim3(256), 0, s, c->Lb, c->Lg, CP, lpv_shift, c->val_a, c->val_a + g_off, c->part, c->part + (size_t)Tb * CP);
+    if (timed) { DSRG_HIP_CHECK(hipEventRecord(c->prof.stop[c->prof.used], s)); c->prof.used++; }
+    float *a = c->val_a, *b = c->val_b;
+    for (int j = 0; j < 6; j++) {
+        const unsigned rows_pb = 256u / (unsigned)CP4;
+        const unsigned nblk = xcd_strip_blocks((size_t)Mb + 1, rows_pb) + (j < 3 ? xcd_strip_blocks((size_t)Mg + 1, rows_pb) : 0u);
+        hipLaunchKernelGGL(lg_blur2_kernel, dim3(nblk), dim3(256), 0, s, c->Lb, c->Lg, CP4, j,
+                           c->C <= 2 ? 1 : 0, (const float4 *)a, (float4 *)b, (const float4 *)(a + g_off), (float4 *)(b + g_off));
+        float *t = a; a = b; b = t;
+    }
+    return DSRG_OK;
+}
+
+// DenseCRF::inference on the large path; q ends up in c->q ([N][CP])
+int large_crf_infer(LargeCrf *c, const dsrg_crf_params *prm, int n_iters) {
+    if (int rc = large_prepare(c, prm)) return rc;
+    hipStream_t s = c->stream;
+    const int Mb = c->Lb.M_host, CP = c->CP;
+    const int T = 256;
+    // 256 pixel rows of CP + 1 floats: above the 64 KiB default from 61 labels on (CP = 64: 66 560 B; CP = 96: 99 328 B)
+    const size_t upd_lds = sizeof(float) * 256 * (size_t)(CP + 1);
+    if (upd_lds > 64 * 1024) {
+        static LdsGrant upd_grant;
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&lg_update_kernel), upd_lds, upd_grant)) return rc;
+    }
+    hipLaunchKernelGGL(lg_update_kernel, dim3(blocks_for(c->N, T)), dim3(T), upd_lds, s, c->N, c->C, CP, c->neg_unary,
+                       nullptr, nullptr, 0, c->q, c->Lb.norm, c->Lg.norm, c->qn_b, c->qn_g);
+    const size_t g_off = ((size_t)Mb + 1) * CP;                          // Gaussian rows follow the bilateral ones
     for (int it = 0; it < n_iters; it++) {
-        const bool timed = c->prof.active && c->prof.used < c->prof.cap;      // the dominant kernel of this path (dsrg_crf_profile_*)
-        if (timed) DSRG_HIP_CHECK(hipEventRecord(c->prof.start[c->prof.used], s));
-        hipLaunchKernelGGL(lg_splat2_kernel,
-                           dim3(xcd_strip_blocks((size_t)Tb + 1, 256 >> lpv_shift) + xcd_strip_blocks((size_t)Tg + 1, 256 >> lpv_shift)),
-                           dim3(256), 0, s, c->Lb, c->Lg, CP, lpv_shift, c->qn_b, c->qn_g, c->val_a, c->val_a + g_off, c->part,
-                           c->part + (size_t)Tb * CP);
-        if (nmulti > 0)
-            hipLaunchKernelGGL(lg_combine_kernel, dim3(blocks_for((size_t)nmulti, 256 >> lpv_shift)), dim3(256), 0, s, c->Lb, c->Lg, CP,
-                               lpv_shift, c->val_a, c->val_a + g_off, c->part, c->part + (size_t)Tb * CP);
-        if (timed) { DSRG_HIP_CHECK(hipEventRecord(c->prof.stop[c->prof.used], s)); c->prof.used++; }
-        float *a = c->val_a, *b = c->val_b;
-        for (int j = 0; j < 6; j++) {
-            const unsigned rows_pb = 256u / (unsigned)CP4;
-            const unsigned nblk = xcd_strip_blocks((size_t)Mb + 1, rows_pb) + (j < 3 ? xcd_strip_blocks((size_t)Mg + 1, rows_pb) : 0u);
-            hipLaunchKernelGGL(lg_blur2_kernel, dim3(nblk), dim3(256), 0, s, c->Lb, c->Lg, CP4, j,
-                               c->C <= 2 ? 1 : 0, (const float4 *)a, (float4 *)b, (const float4 *)(a + g_off), (float4 *)(b + g_off));
-            float *t = a; a = b; b = t;
-        }
-        // after 6 swaps the bilateral result is back in val_a; the Gaussian one stopped after 3 swaps, in val_b
+        if (int rc = large_splat_blur(c)) return rc;
         hipLaunchKernelGGL(lg_slice_update_kernel, dim3(xcd_strip_blocks((size_t)c->N, kSlicePix)), dim3(T),
                            sizeof(float) * (kSlicePix * (size_t)(CP + 1) + kSlicePix), s, c->Lb, c->Lg, c->C, CP,
                            (const float4 *)c->val_a, (const float4 *)(c->val_b + g_off), -prm->w_bilateral,
@@ -1084,6 +1128,127 @@ int large_crf_read_map_select(LargeCrf *c, const CrfSelArgs &sel, int32_t *label
     if (!c->async) DSRG_HIP_CHECK(hipStreamSynchronize(c->stream));
     return DSRG_OK;
 }
+// ---- introspection (tests): one image's lattices in the reference's form, and one application of a normalised kernel ----
+// the slice alone: out [N][CP] = norm . slice(val)  (lg_slice_elem with weight 1: 1 * x = x exactly)
+__global__ void lg_slice_only_kernel(LargeLattice L, int D1, int CP4, int seq, const float4 *__restrict__ val, float4 *__restrict__ out) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)L.N * CP4) return;
+    const size_t i = idx / CP4;
+    out[idx] = lg_slice_elem(L, D1, i, (int)(idx - i * CP4), CP4, seq, val, 1.0f);
+}
+
+// first pixel slot of image b, and the id range [v0, v0 + *Mb) of its vertices: ids are first-occurrence order over the pixel slots, and
+// the first entry of an image (corner 0 of its first pixel) is the first occurrence of the image's first vertex
+static int large_image_range(LargeCrf *c, const LargeLattice &L, int b, size_t *i0, uint32_t *v0, int *Mb) {
+    *i0 = c->nimg > 1 ? (size_t)b * c->Npimg : 0;
+    uint32_t first[2] = {0u, (uint32_t)L.M_host};
+    DSRG_HIP_CHECK(hipMemcpy(&first[0], L.vid + *i0, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (b + 1 < c->nimg) DSRG_HIP_CHECK(hipMemcpy(&first[1], L.vid + *i0 + c->Npimg, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (first[0] > first[1] || first[1] > (uint32_t)L.M_host)
+        return set_error(DSRG_ERR_HIP, "vertex ids of image %d are not a range: %u .. %u of %d", b, first[0], first[1], L.M_host);
+    *v0 = first[0]; *Mb = (int)(first[1] - first[0]);
+    return DSRG_OK;
+}
+
+int large_crf_lattice_dump(LargeCrf *c, const dsrg_crf_params *prm, int kind, int b, int32_t *m_host, int16_t *keys_host,
+                           int32_t *vid_host, float *bary_host, int32_t *n1_host, int32_t *n2_host) {
+    if (b < 0 || b >= c->nimg) return set_error(DSRG_ERR_INVALID, "image %d outside 0..%d", b, c->nimg - 1);
+    if (int rc = large_prepare(c, prm)) return rc;
+    DSRG_HIP_CHECK(hipStreamSynchronize(c->stream));
+    const LargeLattice &L = kind == 0 ? c->Lg : c->Lb;
+    const int d = L.d, d1 = d + 1, KW = (d * 16 + 31) / 32, Nimg = c->Nimg;
+    size_t i0; uint32_t v0; int M;
+    if (int rc = large_image_range(c, L, b, &i0, &v0, &M)) return rc;
+    *m_host = M;
+    const size_t words = std::max(std::max((size_t)M * KW, (size_t)Nimg), (size_t)M) + 1;
+    uint32_t *t = new (std::nothrow) uint32_t[words];
+    if (!t) return set_error(DSRG_ERR_NOMEM, "host allocation failed");
+    hipError_t e = hipSuccess;
+    if (keys_host) {
+        e = hipMemcpy(t, L.key_v + (size_t)v0 * KW, sizeof(uint32_t) * (size_t)M * KW, hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            for (int v = 0; v < M; v++)
+                for (int k = 0; k < d; k++) {              // embed.h pack_key: (short + 0x8000) in 16-bit fields
+                    uint32_t f = (t[(size_t)v * KW + (k >> 1)] >> ((k & 1) * 16)) & 0xFFFFu;
+                    if (d == 2 && k == 0 && c->nimg > 1) f -= (uint32_t)b * 4096u;      // the image number (lg_embed_kernel)
+                    keys_host[(size_t)v * d + k] = (int16_t)(int)(f - 0x8000u);
+                }
+    }
+    for (int r = 0; r < d1 && e == hipSuccess && (vid_host || bary_host); r++) {
+        if (vid_host) {
+            e = hipMemcpy(t, L.vid + (size_t)r * L.N + i0, sizeof(uint32_t) * (size_t)Nimg, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) for (int i = 0; i < Nimg; i++) vid_host[(size_t)i * d1 + r] = (int32_t)(t[i] - v0);
+        }
+        if (bary_host && e == hipSuccess) {
+            e = hipMemcpy(t, L.bary + (size_t)r * L.N + i0, sizeof(float) * (size_t)Nimg, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) for (int i = 0; i < Nimg; i++) memcpy(&bary_host[(size_t)i * d1 + r], &t[i], sizeof(float));
+        }
+    }
+    for (int j = 0; j < d1 && e == hipSuccess && (n1_host || n2_host); j++)
+        for (int side = 0; side < 2 && e == hipSuccess; side++) {
+            int32_t *dst = side ? n2_host : n1_host;
+            if (!dst) continue;
+            e = hipMemcpy(t, (side ? L.nb2 : L.nb1) + (size_t)j * L.Mcap + v0, sizeof(uint32_t) * (size_t)M, hipMemcpyDeviceToHost);
+            if (e == hipSuccess)                           // id M_host of the whole object = the zero row = none
+                for (int v = 0; v < M; v++) dst[(size_t)j * M + v] = t[v] == (uint32_t)L.M_host ? -1 : (int32_t)(t[v] - v0);
+        }
+    delete[] t;
+    DSRG_HIP_CHECK(e);
+    return DSRG_OK;
+}
+
+int large_crf_lattice_norm(LargeCrf *c, const dsrg_crf_params *prm, int kind, int b, float *norm_host) {
+    if (b < 0 || b >= c->nimg) return set_error(DSRG_ERR_INVALID, "image %d outside 0..%d", b, c->nimg - 1);
+    if (int rc = large_prepare(c, prm)) return rc;
+    DSRG_HIP_CHECK(hipStreamSynchronize(c->stream));
+    const LargeLattice &L = kind == 0 ? c->Lg : c->Lb;
+    const size_t i0 = c->nimg > 1 ? (size_t)b * c->Npimg : 0;
+    DSRG_HIP_CHECK(hipMemcpy(norm_host, L.norm + i0, sizeof(float) * (size_t)c->Nimg, hipMemcpyDeviceToHost));
+    return DSRG_OK;
+}
+
+// out = norm . K (norm . x) of kernel `kind` for image b (x, out: [Nimg][C] label-fastest, host or device memory; the other
+// images of a batched object filter zeros): the splat inputs of BOTH lattices are x * norm (the fp32 product of
+// lg_update_kernel, formed on the host), then the launches of a mean-field iteration (large_splat_blur) and the slice alone.
+// Uses q, qn_b, qn_g and the value buffers as scratch: the next inference call rewrites them all.
+int large_crf_filter_once(LargeCrf *c, const dsrg_crf_params *prm, int kind, int b, const float *x, float *out) {
+    if (b < 0 || b >= c->nimg) return set_error(DSRG_ERR_INVALID, "image %d outside 0..%d", b, c->nimg - 1);
+    if (int rc = large_prepare(c, prm)) return rc;
+    hipStream_t s = c->stream;
+    const int C = c->C, CP = c->CP, Nimg = c->Nimg;
+    const size_t i0 = c->nimg > 1 ? (size_t)b * c->Npimg : 0, rows = (size_t)c->N * CP;
+    float *xh = new (std::nothrow) float[(size_t)Nimg * C], *nh = new (std::nothrow) float[(size_t)Nimg];
+    float *in = new (std::nothrow) float[rows];
+    int rc = (xh && nh && in) ? DSRG_OK : set_error(DSRG_ERR_NOMEM, "host allocation failed");
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipStreamSynchronize(s);
+    if (!rc && e == hipSuccess) e = hipMemcpy(xh, x, sizeof(float) * (size_t)Nimg * C, hipMemcpyDefault);
+    for (int k = 0; k < 2 && !rc && e == hipSuccess; k++) {
+        const LargeLattice &L = k == 0 ? c->Lg : c->Lb;
+        e = hipMemcpy(nh, L.norm + i0, sizeof(float) * (size_t)Nimg, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) break;
+        memset(in, 0, sizeof(float) * rows);
+        for (int i = 0; i < Nimg; i++)
+            for (int l = 0; l < C; l++) in[(i0 + i) * CP + l] = xh[(size_t)i * C + l] * nh[i];
+        e = hipMemcpy(k == 0 ? c->qn_g : c->qn_b, in, sizeof(float) * rows, hipMemcpyHostToDevice);
+    }
+    delete[] xh; delete[] nh; delete[] in;
+    if (rc) return rc;
+    DSRG_HIP_CHECK(e);
+    if ((rc = large_splat_blur(c))) return rc;
+    const LargeLattice &L = kind == 0 ? c->Lg : c->Lb;
+    const float *val = kind == 0 ? c->val_b + ((size_t)c->Lb.M_host + 1) * CP : c->val_a;
+    hipLaunchKernelGGL(lg_slice_only_kernel, dim3(blocks_for((size_t)c->N * (CP / 4), 256)), dim3(256), 0, s, L, kind == 0 ? 3 : 6,
+                       CP / 4, C <= 2 ? 1 : 0, (const float4 *)val, (float4 *)c->q);
+    hipLaunchKernelGGL(lg_unpad_rows_kernel, dim3(blocks_for((size_t)c->N * C, 256)), dim3(256), 0, s, c->N, C, CP, c->q, c->stage,
+                       c->Nimg, c->Npimg);
+    c->lab_valid = false;
+    DSRG_LAUNCH_CHECK();
+    DSRG_HIP_CHECK(hipMemcpyAsync(out, c->stage + (size_t)b * Nimg * C, sizeof(float) * (size_t)Nimg * C, hipMemcpyDefault, s));
+    DSRG_HIP_CHECK(hipStreamSynchronize(s));
+    return DSRG_OK;
+}
+
 void large_crf_set_stream(LargeCrf *c, hipStream_t s, bool async) { c->stream = s; c->async = async; }
 int large_crf_lattice_size(LargeCrf *c, int k) { return k == 0 ? c->Lg.M_host : c->Lb.M_host; }
 int large_crf_images(LargeCrf *c) { return c->nimg; }

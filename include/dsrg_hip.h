@@ -110,6 +110,22 @@ int dsrg_crf_npixels(dsrg_crf_t h);
 int dsrg_crf_nlabels(dsrg_crf_t h);
 /* introspection (tests): vertex count of lattice k (0 Gaussian, 1 bilateral), -1 if not built */
 int dsrg_crf_lattice_size(dsrg_crf_t h, int k);
+/* introspection for the parity tests, objects on the global-memory path only (maps beyond DSRG_CTX_MAX_PIXELS, and every object of
+ * dsrg_crf_create_batch): the counterparts of dsrg_ctx_lattice_dump / dsrg_ctx_lattice_norm / dsrg_ctx_filter_once in section 2,
+ * for image b (0 for a one-image object) of the last add_pairwise_energy.  kind 0 = Gaussian, 1 = bilateral lattice.
+ * DSRG_ERR_UNSUPPORTED for an object on the LDS-resident path, DSRG_ERR_INVALID before add_pairwise_energy.  They run on the
+ * object's stream and return when done; the lattices are built here if no inference has run since add_pairwise_energy.
+ *   dump: arrays as dsrg_ctx_lattice_dump, of ONE image: N = W * H pixels, *m_host = the image's vertex count (the vertices
+ *         of the image's SSE padding pixels included), ids local to the image in first-occurrence order, the image number
+ *         removed from the keys.  Any array may be NULL: call once for *m_host, then with arrays of that size.
+ *   norm: norm_host [W*H].
+ *   filter_once: x, out [W*H*nlabels] label-fastest, host or device pointers; out = norm . K (norm . x) through the splat,
+ *         combine and blur launches of one mean-field iteration (same grids and buffers) and the slice.  The other images of
+ *         a batched object filter zeros.  Overwrites the object's marginals (the next inference / map call recomputes them). */
+int dsrg_crf_lattice_dump(dsrg_crf_t h, int kind, int b, int32_t *m_host, int16_t *keys_host, int32_t *vid_host,
+                          float *bary_host, int32_t *n1_host, int32_t *n2_host);
+int dsrg_crf_lattice_norm(dsrg_crf_t h, int kind, int b, float *norm_host);
+int dsrg_crf_filter_once(dsrg_crf_t h, int kind, int b, const float *x, float *out);
 
 /* measurement hook (no reference counterpart): while on, every launch of the dominant kernel of this object's path — the
  * splat of the global-memory path (full-resolution maps), the mean-field filter kernel of the LDS-resident path — is

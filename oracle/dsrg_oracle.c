@@ -314,13 +314,47 @@ static void orc_lattice_init_scalar(orc_lattice *L, const float *feature, int d,
 static int orc_lattice_path = 0;
 ORC_API void orc_set_lattice_path(int scalar) { orc_lattice_path = scalar ? 1 : 0; }
 
+/* Splat order of the filter (never of the normalisation vector): 0 = the reference's, every vertex row summed entry by entry
+ * in pixel order (what every parity test of the reference's arithmetic uses); n > 0 = the order of the HIP global-memory path
+ * (lattice_large.hip, kSplatSeg): a row of more than n entries is summed as partial sums of n consecutive entries, each started
+ * from zero, combined as ((p0 + p1) + p2) + ...  A row of at most n entries has one partial sum, its plain sum. */
+static int orc_splat_seg = 0;
+ORC_API void orc_set_splat_segments(int n) { orc_splat_seg = n > 0 ? n : 0; }
+
+/* values[(o+1)*vs + k] += w * in[i*vs + k] in segment order; values must be zero on entry */
+static void orc_splat_segmented(const orc_lattice *L, float *values, const float *in, int vs, int seg) {
+    const int d1 = L->d + 1, M = L->M, N = L->N;
+    float *cur = (float *)calloc((size_t)(M + 2) * vs, sizeof(float));   /* the running partial sum of every row */
+    int *cnt = (int *)calloc((size_t)(M + 2), sizeof(int));              /* its entries so far */
+    char *cut = (char *)calloc((size_t)(M + 2), 1);                      /* the row has closed a segment already */
+    for (int i = 0; i < N; i++)
+        for (int j = 0; j < d1; j++) {
+            const int o = L->offset[(size_t)i * d1 + j] + 1;
+            const float w = L->bary[(size_t)i * d1 + j];
+            float *c = cur + (size_t)o * vs, *v = values + (size_t)o * vs;
+            if (cnt[o] == seg) {                                         /* close the full segment */
+                for (int k = 0; k < vs; k++) { v[k] = cut[o] ? v[k] + c[k] : c[k]; c[k] = 0.0f; }
+                cut[o] = 1; cnt[o] = 0;
+            }
+            for (int k = 0; k < vs; k++) { float t = w * in[(size_t)i * vs + k]; c[k] = c[k] + t; }
+            cnt[o]++;
+        }
+    for (int o = 0; o < M + 2; o++) {
+        float *c = cur + (size_t)o * vs, *v = values + (size_t)o * vs;
+        for (int k = 0; k < vs; k++) v[k] = cut[o] ? v[k] + c[k] : c[k];
+    }
+    free(cur); free(cnt); free(cut);
+}
+
 /* Permutohedral::seqCompute (permutohedral.cpp:476-527), used when
  * value_size <= 2 (permutohedral.cpp:600-601).  Note the blur is evaluated in
  * double (the literal 0.5) and the slice multiplies (w*value)*alpha. */
-static void orc_seq_compute(const orc_lattice *L, float *out, const float *in, int vs) {
+static void orc_seq_compute(const orc_lattice *L, float *out, const float *in, int vs, int seg) {
     const int d = L->d, d1 = d + 1, M = L->M, N = L->N;
     float *values = (float *)calloc((size_t)(M + 2) * vs, sizeof(float));
     float *newv = (float *)calloc((size_t)(M + 2) * vs, sizeof(float));
+    if (seg > 0) orc_splat_segmented(L, values, in, vs, seg);
+    else
     for (int i = 0; i < N; i++)
         for (int j = 0; j <= d; j++) {
             int o = L->offset[(size_t)i * d1 + j] + 1;
@@ -362,11 +396,13 @@ static void orc_seq_compute(const orc_lattice *L, float *out, const float *in, i
 /* Permutohedral::sseCompute (permutohedral.cpp:529-589), element-wise
  * identical float arithmetic; the 4-wide padding of the channel dimension has
  * no numerical effect and is not reproduced. */
-static void orc_sse_compute(const orc_lattice *L, float *out, const float *in, int vs) {
+static void orc_sse_compute(const orc_lattice *L, float *out, const float *in, int vs, int seg) {
     const int d = L->d, d1 = d + 1, M = L->M, N = L->N;
     float *values = (float *)calloc((size_t)(M + 2) * vs, sizeof(float));
     float *newv = (float *)calloc((size_t)(M + 2) * vs, sizeof(float));
     float *tmp = (float *)malloc(sizeof(float) * vs);
+    if (seg > 0) orc_splat_segmented(L, values, in, vs, seg);
+    else
     for (int i = 0; i < N; i++) {                        /* splat :545-553 */
         memcpy(tmp, in + (size_t)i * vs, sizeof(float) * vs);
         for (int j = 0; j <= d; j++) {
@@ -402,9 +438,13 @@ static void orc_sse_compute(const orc_lattice *L, float *out, const float *in, i
 
 /* Permutohedral::compute dispatch (permutohedral.cpp:596-604). in/out are
  * vs x N column-major and may alias. */
+static void orc_lattice_compute_seg(const orc_lattice *L, float *out, const float *in, int vs, int seg) {
+    if (vs <= 2) orc_seq_compute(L, out, in, vs, seg);
+    else orc_sse_compute(L, out, in, vs, seg);
+}
+/* the filter of kernel_filter / lattice_filter / inference: in the splat order of orc_set_splat_segments */
 static void orc_lattice_compute(const orc_lattice *L, float *out, const float *in, int vs) {
-    if (vs <= 2) orc_seq_compute(L, out, in, vs);
-    else orc_sse_compute(L, out, in, vs);
+    orc_lattice_compute_seg(L, out, in, vs, orc_splat_seg);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -424,7 +464,7 @@ static void orc_kernel_init(orc_kernel *K, const float *feature, int d, int N, f
     K->norm = (float *)malloc(sizeof(float) * N);
     float *ones = (float *)malloc(sizeof(float) * N);
     for (int i = 0; i < N; i++) ones[i] = 1.0f;
-    orc_lattice_compute(&K->lat, K->norm, ones, 1);      /* pairwise.cpp:44 */
+    orc_lattice_compute_seg(&K->lat, K->norm, ones, 1, 0);   /* pairwise.cpp:44; always whole rows, as lg_splat1_kernel */
     for (int i = 0; i < N; i++)                          /* NORMALIZE_SYMMETRIC :54-57 */
         K->norm[i] = (float)(1.0 / sqrt((double)K->norm[i] + 1e-20));
     free(ones);

@@ -174,6 +174,25 @@ class lattice_path(object):
         return False
 
 
+class splat_segments(object):
+    """context manager: the filters applied inside (kernel_filter, lattice_filter, inference / map / CRF) splat in the order of
+    the HIP global-memory path instead of the reference's — a vertex row of more than n entries is summed as partial sums of
+    n consecutive entries, each started from zero and combined as ((p0 + p1) + p2) + ...  The normalisation vector keeps the
+    reference's order (the HIP norm sums rows whole), so it does not matter where the kernels were built.  n = 4096 is
+    lattice_large.hip's kSplatSeg.  Outside: the reference's order, which every other test uses."""
+
+    def __init__(self, n):
+        self.n = int(n)
+
+    def __enter__(self):
+        lib().orc_set_splat_segments(self.n)
+        return self
+
+    def __exit__(self, *exc):
+        lib().orc_set_splat_segments(0)
+        return False
+
+
 def CRF(image, unary, maxiter=10, scale_factor=1.0, color_factor=13):
     """Restatement of krahenbuhl2013.CRF (CRF/krahenbuhl2013/CRF.py:4-37)."""
     assert image.shape[:2] == unary.shape[:2]
