@@ -909,6 +909,10 @@ struct dsrg_crf_s {
 static constexpr int kCrfCacheSlots = 4;
 static dsrg_crf_s *g_crf_cache[kCrfCacheSlots] = {nullptr, nullptr, nullptr, nullptr};
 static std::mutex g_crf_cache_mutex;
+static std::atomic<int> g_crf_cache_hits{0};
+// tests only (not in the public header): how many objects dsrg_crf_create / dsrg_crf_create_batch have handed out from the cache
+// so far — a test that needs a newly made object checks that its creation did not count
+extern "C" __attribute__((visibility("default"))) int dsrg_debug_crf_cache_hits(void) { return g_crf_cache_hits.load(); }
 
 static int crf_create(int W, int H, int nlabels, int nimages, dsrg_crf_t *out);
 extern "C" int dsrg_crf_create(int W, int H, int nlabels, dsrg_crf_t *out) { return crf_create(W, H, nlabels, 1, out); }
@@ -931,6 +935,7 @@ static int crf_create(int W, int H, int nlabels, int nimages, dsrg_crf_t *out) {
             // the global-memory path also for a map the LDS path takes, and dsrg_crf_create must not get that other implementation)
             if (c && c->W == W && c->H == H && c->M == nlabels && c->nimg == nimages && c->forced_large == force_large) {
                 g_crf_cache[i] = nullptr;
+                g_crf_cache_hits++;
                 c->have_unary = c->have_pairwise = false;
                 c->stream = nullptr; c->async = false;
                 if (c->large) large_crf_set_stream(c->large, nullptr, false);

@@ -319,16 +319,17 @@ def crf_prepare(images, C, H, W, scale_factor=12.0, maxiter=10, ctx=None):
     return ctx
 
 
-def crf_meanfield(unary, im_u8, maxiter=10, scale_factor=1.0, color_factor=13, ctx=None):
+def crf_meanfield(unary, im_u8, maxiter=10, scale_factor=1.0, color_factor=13, ctx=None, params=None):
     """krahenbuhl2013.CRF on device blobs: unary (B,C,H,W) f32 (the `unary` argument of CRF.py:28,
-    i.e. minus the energy), im_u8 (B,H,W,3) uint8 -> marginals (B,C,H,W) f32."""
+    i.e. minus the energy), im_u8 (B,H,W,3) uint8 -> marginals (B,C,H,W) f32.  params: a ready CrfParams (kernel weights,
+    widths and iteration count) instead of the ones CRF() derives from maxiter / scale_factor / color_factor."""
     _f32c(unary, "unary")
     if not (im_u8.is_cuda and im_u8.dtype == torch.uint8 and im_u8.is_contiguous()):
         raise ValueError("im_u8 must be a contiguous uint8 CUDA tensor")
     B, C, H, W = unary.shape
     ctx = ctx or get_context(B, C, H, W)
     q = torch.empty_like(unary)
-    prm = CrfParams.from_crf_args(maxiter, scale_factor, color_factor)
+    prm = params if params is not None else CrfParams.from_crf_args(maxiter, scale_factor, color_factor)
     check(_lib.lib().dsrg_crf_meanfield_batch(ctx._h, B, _ptr(unary), _ptr(im_u8), ctypes.byref(prm), _ptr(q),
                                               _stream()))
     return q

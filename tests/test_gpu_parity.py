@@ -418,19 +418,21 @@ def test_pylayers_protocol_vs_reference_glue(golden_glue, tag):
 
 
 # ---------------------------------------------------------------- fused step vs layer-by-layer oracle
-def _check_fused_step(ops, O, logits, images, labels, cues, tag):
+def _check_fused_step(ops, O, logits, images, labels, cues, tag, scale_factor=12.0, maxiter=10):
     """dsrg_supervision_step against the oracle layer by layer in the order of train-s.prototxt:746-810 / SURVEY A.3:
     softmax blob, CRF marginals (1e-4), seeds bit-exact (borderline-proof otherwise), both losses, the fc8 gradient"""
     B, C, H, W = logits.shape
     if ops.lds_path_supports(H, W):
         ctx = ops.get_context(B, C, H, W)
-        losses, grad, blobs = ops.supervision_step(dev(logits), dev(images), dev(labels), dev(cues), want_blobs=True, ctx=ctx)
+        losses, grad, blobs = ops.supervision_step(dev(logits), dev(images), dev(labels), dev(cues), want_blobs=True, ctx=ctx,
+                                                   scale_factor=scale_factor, maxiter=maxiter)
         hip_refined = ctx.read_refined(B).cpu().numpy()
     else:                                                                   # the global-memory composition hands its marginals out
-        losses, grad, blobs = ops.supervision_step(dev(logits), dev(images), dev(labels), dev(cues), want_blobs=True)
+        losses, grad, blobs = ops.supervision_step(dev(logits), dev(images), dev(labels), dev(cues), want_blobs=True,
+                                                   scale_factor=scale_factor, maxiter=maxiter)
         hip_refined = blobs["refined"].cpu().numpy()
     probs = O.softmax_forward(logits)
-    refined, logq = O.crf_refine_batch(probs, images, 12.0, 10)           # clips probs in place
+    refined, logq = O.crf_refine_batch(probs, images, scale_factor, maxiter)           # clips probs in place
     gp = blobs["probs"].cpu().numpy()
     assert np.abs(gp - probs).max() < 1e-6 and gp.min() >= np.float32(1e-4)
     assert np.abs(hip_refined - refined).max() < CRF_TOL
@@ -619,6 +621,22 @@ def test_fused_step_other_shapes_vs_oracle(ops, O, B, C, HW):
     logits = S.make_logits(rng, B, C, H, W)
     labels, cues = S.make_labels_cues(rng, B, C, H, W)
     _check_fused_step(ops, O, logits, images, labels, cues, "fused B=%d C=%d %dx%d" % (B, C, H, W))
+
+
+@pytest.mark.parametrize("HW,scale,maxiter", [((41, 41), 12.0, 0), ((41, 41), 12.0, 1), ((41, 41), 3.0, 10), ((41, 41), 1.0, 2),
+                                              ((70, 70), 3.0, 1)])
+def test_fused_step_off_the_default_crf_arguments(ops, O, HW, scale, maxiter):
+    """the fused step with other CRF arguments than (12, 10), B = 2, 21 labels: no iteration at all (the first update launch
+    writes the marginals and their logarithm, the softmax pass leaves Q0 out), a first iteration that is also the last, and
+    scales 3 and 1, whose Gaussian lattice is not pixel-local (its workgroups are in the filter grid); 70x70: the global-memory
+    composition.  Against the oracle layer by layer, every bar as at the defaults."""
+    H, W = HW
+    rng = np.random.default_rng(7000 + 100 * int(scale) + maxiter + H)
+    images = S.make_images(rng, 2, size=8 * (H - 1) + 1, kind="smooth" if maxiter else "noise")
+    logits = S.make_logits(rng, 2, 21, H, W)
+    labels, cues = S.make_labels_cues(rng, 2, 21, H, W)
+    _check_fused_step(ops, O, logits, images, labels, cues, "fused %dx%d scale %g, %d iterations" % (H, W, scale, maxiter),
+                      scale_factor=scale, maxiter=maxiter)
 
 
 @pytest.mark.parametrize("seed", [50_002, 50_005, 50_011, 50_024, 50_027, 50_049, 50_054])
