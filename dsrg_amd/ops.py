@@ -868,31 +868,34 @@ WGRAD_CONV_SHAPES = ((3, 64), (64, 64), (64, 128), (128, 128))      # (cin, cout
 
 # ---- the packed bf16 kernels of the float32 master parameters, kept from step to step — only for parameters an optimizer that
 # maintains them has claimed (keep_weight_packs: trainer.CaffeSGD).  A convolution node packs the kernel the first time it sees
-# such a parameter and leaves the buffers here; the optimizer's update (sgd_pack_step) rewrites them in the pass that updates the
-# parameter, so from the second step on a forward finds its packs ready and reads no float32 weight.  An entry is good for exactly
-# one value of the parameter: it records the tensor's version counter, which in-place writes bump (load_state_dict, a broadcast)
+# such a parameter and leaves the buffers on it; the optimizer's update (sgd_pack_step) rewrites them in the pass that updates the
+# parameter, so from the second step on a forward finds its packs ready and reads no float32 weight.  A record is good for exactly
+# one value of the parameter: it holds the tensor's version counter, which in-place writes bump (load_state_dict, a broadcast)
 # — then the node packs again, into the same buffers.  NOT every writer bumps it: torch's private fused optimizer ops
 # (torch._fused_sgd_, which torch.optim.SGD(fused=True) calls) leave the counter alone, which is why nothing is kept for a
 # parameter unless its optimizer says it plays along; unclaimed parameters are packed inside every forward as before.  Writes
 # through `param.data` (whose version counter is its own) or by foreign kernels are equally invisible: code that does that to a
 # claimed parameter calls forget_weight_packs afterwards.
-class _WeightPacks(object):
-    __slots__ = ("ref", "version", "fwd", "dg", "plain")
+#
+# All of it sits on the parameter, as its one attribute `_dsrg_packs`: the claim and the packs live and die with the tensor, and
+# nothing is keyed by an address.  The record says where the parameter lay when the packs were written; a parameter whose storage
+# has moved since (net.to(memory_format=...), `p.data = ...` — both keep attributes and version counter) no longer matches it.
+class _KeptPacks(object):
+    """owner: weakref to the claiming optimizer; kind: "igemm" (pack_conv_weight_pair), "direct" (pack_direct_weight_pair),
+    "cast" (cast_weight_kept: `fwd` is the parameter cast to bf16 as it lies) or None = nothing kept yet; at: (address, shape,
+    strides) of the parameter the packs were written from; version: the version counter they belong to; fwd / dg: the buffers"""
+    __slots__ = ("owner", "kind", "at", "version", "fwd", "dg")
+
+    def __init__(self, owner):
+        self.owner = _weakref.ref(owner)
+        self.forget()
+
+    def forget(self):
+        self.kind = self.at = self.version = self.fwd = self.dg = None
 
 
-_weight_packs = {}                                                    # parameter.data_ptr() -> _WeightPacks
-
-
-def _packs_entry(weight, plain):
-    """the entry of this parameter (whatever value it was packed from), or None"""
-    e = _weight_packs.get(weight.data_ptr())
-    if e is None:
-        return None
-    t = e.ref()
-    if t is None or t.data_ptr() != weight.data_ptr() or t.shape != weight.shape or e.plain != plain:
-        del _weight_packs[weight.data_ptr()]                          # the parameter is gone, another tensor took its address
-        return None
-    return e
+def _lies(weight):
+    return weight.data_ptr(), tuple(weight.shape), tuple(weight.stride())
 
 
 def keep_weight_packs(params, owner):
@@ -900,50 +903,39 @@ def keep_weight_packs(params, owner):
     version counter: the convolution nodes may then keep the packed kernels between steps.  The claim lasts as long as `owner`
     (the optimizer object) does — a parameter handed to another optimizer afterwards is packed inside every forward again;
     owner=None withdraws it"""
-    ref = _weakref.ref(owner) if owner is not None else None
-    for p in params:
-        p._dsrg_keep_packs = ref
-        _weight_packs.pop(p.data_ptr(), None)     # whatever an earlier owner left may have missed writes made since
+    for p in params:                              # a new record: whatever an earlier owner left may have missed writes made since
+        p._dsrg_packs = _KeptPacks(owner) if owner is not None else None
 
 
 def forget_weight_packs(params):
     """drop the kept packed kernels of these parameters (after a write that neither sgd_pack_step made nor a version counter saw)"""
     for p in params:
-        _weight_packs.pop(p.data_ptr(), None)
+        if getattr(p, "_dsrg_packs", None) is not None:
+            p._dsrg_packs.forget()
 
 
 def _packs_claimed(weight):
-    ref = getattr(weight, "_dsrg_keep_packs", None)
-    return ref is not None and ref() is not None
+    r = getattr(weight, "_dsrg_packs", None)
+    return r is not None and r.owner() is not None
 
 
-def _packs_kept(weight):
-    # inside a hipGraph capture the packing launches belong in the graph (a replay must see the weights of its own time)
-    return _packs_claimed(weight) and weight.is_cuda and not torch.cuda.is_current_stream_capturing()
+def kept_packs(weight, kind=None):
+    """the record (kind, version, fwd, dg) of what is kept for this parameter — whatever value it was packed from — if it
+    describes the parameter as it lies now (and is of `kind`, where one is given), else None.  A record that does not — the owner
+    is dead, the storage moved, another shape, another kind — loses its buffers here"""
+    r = getattr(weight, "_dsrg_packs", None)
+    if r is None or r.kind is None:
+        return None
+    if r.owner() is None or r.at != _lies(weight) or (kind is not None and r.kind != kind):
+        r.forget()
+        return None
+    return r
 
 
-def _packs_keep(weight, plain, fwd, dg):
-    if not _packs_kept(weight):
-        return
-    if weight.data_ptr() not in _weight_packs:                        # a new parameter (first step of a model): drop those of dead ones
-        for k in [k for k, e in _weight_packs.items() if e.ref() is None]:
-            del _weight_packs[k]
-    e = _WeightPacks()
-    e.ref, e.version, e.fwd, e.dg, e.plain = _weakref.ref(weight), weight._version, fwd, dg, plain
-    _weight_packs[weight.data_ptr()] = e
-
-
-def _packs_for(weight, plain, want_fwd, want_dgrad, fwd_shape, dg_shape, fwd_cl=False):
-    """-> (fwd, dg, fresh): the buffers of the packed forms wanted; fresh = they already hold this value of the parameter"""
-    e = _packs_entry(weight, plain) if _packs_kept(weight) else None
-    if e is not None and e.version == weight._version and (e.fwd is not None or not want_fwd) and (e.dg is not None or not want_dgrad):
-        return (e.fwd if want_fwd else None), (e.dg if want_dgrad else None), True
-    mf = torch.channels_last if fwd_cl else torch.contiguous_format
-    fwd = (e.fwd if e is not None and e.fwd is not None else torch.empty(fwd_shape, dtype=torch.bfloat16, device=weight.device, memory_format=mf)) \
-        if (want_fwd or (e is not None and e.fwd is not None)) else None
-    dg = (e.dg if e is not None and e.dg is not None else torch.empty(dg_shape, dtype=torch.bfloat16, device=weight.device, memory_format=mf)) \
-        if (want_dgrad or (e is not None and e.dg is not None)) else None
-    return fwd, dg, False
+def _packs_keep(weight, kind, fwd, dg):
+    """the one writer of a claimed parameter's record"""
+    r = weight._dsrg_packs
+    r.kind, r.at, r.version, r.fwd, r.dg = kind, _lies(weight), weight._version, fwd, dg
 
 
 # DSRG_CHECK_PACKS=N (debugging aid): every N-th time a forward takes kept packs for good, the parameter is packed again into
@@ -969,6 +961,27 @@ def _check_kept_packs(weight, fwd, dg, pack):
                            "dsrg_amd.ops.forget_weight_packs([param]) after such a write" % (tuple(weight.shape),))
 
 
+def _kept_or_packed(weight, kind, want_fwd, want_dgrad, fwd_shape, dg_shape, mf, pack):
+    """-> (fwd, dg), None where not wanted: the kept packs of `weight` if they hold its present value, else packed now —
+    into the kept buffers where there are any, every form already kept along with the wanted ones — and kept.
+    pack(fwd_buffer_or_None, dg_buffer_or_None) packs `weight` into the buffers given; they have fwd_shape / dg_shape, layout mf"""
+    # inside a hipGraph capture the packing launches belong in the graph (a replay must see the weights of its own time)
+    keep = _packs_claimed(weight) and weight.is_cuda and not torch.cuda.is_current_stream_capturing()
+    r = kept_packs(weight, kind) if keep else None
+    fwd, dg = (r.fwd, r.dg) if r is not None else (None, None)
+    if r is not None and r.version == weight._version and (fwd is not None or not want_fwd) and (dg is not None or not want_dgrad):
+        _check_kept_packs(weight, fwd if want_fwd else None, dg if want_dgrad else None, pack)
+    else:
+        if fwd is None and want_fwd:
+            fwd = torch.empty(fwd_shape, dtype=torch.bfloat16, device=weight.device, memory_format=mf)
+        if dg is None and want_dgrad:
+            dg = torch.empty(dg_shape, dtype=torch.bfloat16, device=weight.device, memory_format=mf)
+        pack(fwd, dg)
+        if keep:
+            _packs_keep(weight, kind, fwd, dg)
+    return (fwd if want_fwd else None), (dg if want_dgrad else None)
+
+
 def sgd_pack_step(params, grads, bufs, lrs, wds, momentum):
     """Caffe's SGD update B <- momentum B + (g + wd W); W <- W - lr B of float32 CUDA parameters in one launch per sixteen
     tensors (dsrg_sgd_pack_cast_f32), rewriting the packed bf16 kernels the convolution nodes keep for them (and conv1_1's plain
@@ -981,14 +994,14 @@ def sgd_pack_step(params, grads, bufs, lrs, wds, momentum):
     ptr = lambda ts: np.array([0 if t is None else t.data_ptr() for t in ts], dtype=np.uint64)
     fwd, dg, cast, shape, entries = [None] * n, [None] * n, [None] * n, np.zeros((n, 4), dtype=np.int32), []
     for i, p in enumerate(params):
-        e = _weight_packs.get(p.data_ptr())
-        if e is None or e.ref() is None or e.ref().data_ptr() != p.data_ptr() or e.ref().shape != p.shape:
+        e = kept_packs(p)
+        if e is None:
             continue
-        if e.plain == _PLAIN_CAST:                                    # conv1_1: a bf16 copy in the parameter's own order
+        if e.kind == "cast":                                          # conv1_1: a bf16 copy in the parameter's own order
             cast[i] = e.fwd
-        else:
+        else:                                                         # the library's `plain` flag: 1 = the direct route's layout
             fwd[i], dg[i] = e.fwd, e.dg
-            shape[i] = (p.shape[0], p.shape[1], p.shape[2] * p.shape[3], e.plain)
+            shape[i] = (p.shape[0], p.shape[1], p.shape[2] * p.shape[3], int(e.kind == "direct"))
         entries.append((e, p))
     pp, gp, bp, fp, dp, cp = ptr(params), ptr(grads), ptr(bufs), ptr(fwd), ptr(dg), ptr(cast)
     numel = np.array([p.numel() for p in params], dtype=np.int64)
@@ -1006,10 +1019,7 @@ def sgd_pack_eligible(p, g, b):
     return p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and b.dtype == torch.float32 and g.is_cuda and \
         g.shape == p.shape and all(n == 1 or (sg == sp and sb == sp) for n, sp, sg, sb in zip(p.shape, p.stride(), g.stride(), b.stride())) and \
         (p.is_contiguous() or (p.dim() == 4 and p.is_contiguous(memory_format=torch.channels_last))) and \
-        ((p.data_ptr() | b.data_ptr()) % 16 == 0 or p.data_ptr() not in _weight_packs)
-
-
-_PLAIN_CAST = 2                           # _WeightPacks.plain of an entry whose `fwd` is the parameter cast to bf16 as it lies
+        ((p.data_ptr() | b.data_ptr()) % 16 == 0 or kept_packs(p) is None)
 
 
 def cast_weight_kept(weight):
@@ -1018,15 +1028,10 @@ def cast_weight_kept(weight):
     whenever the version counter says the kept copy is stale; otherwise the copy sgd_pack_step wrote with the update"""
     w = weight.detach()
     dense = w.is_contiguous() or (w.dim() == 4 and w.is_contiguous(memory_format=torch.channels_last))
-    if not (_packs_kept(weight) and w.dtype == torch.float32 and dense):
+    if not (w.dtype == torch.float32 and dense):
         return w.to(torch.bfloat16)
-    e = _packs_entry(weight, _PLAIN_CAST)
-    if e is not None and e.version == weight._version and e.fwd is not None:
-        _check_kept_packs(weight, e.fwd, None, lambda f, d: f.copy_(w))
-        return e.fwd
-    w16 = w.to(torch.bfloat16)                                        # (the parameter's own strides: sgd_pack_step writes it in that order)
-    _packs_keep(weight, _PLAIN_CAST, w16, None)
-    return w16
+    mf = torch.contiguous_format if w.is_contiguous() else torch.channels_last   # (the parameter's own order: sgd_pack_step writes it so)
+    return _kept_or_packed(weight, "cast", True, False, w.shape, None, mf, lambda f, d: f.copy_(w))[0]
 
 
 def pack_direct_weight_pair(weight, want_dgrad=True):
@@ -1037,14 +1042,8 @@ def pack_direct_weight_pair(weight, want_dgrad=True):
     if not (weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous(memory_format=cl) and tuple(weight.shape[2:]) == (3, 3)
             and cin in DIRECT_CONV_CHANNELS and cout in DIRECT_CONV_CHANNELS):
         raise ValueError("pack_direct_weight_pair needs a float32 channels_last (cout,cin,3,3) CUDA parameter with 64 / 128 channels")
-    fwd, dg, fresh = _packs_for(weight, 1, True, want_dgrad, (cout, cin, 3, 3), (cin, cout, 3, 3), fwd_cl=True)
     pack = lambda f, d: check(_lib.lib().dsrg_pack_conv_weight_direct_f32(_ptr(weight.detach()), _ptr(f), _ptr(d), cout, cin, _stream()))
-    if not fresh:
-        pack(fwd, dg)
-        _packs_keep(weight, 1, fwd, dg)
-    else:
-        _check_kept_packs(weight, fwd, dg, pack)
-    return fwd, (dg if want_dgrad else None)
+    return _kept_or_packed(weight, "direct", True, want_dgrad, (cout, cin, 3, 3), (cin, cout, 3, 3), cl, pack)
 
 
 def conv3x3_wgrad(x, g, out_dtype=torch.bfloat16, out=None):
@@ -1118,14 +1117,9 @@ def pack_conv_weight_pair(weight, want_fwd=True, want_dgrad=True, scale=None):
     if not (weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous(memory_format=torch.channels_last)
             and cout % 64 == 0 and cin % 64 == 0 and k in (1, 3)):
         return (pack_conv_weight(weight) if want_fwd else None, pack_conv_weight(weight, for_dgrad=True) if want_dgrad else None)
-    fwd, dg, fresh = _packs_for(weight, 0, want_fwd, want_dgrad, (cout, cin // 64, k * k, 64), (cin, cout // 64, k * k, 64))
     pack = lambda f, d: check(_lib.lib().dsrg_pack_conv_weight_f32(_ptr(weight.detach()), _ptr(f), _ptr(d), cout, cin, k, _stream()))
-    if not fresh:
-        pack(fwd, dg)
-        _packs_keep(weight, 0, fwd, dg)
-    else:
-        _check_kept_packs(weight, fwd, dg, pack)
-    return (fwd if want_fwd else None), (dg if want_dgrad else None)
+    return _kept_or_packed(weight, "igemm", want_fwd, want_dgrad, (cout, cin // 64, k * k, 64), (cin, cout // 64, k * k, 64),
+                           torch.contiguous_format, pack)
 
 
 def split3_bf16(t, dim):

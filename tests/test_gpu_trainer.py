@@ -387,7 +387,7 @@ def test_sgd_pack_kernel_equals_torch_fused_sgd_and_the_pack_kernel(ops):
             ops.pack_conv_weight_pair(p, True, True)
         elif plain == 1:
             ops.pack_direct_weight_pair(p, True)
-    assert sum(1 for p in ps if p.data_ptr() in ops._weight_packs) == 4
+    assert sum(1 for p in ps if ops.kept_packs(p) is not None) == 4
     for step in range(2):
         grads = [mk(sh) for sh, _ in shapes]
         for i in (0, 2, 4, 5):                                        # views 4 bytes into a larger buffer, strides kept: what a
@@ -408,8 +408,8 @@ def test_sgd_pack_kernel_equals_torch_fused_sgd_and_the_pack_kernel(ops):
         for p, (sh, plain) in zip(ps, shapes):
             if plain is None:
                 continue
-            e = ops._weight_packs[p.data_ptr()]
-            assert e.version == p._version
+            e = ops.kept_packs(p)
+            assert e.version == p._version and e.kind == ("igemm", "direct")[plain]
             w = p.detach().clone(memory_format=torch.preserve_format)                    # not a Parameter: packed afresh
             want = ops.pack_conv_weight_pair(w, True, True) if plain == 0 else ops.pack_direct_weight_pair(w, True)
             assert torch.equal(e.fwd, want[0]) and torch.equal(e.dg, want[1])
@@ -432,6 +432,149 @@ def test_sgd_pack_kernel_equals_torch_fused_sgd_and_the_pack_kernel(ops):
     assert lib.dsrg_sgd_pack_f32(1, arr, arr, arr, None, None, None, one, None, None, 0.9, None) != 0     # not aligned to a float
 
 
+class _Owner(object):
+    pass
+
+
+_PACK_CASES = (("igemm", (192, 64, 3, 3)), ("igemm", (128, 256, 1, 1)), ("direct", (128, 64, 3, 3)), ("cast", (64, 3, 3, 3)))
+
+
+def _pack_param(shape, seed=3):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return torch.nn.Parameter(torch.randn(shape, generator=g).to(torch.device("cuda", 0)).contiguous(memory_format=torch.channels_last))
+
+
+def _packs_of(ops, kind, w, want_dgrad=True):
+    """(fwd, dg) of `w` through the entry point of `kind`"""
+    if kind == "igemm":
+        return ops.pack_conv_weight_pair(w, True, want_dgrad)
+    if kind == "direct":
+        return ops.pack_direct_weight_pair(w, want_dgrad)
+    return ops.cast_weight_kept(w), None
+
+
+def _fresh_packs(ops, kind, p):
+    return _packs_of(ops, kind, p.detach().clone(memory_format=torch.preserve_format))    # not claimed: packed afresh
+
+
+def _same_packs(a, b):
+    return all((x is None and y is None) or (x is not None and y is not None and x.stride() == y.stride() and torch.equal(x, y))
+               for x, y in zip(a, b))
+
+
+def _one_sgd_pack_step_leaves_fresh_packs(ops, kind, p):
+    ops.sgd_pack_step([p], [torch.randn_like(p)], [torch.zeros_like(p)], [1e-2], [5e-4], 0.9)
+    e = ops.kept_packs(p)
+    assert e is not None and e.kind == kind and e.version == p._version
+    assert _same_packs((e.fwd, e.dg), _fresh_packs(ops, kind, p))
+
+
+def test_kept_packs_die_with_their_parameter(ops):
+    """the kept bf16 buffers belong to the parameter: once it (and whoever took the buffers) is gone they are freed, though the
+    claiming optimizer lives on and no other model has taken a step"""
+    import gc
+    import weakref
+    gc.collect()
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    owner = _Owner()
+    ps = [_pack_param(sh) for _, sh in _PACK_CASES]
+    ops.keep_weight_packs(ps, owner)
+    refs = []
+    for (kind, _), p in zip(_PACK_CASES, ps):
+        bufs = _packs_of(ops, kind, p)
+        assert _packs_of(ops, kind, p)[0] is bufs[0]                  # kept
+        refs += [weakref.ref(b) for b in bufs if b is not None]
+    assert len(refs) == 7 and torch.cuda.memory_allocated() > base
+    del ps, p, bufs
+    gc.collect()
+    assert sum(r() is not None for r in refs) == 0
+    assert torch.cuda.memory_allocated() == base
+    assert owner is not None
+
+
+def test_kept_packs_do_not_follow_moved_storage(ops):
+    """`p.data = ...` and module.to(memory_format=...) keep the parameter's attributes and version counter but put it elsewhere:
+    what was kept is dropped, the next call packs what now lies there, and sgd_pack_step maintains the new packs"""
+    owner = _Owner()
+    for kind, sh in _PACK_CASES:
+        p = _pack_param(sh)
+        ops.keep_weight_packs([p], owner)
+        first = _packs_of(ops, kind, p)
+        assert ops.kept_packs(p).fwd is first[0]
+        v = p._version
+        p.data = p.data.clone(memory_format=torch.preserve_format)
+        assert p._version == v
+        got = _packs_of(ops, kind, p)
+        assert got[0] is not first[0] and _same_packs(got, _fresh_packs(ops, kind, p))
+        _one_sgd_pack_step_leaves_fresh_packs(ops, kind, p)
+        v = p._version
+        p.data = p.data * 0.5                                         # elsewhere AND another value
+        assert p._version == v
+        assert _same_packs(_packs_of(ops, kind, p), _fresh_packs(ops, kind, p))
+    conv = torch.nn.Conv2d(64, 192, 3).to(torch.device("cuda", 0))
+    p = conv.weight
+    ops.keep_weight_packs([p], owner)
+    assert p.is_contiguous() and ops.pack_conv_weight_pair(p, True, True)[0] is not None
+    v = p._version
+    conv.to(memory_format=torch.channels_last)
+    assert conv.weight is p and p._version == v and not p.is_contiguous()
+    got = _packs_of(ops, "igemm", p)
+    assert _same_packs(got, _fresh_packs(ops, "igemm", p)) and ops.kept_packs(p).fwd is got[0]       # the claim moved along
+    _one_sgd_pack_step_leaves_fresh_packs(ops, "igemm", p)
+
+
+def test_kept_packs_follow_a_change_of_kind(ops):
+    """one parameter through the implicit-GEMM route, the direct route and back: each call returns its own layout"""
+    owner = _Owner()
+    p = _pack_param((128, 64, 3, 3))
+    ops.keep_weight_packs([p], owner)
+    for kind in ("igemm", "direct", "igemm"):
+        got = _packs_of(ops, kind, p)
+        assert _same_packs(got, _fresh_packs(ops, kind, p))
+        e = ops.kept_packs(p)
+        assert e.kind == kind and e.fwd is got[0] and e.dg is got[1]
+
+
+def test_kept_packs_partial_wants_and_stale_versions_reuse_the_buffers(ops):
+    """a form asked for later joins the kept one; after an in-place write the counter saw, the same buffers are rewritten — every
+    form kept, also one the call does not ask for"""
+    owner = _Owner()
+    for kind, sh in _PACK_CASES[:3]:
+        p = _pack_param(sh)
+        ops.keep_weight_packs([p], owner)
+        f1, d1 = _packs_of(ops, kind, p, want_dgrad=False)
+        assert d1 is None and ops.kept_packs(p).dg is None
+        f2, d2 = _packs_of(ops, kind, p)
+        assert f2 is f1 and _same_packs((f2, d2), _fresh_packs(ops, kind, p))
+        with torch.no_grad():
+            p.mul_(0.5)
+        want = _fresh_packs(ops, kind, p)
+        assert not torch.equal(f1, want[0])
+        f3, d3 = _packs_of(ops, kind, p, want_dgrad=False)
+        e = ops.kept_packs(p)
+        assert f3 is f1 and d3 is None and e.dg is d2 and e.version == p._version and _same_packs((f1, d2), want)
+        f4, d4 = _packs_of(ops, kind, p)
+        assert f4 is f1 and d4 is d2 and _same_packs((f4, d4), want)
+
+
+def test_check_packs_names_a_write_behind_the_version_counter(ops, monkeypatch):
+    """DSRG_CHECK_PACKS=1: a kept pack taken after a write through `.data` raises, for every kind; forget_weight_packs mends it"""
+    monkeypatch.setattr(ops, "_CHECK_PACKS", 1)
+    owner = _Owner()
+    for kind, sh in _PACK_CASES:
+        p = _pack_param(sh)
+        ops.keep_weight_packs([p], owner)
+        first = _packs_of(ops, kind, p)
+        assert _packs_of(ops, kind, p)[0] is first[0]                 # checked, and right
+        p.data.mul_(0.5)
+        with pytest.raises(RuntimeError, match="forget_weight_packs"):
+            _packs_of(ops, kind, p)
+        ops.forget_weight_packs([p])
+        assert _same_packs(_packs_of(ops, kind, p), _fresh_packs(ops, kind, p))
+        assert _same_packs(_packs_of(ops, kind, p), _fresh_packs(ops, kind, p))          # kept again, checked, and right
+
+
 def test_trainer_steps_with_the_sgd_pack_kernel_equal_torch_fused_sgd(ops, monkeypatch):
     """three DSRGTrainer steps with the update + packing kernel (the default) against the same steps with torch._fused_sgd_ and
     the packs made inside each forward: same losses and weights up to the last-bit differences of the two update kernels carried
@@ -447,9 +590,9 @@ def test_trainer_steps_with_the_sgd_pack_kernel_equal_torch_fused_sgd(ops, monke
         tr = T.DSRGTrainer(device, seed=0, net=VGG16ASPP(dropout=0.0))
         losses = [tr.step(images, labels, cues).detach().cpu() for _ in range(3)]
         params = [p for g in tr.opt.groups for p in g["params"]]
-        kept = [e for e, p in ((ops._weight_packs.get(p.data_ptr()), p) for p in params) if e is not None and e.ref() is p]
+        kept = [(e, p) for e, p in ((ops.kept_packs(p), p) for p in params) if e is not None]
         if on:
-            assert len(kept) >= 8 and all(e.version == e.ref()._version for e in kept)   # (which layers take a packed route depends on the batch)
+            assert len(kept) >= 8 and all(e.version == p._version for e, p in kept)      # (which layers take a packed route depends on the batch)
         else:
             assert not kept
         out[on] = (torch.stack(losses), [p.detach().clone() for p in params])

@@ -65,13 +65,20 @@ def test_caffe_sgd_bumps_version_counters_and_packs_are_kept_only_while_their_ow
     o1 = Owner()
     ops.keep_weight_packs([w], o1)
     assert ops._packs_claimed(w)
-    e = ops._WeightPacks()
-    e.ref, e.version, e.fwd, e.dg, e.plain = ops._weakref.ref(w), w._version, torch.zeros(1), None, 0
-    ops._weight_packs[w.data_ptr()] = e
-    assert ops._packs_entry(w, 0) is e and ops._packs_entry(w, 1) is None     # another layout: the entry goes
-    ops._weight_packs[w.data_ptr()] = e
+    assert ops.kept_packs(w) is None
+    buf = torch.zeros(1)
+    ops._packs_keep(w, "igemm", buf, None)
+    e = ops.kept_packs(w, "igemm")
+    assert e is not None and ops.kept_packs(w) is e and (e.kind, e.version, e.dg) == ("igemm", w._version, None) and e.fwd is buf
+    assert ops.kept_packs(w, "direct") is None and ops.kept_packs(w) is None      # another layout: the entry goes
+    ops._packs_keep(w, "igemm", buf, None)
+    o2 = Owner()
+    ops.keep_weight_packs([w], o2)                     # a new claim forgot the old entry
+    assert ops._packs_claimed(w) and ops.kept_packs(w) is None
+    ops.keep_weight_packs([w], o1)
+    ops._packs_keep(w, "igemm", buf, None)
     del o1
     gc.collect()
-    assert not ops._packs_claimed(w)
+    assert not ops._packs_claimed(w) and ops.kept_packs(w) is None
     ops.keep_weight_packs([w], Owner())                # the owner dies at once; the claim forgot the old entry
-    assert w.data_ptr() not in ops._weight_packs and not ops._packs_claimed(w)
+    assert ops.kept_packs(w) is None and not ops._packs_claimed(w)
