@@ -137,6 +137,8 @@ SIGNATURES = {
     "dsrg_conv_igemm_wgrad_splits": (_i, [_i] * 7 + [_vp, _vp]),
     "dsrg_conv_igemm_wgrad_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "dsrg_conv_igemm_backward_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _i, _i, _i, _i, _i, _i, _vp]),
+    "dsrg_conv_igemm_backward_groups_bf16": (_i, [_vp] * 7 + [_i, _vp, _f, _vp, _sz, _vp, _sz] + [_i] * 8 + [_vp]),
+    "dsrg_conv_igemm_backward_groups_plan": (_i, [_i] * 7 + [_vp, _i, _i, _i, _vp, _vp]),
     "dsrg_conv3x3_wgrad_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "dsrg_conv3x3_wgrad_bf16": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "dsrg_conv3x3_wgrad_f32": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),

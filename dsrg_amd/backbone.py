@@ -270,8 +270,9 @@ class _IgemmConvFn(torch.autograd.Function):
     matrices (nothing to gather), the weight gradients of all branches one implicit-GEMM launch.
     x: bf16 channels_last; w, b: the float32 master parameters — the kernel is cast to bf16 by the same copy that packs it
     for the kernel, and the weight gradient comes back in float32, so autocast's per-layer casts both ways disappear.
-    Backward: ReLU / dropout mask + bias gradient in one fused pass (as _ConvFn), data gradients of all branches in one launch
-    (the same kernel on the flipped, transposed kernels), weight gradients in one launch."""
+    Backward: ReLU / dropout mask + bias gradient in one fused pass (as _ConvFn); data and weight gradients in ONE grid
+    (ops.conv_igemm_backward for n = 1, ops.conv_igemm_backward_groups for the four branches) when all inputs need gradients, else
+    data gradients of all branches in one launch (the same kernel on the flipped, transposed kernels), weight gradients in one."""
 
     @staticmethod
     def forward(ctx, k, dils, relu, drop_p, pool, n, links_in, links_out, *t):
@@ -353,6 +354,22 @@ class _IgemmConvFn(torch.autograd.Function):
             if absorb:
                 ctx.links_in[0].leave(gx, gb_below)
             return (None,) * 8 + (gx, _landed(gw, ctx.gw_out[0])) + tuple(gbs)
+        if n > 1 and all(need_x) and ops.conv_igemm_supported(cout, cin, ctx.k) and \
+                ops.conv_igemm_wgrad_supported(cin, cout, ctx.k) and all(x.is_contiguous(memory_format=cl) for x in xs):
+            # the four ASPP branches (fc7_k: 1x1 with the mask and bias gradients of fc6_k in the store; fc6_k: 3x3, dilations 6 - 24):
+            # the same one grid for both gradients, in the grouped forms of both halves (ops.conv_igemm_backward_groups).  With or
+            # without the masks: the weight gradient's pixel split belongs to the grid, so fc7_k's weight gradients are the same
+            # bits whether or not fc6_k's ReLU backward rides along (DSRG_FUSE_CHAIN)
+            packs_d = [p if p is not None else ops.pack_conv_weight(w, for_dgrad=True) for p, w in zip(ctx.packs_d, ws)]
+            gxs, gws, gb_below = ops.conv_igemm_backward_groups(gms, packs_d, list(xs), ctx.dils, ctx.k, list(xs) if absorb else None,
+                                                                ctx.links_in[0].scale if absorb else 1.0, gw_outs=ctx.gw_out)
+            if absorb:
+                for lk, gx_, gb_ in zip(ctx.links_in, gxs, gb_below):
+                    lk.leave(gx_, gb_)
+            gws = [_landed(gw, o) for gw, o in zip(gws, ctx.gw_out)]
+            if ctx.same_x and _sum_takes(gxs):
+                gxs = [ops.sum_bf16(list(gxs))] + [None] * (n - 1)      # (see below)
+            return (None,) * 8 + tuple(gxs) + tuple(gws) + tuple(gbs)
         if absorb:
             packs_d = [p if p is not None else ops.pack_conv_weight(w, for_dgrad=True) for p, w in zip(ctx.packs_d, ws)]
             gxs, gb_below = ops.conv_igemm_dgrad(gms, packs_d, list(xs), ctx.dils, ctx.k, ctx.links_in[0].scale)

@@ -714,6 +714,23 @@ extern "C" int dsrg_conv_igemm_backward_residual_bf16(const void *g_dev, const v
                                                wgrad_workspace_dev, wgrad_workspace_bytes, B, H, W, cin, cout, ksize,
                                                static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_conv_igemm_backward_groups_bf16(const void *const *g_dev, const void *const *w_dgrad_dev, const void *const *x_dev,
+                                                    const void *const *mask_dev, void *const *gx_dev, void *const *gw_dev, const int *dilation,
+                                                    int ngroups, float *const *bias_grad_dev, float mask_scale, void *colsum_workspace_dev,
+                                                    size_t colsum_workspace_bytes, void *wgrad_workspace_dev, size_t wgrad_workspace_bytes,
+                                                    int B, int H, int W, int cin, int cout, int ksize, int force_ksplit, int force_order,
+                                                    void *stream) {
+    if (!g_dev || !w_dgrad_dev || !x_dev || !gx_dev || !gw_dev || B < 1 || H < 1 || W < 1 || (bias_grad_dev && !mask_dev))
+        return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups: bad arguments");
+    return launch_conv_igemm_backward_groups(g_dev, w_dgrad_dev, x_dev, mask_dev, gx_dev, gw_dev, dilation, ngroups, bias_grad_dev, mask_scale,
+                                             colsum_workspace_dev, colsum_workspace_bytes, wgrad_workspace_dev, wgrad_workspace_bytes, B, H,
+                                             W, cin, cout, ksize, force_ksplit, force_order, static_cast<hipStream_t>(stream));
+}
+extern "C" int dsrg_conv_igemm_backward_groups_plan(int ngroups, int B, int H, int W, int cin, int cout, int ksize, const int *dilation,
+                                                    int with_mask, int force_ksplit, int force_order, int *plan_out, double *us_out) {
+    if (B < 1 || H < 1 || W < 1) return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups_plan: bad arguments");
+    return conv_igemm_backward_groups_plan(ngroups, B, H, W, cin, cout, ksize, dilation, with_mask, force_ksplit, force_order, plan_out, us_out);
+}
 extern "C" int dsrg_pack_conv_weight_scaled_f32(const float *w_dev, const float *scale_dev, void *fwd_dev, void *dgrad_dev, int cout, int cin,
                                                 int ksize, void *stream) {
     return launch_pack_conv_weight(w_dev, fwd_dev, dgrad_dev, cout, cin, ksize, static_cast<hipStream_t>(stream), 0, scale_dev);

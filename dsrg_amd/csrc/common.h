@@ -321,6 +321,12 @@ int launch_pack_conv_weight(const float *w, void *fwd, void *dgrad, int cout, in
 int launch_conv_igemm_backward_residual(const void *g, const void *wd, const void *x, const void *mask, const void *res, void *gx, void *gw,
                                         const float *gw_scale, int dil, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W, int cin,
                                         int cout, int k, hipStream_t stream);
+int launch_conv_igemm_backward_groups(const void *const *g, const void *const *wd, const void *const *x, const void *const *mask,
+                                      void *const *gx, void *const *gw, const int *dil, int ngroups, float *const *bias_grad, float mask_scale,
+                                      void *colsum_ws, size_t colsum_ws_bytes, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W,
+                                      int cin, int cout, int k, int forced_ksplit, int forced_order, hipStream_t stream);
+int conv_igemm_backward_groups_plan(int ngroups, int B, int H, int W, int cin, int cout, int k, const int *dil, int with_mask, int forced_ksplit,
+                                    int forced_order, int *out, double *us);
 int heads_bwd_chunks(int M);
 int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float *g, void *gx, size_t gx_branch_stride,
                      float *gw, float *partial, int B, int HW, int K, int O, hipStream_t stream, float relu_scale = 0.0f,

@@ -1558,6 +1558,16 @@ int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *co
     return run_wgrad(L, gw, nullptr, out_bf16, stream);
 }
 
+// the merged grid of two prepared halves (a.nd / a.nw blocks, padded to multiples of 8; a.w_first: the order)
+static int launch_bwd_grid(const IgemmBwdArgs &a, hipStream_t stream) {
+    static LdsGrant grant;
+    constexpr size_t lds = ICfg<64, 2>::LDS > (size_t)(2 * kWStage) ? ICfg<64, 2>::LDS : (size_t)(2 * kWStage);
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_bwd_kernel), lds, grant)) return rc;
+    hipLaunchKernelGGL(conv_igemm_bwd_kernel, dim3(a.w_first ? a.nw_pad + a.nd : a.nd_pad + a.nw), dim3(512), lds, stream, a);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
 // The backward of ONE convolution as one launch (conv_igemm_bwd_kernel): data gradient of g with the flipped kernel `wd` (+ the
 // ReLU / Dropout backward and bias gradient of the layer below when `mask` is given, as launch_conv_igemm's fused form; + a residual in
 // its store, IgemmGroup::res, when `res` is given) and the weight gradient from (x, g), times gw_scale per output when that is given.
@@ -1591,11 +1601,7 @@ static int conv_igemm_backward(const void *g, const void *wd, const void *x, con
     a.w = w.a;
     a.nd = d.grid; a.nd_pad = (a.nd + 7) & ~7; a.nw = w.grid; a.nw_pad = (a.nw + 7) & ~7;
     a.w_first = pick.second;
-    static LdsGrant grant;
-    constexpr size_t lds = ICfg<64, 2>::LDS > (size_t)(2 * kWStage) ? ICfg<64, 2>::LDS : (size_t)(2 * kWStage);
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_bwd_kernel), lds, grant)) return rc;
-    hipLaunchKernelGGL(conv_igemm_bwd_kernel, dim3(a.w_first ? a.nw_pad + a.nd : a.nd_pad + a.nw), dim3(512), lds, stream, a);
-    DSRG_LAUNCH_CHECK();
+    if (int rc = launch_bwd_grid(a, stream)) return rc;
     if (bias_grad) {
         const float *parts[1] = {a.d.g[0].colsum};
         if (int rc = launch_igemm_colsum(parts, bgp, 1, a.d.tiles_m, cin, stream)) return rc;
@@ -1608,6 +1614,98 @@ int launch_conv_igemm_backward(const void *g, const void *wd, const void *x, con
                                int W, int cin, int cout, int k, hipStream_t stream) {
     return conv_igemm_backward(g, wd, x, mask, nullptr, gx, gw, nullptr, dil, bias_grad, mask_scale, colsum_ws, colsum_ws_bytes, wgrad_ws,
                                wgrad_ws_bytes, B, H, W, cin, cout, k, stream);
+}
+
+// The backward of 1 - 4 convolutions of one geometry (the four ASPP branches) as one launch: conv_igemm_backward's merged grid with
+// both halves in their GROUPED forms — the data gradient with its XCD-interleaved map and class-ordered or row tiles where the
+// kernels are dilated (fc6 x4), mask and bias sums in its store where `mask` is given (fc7 x4); the weight gradient on its uniform
+// split (fc7 x4: searched for this grid) or on its per-tap work list (fc6 x4: the list of the launch alone, so its bits are that
+// launch's; the list is stored in front of the grid as in front of every launch that reads it).  Both bodies decode group, tile
+// and list entry from (arguments, block id, blocks of their half), so the kernel is conv_igemm_bwd_kernel as it is; what is new
+// is the planner, which prices both halves block by block (merged_groups_plan, igemm_plan.h).  Where it declines, or the variant
+// has no merged backward, the same prepared halves run as two launches: the same bits.
+namespace {
+struct GroupsBackward {
+    IgemmLaunch d;
+    WgradLaunch w;
+    MergedGroupsPlan plan;
+};
+// forced_ksplit > 0 (tests): that uniform split instead of the planner's; forced_order 1 / 2 (tests): a merged grid with the data /
+// weight gradient's blocks first, whichever the planner prices lower.  Launches nothing, enqueues nothing
+int prepare_backward_groups(const void *const *g, const void *const *wd, const void *const *x, const void *const *mask, void *const *gx,
+                            void *const *gw, const int *dil, int ngroups, float *const *bias_grad, float mask_scale, void *colsum_ws,
+                            size_t colsum_ws_bytes, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W, int cin, int cout, int k,
+                            int forced_ksplit, int forced_order, const IgemmVariant &v, GroupsBackward &P) {
+    if (int rc = prepare_igemm(g, wd, nullptr, gx, dil, ngroups, B, H, W, cout, cin, k, 0, 0.0f, 0ull, nullptr, 0, mask, mask_scale, bias_grad,
+                               colsum_ws, colsum_ws_bytes, nullptr, 0, false, v, P.d)) return rc;
+    if (int rc = prepare_wgrad(x, g, gw, dil, ngroups, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout, k, v, 0, P.w)) return rc;
+    const IgemmArgs &a = P.d.sk.base;
+    // the planner's own reading of the geometry must be what was prepared: its block costs follow the kernels' id decode
+    const DgradShape ds = dgrad_shape_for(ngroups, B, H, W, cin, cout, k, dil, v);
+    const WgradShape ws = wgrad_shape_for(ngroups, B, H, W, cin, cout, k, dil, v, 0, igemm_cus());
+    if (ds.grid != P.d.grid || ds.tiles_m != a.tiles_m || ds.tiles_n != a.tiles_n || ds.xcd_mix != a.xcd_mix || ds.row_tiles != a.row_tiles ||
+        ds.cls_tiles != a.cls_tiles || ws.grid != P.w.grid || ws.ksplit != P.w.a.ksplit || ws.xcd_mix != P.w.a.xcd_mix ||
+        ws.compact != P.w.a.compact || ws.nent != P.w.a.nent || (ws.plan != nullptr) != (P.w.plan != nullptr))
+        return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups: the planner and the launcher disagree on the grid");
+    if (!v.merged_backward || P.d.grid < 1 || P.w.grid < 1) {
+        P.plan = MergedGroupsPlan{false, 0, P.w.plan ? 0 : P.w.a.ksplit, 0.0, 0.0};
+        return DSRG_OK;
+    }
+    P.plan = merged_groups_plan(ds, cin, cout, k, v, P.w.plan ? 0 : forced_ksplit, igemm_cus());
+    if (P.plan.merge && forced_order > 0) P.plan.w_first = forced_order == 2;
+    if (P.plan.ksplit > 0 && P.plan.ksplit != P.w.a.ksplit)
+        if (int rc = prepare_wgrad(x, g, gw, dil, ngroups, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout, k, v, P.plan.ksplit, P.w)) return rc;
+    return DSRG_OK;
+}
+}  // namespace
+
+int launch_conv_igemm_backward_groups(const void *const *g, const void *const *wd, const void *const *x, const void *const *mask,
+                                      void *const *gx, void *const *gw, const int *dil, int ngroups, float *const *bias_grad, float mask_scale,
+                                      void *colsum_ws, size_t colsum_ws_bytes, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W,
+                                      int cin, int cout, int k, int forced_ksplit, int forced_order, hipStream_t stream) {
+    if (bias_grad && !mask) return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups: bias gradients come with the masks");
+    GroupsBackward P;
+    if (int rc = prepare_backward_groups(g, wd, x, mask, gx, gw, dil, ngroups, bias_grad, mask_scale, colsum_ws, colsum_ws_bytes, wgrad_ws,
+                                         wgrad_ws_bytes, B, H, W, cin, cout, k, forced_ksplit, forced_order, igemm_variant(), P)) return rc;
+    if (!P.plan.merge) {
+        if (int rc = run_igemm(P.d, bias_grad, stream)) return rc;
+        return run_wgrad(P.w, gw, nullptr, 0, stream);
+    }
+    if (int rc = upload_wgrad_plan(P.w, stream)) return rc;
+    IgemmBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = P.d.sk.base;
+    a.w = P.w.a;
+    a.nd = P.d.grid; a.nd_pad = merged_second_half_start(a.nd); a.nw = P.w.grid; a.nw_pad = merged_second_half_start(a.nw);
+    a.w_first = P.plan.w_first;
+    if (int rc = launch_bwd_grid(a, stream)) return rc;
+    if (bias_grad) {
+        const float *parts[4];
+        for (int q = 0; q < ngroups; q++) parts[q] = a.d.g[q].colsum;
+        if (int rc = launch_igemm_colsum(parts, bias_grad, ngroups, a.d.tiles_m, cin, stream)) return rc;
+    }
+    return reduce_wgrad(a.w, gw, nullptr, 0, stream);
+}
+
+// host only: what launch_conv_igemm_backward_groups would do for this geometry under the current variant — out[0] merged grid or two
+// launches, out[1] w_first, out[2] the weight gradient's uniform split (0: its work list), out[3] / out[4] blocks of the data /
+// weight gradient half; us[0] / us[1] the model's price of the choice and of the two launches (0 where nothing was priced)
+int conv_igemm_backward_groups_plan(int ngroups, int B, int H, int W, int cin, int cout, int k, const int *dil, int with_mask, int forced_ksplit,
+                                    int forced_order, int *out, double *us) {
+    if (ngroups < 1 || ngroups > 4 || !out || !us) return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups_plan: 1..4 groups");
+    const size_t need = wgrad_workspace_bytes(ngroups, B, H, W, cin, cout, k), cneed = conv_igemm_colsum_workspace(ngroups, B, H, W, cin);
+    // (nothing is launched: the prepared argument blocks only ever hold these stand-in addresses)
+    void *const fake = reinterpret_cast<void *>(uintptr_t(256));
+    const void *cp[4] = {fake, fake, fake, fake};
+    void *vp[4] = {fake, fake, fake, fake};
+    float *fp[4] = {static_cast<float *>(fake), static_cast<float *>(fake), static_cast<float *>(fake), static_cast<float *>(fake)};
+    GroupsBackward P;
+    if (int rc = prepare_backward_groups(cp, cp, cp, with_mask ? cp : nullptr, vp, vp, dil, ngroups, with_mask ? fp : nullptr, 1.0f,
+                                         with_mask ? fake : nullptr, cneed, fake, need, B, H, W, cin, cout, k, forced_ksplit, forced_order, igemm_variant(), P))
+        return rc;
+    out[0] = P.plan.merge; out[1] = P.plan.w_first; out[2] = P.plan.ksplit; out[3] = P.d.grid; out[4] = P.w.grid;
+    us[0] = P.plan.merged_us; us[1] = P.plan.separate_us;
+    return DSRG_OK;
 }
 
 // launch_conv_igemm_backward with a residual in the data gradient's store (res may be nullptr) and a per-output-channel factor on the

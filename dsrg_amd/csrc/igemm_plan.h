@@ -1,8 +1,8 @@
 // Host-side planning of the implicit-GEMM launches (conv_igemm.hip): which shapes a launch takes, how its pixels are tiled and
 // ordered, how a weight gradient's pixels are split, the work list of a dilated launch, the split and block order of a merged
-// backward grid, and what a debug variant number means.  Pure integer and double arithmetic on shapes: C++17 and the standard
+// backward grid (one layer, or 1 - 4 groups priced block by block), and what a debug variant number means.  Pure integer and double arithmetic on shapes: C++17 and the standard
 // library only, no HIP — the CU count is an argument — so that every decision can be checked on a CPU
-// (tests/igemm_plan_check.cpp, tests/golden/igemm_plan_decisions.txt).
+// (tests/igemm_plan_check.cpp, tests/golden/igemm_plan_decisions.txt; tests/igemm_merged_plan_check.cpp).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -365,6 +365,270 @@ inline std::pair<int, int> merged_backward_split(int B, int H, int W, int cin, i
             }
         }
         return pick;
+    });
+}
+
+// ---- the merged backward grid of a launch of 1 - 4 GROUPS (the four ASPP branches: fc7 x4, 1x1; fc6 x4, 3x3 with dilations 6 - 24).
+// Its blocks do not cost the same — a class-ordered data-gradient tile runs its live taps only, a work-list entry its own K-steps —
+// so both halves are priced block by block, in block-id order, exactly as the kernels decode their ids: the two shapes below
+// hold what prepare_igemm / prepare_wgrad decided (conv_igemm.hip; dgrad_shape_for / wgrad_shape_for decide the same from the
+// geometry alone, for the CPU check and cross-checked by the launcher), dgrad_block_costs / wgrad_block_costs turn them into us
+// per block (a block that exits at once costs 0), merged_grid_makespan runs one order of the two lists through dispatch_makespan
+// with the second half starting at the next multiple of 8, and merged_groups_plan picks.
+struct DgradShape {
+    int ngroups, B, H, W, kch, taps, tiles_m, tiles_n, xcd_mix, row_tiles, cls_tiles, skip_taps, grid, dil[4];      // kch: 64-channel chunks of g
+};
+struct WgradShape {
+    int ngroups, B, H, W, cin, cout, taps, tiles_n, tiles_c, ksplit, compact, xcd_mix, nent, grid, dil[4];
+    const uint32_t *plan;           // nullptr, or the work list's words (WgradPlan::words: host memory)
+};
+
+// live taps of every pixel tile of one group, in tile order (tile_taps's three tilings, tile by tile)
+inline std::vector<int> tile_tap_list(int B, int H, int W, int d, int mode) {
+    const long long M = (long long)B * H * W;
+    std::vector<int> out;
+    if (mode == 1) {
+        const int r = kBM / W;
+        for (int b = 0; b < B; b++)
+            for (int y0 = 0; y0 < H; y0 += r) out.push_back(__builtin_popcount(tap_mask_rect(H, W, d, y0, std::min(H, y0 + r), 0, W)));
+        return out;
+    }
+    HostClass c[kMaxClasses];
+    const int n = mode == 2 ? build_classes(H, W, d, c) : 0;
+    long long q0[kMaxClasses + 1] = {0};
+    for (int k = 0; k < n; k++) q0[k + 1] = q0[k] + (long long)B * (c[k].y1 - c[k].y0) * (c[k].x1 - c[k].x0);
+    for (long long t0 = 0; t0 < M; t0 += kBM) {
+        const long long t1 = std::min(M, t0 + kBM);
+        uint32_t m = 0;
+        for (int k = 0; k < n; k++)
+            if (q0[k] < t1 && q0[k + 1] > t0) m |= c[k].mask;
+        for (long long p = t0; mode == 0 && p < t1;) {
+            const int rem = (int)(p % ((long long)H * W)), y = rem / W, x = rem % W;
+            const int x1 = (int)std::min<long long>(W, x + (t1 - p));
+            m |= tap_mask_rect(H, W, d, y, y + 1, x, x1);
+            p += x1 - x;
+        }
+        out.push_back(__builtin_popcount(m));
+    }
+    return out;
+}
+
+// the data gradient of a forward convolution cin -> cout: g has cout channels (the K axis), gx has cin (the output columns)
+inline DgradShape dgrad_shape_for(int ngroups, int B, int H, int W, int cin, int cout, int k, const int *dil, const IgemmVariant &v) {
+    DgradShape s{};
+    const long long M = (long long)B * H * W;
+    s.ngroups = ngroups; s.B = B; s.H = H; s.W = W; s.kch = cout / 64; s.taps = k * k;
+    s.tiles_m = (int)((M + kBM - 1) / kBM);
+    s.tiles_n = (cin + kBN - 1) / kBN;
+    s.skip_taps = v.skip_dead_steps;
+    for (int g = 0; g < ngroups; g++) {
+        s.dil[g] = dil ? dil[g] : 1;
+        if (s.skip_taps && k == 3 && s.dil[g] >= 3) s.xcd_mix = 1;
+    }
+    const bool rows_ok = s.xcd_mix && W <= kBM && conv_igemm_row_tiles(H, W);
+    if (s.xcd_mix && v.class_tiles_allowed && H <= 255 && W <= 255 && (class_order_pays(B, H, W, s.dil, ngroups, rows_ok) || v.class_tiles_forced))
+        s.cls_tiles = 1;
+    if (!s.cls_tiles && rows_ok) {
+        s.row_tiles = 1;
+        s.tiles_m = B * ((H + kBM / W - 1) / (kBM / W));
+    }
+    s.grid = s.xcd_mix ? 8 * ngroups * ((s.tiles_m + 7) / 8) * s.tiles_n : s.tiles_m * s.tiles_n * ngroups;
+    return s;
+}
+// the weight gradient of the same launch; forced_ksplit > 0: that uniform split, no work list (prepare_wgrad's rule)
+inline WgradShape wgrad_shape_for(int ngroups, int B, int H, int W, int cin, int cout, int k, const int *dil, const IgemmVariant &v,
+                                  int forced_ksplit, int cus) {
+    WgradShape s{};
+    const long long M = (long long)B * H * W;
+    s.ngroups = ngroups; s.B = B; s.H = H; s.W = W; s.cin = cin; s.cout = cout; s.taps = k * k;
+    s.tiles_n = (cout + 255) / 256;
+    s.tiles_c = wgrad_col_tiles(cin, k);
+    for (int q = 0; q < ngroups; q++) s.dil[q] = dil ? dil[q] : 1;
+    const WgradPlan *p = (forced_ksplit <= 0 && wgrad_wants_plan(v, dil, ngroups, cin, k)) ? &build_wgrad_plan(ngroups, B, H, W, cin, cout, dil, cus) : nullptr;
+    s.ksplit = forced_ksplit > 0 ? forced_ksplit : wgrad_uniform_ksplit(ngroups, M, cin, cout, k, wgrad_wants_mix(dil, ngroups, k));
+    for (int q = 0; q < ngroups; q++) {
+        if (v.skip_dead_steps && k == 3 && s.dil[q] >= 3 &&
+            (s.ksplit % 8 == 0 || (8 % s.ksplit == 0 && (s.tiles_n * s.tiles_c) % (8 / s.ksplit) == 0))) s.xcd_mix = 1;
+        if (v.skip_dead_steps && v.wgrad_compact && k == 3 && cin != 128 && s.dil[q] >= 1) s.compact = 1;
+    }
+    s.grid = s.tiles_n * s.tiles_c * s.ksplit * ngroups;
+    if (p) {
+        s.plan = p->words.data();
+        s.nent = p->nent;
+        s.grid = (s.nent + 7) / 8 * 8 * (s.tiles_n * ((cin + 255) / 256));
+    }
+    return s;
+}
+
+// conv_igemm_body's tile map: block id of the half -> (group, pixel tile, channel tile); false: the block exits at once
+inline bool dgrad_block_tile(const DgradShape &s, int id, int &grp, int &tm, int &tn) {
+    const int xcd = id & 7, k = id >> 3;
+    if (s.xcd_mix) {
+        const int cm = (s.tiles_m - xcd + 7) >> 3, per_group = cm * s.tiles_n;
+        if (cm <= 0 || k >= per_group * s.ngroups) return false;
+        grp = k / per_group;
+        const int r = k - grp * per_group, tml = r / s.tiles_n;
+        tn = r - tml * s.tiles_n;
+        tm = xcd + 8 * tml;
+        return true;
+    }
+    const int q = s.grid >> 3, r = s.grid & 7, per_group = s.tiles_m * s.tiles_n;
+    int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+    grp = t / per_group;
+    t -= grp * per_group;
+    tm = t / s.tiles_n;
+    tn = t - tm * s.tiles_n;
+    return true;
+}
+// conv_igemm_wgrad_body's three maps: block id of the half -> (group, pixel split of ksp, output tile t); false: the block exits at once
+inline bool wgrad_block_unit(const WgradShape &s, int id, int &grp, int &split, int &ksp, int &t) {
+    const int xcd = id & 7, k = id >> 3, tiles = s.tiles_n * s.tiles_c;
+    ksp = s.ksplit;
+    if (s.plan) {
+        const int ncb = (s.cin + 255) >> 8, tpe = s.tiles_n * ncb, pos = k / tpe, te = k - pos * tpe, e = pos * 8 + xcd;
+        if (e >= s.nent) return false;
+        const uint32_t w = s.plan[kPlanHdr + e];
+        grp = (int)(w & 3u);
+        split = (int)((w >> 6) & 255u);
+        ksp = (int)((w >> 14) & 255u);
+        t = (te / ncb) * s.tiles_c + (int)((w >> 2) & 15u) * ncb + te % ncb;
+    } else if (s.xcd_mix && s.ksplit >= 8) {
+        const int per_group = (s.ksplit >> 3) * tiles;
+        grp = k / per_group;
+        const int r = k - grp * per_group;
+        split = xcd + 8 * (r / tiles);
+        t = r % tiles;
+    } else if (s.xcd_mix) {
+        const int xpc = 8 / s.ksplit, per_group = tiles / xpc;
+        split = xcd / xpc;
+        grp = k / per_group;
+        t = xcd % xpc + xpc * (k - grp * per_group);
+    } else {
+        const int q = s.grid >> 3, r = s.grid & 7, tiles_per_group = tiles * s.ksplit;
+        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+        grp = t / tiles_per_group;
+        t -= grp * tiles_per_group;
+        split = t / tiles;
+        t -= split * tiles;
+    }
+    return true;
+}
+
+// us per block, in block-id order: a tile costs its live K-steps + 6 at 1.85 us (merged_backward_split's price)
+inline std::vector<double> dgrad_block_costs(const DgradShape &s) {
+    std::vector<std::vector<int>> live(s.ngroups);
+    for (int g = 0; g < s.ngroups; g++) {
+        if (s.taps == 9 && s.skip_taps) live[g] = tile_tap_list(s.B, s.H, s.W, s.dil[g], s.cls_tiles ? 2 : s.row_tiles ? 1 : 0);
+        else live[g].assign((size_t)s.tiles_m, s.taps);
+    }
+    std::vector<double> c((size_t)std::max(s.grid, 0), 0.0);
+    for (int id = 0; id < s.grid; id++) {
+        int grp, tm, tn;
+        if (dgrad_block_tile(s, id, grp, tm, tn)) c[(size_t)id] = (s.kch * live[grp][(size_t)tm] + 6) * 1.85;
+    }
+    return c;
+}
+// ... conv_igemm_wgrad_body's three maps: a workgroup costs its K-steps + 8 at 2.3 us
+inline std::vector<double> wgrad_block_costs(const WgradShape &s) {
+    std::vector<double> c((size_t)std::max(s.grid, 0), 0.0);
+    const long long M = (long long)s.B * s.H * s.W;
+    const bool two = s.cin == 128 && s.taps == 9;
+    const int ncb = two ? 1 : (s.cin + 255) >> 8;
+    for (int id = 0; id < s.grid; id++) {
+        int grp, split, ksp, t;
+        if (!wgrad_block_unit(s, id, grp, split, ksp, t)) continue;
+        const int tc = t % s.tiles_c, tap = two ? 2 * tc : tc / ncb;
+        long long Kc = M, chunk = ((M + s.ksplit - 1) / s.ksplit + 63) / 64 * 64;
+        if (s.compact && !two && s.taps == 9) {
+            const int rh = s.H - abs((tap / 3 - 1) * s.dil[grp]), rw = s.W - abs((tap % 3 - 1) * s.dil[grp]);
+            Kc = (rh > 0 && rw > 0) ? (long long)s.B * rh * rw : 0;
+            chunk = ((Kc + ksp - 1) / ksp + 63) / 64 * 64;
+        }
+        const long long beg = split * chunk, end = std::min(Kc, beg + chunk);
+        c[(size_t)id] = ((end > beg ? (end - beg + 63) / 64 : 0) + 8) * 2.3;
+    }
+    return c;
+}
+
+// when the last block of the grid [first | padding to a multiple of 8 | second] ends (an empty second: the first launched alone)
+inline int merged_second_half_start(int n_first) { return (n_first + 7) & ~7; }      // both halves keep their block-id -> XCD relation
+inline double merged_grid_makespan(const std::vector<double> &first, const std::vector<double> &second, int cus) {
+    const size_t n0 = first.size(), pad = (size_t)merged_second_half_start((int)n0);
+    return dispatch_makespan(cus, [&](int x, int b) {
+        const size_t id = (size_t)x + 8 * (size_t)b;
+        if (id < n0) return first[id];
+        if (id < pad) return 0.0;
+        return id - pad < second.size() ? second[id - pad] : -1.0;
+    });
+}
+
+struct MergedGroupsPlan {
+    bool merge;                     // one grid (conv_igemm_bwd_kernel) — else the two halves as two launches
+    int w_first;                    // the weight gradient's workgroups take the first block ids
+    int ksplit;                     // the weight gradient's uniform pixel split for this grid (0: it runs its work list, as it does alone)
+    double merged_us, separate_us;  // the model's price of the choice and of the two launches (both with the reduction's share)
+};
+// one pair of cost lists: the cheaper block order — where the model prices both alike (it runs one workgroup per CU at a time,
+// the chip two: fc7 x4's 256 weight-gradient workgroups are exactly one round of its 256 CUs, and every order comes out as the two
+// launches one behind the other), the half with the longest block goes first, as list scheduling would have it: its blocks then
+// run beside the other half's instead of alone at the end — merged where the model does not price it above the two launches.
+// An empty half leaves nothing to merge
+inline MergedGroupsPlan merged_groups_decide(const std::vector<double> &dcost, const std::vector<double> &wcost, int cus) {
+    MergedGroupsPlan p{false, 0, 0, 0.0, 0.0};
+    const std::vector<double> none;
+    p.separate_us = merged_grid_makespan(dcost, none, cus) + merged_grid_makespan(wcost, none, cus);
+    p.merged_us = p.separate_us;
+    if (dcost.empty() || wcost.empty()) return p;
+    const double d_first = merged_grid_makespan(dcost, wcost, cus), w_first = merged_grid_makespan(wcost, dcost, cus);
+    p.w_first = w_first < d_first || (w_first == d_first && *std::max_element(wcost.begin(), wcost.end()) > *std::max_element(dcost.begin(), dcost.end()));
+    p.merged_us = std::min(d_first, w_first);
+    p.merge = p.merged_us <= p.separate_us;
+    if (!p.merge) p.merged_us = p.separate_us;
+    return p;
+}
+// The plan of a launch: d as prepared; the weight gradient either keeps its work list (fc6 x4: its bits stay those of the launch
+// alone) or — a uniform split on the plain map (fc7 x4) — has its split searched for THIS grid among 1 .. the bound its workspace
+// was sized for: fc7 x4's four splits are 256 workgroups of 106 K-steps, exactly one round of the chip with nothing to fill, two
+// splits are 128 workgroups that take half the CUs for the whole launch while the 1 696 data-gradient tiles run on the other
+// half.  Every split is priced with its share of the reduction as merged_backward_split prices it (3 us + 2.4 us per 512 x 4608
+// floats of partials); the price of the two launches is that of the split the launch runs alone.  forced_ksplit > 0 (tests): that
+// split only, where the workspace holds it.  Decided once per key
+inline const MergedGroupsPlan &merged_groups_plan(const DgradShape &d, int cin, int cout, int k, const IgemmVariant &v, int forced_ksplit, int cus) {
+    static PlanMemo<std::array<int, 20>, MergedGroupsPlan> memo;
+    const int vbits = v.skip_dead_steps | v.class_tiles_allowed << 1 | v.class_tiles_forced << 2 | v.wgrad_work_list << 3 | v.wgrad_compact << 4;
+    const std::array<int, 20> key = {d.ngroups, d.B, d.H, d.W, cin, cout, k, d.dil[0], d.dil[1], d.dil[2], d.dil[3], d.tiles_m, d.xcd_mix,
+                                     d.row_tiles, d.cls_tiles, d.skip_taps, d.grid, vbits, forced_ksplit, cus};
+    return memo.get(key, [&] {
+        const long long M = (long long)d.B * d.H * d.W;
+        const std::vector<double> dcost = dgrad_block_costs(d);
+        const WgradShape w0 = wgrad_shape_for(d.ngroups, d.B, d.H, d.W, cin, cout, k, d.dil, v, 0, cus);
+        auto priced = [&](const WgradShape &w) {
+            double planes = (double)w.ksplit * w.taps * d.ngroups;
+            if (w.plan) { planes = 0.0; for (int i = 0; i < d.ngroups * 9; i++) planes += (double)w.plan[2 * i]; }
+            const double tail = 3.0 + 2.4 * planes * ((double)cout * cin / (512.0 * 4608.0));
+            MergedGroupsPlan p = merged_groups_decide(dcost, wgrad_block_costs(w), cus);
+            p.merged_us += tail;
+            p.separate_us += tail;
+            p.ksplit = w.plan ? 0 : w.ksplit;
+            return p;
+        };
+        MergedGroupsPlan best = priced(w0);
+        const double separate = best.separate_us;
+        if (!w0.plan && (forced_ksplit > 0 || !wgrad_wants_mix(d.dil, d.ngroups, k))) {
+            const int bound = wgrad_ksplit_bound(d.ngroups, d.B, d.H, d.W, cin, cout, k);
+            for (int ks = 1; ks <= bound; ks++) {
+                if ((long long)(ks - 1) * (((M + ks - 1) / ks + 63) / 64 * 64) >= M) continue;      // an empty last split
+                if (forced_ksplit > 0 ? ks != forced_ksplit : ks == w0.ksplit) continue;
+                const MergedGroupsPlan p = priced(wgrad_shape_for(d.ngroups, d.B, d.H, d.W, cin, cout, k, d.dil, v, ks, cus));
+                if (forced_ksplit > 0 || (p.merge && p.merged_us < best.merged_us)) best = p;
+            }
+        }
+        if (forced_ksplit <= 0) {
+            best.separate_us = separate;
+            best.merge = best.merge && best.merged_us <= separate;
+            if (!best.merge) { best.merged_us = separate; best.ksplit = w0.plan ? 0 : w0.ksplit; }      // two launches: the split of the launch alone
+        }
+        return best;
     });
 }
 

@@ -1319,6 +1319,65 @@ def conv_igemm_backward_residual(g, packed_d, x, dilation, ksize, mask=None, res
     return gx, gw
 
 
+def conv_igemm_backward_groups(gs, packed_d, xs, dilations, ksize, masks=None, mask_scale=1.0, gw_outs=None, gb_outs=None, gx_outs=None,
+                               force_ksplit=0, force_order=0):
+    """conv_igemm_backward for 1 .. 4 convolutions of one geometry (the four ASPP branches; dsrg_conv_igemm_backward_groups_bf16):
+    gs[i] (B,cout,H,W) and xs[i] (B,cin,H,W) bf16 channels_last, packed_d[i] = pack_conv_weight(w_i, for_dgrad=True), masks: None or
+    the layers' inputs where they are sole-consumer ReLU outputs (then the ReLU / Dropout backward and bias gradients of the layers
+    below ride in the data gradients) -> (list of gx, list of gw (cout,cin,k,k) float32 channels_last, list of bias gradients or
+    None).  One grid for both gradients where the planner takes it (conv_igemm_backward_groups_plan), else two launches: the same
+    bits.  gx and the bias gradients equal conv_igemm(_dgrad)'s bit for bit; gw equals conv_igemm_wgrad's bit for bit wherever the
+    pixel split is that launch's (a dilated 3x3 launch: always; a uniform split is chosen for the merged grid, force_ksplit > 0
+    sets it) and else up to fp32 reassociation.  force_order
+    1 / 2 (tests): a merged grid takes the data / weight gradient's blocks first."""
+    n = len(gs)
+    B, cout, H, W = gs[0].shape
+    cin = xs[0].shape[1]
+    cl = torch.channels_last
+    if not (1 <= n <= 4 and len(packed_d) == n and len(xs) == n and len(dilations) == n and (masks is None or len(masks) == n)):
+        raise ValueError("conv_igemm_backward_groups: 1..4 groups")
+    ok = lambda t: t.dtype == torch.bfloat16 and tuple(t.shape) == (B, cin, H, W) and t.is_contiguous(memory_format=cl)      # noqa: E731
+    for i in range(n):
+        if not (gs[i].is_cuda and gs[i].dtype == torch.bfloat16 and tuple(gs[i].shape) == (B, cout, H, W) and ok(xs[i])
+                and packed_d[i].dtype == torch.bfloat16 and tuple(packed_d[i].shape) == (cin, cout // 64, ksize * ksize, 64)
+                and packed_d[i].is_contiguous() and (masks is None or ok(masks[i]))):
+            raise ValueError("conv_igemm_backward_groups needs bf16 channels_last g / x (/ mask) of one geometry and the data-gradient packing")
+    gs = [g.contiguous(memory_format=cl) for g in gs]
+    dev = gs[0].device
+    L = _lib.lib()
+    need = L.dsrg_conv_igemm_wgrad_workspace(n, B, H, W, cin, cout, ksize)
+    if need == 0 or not conv_igemm_supported(cout, cin, ksize):
+        raise ValueError("conv_igemm_backward_groups: 64 | cout, 128 | cin, k in (1, 3) required (got %d, %d, %d)" % (cout, cin, ksize))
+    ws = _stream_scratch("igemm_wgrad", dev, need)                   # shared with conv_igemm_wgrad
+    gxs = [_dest(gx_outs[i] if gx_outs is not None else None, (B, cin, H, W), torch.bfloat16, dev, True) for i in range(n)]
+    gws = [_dest(gw_outs[i] if gw_outs is not None else None, (cout, cin, ksize, ksize), torch.float32, dev, True) for i in range(n)]
+    gbs = cws = None
+    if masks is not None:
+        gbs = [_bias_grad_dest(gb_outs[i] if gb_outs is not None else None, (cin,), dev) for i in range(n)]
+        cws = _reduction_scratch(dev, L.dsrg_conv_igemm_dgrad_workspace(n, B, H, W, cin))
+    vp = ctypes.c_void_p * n
+    ptrs = lambda ts: vp(*[t.data_ptr() for t in ts])      # noqa: E731
+    check(L.dsrg_conv_igemm_backward_groups_bf16(ptrs(gs), ptrs(packed_d), ptrs(xs), ptrs(masks) if masks is not None else None, ptrs(gxs),
+                                                 ptrs(gws), (ctypes.c_int * n)(*[int(d) for d in dilations]), n,
+                                                 ptrs(gbs) if gbs is not None else None, float(mask_scale), _ptr(cws),
+                                                 cws.numel() if cws is not None else 0, _ptr(ws), ws.numel(), B, H, W, cin, cout, ksize,
+                                                 int(force_ksplit), int(force_order), _stream()))
+    return gxs, gws, gbs
+
+
+def conv_igemm_backward_groups_plan(n, B, H, W, cin, cout, ksize, dilations, with_mask=False, force_ksplit=0, force_order=0):
+    """what conv_igemm_backward_groups does for this geometry under the current variant: a dict with merged (one grid or two launches),
+    w_first (the weight gradient's workgroups take the first block ids), ksplit (its uniform pixel split; 0: its work list), nd / nw
+    (blocks of the two halves), merged_us / separate_us (the dispatch model's prices).  Host only: nothing is launched"""
+    out = (ctypes.c_int * 5)()
+    us = (ctypes.c_double * 2)()
+    check(_lib.lib().dsrg_conv_igemm_backward_groups_plan(int(n), int(B), int(H), int(W), int(cin), int(cout), int(ksize),
+                                                           (ctypes.c_int * n)(*[int(d) for d in dilations]), int(bool(with_mask)),
+                                                           int(force_ksplit), int(force_order), out, us))
+    return {"merged": bool(out[0]), "w_first": bool(out[1]), "ksplit": out[2], "nd": out[3], "nw": out[4],
+            "merged_us": us[0], "separate_us": us[1]}
+
+
 def _igemm_sk_workspace(device):
     """the stream-K scratch of (device, current stream): one accumulator tile per CU + flags — a fixed size, so never replaced"""
     return _stream_scratch("igemm_stream_k", device, _lib.lib().dsrg_conv_igemm_workspace())

@@ -612,6 +612,27 @@ int dsrg_conv_igemm_backward_residual_bf16(const void *g_dev, const void *w_dgra
                                            const void *res_dev, void *gx_dev, float *gw_dev, const float *gw_scale_dev, int dilation,
                                            void *wgrad_workspace_dev, size_t wgrad_workspace_bytes, int B, int H, int W, int cin, int cout,
                                            int ksize, void *stream);
+/* dsrg_conv_igemm_backward_bf16 for 1 - 4 convolutions of one geometry (the four ASPP branches; 3x3 with any dilations, or 1x1): host
+ * arrays of ngroups device pointers as dsrg_conv_igemm_dgrad_bf16 / dsrg_conv_igemm_wgrad_bf16 take them.  mask_dev / bias_grad_dev may
+ * be NULL (both or neither: the layer's inputs are not ReLU outputs with a single consumer).  The grouped data gradient (XCD-interleaved,
+ * class-ordered or row tiles for dilated kernels) and the grouped weight gradient (its per-tap work list for dilated kernels) share one
+ * grid where the launch planner prices that below the two launches, else they run one after the other: the same bits either way.
+ * Data and bias gradients equal dsrg_conv_igemm_dgrad_bf16 / dsrg_conv_igemm_bf16 bit for bit; a weight gradient that runs its work
+ * list equals dsrg_conv_igemm_wgrad_bf16 bit for bit, one on a uniform split does wherever the split is that launch's (it is chosen
+ * for the merged grid; force_ksplit > 0, for tests, sets it as far as the workspace holds it) and else up to fp32 reassociation.  force_order 1 / 2: a merged grid takes the data / weight gradient's
+ * blocks first (0: the planner's order; for tests — the results do not depend on it).  Workspaces: dsrg_conv_igemm_dgrad_workspace(ngroups, B, H, W, cin)
+ * bytes (only with bias_grad_dev) and dsrg_conv_igemm_wgrad_workspace(ngroups, B, H, W, cin, cout, ksize) bytes. */
+int dsrg_conv_igemm_backward_groups_bf16(const void *const *g_dev, const void *const *w_dgrad_dev, const void *const *x_dev,
+                                         const void *const *mask_dev, void *const *gx_dev, void *const *gw_dev, const int *dilation,
+                                         int ngroups, float *const *bias_grad_dev, float mask_scale, void *colsum_workspace_dev,
+                                         size_t colsum_workspace_bytes, void *wgrad_workspace_dev, size_t wgrad_workspace_bytes, int B,
+                                         int H, int W, int cin, int cout, int ksize, int force_ksplit, int force_order, void *stream);
+/* Read-only query (host only, no launch) of what that call does under the current variant: plan_out[0] 1 = one merged grid, 0 = two
+ * launches; [1] 1 = the weight gradient's workgroups take the first block ids; [2] the weight gradient's uniform pixel split (0: it
+ * runs its work list); [3], [4] blocks of the data- / weight-gradient half.  us_out[0], [1]: the dispatch model's price of the choice
+ * and of the two launches, microseconds. */
+int dsrg_conv_igemm_backward_groups_plan(int ngroups, int B, int H, int W, int cin, int cout, int ksize, const int *dilation, int with_mask,
+                                         int force_ksplit, int force_order, int *plan_out, double *us_out);
 /* The four fc8-SEC_k 1x1 classifiers and their Eltwise SUM (train-s.prototxt:461-744) in one pass with float32 weights,
  * float32 accumulation and a float32 NCHW result: out[b][o][hw] = sum_k ( x_k[(b,hw)][:] . w[k][o][:] + bias[k][o] ).
  * x_dev: host array of n_branches (<= 4) device pointers to (B*HW, K) bf16 row-major (NHWC) activations; w_dev

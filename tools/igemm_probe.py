@@ -7,6 +7,8 @@ Prints one line per layer: microseconds (median of the rounds; variants interlea
   python tools/igemm_probe.py --ab A B [--rounds 7]     two debug variants (ops.set_igemm_variant; -1 = the default) of the layer table and
                                                         then of the weight-gradient table, interleaved in every round (after --warm seconds of
                                                         both): every round's time, each arm's spread, each table summed
+  python tools/igemm_probe.py --ab 4 -1 --backward-groups   the whole backward of fc6 x4 and fc7 x4 (ops.conv_igemm_backward_groups: data
+                                                        gradient + weight gradient + reductions per arm), two launches against the merged grid
 """
 import argparse
 import os
@@ -46,6 +48,8 @@ def main():
     ap.add_argument("--ab", type=int, nargs=2, metavar=("A", "B"), default=None)
     ap.add_argument("--warm", type=float, default=1.0, help="--ab: seconds of alternating launches per layer before the timed rounds")
     ap.add_argument("--wgrad-only", action="store_true", help="--ab: the weight-gradient table alone")
+    ap.add_argument("--backward-groups", action="store_true", help="--ab: the grouped whole-backward table alone (fc6 x4, fc7 x4)")
+    ap.add_argument("--force-order", type=int, default=0, help="--backward-groups: 1 / 2 = the data / weight gradient's blocks first in a merged grid")
     args = ap.parse_args()
     B = args.batch
     layers = [  # name, H, W, cin, cout, k, dilations (len = groups)
@@ -62,6 +66,8 @@ def main():
         ("conv3_2 256->256 81x81", 81, 81, 256, 256, 3, [1]),
         ("conv3_1 128->256 81x81", 81, 81, 128, 256, 3, [1]),
     ]
+    if args.ab and args.backward_groups:
+        return variant_ab(BWD_GROUP_LAYERS, B, args.ab, args.rounds, args.iters, args.warm, bwd=True, order=args.force_order)
     if args.ab:
         if not args.wgrad_only:
             variant_ab(layers, B, args.ab, args.rounds, args.iters, args.warm)
@@ -121,15 +127,16 @@ def main():
     absorb_probe(B, args.rounds, args.iters)
 
 
-def variant_ab(layers, B, ab, rounds, iters, warm_s, wgrad=False):
+def variant_ab(layers, B, ab, rounds, iters, warm_s, wgrad=False, bwd=False, order=0):
     """two variants of every layer of the table on random operands, alternating inside every round (A B A B ..), stream-K where the
     launcher picks it (as the train step runs them); wgrad: the weight gradient (ops.conv_igemm_wgrad, float32) of the table
-    instead of the forward.  Per layer: every round of both arms, medians, max - min of each arm; then the
+    instead of the forward; bwd: the whole backward of the table's grouped layers (ops.conv_igemm_backward_groups; a 1x1 layer with
+    masks, Dropout scale and bias gradients as fc7_k runs it).  Per layer: every round of both arms, medians, max - min of each arm; then the
     table summed per round — the figure a decision between the two is taken on: the gain of the summed medians against twice the
     spread of arm A's own rounds"""
     arms = ("A = variant %d" % ab[0], "B = variant %d" % ab[1])
     print("%s%s, %s; batch %d, %.1f s of warm-up per layer, %d rounds of %d launches each; microseconds per launch" % (
-        ("weight gradients: " if wgrad else "",) + arms + (B, warm_s, rounds, iters)))
+        ("whole backward: " if bwd else "weight gradients: " if wgrad else "",) + arms + (B, warm_s, rounds, iters)))
     tot = np.zeros((2, rounds))
     for name, H, W, cin, cout, k, dils in layers:
         n = len(dils)
@@ -138,9 +145,17 @@ def variant_ab(layers, B, ab, rounds, iters, warm_s, wgrad=False):
         packed = [ops.pack_conv_weight((torch.randn(cout, cin, k, k, device="cuda") * (2.0 / (cin * k * k)) ** 0.5).bfloat16()) for _ in range(n)]
         bs = [torch.randn(cout, device="cuda") for _ in range(n)]
 
-        gs = [torch.randn(B, cout, H, W, device="cuda").bfloat16().contiguous(memory_format=CL) for _ in range(n)] if wgrad else None
+        gs = [torch.randn(B, cout, H, W, device="cuda").bfloat16().contiguous(memory_format=CL) for _ in range(n)] if (wgrad or bwd) else None
+        if bwd:
+            xs = [x.relu() for x in xs]                   # the layer's inputs as masks: ReLU outputs
+            packs_d = [ops.pack_conv_weight(torch.randn(cout, cin, k, k, device="cuda") * (2.0 / (cin * k * k)) ** 0.5, for_dgrad=True) for _ in range(n)]
+            print("%-28s plan A %s" % (name, _plan_of(ab[0], n, B, H, W, cin, cout, k, dils, order)))
+            print("%-28s plan B %s" % ("", _plan_of(ab[1], n, B, H, W, cin, cout, k, dils, order)))
 
         def run():
+            if bwd:
+                gx, gw, gb = ops.conv_igemm_backward_groups(gs, packs_d, xs, dils, k, xs if k == 1 else None, 2.0 if k == 1 else 1.0, force_order=order)
+                return list(gx) + list(gw) + list(gb or [])
             if wgrad:
                 return ops.conv_igemm_wgrad(xs, gs, dils, k)
             return ops.conv_igemm(xs, packed, bs, dils, k, True, stream_k=True)
@@ -173,6 +188,14 @@ def variant_ab(layers, B, ab, rounds, iters, warm_s, wgrad=False):
     print("%-28s A %s | med %7.1f spread %5.1f" % ("sum of the table", " ".join("%7.1f" % v for v in tot[0]), med[0], tot[0].max() - tot[0].min()))
     print("%-28s B %s | med %7.1f spread %5.1f | B/A %.4f" % ("", " ".join("%7.1f" % v for v in tot[1]), med[1], tot[1].max() - tot[1].min(), med[1] / med[0]))
     print("gain of the summed medians %.1f us; twice the spread of A's rounds %.1f us" % (med[0] - med[1], 2.0 * (tot[0].max() - tot[0].min())))
+
+
+def _plan_of(variant, n, B, H, W, cin, cout, k, dils, order=0):
+    ops.set_igemm_variant(variant)
+    try:
+        return ops.conv_igemm_backward_groups_plan(n, B, H, W, cin, cout, k, dils, with_mask=k == 1, force_order=order)
+    finally:
+        ops.set_igemm_variant(-1)
 
 
 def absorb_probe(B, rounds, iters):
@@ -210,6 +233,9 @@ WGRAD_LAYERS = [("conv4_2 512->512", 41, 41, 512, 512, 3, [1]), ("conv4_1 256->5
                 ("fc6 512->1024 d12", 41, 41, 512, 1024, 3, [12]), ("fc6 x4 (one launch)", 41, 41, 512, 1024, 3, [6, 12, 18, 24]),
                 ("fc7 1024->1024 1x1", 41, 41, 1024, 1024, 1, [1]), ("fc7 x4 (one launch)", 41, 41, 1024, 1024, 1, [1] * 4),
                 ("conv3_2 256->256 81x81", 81, 81, 256, 256, 3, [1])]
+
+
+BWD_GROUP_LAYERS = [("fc6 x4 backward", 41, 41, 512, 1024, 3, [6, 12, 18, 24]), ("fc7 x4 backward", 41, 41, 1024, 1024, 1, [1] * 4)]
 
 
 def wgrad_probe(B, rounds, iters):
