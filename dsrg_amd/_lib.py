@@ -162,6 +162,11 @@ SIGNATURES = {
     "dsrg_sgd_pack_cast_f32": (_i, [_i] + [_vp] * 10 + [_f, _vp]),
 }
 
+# tests / tools only: exported by api.hip, deliberately not in the public header
+DEBUG_SIGNATURES = {
+    "dsrg_debug_set_direct_grid": (None, [_i]),
+}
+
 _LIB = None
 
 
@@ -178,6 +183,11 @@ def lib():
             fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
+        for name, (res, args) in DEBUG_SIGNATURES.items():
+            if hasattr(L, name):           # (another build named by DSRG_LIB may lack a knob: it then fails where it is used)
+                fn = getattr(L, name)
+                fn.restype = res
+                fn.argtypes = args
         _LIB = L
     return _LIB
 

@@ -64,6 +64,12 @@ extern "C" __attribute__((visibility("default"))) void dsrg_debug_set_build_trac
 // tools only (not in the public header): device buffer of 16 u64 per filter block receiving phase timestamps
 extern "C" __attribute__((visibility("default"))) void dsrg_debug_set_filter_trace(void *dev_buf) { dsrg::g_filter_dbg = dev_buf; }
 
+namespace dsrg { void set_direct_grid_cap(int n); }
+// tests only (not in the public header): the direct 3x3 convolutions (conv_direct.hip) launch at most n persistent workgroups,
+// so that small maps put many tiles on one workgroup; n <= 0 = back to the default.  Never more than the default grid, which is
+// what the column-sum scratch is sized for.  Results do not depend on it, except the summation order of the masked form's bias gradient.
+extern "C" __attribute__((visibility("default"))) void dsrg_debug_set_direct_grid(int n) { dsrg::set_direct_grid_cap(n); }
+
 extern "C" const char *dsrg_last_error(void) { return g_err; }
 
 extern "C" int dsrg_device_count(void) {

@@ -19,8 +19,21 @@
 //    128 -> 64    a wave holds 32 of the outputs, 2 x 2 waves split outputs x pixels
 // so LDS carries only the input: an 8 x 16 pixel output tile with its 10 x 18 halo (pixel stride = channels * 2 + 16 bytes:
 // conflict-free 16-byte reads), double buffered — the next tile's halo is fetched into registers before the MFMAs
-// (v_mfma_f32_32x32x16_bf16) of an M-tile and parked in the other buffer after them.  The output tile goes back through LDS
-// for 16-byte coalesced NHWC stores.
+// (v_mfma_f32_32x32x16_bf16) of an M-tile and parked in the other buffer after them.
+//
+// Two schedules for the tail of an M-tile (template flag PIPE, kPipelined<> says which shape runs which):
+//   pipelined  every shape but the 128 -> 128 forward.  The M-tiles of all of a workgroup's tiles form one sequence; the
+//              accumulators of M-tile k - 1 are finished under the MFMAs of M-tile k: one conversion slice (bias, ReLU, four
+//              bf16, one 8-byte LDS store into the WAVE's OWN staging strip of 32 pixel rows) between the MFMAs of each of the
+//              first 4 TPW steps, then the strip is read back as 16-byte vectors and stored, each pixel's 64 TPW-byte run
+//              contiguous.  No other wave is involved, so a tile has one barrier ("this halo is read, the next has landed");
+//              the last M-tile of a tile is finished under the first of the next, a drain behind the loop finishes the last
+//              one.  Loads, stores and (masked form) the 16 mask bytes of each store vector — loaded one M-tile ahead, the
+//              column sums in 8 registers per lane — are buffer operations with out-of-range offsets for what lies off the
+//              image: the loop body is straight-line code, every wave issues the same number of memory operations per M-tile,
+//              and every wait in front of a halo is counted (vmcnt(N)) — none waits for an output store.
+//   serial     the 128 -> 128 forward (halo by LDS-DMA) and maps of 2 GiB or more: all M-tiles multiplied, barrier, the whole
+//              output tile converted into the halo's buffer, barrier, read back and stored, barrier.
 #include "common.h"
 
 namespace dsrg {
@@ -66,6 +79,14 @@ template <int CIN, int COUT, int TPW_ = (CIN == 64 ? 2 : 1)> struct Cfg {
     static constexpr int VPC = (VPT + MT - 1) / MT;        // per thread and chunk: the fetch is spread over the M-tiles
     static constexpr int OVP = COUT / 8;                   // 16-byte vectors per output pixel
     static constexpr int OVT = kTH * kTW * OVP / 256;      // per thread: 4 / 8
+    // pipelined schedule: a wave's private staging strip, 32 pixel rows of its 32 TPW channels (+ 16 bytes: the rows of a
+    // 16-byte read-back fall on distinct bank groups)
+    static constexpr int SROW = 64 * TPW + 16, STRIP = 32 * SROW;
+    static constexpr int NSL = 4 * TPW;                    // conversion slices per M-tile: one 8-byte LDS store per lane each
+    static constexpr int NV = 2 * TPW;                     // 16-byte vectors per lane and M-tile of the read-back and the store
+    // ... its halo buffer: every thread parks all its VPT vectors, the last ones past the halo in 12 pixel rows of padding
+    static constexpr int HB = (VPT * 256 / VPP) * IN_STRIDE;
+    static constexpr int PIPE_LDS = 2 * HB + 4 * STRIP + COUT * 4;   // halo x 2, strips, bias
     static_assert(NG * PG == 4 && NG >= 1 && MT * PG == 4, "4 waves");
     static_assert(BUF % 16 == 0, "alignment");
 };
@@ -88,7 +109,8 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {   // v_cvt_pk_bf
     return *reinterpret_cast<uint32_t *>(&b);
 }
 
-template <int CIN, int COUT, int TPW_, bool BWD = false>      // BWD: the masked data-gradient form (a.mask / a.colsum)
+// BWD: the masked data-gradient form (a.mask / a.colsum); PIPE: the pipelined schedule (header comment), else the serial one
+template <int CIN, int COUT, int TPW_, bool BWD, bool PIPE>
 __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direct_kernel(ConvArgs a) {
     using C = Cfg<CIN, COUT, TPW_>;
     extern __shared__ __attribute__((aligned(16))) unsigned char conv_lds[];
@@ -124,7 +146,8 @@ __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direc
         y0 = (r / a.tiles_x) * kTH;
         x0 = (r % a.tiles_x) * kTW;
     };
-    constexpr bool kDma = C::DMA && !BWD;                        // (the masked data-gradient instantiation spills 428 bytes a lane with it)
+    // (the masked data-gradient instantiation spills 428 bytes a lane with it; the pipelined schedule stages through registers)
+    constexpr bool kDma = C::DMA && !BWD && !PIPE;
     // (kDma) the halo of tile t straight into LDS.  Wave instruction q = chunk * PB + block lands the 64 pixels [64 block, 64 block + 64) of
     // chunk plane `chunk`; lane = pixel inside the block; a pixel outside the image or beyond the halo reads zeros through the
     // descriptor's range check.  No staging registers, no ds_write pass; the wait moves to the barrier at the end of the tile.
@@ -191,6 +214,190 @@ __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direc
         }
     }
     __syncthreads();
+    if constexpr (PIPE) {
+        // ---- the pipelined schedule.  The M-tiles of all of this workgroup's tiles form one sequence; the accumulators of
+        // M-tile k - 1 (pacc, with the byte offsets poff of its store vectors and, masked form, their mask vectors pmk) are
+        // converted, staged in the wave's own strip and stored between the MFMA clusters of M-tile k: one conversion slice (4
+        // adds, 4 max, 2 packs, one 8-byte LDS store) per step, then the 16-byte read-back, then the stores.  Nothing here
+        // needs another wave, so the tile has ONE barrier: everybody is done with this halo and the next one has landed.
+        // Stores and mask loads are buffer operations — a lane off the image carries an offset beyond the descriptor's range —
+        // so that every wave issues the same number of them whatever the tile: the waits in front of a halo are counted
+        // (vmcnt(N), N younger operations) and none waits for an output store.  Before the first M-tile pacc is zero and every
+        // offset out of range: the same code runs and stores nothing.
+        using v4u = decltype(__builtin_amdgcn_raw_buffer_load_b128(rsrc_t(), 0, 0, 0));
+        constexpr uint32_t kOff = 0x80000000u;
+        constexpr int kRowsPerVec = 64 / C::NSL;                     // strip rows between a lane's read-back vectors
+        const int wv = __builtin_amdgcn_readfirstlane(wave), ngs = wv % C::NG, pgs = wv / C::NG;   // (wave-uniform, and known to be)
+        unsigned char *strip = conv_lds + 2 * C::HB + wv * C::STRIP;
+        const int cgl = lane % C::NSL, row0 = lane / C::NSL;         // this lane's 16-byte channel group of the wave's run, its first row
+        unsigned char *wr = strip + m * C::SROW + kgrp * 8;
+        const unsigned char *rd = strip + row0 * C::SROW + cgl * 16;
+        const rsrc_t ry = make_rsrc(a.y, (size_t)a.B * a.H * a.W * COUT * 2);
+        const rsrc_t rmk = make_rsrc(a.mask, BWD ? (size_t)a.B * a.H * a.W * COUT * 2 : 0);
+        // the bias where the registers have no room for it: in LDS behind the strips, a slice's four values read with the step's operands
+        constexpr bool kBiasLds = !BWD && !kBiasRegs;
+        float *lbias = reinterpret_cast<float *>(conv_lds + 2 * C::HB + 4 * C::STRIP);
+        if (kBiasLds) {
+            if (tid < COUT) lbias[tid] = a.bias ? a.bias[tid] : 0.0f;
+            __syncthreads();
+        }
+        auto bias_slice = [&](int sl) {
+            return kBiasLds ? *reinterpret_cast<const float4 *>(lbias + (ngs * C::TPW + (sl >> 2)) * 32 + (sl & 3) * 8 + kgrp * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        };
+        f32x16 pacc[C::TPW];
+#pragma unroll
+        for (int j = 0; j < C::TPW; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) pacc[j][r] = 0.0f;
+        uint32_t poff[C::NV];
+        v4u pmk[C::NV];
+#pragma unroll
+        for (int u = 0; u < C::NV; u++) {
+            poff[u] = kOff;
+            pmk[u] = v4u{0u, 0u, 0u, 0u};
+        }
+        float csr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // masked form: column sums of this lane's channel group
+        v4u rb[C::NV];
+        // slice sl of the pending M-tile: bias, ReLU, four bf16 = one 8-byte LDS store (the arithmetic of the serial schedule)
+        auto stage = [&](int sl, const float4 &b4) {
+            const int j = sl >> 2, q = sl & 3;
+            const float bq[4] = {b4.x, b4.y, b4.z, b4.w};
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                v[e] = pacc[j][q * 4 + e] + (BWD ? 0.0f : kBiasRegs ? bias_r[j][q][e] : bq[e]);   // (masked form: no bias, by the launcher)
+                v[e] = a.relu ? fmaxf(v[e], 0.0f) : v[e];
+            }
+            *reinterpret_cast<uint2 *>(wr + j * 64 + q * 16) = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+        };
+        auto readback = [&]() {
+#pragma unroll
+            for (int u = 0; u < C::NV; u++) rb[u] = *reinterpret_cast<const v4u *>(rd + u * kRowsPerVec * C::SROW);
+        };
+        auto store = [&]() {
+#pragma unroll
+            for (int u = 0; u < C::NV; u++) {
+                uint32_t w4[4] = {rb[u][0], rb[u][1], rb[u][2], rb[u][3]};
+                if (BWD) {
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const uint32_t y4 = pmk[u][e];
+                        w4[e] &= ((int16_t)(y4 & 0xffffu) > 0 ? 0x0000ffffu : 0u) | ((int32_t)y4 >= 0x10000 ? 0xffff0000u : 0u);
+                        csr[2 * e] += __uint_as_float(w4[e] << 16);          // (pixels outside the image: mask 0)
+                        csr[2 * e + 1] += __uint_as_float(w4[e] & 0xffff0000u);
+                    }
+                }
+                __builtin_amdgcn_raw_buffer_store_b128(v4u{w4[0], w4[1], w4[2], w4[3]}, ry, poff[u], 0, 0);
+            }
+        };
+        // fetch() and park() without a branch: a vector outside the image, past the halo or of a tile that does not exist
+        // reads zeros through the descriptor's range check and is parked all the same (past the halo: in the buffer's padding), so
+        // the loop body is straight-line code and every wave issues the same VPC loads per M-tile
+        auto fetch_b = [&](int tt, bool valid, int c) {
+            int b, y0, x0;
+            tile_origin(tt, b, y0, x0);
+#pragma unroll
+            for (int u = 0; u < C::VPC; u++) {
+                const int v = tid + (c * C::VPC + u) * 256;
+                const int px = v / C::VPP, cg = v % C::VPP, hy = px / kHW, hx = px - hy * kHW;
+                const int yy = y0 - 1 + hy, xx = x0 - 1 + hx;
+                const bool in = valid & (c * C::VPC + u < C::VPT) & (v < C::HALO_VECS) & (yy >= 0) & (yy < a.H) & (xx >= 0) & (xx < a.W);
+                const v4u r = __builtin_amdgcn_raw_buffer_load_b128(rxh, in ? (uint32_t)((b * a.H + yy) * a.W + xx) * (uint32_t)(CIN * 2) + (uint32_t)(cg * 16) : kOff, 0, 0);
+                pre[u] = make_uint4(r[0], r[1], r[2], r[3]);
+            }
+        };
+        auto park_b = [&](unsigned char *buf, int c) {
+#pragma unroll
+            for (int u = 0; u < C::VPC; u++) {
+                const int v = tid + (c * C::VPC + u) * 256;
+                if (c * C::VPC + u < C::VPT) *reinterpret_cast<uint4 *>(buf + (v / C::VPP) * C::IN_STRIDE + (v % C::VPP) * 16) = pre[u];
+            }
+        };
+        for (; t < a.ntiles; t += gridDim.x) {
+            const int tn = t + gridDim.x;
+            const bool more = tn < a.ntiles;
+            unsigned char *in = conv_lds + cur * C::HB, *other = conv_lds + (cur ^ 1) * C::HB;
+            int tb, ty0, tx0;
+            tile_origin(t, tb, ty0, tx0);
+#pragma unroll
+            for (int mt = 0; mt < C::MT; mt++) {
+                fetch_b(tn, more, mt);
+                f32x16 acc[C::TPW];
+#pragma unroll
+                for (int j = 0; j < C::TPW; j++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++) acc[j][r] = 0.0f;
+                const int ty = 2 * (pgs * C::MT + mt) + (m >> 4), tx = m & 15;
+                const unsigned char *lane_base = in + (ty * kHW + tx) * C::IN_STRIDE + kgrp * 16;
+                auto a_ptr = [&](int s) {                            // (the pixel-major image of the serial schedule's loop)
+                    const int tap = s / C::SPT, h = s % C::SPT;
+                    return lane_base + ((tap / 3) * kHW + tap % 3) * C::IN_STRIDE + h * 32 * C::KPS;
+                };
+                constexpr int kFragStep = 32;
+                bf16x8 ar[2][C::KPS];
+#pragma unroll
+                for (int i = 0; i < C::KPS; i++) ar[0][i] = *reinterpret_cast<const bf16x8 *>(a_ptr(0) + i * kFragStep);
+#pragma unroll
+                for (int s = 0; s < C::STEPS; s++) {
+                    if (s + 1 < C::STEPS) {
+#pragma unroll
+                        for (int i = 0; i < C::KPS; i++) ar[(s + 1) & 1][i] = *reinterpret_cast<const bf16x8 *>(a_ptr(s + 1) + i * kFragStep);
+                    }
+                    const float4 b4 = bias_slice(s < C::NSL ? s : 0);
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < C::KPS; i++)
+#pragma unroll
+                        for (int j = 0; j < C::TPW; j++)
+                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][s * C::KPS + i], ar[s & 1][i], acc[j], 0, 0, 0);
+                    if (s < C::NSL) stage(s, b4);                    // the pending M-tile under this one's MFMAs
+                    else if (s == C::NSL) readback();
+                    else if (s == C::NSL + 1) store();
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (C::STEPS <= C::NSL) readback();
+                if (C::STEPS <= C::NSL + 1) store();
+                park_b(other, mt);
+                // this M-tile becomes the pending one: vector u of the lane = strip row row0 + u kRowsPerVec = pixel (row / 16, row % 16)
+                // of tile rows 2 (pg MT + mt), + 1
+#pragma unroll
+                for (int j = 0; j < C::TPW; j++) pacc[j] = acc[j];
+#pragma unroll
+                for (int u = 0; u < C::NV; u++) {
+                    const int row = row0 + u * kRowsPerVec;
+                    const int yy = ty0 + 2 * (pgs * C::MT + mt) + (row >> 4), xx = tx0 + (row & 15);
+                    poff[u] = (yy < a.H && xx < a.W) ? (uint32_t)((tb * a.H + yy) * a.W + xx) * (uint32_t)(COUT * 2) + (uint32_t)(ngs * C::TPW * 64 + cgl * 16) : kOff;
+                    if (BWD) pmk[u] = __builtin_amdgcn_raw_buffer_load_b128(rmk, poff[u], 0, 0);   // one M-tile ahead of its use
+                }
+            }
+            // every wave is done reading `in` and has parked its share of the next halo in `other`.  The instructions, not
+            // __syncthreads(): its fence would wait for this tile's stores (vmcnt(0)); the halo loads were waited for, counted,
+            // by the LDS stores that parked them
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            cur ^= 1;
+        }
+#pragma unroll
+        for (int sl = 0; sl < C::NSL; sl++) stage(sl, bias_slice(sl));   // drain: the last M-tile
+        readback();
+        store();
+        if (BWD) {
+            // one partial bias row per workgroup, fixed order: channel c is summed over the lanes whose channel group holds it, of
+            // the waves that own its 32 TPW outputs (the halo buffers are free: every wave has passed the last tile's barrier)
+            float *red = reinterpret_cast<float *>(conv_lds);       // [256 threads][8]
+#pragma unroll
+            for (int e = 0; e < 8; e++) red[tid * 8 + e] = csr[e];
+            __syncthreads();
+            if (tid < COUT) {
+                const int ngc = tid / (32 * C::TPW), cgc = (tid % (32 * C::TPW)) >> 3, e = tid & 7;
+                float s0 = 0.0f;
+                for (int p = 0; p < C::PG; p++)
+                    for (int i = 0; i < kRowsPerVec; i++) s0 += red[(((p * C::NG + ngc) * 64) + cgc + C::NSL * i) * 8 + e];
+                a.colsum[(size_t)blockIdx.x * COUT + tid] = s0;
+            }
+        }
+        return;
+    }
+    // ---- the serial schedule
     // masked launch: the column sums of this thread's channel group (tid % OVP) over all its tiles live in LDS behind the two
     // tile buffers (own slot per thread: no barrier) — the kernel has no registers to spare
     float *csl = reinterpret_cast<float *>(conv_lds + 2 * C::BUF) + tid * 8;
@@ -340,24 +547,42 @@ __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direc
     }
 }
 
+// tests only (dsrg_debug_set_direct_grid): at most this many workgroups per direct launch; <= 0: the default
+std::atomic<int> g_direct_grid_cap{0};
+
 template <int CIN, int COUT, int TPW_>
 int variant_grid(const ConvArgs &a, int n_cus) {
-    const int slots = n_cus * Cfg<CIN, COUT, TPW_>::WGS;
-    return a.ntiles < slots ? a.ntiles : slots;
+    const int slots = n_cus * Cfg<CIN, COUT, TPW_>::WGS, cap = g_direct_grid_cap.load(std::memory_order_relaxed);
+    const int grid = a.ntiles < slots ? a.ntiles : slots;           // (never above 2 n_cus: what the column-sum scratch is sized for)
+    return cap > 0 && cap < grid ? cap : grid;
+}
+// which schedule a shape runs: the pipelined one where it measured faster
+template <int CIN, int COUT, int TPW_, bool BWD> constexpr bool kPipelined = true;
+// 128 -> 128 forward: a quarter of its tile is LDS-bound MFMA time and 19 % lies behind the last MFMA; pipelined (halo through
+// registers) it measured 126-130 us against 130 us with the DMA halo: inside the noise, so it keeps the serial schedule
+template <> constexpr bool kPipelined<128, 128, 1, false> = false;
+
+template <int CIN, int COUT, int TPW_, bool BWD, bool PIPE>
+int launch_schedule(const ConvArgs &a, int grid, hipStream_t stream) {
+    using C = Cfg<CIN, COUT, TPW_>;
+    static LdsGrant grant;
+    // (serial, masked: + 8 KB of column sums and the tile's mask rows)
+    const size_t lds = PIPE ? (size_t)C::PIPE_LDS : 2 * (size_t)C::BUF + (BWD ? 256 * 8 * sizeof(float) + (size_t)kTH * kTW * COUT * 2 : 0);
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv3x3_direct_kernel<CIN, COUT, TPW_, BWD, PIPE>), lds, grant)) return rc;
+    hipLaunchKernelGGL((conv3x3_direct_kernel<CIN, COUT, TPW_, BWD, PIPE>), dim3(grid), dim3(256), lds, stream, a);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
 }
 template <int CIN, int COUT, int TPW_, bool BWD>              // BWD: the masked data gradient (a.mask set)
 int launch_variant(const ConvArgs &a, int n_cus, hipStream_t stream, int &grid) {
     using C = Cfg<CIN, COUT, TPW_>;
-    static LdsGrant grant;
     // (the DMA halo marks a lane outside the image with byte offset 2^31, which must lie beyond the descriptor's range)
     if (C::DMA && !BWD && (size_t)a.B * a.H * a.W * CIN * 2 >= ((size_t)1 << 31)) return DSRG_ERR_UNSUPPORTED;
     grid = variant_grid<CIN, COUT, TPW_>(a, n_cus);              // persistent: one or two workgroups per CU
-    // (masked: + 8 KB of column sums and the tile's mask rows)
-    const size_t lds = 2 * (size_t)C::BUF + (BWD ? 256 * 8 * sizeof(float) + (size_t)kTH * kTW * COUT * 2 : 0);
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv3x3_direct_kernel<CIN, COUT, TPW_, BWD>), lds, grant)) return rc;
-    hipLaunchKernelGGL((conv3x3_direct_kernel<CIN, COUT, TPW_, BWD>), dim3(grid), dim3(256), lds, stream, a);
-    DSRG_LAUNCH_CHECK();
-    return DSRG_OK;
+    // (the pipelined schedule loads and stores through buffer descriptors with the same out-of-range mark: larger maps run the serial one)
+    if constexpr (kPipelined<CIN, COUT, TPW_, BWD>)
+        if ((size_t)a.B * a.H * a.W * (CIN > COUT ? CIN : COUT) * 2 < ((size_t)1 << 31)) return launch_schedule<CIN, COUT, TPW_, BWD, true>(a, grid, stream);
+    return launch_schedule<CIN, COUT, TPW_, BWD, false>(a, grid, stream);
 }
 // either form of one shape
 template <int CIN, int COUT, int TPW_>
@@ -857,6 +1082,8 @@ int wgrad_grid(int B, int H, int W, int cin, int cout) {
 }
 }  // namespace
 
+void set_direct_grid_cap(int n) { g_direct_grid_cap.store(n > 0 ? n : 0, std::memory_order_relaxed); }
+
 size_t conv3x3_wgrad_workspace(int B, int H, int W, int cin, int cout) {
     if (!wgrad_supported(cin, cout) || B < 1 || H < 1 || W < 1) return 0;
     if (cin == 3) return (size_t)wgrad_grid(B, H, W, cin, cout) * 64 * 64 * sizeof(float);
@@ -912,6 +1139,7 @@ int launch_conv3x3_direct(const void *x, const void *w, const float *bias, void 
         return set_error(DSRG_ERR_INVALID, "conv3x3_direct: %d -> %d channels is not one of 64/128 -> 64/128 or 3 -> 64", cin, cout);
     if ((mask || colsum) && (cin == 3 || !mask || !colsum))
         return set_error(DSRG_ERR_UNSUPPORTED, "conv3x3_direct: the masked form takes 64 / 128 channels, mask and bias gradient together");
+    if (mask && bias) return set_error(DSRG_ERR_UNSUPPORTED, "conv3x3_direct: the masked form adds no bias");
     if (mask && (long long)B * H * W * cout * 2 >= 0x7fffffffLL)
         return set_error(DSRG_ERR_UNSUPPORTED, "conv3x3_direct: mask too large for a 32-bit buffer offset");
     if (colsum && (!colsum_ws || colsum_ws_bytes < conv3x3_direct_colsum_workspace(cout)))
