@@ -5,35 +5,41 @@
 //
 // Why they exist: these layers have few channels and many pixels (1.65 M / 0.41 M per batch of 16).  The im2col route
 // moves 9x the activation (1.9 GB for conv1_2, 0.96 GB for conv2_2) and MIOpen's implicit-GEMM kernels run at ~255 TFLOP/s
-// here (conv1_2: 0.48 ms forward, 0.35 ms data gradient); the layers are memory-bound at ~0.1 ms.  One kernel serves the
-// forward (bias + ReLU in the epilogue) and the data gradient (the same convolution with the kernel flipped and its channel
-// axes swapped, prepared by the caller).
+// here (conv1_2: 0.48 ms forward, 0.35 ms data gradient); the layers are memory-bound at ~0.1 ms.  The same convolution
+// serves the forward (bias + ReLU in the epilogue) and the data gradient (the kernel flipped and its channel axes swapped,
+// prepared by the caller; the masked form applies the ReLU backward of the layer below in its store).
 //
-// Shape of the kernel: persistent workgroups of 4 waves, each wave with its share of the weight tensor in registers as MFMA
-// fragments — 288 VGPRs at one wave per SIMD (the file has 512 at that occupancy), or 144 at two:
+// What the two kernels share: persistent workgroups of 4 waves, each wave with its share of the weight tensor in registers
+// as MFMA fragments — 288 VGPRs at one wave per SIMD (the file has 512 at that occupancy), or 144 at two:
 //     64 -> 64    a wave holds 32 of the outputs (1 tile x 36 k-steps = 144 VGPRs), 2 x 2 waves split outputs x pixels, and TWO
 //                 workgroups share a CU: the 24 KB halo fetch of a workgroup is its only memory parallelism and the kernel is
 //                 bound by exactly that (all 64 outputs per wave, one workgroup per CU: 202 instead of 169 us)
 //     64 -> 128   a wave holds 64 of the outputs, 2 x 2 waves split outputs x pixels (2 M-tiles of 32 pixels per wave)
 //    128 -> 128   a wave holds 32 of the outputs (1 tile x 72 k-steps) and visits all 4 M-tiles
 //    128 -> 64    a wave holds 32 of the outputs, 2 x 2 waves split outputs x pixels
-// so LDS carries only the input: an 8 x 16 pixel output tile with its 10 x 18 halo (pixel stride = channels * 2 + 16 bytes:
-// conflict-free 16-byte reads), double buffered — the next tile's halo is fetched into registers before the MFMAs
-// (v_mfma_f32_32x32x16_bf16) of an M-tile and parked in the other buffer after them.
+// so LDS carries only the input: an 8 x 16 pixel output tile with its 10 x 18 halo, double buffered, multiplied by
+// v_mfma_f32_32x32x16_bf16 with the operands of step s + 1 read before the MFMAs of step s.
 //
-// Two schedules for the tail of an M-tile (template flag PIPE, kPipelined<> says which shape runs which):
-//   pipelined  every shape but the 128 -> 128 forward.  The M-tiles of all of a workgroup's tiles form one sequence; the
-//              accumulators of M-tile k - 1 are finished under the MFMAs of M-tile k: one conversion slice (bias, ReLU, four
-//              bf16, one 8-byte LDS store into the WAVE's OWN staging strip of 32 pixel rows) between the MFMAs of each of the
-//              first 4 TPW steps, then the strip is read back as 16-byte vectors and stored, each pixel's 64 TPW-byte run
-//              contiguous.  No other wave is involved, so a tile has one barrier ("this halo is read, the next has landed");
-//              the last M-tile of a tile is finished under the first of the next, a drain behind the loop finishes the last
-//              one.  Loads, stores and (masked form) the 16 mask bytes of each store vector — loaded one M-tile ahead, the
-//              column sums in 8 registers per lane — are buffer operations with out-of-range offsets for what lies off the
-//              image: the loop body is straight-line code, every wave issues the same number of memory operations per M-tile,
-//              and every wait in front of a halo is counted (vmcnt(N)) — none waits for an output store.
-//   serial     the 128 -> 128 forward (halo by LDS-DMA) and maps of 2 GiB or more: all M-tiles multiplied, barrier, the whole
-//              output tile converted into the halo's buffer, barrier, read back and stored, barrier.
+// conv3x3_direct_pipe_kernel<CIN, COUT, TPW, BWD>: every shape and form but the 128 -> 128 forward.  The halo is a
+//     pixel-major image (pixel stride = channels * 2 + 16 bytes: conflict-free 16-byte reads); the next tile's halo is
+//     fetched into registers before the MFMAs of an M-tile and parked in the other buffer after them.  The M-tiles of all of
+//     a workgroup's tiles form one sequence; the accumulators of M-tile k - 1 are finished under the MFMAs of M-tile k: one
+//     conversion slice (bias, ReLU, four bf16, one 8-byte LDS store into the WAVE's OWN staging strip of 32 pixel rows)
+//     between the MFMAs of each of the first 4 TPW steps, then the strip is read back as 16-byte vectors and stored, each
+//     pixel's 64 TPW-byte run contiguous.  No other wave is involved, so a tile has one barrier ("this halo is read, the
+//     next has landed"); the last M-tile of a tile is finished under the first of the next, a drain behind the loop finishes
+//     the last one.  Loads, stores and (masked form) the 16 mask bytes of each store vector — loaded one M-tile ahead, the
+//     column sums in 8 registers per lane — are buffer operations with out-of-range offsets for what lies off the image: the
+//     loop body is straight-line code, every wave issues the same number of memory operations per M-tile, and every wait
+//     in front of a halo is counted (vmcnt(N)) — none waits for an output store.
+// conv3x3_direct_dma_kernel: the 128 -> 128 forward, where that schedule measured inside the noise (126-130 us against
+//     130 us).  The halo goes straight into LDS by DMA (buffer_load ... lds) as a chunk-major image; per tile: all M-tiles
+//     multiplied, barrier, the whole output tile converted into the halo's buffer, barrier, read back and stored, barrier.
+//
+// Size limit: both kernels address their maps with 32-bit buffer offsets and mark what lies off the image with offset 2^31, so
+// a launch with 64 / 128 channels whose B * H * W * max(cin, cout) * 2 bytes reach 2^31 is refused with DSRG_ERR_UNSUPPORTED,
+// forward and masked alike (until the serial register-halo kernels were retired, forward maps of that size ran for every
+// shape but 128 -> 128).  The 3 -> 64 kernel addresses with 64 bits and has no such limit.
 #include "common.h"
 
 namespace dsrg {
@@ -47,6 +53,7 @@ constexpr int kTH = 8, kTW = 16;             // output tile (pixels): 4 M-tiles 
 constexpr int kHH = kTH + 2, kHW = kTW + 2;  // halo tile
 
 template <int CIN, int COUT, int TPW_ = (CIN == 64 ? 2 : 1)> struct Cfg {
+    // ---- read by both kernels (WGS by variant_grid too)
     static constexpr int CG = CIN / 16;                    // 16-channel k-steps per tap
     static constexpr int KS = 9 * CG;                      // k-steps
     static constexpr int TPW = TPW_;                       // 32-channel output tiles per wave: TPW * KS * 4 = 288 (or 144) VGPRs
@@ -57,39 +64,42 @@ template <int CIN, int COUT, int TPW_ = (CIN == 64 ? 2 : 1)> struct Cfg {
     static constexpr int KPS = WGS == 2 ? 2 : 4;           // k-steps per step of the MFMA loop (the operand prefetch unit)
     static constexpr int SPT = CG / KPS;                   // steps per tap
     static constexpr int STEPS = 9 * SPT;
-    // halo by LDS-DMA (buffer_load ... lds) where it pays (measured at batch 16, round 6: 128 -> 128 152 -> 141 us; 64 -> 64 and
-    // 128 -> 64 unchanged; 64 -> 128 slower, its M-tile pair spills): image CHUNK-MAJOR, [16-byte channel chunk c][halo pixel p],
-    // 16 bytes each.  A DMA wave instruction lands 64 consecutive pixels of one chunk (lane-linear, as the instruction requires); a
-    // fragment read's 16-lane group touches 16 (nearly) consecutive pixels of one chunk = consecutive 16-byte slots: conflict-free
-    // without padding or swizzle, and the address is lane part (pixel * 16 + kgrp * PLANE) + compile-time constant (chunk * PLANE +
-    // tap offset * 16): immediate offsets, as the padded pixel-major image has (an XOR-swizzled pixel-major image makes hipcc form
-    // every step's address up front and spill the register-resident weights)
-    static constexpr bool DMA = CIN == 128 && COUT == 128;
-    static constexpr int CPR = CIN / 8;                    // 16-byte chunks per halo pixel (8 / 16)
-    static constexpr int PB = (kHH * kHW + 63) / 64;       // 64-pixel blocks per chunk plane (3)
-    static constexpr int PLANE = PB * 1024;                // bytes per chunk plane
-    static constexpr int NI = CPR * PB;                    // DMA wave instructions per halo tile (24 / 48)
-    static constexpr int IN_STRIDE = CIN * 2 + 16;         // bytes per halo pixel in LDS (pixel-major image, through registers)
-    static constexpr int OUT_STRIDE = COUT * 2 + 16;       // bytes per pixel of the output tile in LDS (2-way on the 8-byte stores)
-    static constexpr int IN_BYTES = DMA && CPR * PLANE > kHH * kHW * IN_STRIDE ? CPR * PLANE : kHH * kHW * IN_STRIDE, OUT_BYTES = kTH * kTW * OUT_STRIDE;
-    static constexpr int BUF = IN_BYTES > OUT_BYTES ? IN_BYTES : OUT_BYTES;   // a buffer is a halo tile, then an output tile
+    // ---- read by conv3x3_direct_pipe_kernel: the halo through registers into a pixel-major image
+    static constexpr int IN_STRIDE = CIN * 2 + 16;         // bytes per halo pixel in LDS
     static constexpr int VPP = CIN / 8;                    // 16-byte vectors per input pixel
     static constexpr int HALO_VECS = kHH * kHW * VPP;
     static constexpr int VPT = (HALO_VECS + 255) / 256;    // per thread: 6 / 12
-    static constexpr int VPC = (VPT + MT - 1) / MT;        // per thread and chunk: the fetch is spread over the M-tiles
-    static constexpr int OVP = COUT / 8;                   // 16-byte vectors per output pixel
-    static constexpr int OVT = kTH * kTW * OVP / 256;      // per thread: 4 / 8
-    // pipelined schedule: a wave's private staging strip, 32 pixel rows of its 32 TPW channels (+ 16 bytes: the rows of a
-    // 16-byte read-back fall on distinct bank groups)
+    static constexpr int VPC = (VPT + MT - 1) / MT;        // per thread and M-tile: the fetch is spread over the M-tiles
+    // a halo buffer: every thread parks all its VPT vectors, the last ones past the halo in 12 pixel rows of padding
+    static constexpr int HB = (VPT * 256 / VPP) * IN_STRIDE;
+    // a wave's private staging strip, 32 pixel rows of its 32 TPW channels (+ 16 bytes: the rows of a 16-byte read-back fall
+    // on distinct bank groups)
     static constexpr int SROW = 64 * TPW + 16, STRIP = 32 * SROW;
     static constexpr int NSL = 4 * TPW;                    // conversion slices per M-tile: one 8-byte LDS store per lane each
     static constexpr int NV = 2 * TPW;                     // 16-byte vectors per lane and M-tile of the read-back and the store
-    // ... its halo buffer: every thread parks all its VPT vectors, the last ones past the halo in 12 pixel rows of padding
-    static constexpr int HB = (VPT * 256 / VPP) * IN_STRIDE;
-    static constexpr int PIPE_LDS = 2 * HB + 4 * STRIP + COUT * 4;   // halo x 2, strips, bias
+    static constexpr int PIPE_LDS = 2 * HB + 4 * STRIP + COUT * 4;   // its dynamic LDS: halo x 2, strips, bias
+    // ---- read by conv3x3_direct_dma_kernel (Cfg<128, 128, 1> only): the halo by LDS-DMA (buffer_load ... lds), which pays
+    // for this shape alone (measured at batch 16: 128 -> 128 152 -> 141 us; 64 -> 64 and 128 -> 64 unchanged; 64 -> 128 slower,
+    // its M-tile pair spills), as a CHUNK-MAJOR image, [16-byte channel chunk c][halo pixel p], 16 bytes each.  A DMA wave
+    // instruction lands 64 consecutive pixels of one chunk (lane-linear, as the instruction requires); a fragment read's
+    // 16-lane group touches 16 (nearly) consecutive pixels of one chunk = consecutive 16-byte slots: conflict-free without
+    // padding or swizzle, and the address is lane part (pixel * 16 + kgrp * PLANE) + compile-time constant (chunk * PLANE + tap
+    // offset * 16): immediate offsets, as the padded pixel-major image has (an XOR-swizzled pixel-major image makes hipcc form
+    // every step's address up front and spill the register-resident weights)
+    static constexpr int CPR = CIN / 8;                    // 16-byte chunks per halo pixel (16)
+    static constexpr int PB = (kHH * kHW + 63) / 64;       // 64-pixel blocks per chunk plane (3)
+    static constexpr int PLANE = PB * 1024;                // bytes per chunk plane
+    static constexpr int NI = CPR * PB;                    // DMA wave instructions per halo tile (48)
+    static constexpr int OUT_STRIDE = COUT * 2 + 16;       // bytes per pixel of the output tile in LDS (2-way on the 8-byte stores)
+    static constexpr int OVP = COUT / 8;                   // 16-byte vectors per output pixel
+    static constexpr int OVT = kTH * kTW * OVP / 256;      // per thread (8)
+    static constexpr int BUF = CPR * PLANE;                // a buffer is a halo tile, then an output tile; its dynamic LDS: 2 BUF
     static_assert(NG * PG == 4 && NG >= 1 && MT * PG == 4, "4 waves");
-    static_assert(BUF % 16 == 0, "alignment");
 };
+// the dynamic LDS every kernel is launched with (64 -> 64 forward: two workgroups per CU, 131 584 of 163 840 B)
+static_assert(Cfg<64, 64, 1>::PIPE_LDS == 65792 && Cfg<64, 64, 2>::PIPE_LDS == 73984 && Cfg<64, 128, 2>::PIPE_LDS == 74240, "LDS");
+static_assert(Cfg<128, 64, 1>::PIPE_LDS == 114944 && Cfg<128, 128, 1>::PIPE_LDS == 115200, "LDS");
+static_assert(2 * Cfg<128, 128, 1>::BUF == 98304 && kTH * kTW * Cfg<128, 128, 1>::OUT_STRIDE <= Cfg<128, 128, 1>::BUF, "LDS");
 
 struct ConvArgs {
     const uint16_t *x;      // (B, H, W, CIN) bf16
@@ -98,7 +108,7 @@ struct ConvArgs {
     uint16_t *y;            // (B, H, W, COUT) bf16
     int B, H, W, relu, tiles_x, tiles_y, ntiles;
     const uint16_t *mask;   // (B, H, W, COUT) bf16 or nullptr: outputs kept where mask > 0, else zeroed — the ReLU backward of the
-                            // layer below when this launch is a data gradient (conv3x3_direct_kernel only)
+                            // layer below when this launch is a data gradient (conv3x3_direct_pipe_kernel only)
     float *colsum;          // (workgroups, COUT) f32 or nullptr: every workgroup's column sums of what it stored (that layer's
                             // partial bias gradient)
 };
@@ -109,27 +119,60 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {   // v_cvt_pk_bf
     return *reinterpret_cast<uint32_t *>(&b);
 }
 
-// BWD: the masked data-gradient form (a.mask / a.colsum); PIPE: the pipelined schedule (header comment), else the serial one
-template <int CIN, int COUT, int TPW_, bool BWD, bool PIPE>
-__global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direct_kernel(ConvArgs a) {
-    using C = Cfg<CIN, COUT, TPW_>;
-    extern __shared__ __attribute__((aligned(16))) unsigned char conv_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m = lane & 31, kgrp = lane >> 5;
-    const int ng = wave % C::NG, pg = wave / C::NG;
-
-    // ---- this wave's share of the kernel tensor as MFMA fragments: [k][n], n = output channel, k = (tap, input channel)
-    bf16x8 wf[C::TPW][C::KS];
+// ---- what the two kernels share.  m = lane % 32, kgrp = lane / 32; ng: the wave's place across the output channels
+// this wave's share of the kernel tensor as MFMA fragments: [k][n], n = output channel, k = (tap, input channel)
+template <class C>
+__device__ __forceinline__ void load_weight_frags(const uint16_t *w, int ng, int m, int kgrp, bf16x8 (&wf)[C::TPW][C::KS]) {
 #pragma unroll
     for (int j = 0; j < C::TPW; j++)
 #pragma unroll
         for (int ks = 0; ks < C::KS; ks++)
-            wf[j][ks] = *reinterpret_cast<const bf16x8 *>(a.w + (size_t)((ng * C::TPW + j) * 32 + m) * (9 * CIN) + ks * 16 + kgrp * 8);
+            wf[j][ks] = *reinterpret_cast<const bf16x8 *>(w + (size_t)((ng * C::TPW + j) * 32 + m) * (C::KS * 16) + ks * 16 + kgrp * 8);
+}
+// The product is taken transposed, C[row = output channel][col = pixel], so a lane holds runs of four consecutive channels of
+// ONE pixel (row = (reg & 3) + 8 (reg >> 2) + 4 kgrp).  Run q of an accumulator tile: bias, ReLU, four bf16
+__device__ __forceinline__ uint2 finish_run(const f32x16 &acc, int q, const float *bias, int relu) {
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        v[e] = acc[q * 4 + e] + bias[e];
+        v[e] = relu ? fmaxf(v[e], 0.0f) : v[e];
+    }
+    return make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
+}
+__device__ __forceinline__ void tile_origin(const ConvArgs &a, int t, int &b, int &y0, int &x0) {
+    const int per = a.tiles_x * a.tiles_y;
+    b = t / per;
+    const int r = t - b * per;
+    y0 = (r / a.tiles_x) * kTH;
+    x0 = (r % a.tiles_x) * kTW;
+}
+// Two pieces are NOT among them and stand in each kernel: as shared functions they compiled to other kernels than the ones that
+// were measured (profiles/direct_split_isa.txt, direct_split_probe.txt).
+//   the bias registers (7 lines)   as a function its loads pair up into 8-byte ones and the register allocation of the whole kernel
+//                                  shifts: 36 TPW instructions fewer, and the 128 -> 64 forward 1.5 % SLOWER in four runs of four
+//   the MFMA step loop (20 lines)  with the operand address and the work under the MFMAs handed in: other instructions for four of
+//                                  the seven pipelined kernels, two of them masked forms that no probe times
+// About that loop: one wave per SIMD, nothing else hides the LDS latency of the pixel operand, so the 16-byte reads of step
+// s + 1 are issued before the MFMAs of step s; sched_barrier pins that order (left alone, the scheduler sinks every read next to
+// its use and the wave waits out the LDS latency at every step).
 
-    // the bias of the output channels this lane writes: in registers where there is room, re-read in the epilogue otherwise
-    constexpr bool kBiasRegs = C::WGS == 1;
-    float bias_r[kBiasRegs ? C::TPW : 1][4][4];
-    if (kBiasRegs) {
+// BWD: the masked data-gradient form (a.mask / a.colsum)
+template <int CIN, int COUT, int TPW_, bool BWD>
+__global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direct_pipe_kernel(ConvArgs a) {
+    using C = Cfg<CIN, COUT, TPW_>;
+    using v4u = decltype(__builtin_amdgcn_raw_buffer_load_b128(rsrc_t(), 0, 0, 0));
+    extern __shared__ __attribute__((aligned(16))) unsigned char conv_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m = lane & 31, kgrp = lane >> 5;
+    const int ng = wave % C::NG;
+
+    bf16x8 wf[C::TPW][C::KS];
+    load_weight_frags<C>(a.w, ng, m, kgrp, wf);
+    // the bias in registers where there is room; else in LDS behind the strips, a slice's four values read with the step's operands
+    constexpr bool kBiasRegs = C::WGS == 1, kBiasLds = !BWD && !kBiasRegs;   // (masked form: no bias, by the launcher)
+    float bias_r[C::TPW][4][4];
+    if (kBiasRegs) {                                             // bias_r[j][q]: the bias of run q of this lane's tile j
 #pragma unroll
         for (int j = 0; j < C::TPW; j++)
 #pragma unroll
@@ -139,47 +182,11 @@ __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direc
                     bias_r[j][q][e] = a.bias ? a.bias[(ng * C::TPW + j) * 32 + q * 8 + kgrp * 4 + e] : 0.0f;
     }
 
-    auto tile_origin = [&](int t, int &b, int &y0, int &x0) {
-        const int per = a.tiles_x * a.tiles_y;
-        b = t / per;
-        const int r = t - b * per;
-        y0 = (r / a.tiles_x) * kTH;
-        x0 = (r % a.tiles_x) * kTW;
-    };
-    // (the masked data-gradient instantiation spills 428 bytes a lane with it; the pipelined schedule stages through registers)
-    constexpr bool kDma = C::DMA && !BWD && !PIPE;
-    // (kDma) the halo of tile t straight into LDS.  Wave instruction q = chunk * PB + block lands the 64 pixels [64 block, 64 block + 64) of
-    // chunk plane `chunk`; lane = pixel inside the block; a pixel outside the image or beyond the halo reads zeros through the
-    // descriptor's range check.  No staging registers, no ds_write pass; the wait moves to the barrier at the end of the tile.
-    const rsrc_t rxh = make_rsrc(a.x, (size_t)a.B * a.H * a.W * CIN * 2);
-    auto issue_halo = [&](int t, unsigned char *buf) {
-        int b, y0, x0;
-        tile_origin(t, b, y0, x0);
-        const int wv = __builtin_amdgcn_readfirstlane(wave);
-        uint32_t poff[C::PB];                                    // this lane's pixel of each block: byte offset of its row in x, or out of range
-#pragma unroll
-        for (int blk = 0; blk < C::PB; blk++) {
-            const int px = blk * 64 + lane, hy = px / kHW, hx = px - hy * kHW, yy = y0 - 1 + hy, xx = x0 - 1 + hx;
-            const bool in = px < kHH * kHW && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-            poff[blk] = in ? (uint32_t)((b * a.H + yy) * a.W + xx) * (uint32_t)(CIN * 2) : 0x80000000u;
-        }
-#pragma unroll
-        for (int u = 0; u < (C::NI + 3) / 4; u++) {
-            const int q = wv + 4 * u;                            // (wave-uniform)
-            if (q < C::NI) {
-                const int c = q / C::PB, blk = q - c * C::PB;
-                uint32_t off = poff[0];
-#pragma unroll
-                for (int k = 1; k < C::PB; k++) off = blk == k ? poff[k] : off;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rxh, (lds_void *)(buf + q * 1024), 16, off, (uint32_t)(c * 16), 0, 0);
-            }
-        }
-    };
-    // (!kDma) halo vector v of a tile: pixel (hy, hx) of the 10 x 18 halo, 16-byte channel group cg; chunk c of MT per thread
+    // halo vector v of a tile: pixel (hy, hx) of the 10 x 18 halo, 16-byte channel group cg; chunk c of MT per thread
     uint4 pre[C::VPC];
-    auto fetch = [&](int t, int c) {
+    auto fetch = [&](int t, int c) {                             // (the workgroup's first halo only)
         int b, y0, x0;
-        tile_origin(t, b, y0, x0);
+        tile_origin(a, t, b, y0, x0);
 #pragma unroll
         for (int u = 0; u < C::VPC; u++) {
             const int v = tid + (c * C::VPC + u) * 256;
@@ -200,256 +207,267 @@ __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direc
             if (v < C::HALO_VECS) *reinterpret_cast<uint4 *>(buf + (v / C::VPP) * C::IN_STRIDE + (v % C::VPP) * 16) = pre[u];
         }
     };
+    // fetch() and park() without a branch, for the tile loop: a vector outside the image, past the halo or of a tile that does not
+    // exist reads zeros through the descriptor's range check and is parked all the same (past the halo: in the buffer's padding),
+    // so the loop body is straight-line code and every wave issues the same VPC loads per M-tile.  (The first halo keeps the
+    // branchy pair: with this one in its place every kernel comes out one to three hundred instructions shorter, but as another
+    // kernel than the one that was measured, and the probes time only five of the seven.)
+    constexpr uint32_t kOff = 0x80000000u;
+    const rsrc_t rxh = make_rsrc(a.x, (size_t)a.B * a.H * a.W * CIN * 2);
+    auto fetch_b = [&](int tt, bool valid, int c) {
+        int b, y0, x0;
+        tile_origin(a, tt, b, y0, x0);
+#pragma unroll
+        for (int u = 0; u < C::VPC; u++) {
+            const int v = tid + (c * C::VPC + u) * 256;
+            const int px = v / C::VPP, cg = v % C::VPP, hy = px / kHW, hx = px - hy * kHW;
+            const int yy = y0 - 1 + hy, xx = x0 - 1 + hx;
+            const bool in = valid & (c * C::VPC + u < C::VPT) & (v < C::HALO_VECS) & (yy >= 0) & (yy < a.H) & (xx >= 0) & (xx < a.W);
+            const v4u r = __builtin_amdgcn_raw_buffer_load_b128(rxh, in ? (uint32_t)((b * a.H + yy) * a.W + xx) * (uint32_t)(CIN * 2) + (uint32_t)(cg * 16) : kOff, 0, 0);
+            pre[u] = make_uint4(r[0], r[1], r[2], r[3]);
+        }
+    };
+    auto park_b = [&](unsigned char *buf, int c) {
+#pragma unroll
+        for (int u = 0; u < C::VPC; u++) {
+            const int v = tid + (c * C::VPC + u) * 256;
+            if (c * C::VPC + u < C::VPT) *reinterpret_cast<uint4 *>(buf + (v / C::VPP) * C::IN_STRIDE + (v % C::VPP) * 16) = pre[u];
+        }
+    };
 
     int t = blockIdx.x, cur = 0;
     if (t >= a.ntiles) return;
-    if constexpr (kDma) {
-        issue_halo(t, conv_lds);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
 #pragma unroll
-        for (int c = 0; c < C::MT; c++) {
-            fetch(t, c);
-            park(conv_lds, c);
-        }
+    for (int c = 0; c < C::MT; c++) {
+        fetch(t, c);
+        park(conv_lds, c);
     }
     __syncthreads();
-    if constexpr (PIPE) {
-        // ---- the pipelined schedule.  The M-tiles of all of this workgroup's tiles form one sequence; the accumulators of
-        // M-tile k - 1 (pacc, with the byte offsets poff of its store vectors and, masked form, their mask vectors pmk) are
-        // converted, staged in the wave's own strip and stored between the MFMA clusters of M-tile k: one conversion slice (4
-        // adds, 4 max, 2 packs, one 8-byte LDS store) per step, then the 16-byte read-back, then the stores.  Nothing here
-        // needs another wave, so the tile has ONE barrier: everybody is done with this halo and the next one has landed.
-        // Stores and mask loads are buffer operations — a lane off the image carries an offset beyond the descriptor's range —
-        // so that every wave issues the same number of them whatever the tile: the waits in front of a halo are counted
-        // (vmcnt(N), N younger operations) and none waits for an output store.  Before the first M-tile pacc is zero and every
-        // offset out of range: the same code runs and stores nothing.
-        using v4u = decltype(__builtin_amdgcn_raw_buffer_load_b128(rsrc_t(), 0, 0, 0));
-        constexpr uint32_t kOff = 0x80000000u;
-        constexpr int kRowsPerVec = 64 / C::NSL;                     // strip rows between a lane's read-back vectors
-        const int wv = __builtin_amdgcn_readfirstlane(wave), ngs = wv % C::NG, pgs = wv / C::NG;   // (wave-uniform, and known to be)
-        unsigned char *strip = conv_lds + 2 * C::HB + wv * C::STRIP;
-        const int cgl = lane % C::NSL, row0 = lane / C::NSL;         // this lane's 16-byte channel group of the wave's run, its first row
-        unsigned char *wr = strip + m * C::SROW + kgrp * 8;
-        const unsigned char *rd = strip + row0 * C::SROW + cgl * 16;
-        const rsrc_t ry = make_rsrc(a.y, (size_t)a.B * a.H * a.W * COUT * 2);
-        const rsrc_t rmk = make_rsrc(a.mask, BWD ? (size_t)a.B * a.H * a.W * COUT * 2 : 0);
-        // the bias where the registers have no room for it: in LDS behind the strips, a slice's four values read with the step's operands
-        constexpr bool kBiasLds = !BWD && !kBiasRegs;
-        float *lbias = reinterpret_cast<float *>(conv_lds + 2 * C::HB + 4 * C::STRIP);
-        if (kBiasLds) {
-            if (tid < COUT) lbias[tid] = a.bias ? a.bias[tid] : 0.0f;
-            __syncthreads();
-        }
-        auto bias_slice = [&](int sl) {
-            return kBiasLds ? *reinterpret_cast<const float4 *>(lbias + (ngs * C::TPW + (sl >> 2)) * 32 + (sl & 3) * 8 + kgrp * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        };
-        f32x16 pacc[C::TPW];
+    // The M-tiles of all of this workgroup's tiles form one sequence; the accumulators of M-tile k - 1 (pacc, with the byte
+    // offsets poff of its store vectors and, masked form, their mask vectors pmk) are converted, staged in the wave's own strip
+    // and stored between the MFMA clusters of M-tile k: one conversion slice (4 adds, 4 max, 2 packs, one 8-byte LDS store) per
+    // step, then the 16-byte read-back, then the stores.  Nothing here needs another wave, so the tile has ONE barrier:
+    // everybody is done with this halo and the next one has landed.  Stores and mask loads are buffer operations — a lane off
+    // the image carries an offset beyond the descriptor's range — so that every wave issues the same number of them whatever
+    // the tile: the waits in front of a halo are counted (vmcnt(N), N younger operations) and none waits for an output store.
+    // Before the first M-tile pacc is zero and every offset out of range: the same code runs and stores nothing.
+    constexpr int kRowsPerVec = 64 / C::NSL;                     // strip rows between a lane's read-back vectors
+    const int wv = __builtin_amdgcn_readfirstlane(wave), ngs = wv % C::NG, pgs = wv / C::NG;   // (wave-uniform, and known to be)
+    unsigned char *strip = conv_lds + 2 * C::HB + wv * C::STRIP;
+    const int cgl = lane % C::NSL, row0 = lane / C::NSL;         // this lane's 16-byte channel group of the wave's run, its first row
+    unsigned char *wr = strip + m * C::SROW + kgrp * 8;
+    const unsigned char *rd = strip + row0 * C::SROW + cgl * 16;
+    const rsrc_t ry = make_rsrc(a.y, (size_t)a.B * a.H * a.W * COUT * 2);
+    const rsrc_t rmk = make_rsrc(a.mask, BWD ? (size_t)a.B * a.H * a.W * COUT * 2 : 0);
+    float *lbias = reinterpret_cast<float *>(conv_lds + 2 * C::HB + 4 * C::STRIP);
+    if (kBiasLds) {
+        if (tid < COUT) lbias[tid] = a.bias ? a.bias[tid] : 0.0f;
+        __syncthreads();
+    }
+    auto bias_slice = [&](int sl) {
+        return kBiasLds ? *reinterpret_cast<const float4 *>(lbias + (ngs * C::TPW + (sl >> 2)) * 32 + (sl & 3) * 8 + kgrp * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+    f32x16 pacc[C::TPW];
 #pragma unroll
-        for (int j = 0; j < C::TPW; j++)
+    for (int j = 0; j < C::TPW; j++)
 #pragma unroll
-            for (int r = 0; r < 16; r++) pacc[j][r] = 0.0f;
-        uint32_t poff[C::NV];
-        v4u pmk[C::NV];
+        for (int r = 0; r < 16; r++) pacc[j][r] = 0.0f;
+    uint32_t poff[C::NV];
+    v4u pmk[C::NV];
+#pragma unroll
+    for (int u = 0; u < C::NV; u++) {
+        poff[u] = kOff;
+        pmk[u] = v4u{0u, 0u, 0u, 0u};
+    }
+    float csr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // masked form: column sums of this lane's channel group
+    v4u rb[C::NV];
+    // slice sl of the pending M-tile = run sl % 4 of its accumulator tile sl / 4: one 8-byte LDS store
+    auto stage = [&](int sl, const float4 &b4) {
+        const int j = sl >> 2, q = sl & 3;
+        const float bq[4] = {b4.x, b4.y, b4.z, b4.w}, zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        *reinterpret_cast<uint2 *>(wr + j * 64 + q * 16) = finish_run(pacc[j], q, BWD ? zero : kBiasRegs ? bias_r[j][q] : bq, a.relu);
+    };
+    auto readback = [&]() {
+#pragma unroll
+        for (int u = 0; u < C::NV; u++) rb[u] = *reinterpret_cast<const v4u *>(rd + u * kRowsPerVec * C::SROW);
+    };
+    auto store = [&]() {
 #pragma unroll
         for (int u = 0; u < C::NV; u++) {
-            poff[u] = kOff;
-            pmk[u] = v4u{0u, 0u, 0u, 0u};
-        }
-        float csr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // masked form: column sums of this lane's channel group
-        v4u rb[C::NV];
-        // slice sl of the pending M-tile: bias, ReLU, four bf16 = one 8-byte LDS store (the arithmetic of the serial schedule)
-        auto stage = [&](int sl, const float4 &b4) {
-            const int j = sl >> 2, q = sl & 3;
-            const float bq[4] = {b4.x, b4.y, b4.z, b4.w};
-            float v[4];
+            uint32_t w4[4] = {rb[u][0], rb[u][1], rb[u][2], rb[u][3]};
+            if (BWD) {
 #pragma unroll
-            for (int e = 0; e < 4; e++) {
-                v[e] = pacc[j][q * 4 + e] + (BWD ? 0.0f : kBiasRegs ? bias_r[j][q][e] : bq[e]);   // (masked form: no bias, by the launcher)
-                v[e] = a.relu ? fmaxf(v[e], 0.0f) : v[e];
+                for (int e = 0; e < 4; e++) {
+                    const uint32_t y4 = pmk[u][e];
+                    w4[e] &= ((int16_t)(y4 & 0xffffu) > 0 ? 0x0000ffffu : 0u) | ((int32_t)y4 >= 0x10000 ? 0xffff0000u : 0u);
+                    csr[2 * e] += __uint_as_float(w4[e] << 16);          // (pixels outside the image: mask 0)
+                    csr[2 * e + 1] += __uint_as_float(w4[e] & 0xffff0000u);
+                }
             }
-            *reinterpret_cast<uint2 *>(wr + j * 64 + q * 16) = make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-        };
-        auto readback = [&]() {
+            __builtin_amdgcn_raw_buffer_store_b128(v4u{w4[0], w4[1], w4[2], w4[3]}, ry, poff[u], 0, 0);
+        }
+    };
+    for (; t < a.ntiles; t += gridDim.x) {
+        const int tn = t + gridDim.x;
+        const bool more = tn < a.ntiles;
+        unsigned char *in = conv_lds + cur * C::HB, *other = conv_lds + (cur ^ 1) * C::HB;
+        int tb, ty0, tx0;
+        tile_origin(a, t, tb, ty0, tx0);
 #pragma unroll
-            for (int u = 0; u < C::NV; u++) rb[u] = *reinterpret_cast<const v4u *>(rd + u * kRowsPerVec * C::SROW);
-        };
-        auto store = [&]() {
+        for (int mt = 0; mt < C::MT; mt++) {
+            fetch_b(tn, more, mt);
+            f32x16 acc[C::TPW];
+#pragma unroll
+            for (int j = 0; j < C::TPW; j++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) acc[j][r] = 0.0f;
+            // this wave's 32 pixels of the M-tile: tile rows 2 i, 2 i + 1; A[m][k]: m = pixel, k = (tap, channel).  Fragment i of
+            // step s: bytes [h * 32 KPS + 32 i + 16 kgrp, + 16) of the row of halo pixel (ty + tap / 3, tx + tap % 3)
+            const int ty = 2 * (pgs * C::MT + mt) + (m >> 4), tx = m & 15;
+            const unsigned char *lane_base = in + (ty * kHW + tx) * C::IN_STRIDE + kgrp * 16;
+            auto a_ptr = [&](int s) {
+                const int tap = s / C::SPT, h = s % C::SPT;
+                return lane_base + ((tap / 3) * kHW + tap % 3) * C::IN_STRIDE + h * 32 * C::KPS;
+            };
+            constexpr int kFragStep = 32;
+            bf16x8 ar[2][C::KPS];
+#pragma unroll
+            for (int i = 0; i < C::KPS; i++) ar[0][i] = *reinterpret_cast<const bf16x8 *>(a_ptr(0) + i * kFragStep);
+#pragma unroll
+            for (int s = 0; s < C::STEPS; s++) {
+                if (s + 1 < C::STEPS) {
+#pragma unroll
+                    for (int i = 0; i < C::KPS; i++) ar[(s + 1) & 1][i] = *reinterpret_cast<const bf16x8 *>(a_ptr(s + 1) + i * kFragStep);
+                }
+                const float4 b4 = bias_slice(s < C::NSL ? s : 0);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < C::KPS; i++)
+#pragma unroll
+                    for (int j = 0; j < C::TPW; j++)
+                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][s * C::KPS + i], ar[s & 1][i], acc[j], 0, 0, 0);
+                if (s < C::NSL) stage(s, b4);                    // the pending M-tile under this one's MFMAs
+                else if (s == C::NSL) readback();
+                else if (s == C::NSL + 1) store();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (C::STEPS <= C::NSL) readback();
+            if (C::STEPS <= C::NSL + 1) store();
+            park_b(other, mt);
+            // this M-tile becomes the pending one: vector u of the lane = strip row row0 + u kRowsPerVec = pixel (row / 16, row % 16)
+            // of tile rows 2 (pg MT + mt), + 1
+#pragma unroll
+            for (int j = 0; j < C::TPW; j++) pacc[j] = acc[j];
 #pragma unroll
             for (int u = 0; u < C::NV; u++) {
-                uint32_t w4[4] = {rb[u][0], rb[u][1], rb[u][2], rb[u][3]};
-                if (BWD) {
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const uint32_t y4 = pmk[u][e];
-                        w4[e] &= ((int16_t)(y4 & 0xffffu) > 0 ? 0x0000ffffu : 0u) | ((int32_t)y4 >= 0x10000 ? 0xffff0000u : 0u);
-                        csr[2 * e] += __uint_as_float(w4[e] << 16);          // (pixels outside the image: mask 0)
-                        csr[2 * e + 1] += __uint_as_float(w4[e] & 0xffff0000u);
-                    }
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(v4u{w4[0], w4[1], w4[2], w4[3]}, ry, poff[u], 0, 0);
-            }
-        };
-        // fetch() and park() without a branch: a vector outside the image, past the halo or of a tile that does not exist
-        // reads zeros through the descriptor's range check and is parked all the same (past the halo: in the buffer's padding), so
-        // the loop body is straight-line code and every wave issues the same VPC loads per M-tile
-        auto fetch_b = [&](int tt, bool valid, int c) {
-            int b, y0, x0;
-            tile_origin(tt, b, y0, x0);
-#pragma unroll
-            for (int u = 0; u < C::VPC; u++) {
-                const int v = tid + (c * C::VPC + u) * 256;
-                const int px = v / C::VPP, cg = v % C::VPP, hy = px / kHW, hx = px - hy * kHW;
-                const int yy = y0 - 1 + hy, xx = x0 - 1 + hx;
-                const bool in = valid & (c * C::VPC + u < C::VPT) & (v < C::HALO_VECS) & (yy >= 0) & (yy < a.H) & (xx >= 0) & (xx < a.W);
-                const v4u r = __builtin_amdgcn_raw_buffer_load_b128(rxh, in ? (uint32_t)((b * a.H + yy) * a.W + xx) * (uint32_t)(CIN * 2) + (uint32_t)(cg * 16) : kOff, 0, 0);
-                pre[u] = make_uint4(r[0], r[1], r[2], r[3]);
-            }
-        };
-        auto park_b = [&](unsigned char *buf, int c) {
-#pragma unroll
-            for (int u = 0; u < C::VPC; u++) {
-                const int v = tid + (c * C::VPC + u) * 256;
-                if (c * C::VPC + u < C::VPT) *reinterpret_cast<uint4 *>(buf + (v / C::VPP) * C::IN_STRIDE + (v % C::VPP) * 16) = pre[u];
-            }
-        };
-        for (; t < a.ntiles; t += gridDim.x) {
-            const int tn = t + gridDim.x;
-            const bool more = tn < a.ntiles;
-            unsigned char *in = conv_lds + cur * C::HB, *other = conv_lds + (cur ^ 1) * C::HB;
-            int tb, ty0, tx0;
-            tile_origin(t, tb, ty0, tx0);
-#pragma unroll
-            for (int mt = 0; mt < C::MT; mt++) {
-                fetch_b(tn, more, mt);
-                f32x16 acc[C::TPW];
-#pragma unroll
-                for (int j = 0; j < C::TPW; j++)
-#pragma unroll
-                    for (int r = 0; r < 16; r++) acc[j][r] = 0.0f;
-                const int ty = 2 * (pgs * C::MT + mt) + (m >> 4), tx = m & 15;
-                const unsigned char *lane_base = in + (ty * kHW + tx) * C::IN_STRIDE + kgrp * 16;
-                auto a_ptr = [&](int s) {                            // (the pixel-major image of the serial schedule's loop)
-                    const int tap = s / C::SPT, h = s % C::SPT;
-                    return lane_base + ((tap / 3) * kHW + tap % 3) * C::IN_STRIDE + h * 32 * C::KPS;
-                };
-                constexpr int kFragStep = 32;
-                bf16x8 ar[2][C::KPS];
-#pragma unroll
-                for (int i = 0; i < C::KPS; i++) ar[0][i] = *reinterpret_cast<const bf16x8 *>(a_ptr(0) + i * kFragStep);
-#pragma unroll
-                for (int s = 0; s < C::STEPS; s++) {
-                    if (s + 1 < C::STEPS) {
-#pragma unroll
-                        for (int i = 0; i < C::KPS; i++) ar[(s + 1) & 1][i] = *reinterpret_cast<const bf16x8 *>(a_ptr(s + 1) + i * kFragStep);
-                    }
-                    const float4 b4 = bias_slice(s < C::NSL ? s : 0);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < C::KPS; i++)
-#pragma unroll
-                        for (int j = 0; j < C::TPW; j++)
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][s * C::KPS + i], ar[s & 1][i], acc[j], 0, 0, 0);
-                    if (s < C::NSL) stage(s, b4);                    // the pending M-tile under this one's MFMAs
-                    else if (s == C::NSL) readback();
-                    else if (s == C::NSL + 1) store();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if (C::STEPS <= C::NSL) readback();
-                if (C::STEPS <= C::NSL + 1) store();
-                park_b(other, mt);
-                // this M-tile becomes the pending one: vector u of the lane = strip row row0 + u kRowsPerVec = pixel (row / 16, row % 16)
-                // of tile rows 2 (pg MT + mt), + 1
-#pragma unroll
-                for (int j = 0; j < C::TPW; j++) pacc[j] = acc[j];
-#pragma unroll
-                for (int u = 0; u < C::NV; u++) {
-                    const int row = row0 + u * kRowsPerVec;
-                    const int yy = ty0 + 2 * (pgs * C::MT + mt) + (row >> 4), xx = tx0 + (row & 15);
-                    poff[u] = (yy < a.H && xx < a.W) ? (uint32_t)((tb * a.H + yy) * a.W + xx) * (uint32_t)(COUT * 2) + (uint32_t)(ngs * C::TPW * 64 + cgl * 16) : kOff;
-                    if (BWD) pmk[u] = __builtin_amdgcn_raw_buffer_load_b128(rmk, poff[u], 0, 0);   // one M-tile ahead of its use
-                }
-            }
-            // every wave is done reading `in` and has parked its share of the next halo in `other`.  The instructions, not
-            // __syncthreads(): its fence would wait for this tile's stores (vmcnt(0)); the halo loads were waited for, counted,
-            // by the LDS stores that parked them
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            cur ^= 1;
-        }
-#pragma unroll
-        for (int sl = 0; sl < C::NSL; sl++) stage(sl, bias_slice(sl));   // drain: the last M-tile
-        readback();
-        store();
-        if (BWD) {
-            // one partial bias row per workgroup, fixed order: channel c is summed over the lanes whose channel group holds it, of
-            // the waves that own its 32 TPW outputs (the halo buffers are free: every wave has passed the last tile's barrier)
-            float *red = reinterpret_cast<float *>(conv_lds);       // [256 threads][8]
-#pragma unroll
-            for (int e = 0; e < 8; e++) red[tid * 8 + e] = csr[e];
-            __syncthreads();
-            if (tid < COUT) {
-                const int ngc = tid / (32 * C::TPW), cgc = (tid % (32 * C::TPW)) >> 3, e = tid & 7;
-                float s0 = 0.0f;
-                for (int p = 0; p < C::PG; p++)
-                    for (int i = 0; i < kRowsPerVec; i++) s0 += red[(((p * C::NG + ngc) * 64) + cgc + C::NSL * i) * 8 + e];
-                a.colsum[(size_t)blockIdx.x * COUT + tid] = s0;
+                const int row = row0 + u * kRowsPerVec;
+                const int yy = ty0 + 2 * (pgs * C::MT + mt) + (row >> 4), xx = tx0 + (row & 15);
+                poff[u] = (yy < a.H && xx < a.W) ? (uint32_t)((tb * a.H + yy) * a.W + xx) * (uint32_t)(COUT * 2) + (uint32_t)(ngs * C::TPW * 64 + cgl * 16) : kOff;
+                if (BWD) pmk[u] = __builtin_amdgcn_raw_buffer_load_b128(rmk, poff[u], 0, 0);   // one M-tile ahead of its use
             }
         }
-        return;
+        // every wave is done reading `in` and has parked its share of the next halo in `other`.  The instructions, not
+        // __syncthreads(): its fence would wait for this tile's stores (vmcnt(0)); the halo loads were waited for, counted,
+        // by the LDS stores that parked them
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        cur ^= 1;
     }
-    // ---- the serial schedule
-    // masked launch: the column sums of this thread's channel group (tid % OVP) over all its tiles live in LDS behind the two
-    // tile buffers (own slot per thread: no barrier) — the kernel has no registers to spare
-    float *csl = reinterpret_cast<float *>(conv_lds + 2 * C::BUF) + tid * 8;
+#pragma unroll
+    for (int sl = 0; sl < C::NSL; sl++) stage(sl, bias_slice(sl));   // drain: the last M-tile
+    readback();
+    store();
     if (BWD) {
+        // one partial bias row per workgroup, fixed order: channel c is summed over the lanes whose channel group holds it, of
+        // the waves that own its 32 TPW outputs (the halo buffers are free: every wave has passed the last tile's barrier)
+        float *red = reinterpret_cast<float *>(conv_lds);       // [256 threads][8]
 #pragma unroll
-        for (int e = 0; e < 8; e++) csl[e] = 0.0f;
+        for (int e = 0; e < 8; e++) red[tid * 8 + e] = csr[e];
+        __syncthreads();
+        if (tid < COUT) {
+            const int ngc = tid / (32 * C::TPW), cgc = (tid % (32 * C::TPW)) >> 3, e = tid & 7;
+            float s0 = 0.0f;
+            for (int p = 0; p < C::PG; p++)
+                for (int i = 0; i < kRowsPerVec; i++) s0 += red[(((p * C::NG + ngc) * 64) + cgc + C::NSL * i) * 8 + e];
+            a.colsum[(size_t)blockIdx.x * COUT + tid] = s0;
+        }
     }
-    // ... and the tile's mask rows are brought into LDS by DMA while the tile is computed (vector v = tid + 256 u of the store
-    // phase at byte 16 v: a wave's 64 lanes land back to back, pixels outside the image read zeros through the descriptor's range)
-    unsigned char *mtile = conv_lds + 2 * C::BUF + 256 * 8 * sizeof(float);
-    const rsrc_t rmask = make_rsrc(a.mask, BWD ? (size_t)a.B * a.H * a.W * COUT * 2 : 0);
+}
+
+// The 128 -> 128 forward.  The halo of a tile goes straight into LDS: wave instruction q = chunk * PB + block lands the 64 pixels
+// [64 block, 64 block + 64) of chunk plane `chunk`; lane = pixel inside the block; a pixel outside the image or beyond the halo
+// reads zeros through the descriptor's range check.  No staging registers, no ds_write pass; the wait for the next tile's halo
+// sits at the barrier at the end of the tile.
+__global__ __launch_bounds__(256, 1) void conv3x3_direct_dma_kernel(ConvArgs a) {
+    using C = Cfg<128, 128, 1>;
+    constexpr int CIN = 128, COUT = 128;
+    extern __shared__ __attribute__((aligned(16))) unsigned char conv_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m = lane & 31, kgrp = lane >> 5;
+    const int ng = wave % C::NG, pg = wave / C::NG;
+
+    bf16x8 wf[C::TPW][C::KS];
+    load_weight_frags<C>(a.w, ng, m, kgrp, wf);
+    float bias_r[C::TPW][4][4];
+#pragma unroll
+    for (int j = 0; j < C::TPW; j++)                             // (as in the pipelined kernel: see the note above it)
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                bias_r[j][q][e] = a.bias ? a.bias[(ng * C::TPW + j) * 32 + q * 8 + kgrp * 4 + e] : 0.0f;
+
+    const rsrc_t rxh = make_rsrc(a.x, (size_t)a.B * a.H * a.W * CIN * 2);
+    auto issue_halo = [&](int t, unsigned char *buf) {
+        int b, y0, x0;
+        tile_origin(a, t, b, y0, x0);
+        const int wv = __builtin_amdgcn_readfirstlane(wave);
+        uint32_t poff[C::PB];                                    // this lane's pixel of each block: byte offset of its row in x, or out of range
+#pragma unroll
+        for (int blk = 0; blk < C::PB; blk++) {
+            const int px = blk * 64 + lane, hy = px / kHW, hx = px - hy * kHW, yy = y0 - 1 + hy, xx = x0 - 1 + hx;
+            const bool in = px < kHH * kHW && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
+            poff[blk] = in ? (uint32_t)((b * a.H + yy) * a.W + xx) * (uint32_t)(CIN * 2) : 0x80000000u;
+        }
+#pragma unroll
+        for (int u = 0; u < (C::NI + 3) / 4; u++) {
+            const int q = wv + 4 * u;                            // (wave-uniform)
+            if (q < C::NI) {
+                const int c = q / C::PB, blk = q - c * C::PB;
+                uint32_t off = poff[0];
+#pragma unroll
+                for (int k = 1; k < C::PB; k++) off = blk == k ? poff[k] : off;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rxh, (lds_void *)(buf + q * 1024), 16, off, (uint32_t)(c * 16), 0, 0);
+            }
+        }
+    };
+
+    int t = blockIdx.x, cur = 0;
+    if (t >= a.ntiles) return;
+    issue_halo(t, conv_lds);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
     for (; t < a.ntiles; t += gridDim.x) {
         const int tn = t + gridDim.x;
         const bool more = tn < a.ntiles;
         unsigned char *in = conv_lds + cur * C::BUF, *other = conv_lds + (cur ^ 1) * C::BUF;
-        if (BWD) {
-            int b, y0, x0;
-            tile_origin(t, b, y0, x0);
-            const int wv = __builtin_amdgcn_readfirstlane(wave);
-#pragma unroll
-            for (int u = 0; u < C::OVT; u++) {
-                const int v = tid + u * 256, px = v / C::OVP, cg = v % C::OVP;
-                const int yy = y0 + (px >> 4), xx = x0 + (px & 15);
-                const uint32_t off = (yy < a.H && xx < a.W) ? (uint32_t)((b * a.H + yy) * a.W + xx) * (uint32_t)(COUT * 2) + (uint32_t)(cg * 16) : 0x80000000u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rmask, (lds_void *)(mtile + (u * 256 + wv * 64) * 16), 16, off, 0, 0, 0);
-            }
-        }
-        if constexpr (kDma)
-            if (more) issue_halo(tn, other);                     // the next tile's halo on its way while this one is computed
+        if (more) issue_halo(tn, other);                         // the next tile's halo on its way while this one is computed
         f32x16 acc[C::MT][C::TPW];
 #pragma unroll
         for (int mt = 0; mt < C::MT; mt++) {
-            if constexpr (!kDma)
-                if (more) fetch(tn, mt);                         // a slice of the next halo on its way while this M-tile computes
 #pragma unroll
             for (int j = 0; j < C::TPW; j++)
 #pragma unroll
                 for (int r = 0; r < 16; r++) acc[mt][j][r] = 0.0f;
-            // this wave's 32 pixels of the M-tile: tile rows 2 i, 2 i + 1; A[m][k]: m = pixel, k = (tap, channel)
+            // this wave's 32 pixels of the M-tile: tile rows 2 i, 2 i + 1; A[m][k]: m = pixel, k = (tap, channel).  Fragment i of
+            // step s: chunk h * 2 KPS + 2 i + kgrp of halo pixel (ty + tap / 3, tx + tap % 3)
             const int ty = 2 * (pg * C::MT + mt) + (m >> 4), tx = m & 15;
-            // one wave per SIMD: nothing else hides the LDS latency of the pixel operand, so the four 16-byte reads of step
-            // s + 1 are issued before the MFMAs of step s; sched_barrier pins that order (left alone, the scheduler sinks
-            // every read next to its use and the wave waits out the LDS latency at every step)
-            // fragment i of step s — chunk-major image: chunk h * 2 KPS + 2 i + kgrp of halo pixel (ty + tap / 3, tx + tap % 3);
-            // pixel-major image: bytes [h * 32 KPS + 32 i + 16 kgrp, + 16) of that pixel's row
-            const unsigned char *lane_base = kDma ? in + (ty * kHW + tx) * 16 + kgrp * C::PLANE : in + (ty * kHW + tx) * C::IN_STRIDE + kgrp * 16;
+            const unsigned char *lane_base = in + (ty * kHW + tx) * 16 + kgrp * C::PLANE;
             auto a_ptr = [&](int s) {
                 const int tap = s / C::SPT, h = s % C::SPT;
-                return lane_base + ((tap / 3) * kHW + tap % 3) * (kDma ? 16 : C::IN_STRIDE) + h * (kDma ? 2 * C::KPS * C::PLANE : 32 * C::KPS);
+                return lane_base + ((tap / 3) * kHW + tap % 3) * 16 + h * 2 * C::KPS * C::PLANE;
             };
-            constexpr int kFragStep = kDma ? 2 * C::PLANE : 32;  // fragment i + 1: two chunks further
-            bf16x8 ar[2][C::KPS];
+            constexpr int kFragStep = 2 * C::PLANE;              // fragment i + 1: two chunks further
+            bf16x8 ar[2][C::KPS];                                // (the step loop of the pipelined kernel without its tail work)
 #pragma unroll
             for (int i = 0; i < C::KPS; i++) ar[0][i] = *reinterpret_cast<const bf16x8 *>(a_ptr(0) + i * kFragStep);
 #pragma unroll
@@ -466,84 +484,34 @@ __global__ __launch_bounds__(256, (TPW_ * CIN <= 64 ? 2 : 1)) void conv3x3_direc
                         acc[mt][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j][s * C::KPS + i], ar[s & 1][i], acc[mt][j], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (!kDma)
-                if (more) park(other, mt);
         }
         __syncthreads();                                         // every wave is done reading the halo in `in`
-        // epilogue: the product is taken transposed, C[row = output channel][col = pixel], so a lane holds runs of four
-        // consecutive channels of ONE pixel (row = (reg & 3) + 8 (reg >> 2) + 4 kgrp): bias, ReLU, four bf16 = one 8-byte LDS
-        // store per run into the output tile [128 pixels][COUT channels] (rows of OUT_STRIDE bytes) in the same buffer
+        // epilogue: one 8-byte LDS store per run into the output tile [128 pixels][COUT channels] (rows of OUT_STRIDE bytes) in
+        // the same buffer
         unsigned char *ot = in;
 #pragma unroll
-        for (int mt = 0; mt < C::MT; mt++) {
+        for (int mt = 0; mt < C::MT; mt++)
 #pragma unroll
-            for (int j = 0; j < C::TPW; j++) {
+            for (int j = 0; j < C::TPW; j++)
 #pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int c0 = (ng * C::TPW + j) * 32 + q * 8 + kgrp * 4;
-                    float v[4], bq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                    if (!kBiasRegs && a.bias) {
-                        const float4 b4 = *reinterpret_cast<const float4 *>(a.bias + c0);
-                        bq[0] = b4.x; bq[1] = b4.y; bq[2] = b4.z; bq[3] = b4.w;
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        v[e] = acc[mt][j][q * 4 + e] + (kBiasRegs ? bias_r[j][q][e] : bq[e]);
-                        if (a.relu) v[e] = fmaxf(v[e], 0.0f);
-                    }
-                    *reinterpret_cast<uint2 *>(ot + ((pg * C::MT + mt) * 32 + m) * C::OUT_STRIDE + c0 * 2) =
-                        make_uint2(pack2(v[0], v[1]), pack2(v[2], v[3]));
-                }
-            }
-        }
-        if (BWD) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this thread's mask rows have landed (it reads back its own)
+                for (int q = 0; q < 4; q++)
+                    *reinterpret_cast<uint2 *>(ot + ((pg * C::MT + mt) * 32 + m) * C::OUT_STRIDE + ((ng * C::TPW + j) * 32 + q * 8 + kgrp * 4) * 2) =
+                        finish_run(acc[mt][j], q, bias_r[j][q], a.relu);
         __syncthreads();
         {
             int b, y0, x0;
-            tile_origin(t, b, y0, x0);
-            float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            tile_origin(a, t, b, y0, x0);
 #pragma unroll
             for (int u = 0; u < C::OVT; u++) {                   // 128 pixels x OVP vectors of 16 bytes
                 const int v = tid + u * 256, px = v / C::OVP, cg = v % C::OVP;
                 const int yy = y0 + (px >> 4), xx = x0 + (px & 15);
-                uint4 val = *reinterpret_cast<const uint4 *>(ot + px * C::OUT_STRIDE + cg * 16);
-                if (BWD) {
-                    uint32_t w4[4] = {val.x, val.y, val.z, val.w};
-                    const uint4 mkv = *reinterpret_cast<const uint4 *>(mtile + v * 16);
-                    const uint32_t y4[4] = {mkv.x, mkv.y, mkv.z, mkv.w};
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        w4[e] &= ((int16_t)(y4[e] & 0xffffu) > 0 ? 0x0000ffffu : 0u) | ((int32_t)y4[e] >= 0x10000 ? 0xffff0000u : 0u);
-                        cs[2 * e] += __uint_as_float(w4[e] << 16);          // (pixels outside the image: mask 0)
-                        cs[2 * e + 1] += __uint_as_float(w4[e] & 0xffff0000u);
-                    }
-                    val = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-                }
-                if (yy < a.H && xx < a.W)
-                    *reinterpret_cast<uint4 *>(a.y + (((size_t)b * a.H + yy) * a.W + xx) * COUT + cg * 8) = val;
-            }
-            if (BWD) {
-#pragma unroll
-                for (int e = 0; e < 8; e++) csl[e] += cs[e];
+                const uint4 val = *reinterpret_cast<const uint4 *>(ot + px * C::OUT_STRIDE + cg * 16);
+                if (yy < a.H && xx < a.W) *reinterpret_cast<uint4 *>(a.y + (((size_t)b * a.H + yy) * a.W + xx) * COUT + cg * 8) = val;
             }
         }
-        if constexpr (kDma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the next halo have landed (the barrier: everybody's)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this wave's pieces of the next halo have landed (the barrier: everybody's)
         __syncthreads();                                         // this buffer is free for the tile after next
         cur ^= 1;
-    }
-    if (BWD) {                                                   // one partial bias row per workgroup, fixed order
-        const float *red = reinterpret_cast<const float *>(conv_lds + 2 * C::BUF);        // [256 threads][8]
-        __syncthreads();
-        if (tid < COUT) {
-            const int cg = tid >> 3, e = tid & 7;
-            float s0 = 0.0f, s1 = 0.0f;
-#pragma unroll 4
-            for (int i = 0; i < 256 / C::OVP; i += 2) {
-                s0 += red[(cg + C::OVP * i) * 8 + e];
-                s1 += red[(cg + C::OVP * (i + 1)) * 8 + e];
-            }
-            a.colsum[(size_t)blockIdx.x * COUT + tid] = s0 + s1;
-        }
     }
 }
 
@@ -556,38 +524,29 @@ int variant_grid(const ConvArgs &a, int n_cus) {
     const int grid = a.ntiles < slots ? a.ntiles : slots;           // (never above 2 n_cus: what the column-sum scratch is sized for)
     return cap > 0 && cap < grid ? cap : grid;
 }
-// which schedule a shape runs: the pipelined one where it measured faster
-template <int CIN, int COUT, int TPW_, bool BWD> constexpr bool kPipelined = true;
-// 128 -> 128 forward: a quarter of its tile is LDS-bound MFMA time and 19 % lies behind the last MFMA; pipelined (halo through
-// registers) it measured 126-130 us against 130 us with the DMA halo: inside the noise, so it keeps the serial schedule
-template <> constexpr bool kPipelined<128, 128, 1, false> = false;
-
-template <int CIN, int COUT, int TPW_, bool BWD, bool PIPE>
-int launch_schedule(const ConvArgs &a, int grid, hipStream_t stream) {
-    using C = Cfg<CIN, COUT, TPW_>;
+// one 64 / 128-channel launch: the kernel, its dynamic LDS (and who remembers that it was granted), its persistent grid
+struct DirectLaunch {
+    void (*kernel)(ConvArgs);
+    size_t lds;
+    int grid;
+    LdsGrant *grant;
+};
+template <int CIN, int COUT, int TPW_, bool BWD>
+DirectLaunch pipe_launch(const ConvArgs &a, int n_cus) {
     static LdsGrant grant;
-    // (serial, masked: + 8 KB of column sums and the tile's mask rows)
-    const size_t lds = PIPE ? (size_t)C::PIPE_LDS : 2 * (size_t)C::BUF + (BWD ? 256 * 8 * sizeof(float) + (size_t)kTH * kTW * COUT * 2 : 0);
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv3x3_direct_kernel<CIN, COUT, TPW_, BWD, PIPE>), lds, grant)) return rc;
-    hipLaunchKernelGGL((conv3x3_direct_kernel<CIN, COUT, TPW_, BWD, PIPE>), dim3(grid), dim3(256), lds, stream, a);
-    DSRG_LAUNCH_CHECK();
-    return DSRG_OK;
+    return {&conv3x3_direct_pipe_kernel<CIN, COUT, TPW_, BWD>, (size_t)Cfg<CIN, COUT, TPW_>::PIPE_LDS, variant_grid<CIN, COUT, TPW_>(a, n_cus), &grant};
 }
-template <int CIN, int COUT, int TPW_, bool BWD>              // BWD: the masked data gradient (a.mask set)
-int launch_variant(const ConvArgs &a, int n_cus, hipStream_t stream, int &grid) {
-    using C = Cfg<CIN, COUT, TPW_>;
-    // (the DMA halo marks a lane outside the image with byte offset 2^31, which must lie beyond the descriptor's range)
-    if (C::DMA && !BWD && (size_t)a.B * a.H * a.W * CIN * 2 >= ((size_t)1 << 31)) return DSRG_ERR_UNSUPPORTED;
-    grid = variant_grid<CIN, COUT, TPW_>(a, n_cus);              // persistent: one or two workgroups per CU
-    // (the pipelined schedule loads and stores through buffer descriptors with the same out-of-range mark: larger maps run the serial one)
-    if constexpr (kPipelined<CIN, COUT, TPW_, BWD>)
-        if ((size_t)a.B * a.H * a.W * (CIN > COUT ? CIN : COUT) * 2 < ((size_t)1 << 31)) return launch_schedule<CIN, COUT, TPW_, BWD, true>(a, grid, stream);
-    return launch_schedule<CIN, COUT, TPW_, BWD, false>(a, grid, stream);
-}
-// either form of one shape
-template <int CIN, int COUT, int TPW_>
-int launch_shape(const ConvArgs &a, int n_cus, hipStream_t stream, int &grid) {
-    return a.mask ? launch_variant<CIN, COUT, TPW_, true>(a, n_cus, stream, grid) : launch_variant<CIN, COUT, TPW_, false>(a, n_cus, stream, grid);
+// (cin, cout, masked?) -> launch.  64 -> 64 forward: one output tile per wave (144 weight VGPRs) and two workgroups per CU — the
+// halo loads of a workgroup are its only memory parallelism (24 KB in flight), a second one doubles it; its masked form has no
+// registers for that (25 VGPRs spilled) and takes two tiles per wave
+DirectLaunch direct_launch(int cin, int cout, const ConvArgs &a, int n_cus) {
+    const bool bwd = a.mask != nullptr;
+    if (cin == 64 && cout == 64) return bwd ? pipe_launch<64, 64, 2, true>(a, n_cus) : pipe_launch<64, 64, 1, false>(a, n_cus);
+    if (cin == 64) return bwd ? pipe_launch<64, 128, 2, true>(a, n_cus) : pipe_launch<64, 128, 2, false>(a, n_cus);
+    if (cout == 64) return bwd ? pipe_launch<128, 64, 1, true>(a, n_cus) : pipe_launch<128, 64, 1, false>(a, n_cus);
+    if (bwd) return pipe_launch<128, 128, 1, true>(a, n_cus);
+    static LdsGrant grant;
+    return {&conv3x3_direct_dma_kernel, 2 * (size_t)Cfg<128, 128, 1>::BUF, variant_grid<128, 128, 1>(a, n_cus), &grant};
 }
 // ------------------------------------------------------------------------------------------------------------------
 // The first layer, 3 -> 64 channels at full resolution (conv1_1, train-s.prototxt:44-64): output-bandwidth-bound (211 MB at
@@ -1140,8 +1099,10 @@ int launch_conv3x3_direct(const void *x, const void *w, const float *bias, void 
     if ((mask || colsum) && (cin == 3 || !mask || !colsum))
         return set_error(DSRG_ERR_UNSUPPORTED, "conv3x3_direct: the masked form takes 64 / 128 channels, mask and bias gradient together");
     if (mask && bias) return set_error(DSRG_ERR_UNSUPPORTED, "conv3x3_direct: the masked form adds no bias");
-    if (mask && (long long)B * H * W * cout * 2 >= 0x7fffffffLL)
-        return set_error(DSRG_ERR_UNSUPPORTED, "conv3x3_direct: mask too large for a 32-bit buffer offset");
+    // (input, output and mask are addressed with 32-bit buffer offsets, and offset 2^31 marks what lies off the image)
+    const long long wide_bytes = (long long)B * H * W * (cin > cout ? cin : cout) * 2;
+    if (cin != 3 && wide_bytes >= (1LL << 31))
+        return set_error(DSRG_ERR_UNSUPPORTED, "conv3x3_direct: B * H * W * max(cin, cout) * 2 = %lld bytes reach 2^31, the limit of a 32-bit buffer offset", wide_bytes);
     if (colsum && (!colsum_ws || colsum_ws_bytes < conv3x3_direct_colsum_workspace(cout)))
         return set_error(DSRG_ERR_INVALID, "conv3x3_direct: column-sum scratch missing or too small");
     ConvArgs a;
@@ -1158,18 +1119,14 @@ int launch_conv3x3_direct(const void *x, const void *w, const float *bias, void 
         DSRG_LAUNCH_CHECK();
         return DSRG_OK;
     }
-    // 64 -> 64: one output tile per wave (144 weight VGPRs) and two workgroups per CU — the halo loads of a workgroup are its
-    // only memory parallelism (24 KB in flight), a second one doubles it.  The masked form of that variant spills a few
-    // loop-invariant addresses (281 against 267 us for conv1_2's data gradient + the separate pass); two tiles per wave does not
-    int rc, grid = 0;
-    if (cin == 64 && cout == 64) rc = mask ? launch_variant<64, 64, 2, true>(a, n_cus, stream, grid) : launch_variant<64, 64, 1, false>(a, n_cus, stream, grid);
-    else if (cin == 64) rc = launch_shape<64, 128, 2>(a, n_cus, stream, grid);
-    else if (cout == 64) rc = launch_shape<128, 64, 1>(a, n_cus, stream, grid);
-    else rc = launch_shape<128, 128, 1>(a, n_cus, stream, grid);
-    if (rc || !colsum) return rc;
+    const DirectLaunch d = direct_launch(cin, cout, a, n_cus);
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(d.kernel), d.lds, *d.grant)) return rc;
+    hipLaunchKernelGGL(d.kernel, dim3(d.grid), dim3(256), d.lds, stream, a);
+    DSRG_LAUNCH_CHECK();
+    if (!colsum) return DSRG_OK;
     const float *parts[1] = {a.colsum};
     float *outs[1] = {colsum};
-    return launch_igemm_colsum(parts, outs, 1, grid, cout, stream);
+    return launch_igemm_colsum(parts, outs, 1, d.grid, cout, stream);
 }
 
 }  // namespace dsrg

@@ -455,12 +455,14 @@ int dsrg_avgpool3x3_s1_bf16(const void *in_dev, void *out_dev, int B, int H, int
  * accumulation, optional bias (cout f32) and ReLU in the epilogue:
  *   y[b,y,x,o] = relu?( bias[o] + sum_{dy,dx,c} w[o][dy+1][dx+1][c] * x[b,y+dy,x+dx,c] )
  * w_dev: (cout, 3, 3, cin) bf16 = the memory of a channels_last (out, in, 3, 3) tensor.  With the kernel flipped and its
- * channel axes swapped the same call is the data gradient of that convolution.  Other channel counts: DSRG_ERR_INVALID. */
+ * channel axes swapped the same call is the data gradient of that convolution.  Other channel counts: DSRG_ERR_INVALID.
+ * Size limit (this call and dsrg_conv3x3_direct_dgrad_bf16): a launch with 64 / 128 channels whose B * H * W * max(cin, cout) * 2
+ * bytes reach 2^31 is refused with DSRG_ERR_UNSUPPORTED, forward and masked alike; 3 -> 64 has no such limit. */
 int dsrg_conv3x3_direct_bf16(const void *x_dev, const void *w_dev, const float *bias_dev, void *y_dev, int B, int H, int W,
                              int cin, int cout, int relu, void *stream);
 /* The data-gradient form with the ReLU backward of the layer below in its store (cin, cout in {64, 128}): gx = conv(g, w) where
  * mask_dev (B,H,W,cout) bf16 — that layer's output — is positive, else 0; bias_grad_dev (cout f32) = sum over pixels of gx
- * (fixed summation order).  workspace_dev: dsrg_conv3x3_direct_dgrad_workspace(cout) bytes. */
+ * (fixed summation order).  workspace_dev: dsrg_conv3x3_direct_dgrad_workspace(cout) bytes.  The size limit above applies. */
 size_t dsrg_conv3x3_direct_dgrad_workspace(int cout);
 int dsrg_conv3x3_direct_dgrad_bf16(const void *g_dev, const void *w_dev, const void *mask_dev, void *gx_dev, float *bias_grad_dev,
                                    void *workspace_dev, size_t workspace_bytes, int B, int H, int W, int cin, int cout, void *stream);
