@@ -1,11 +1,20 @@
 """VGG16 DeepLab-v2 ASPP backbone of training/experiment/seed_mc/train-s.prototxt:41-744.
 
-Plumbing around the hot path: the convolutions run through PyTorch-ROCm (MIOpen /
-hipBLASLt, MFMA bf16 under autocast) — the only GEMM-shaped part of a DSRG step.
 Layer shapes follow the prototxt exactly: 3x3/2 ceil-mode max pools with pad 1
 (321 -> 161 -> 81 -> 41), pool4/pool5 stride 1, conv5_x dilation 2, AVE pool5a,
 four branches fc6_k (3x3, dilation 6/12/18/24) -> fc7_k (1x1) -> fc8-SEC_k (1x1, 21
 outputs, N(0, 0.01) init), summed (Eltwise SUM, train-s.prototxt:737-744).
+
+On the default step (bf16 autocast, float32 channels_last master parameters, a training batch) every layer runs on this
+package's HIP kernels, one autograd node per layer or group of layers:
+  conv1_1 .. conv2_2             _DirectConvFn   direct MFMA kernels (csrc/conv_direct.hip), pool1 / pool2 inside the node
+  conv3_1 .. conv5_3             _IgemmConvFn    implicit-GEMM kernels (csrc/conv_igemm.hip), n = 1, pool3 inside conv3_3's node
+  fc6_1..4, then fc7_1..4        _IgemmConvFn    n = 4: the four branches of a level share every launch
+  fc8-SEC_1..4 + Eltwise SUM     _HeadsPtrFn     (_HeadsFn where the parameters are not float32 channels_last)
+  pool4, pool5, pool5a           _MaxPool3x3Fn, _AvgPool3x3Fn
+Everything else — float32, small launches, other parameter layouts, the reference of the route comparisons — is _ConvFn's
+(see its docstring): im2col + hipBLASLt GEMM or MIOpen.  Adjacent conv nodes hand the ReLU backward and the bias gradient of
+the lower one to the upper one's data gradient through a _GradLink.
 """
 import torch
 import torch.nn as nn
@@ -16,26 +25,26 @@ import os as _os
 from . import ops
 from .streams import capture_stream
 
-# Which kernels a convolution runs is decided from what the call observes (device, dtype, layout, shape), by measured thresholds:
-# output channels from which the weight gradient of a 3x3 convolution at the 41x41 stages is the GEMM g^T @ im2col(x) (round 2, A/B
-# on one box: 932.8 / 931.4 images/s with 1024, 939.9 / 938.9 with 512, 934.1 / 932.4 with 256; see _ConvFn.backward)
+# Which kernels a convolution runs is decided from what the call observes (device, dtype, layout, shape), by measured thresholds.
+# _ConvFn: fewest output channels for the GEMM weight gradient g^T @ im2col(x) (round 2 A/B: 939.9 images/s with 512, 932.8 with 1024)
 _WGRAD_MIN_COUT = 512
-# largest map (pixels) whose 3x3 data gradient is im2col(g) + GEMM: the 41x41 stages.  Larger maps: the im2col of g costs more than it
-# saves (81x81, again with nontemporal im2col stores: 1 221 / 1 225 against 1 233 / 1 227 images/s)
+# _ConvFn: largest map (pixels) whose 3x3 data gradient is im2col(g) + GEMM, the 41x41 stages (round 2: at 81x81 1 221 against 1 233)
 _GEMM_DGRAD_MAX_MAP = 2048
-# largest map (pixels) whose 3x3 weight gradient is a GEMM over im2col(x), the matrix the forward keeps for it: the 41x41 stages again
-# (MIOpen's wrw 650 TFLOP/s on fc6 there; 883 -> 902 images/s in round 1)
+# _ConvFn: largest map (pixels) whose 3x3 weight gradient is a GEMM over the kept im2col(x) (round 1: 883 -> 902 images/s)
 _GEMM_WGRAD_MAX_MAP = 2048
 # fewest 256 x 256 output tiles for which a layer takes the implicit-GEMM kernels: one image at 41x41 is 14 tiles of 72 K-steps for
 # 256 CUs, where the library GEMM's small-M kernels win (batch-1 inference 740 against 970 images/s; see _igemm_route)
 _IGEMM_MIN_TILES = 64
 # The two switches left are the references of comparisons (tests/test_gpu_igemm.py, tools/igemm_route_diag.py assign them between
 # two runs): module globals read at call time, never captured at import or construction.
-# 3x3 layers with >= 256 output channels (conv3_x, conv4_x, conv5_x, fc6_k) through the implicit-GEMM kernels (csrc/conv_igemm.hip:
-# no im2col matrix in the forward, the data gradient or the weight gradient; the four fc6_k in one launch); "0": the im2col +
-# hipBLASLt route of rounds 1-3
+# 3x3 layers with >= 256 output channels (conv3_x .. fc6_k) through the implicit-GEMM kernels; "0": the im2col + hipBLASLt route of
+# rounds 1-3 (_ConvFn)
 _IGEMM = _os.environ.get("DSRG_IGEMM", "1") == "1"
-# (_FUSE_CHAIN: below, beside _GradLink)
+# adjacent conv nodes fold the lower one's ReLU (+ Dropout) backward and bias gradient into the upper one's data gradient
+# (_GradLink); "0": one ordinary autograd node per layer
+_FUSE_CHAIN = _os.environ.get("DSRG_FUSE_CHAIN", "1") != "0"
+# (measured and dropped in round 5, CHANGELOG.md: the wide layers' packs on a second stream under conv1_x / conv2_x, 1 822 -> 1 798
+# images/s; an implicit-GEMM layer's weight gradient on a second stream beside its data gradient, 1 761 -> 1 715)
 
 
 def _bf16_run(x):
@@ -73,26 +82,97 @@ def _im2col_gemm(x, weight, bias, dilation, relu, want_cols=False):
     return (out, a) if want_cols else out
 
 
-def _relu_bias_backward(g, pool, code, out_shape, relu, y, scale):
-    """first step of a conv node's backward when its consumer left nothing in the _GradLink: the incoming bf16 gradient -> (gradient
-    of the pre-activation, channels_last; bias gradient), one fused HIP pass.  pool: the node ended in the 3x3 max pool — its backward
-    masks with the ReLU the window codes carry (ops.maxpool3x3_bwd_relu); relu: mask by the sign of the output y and the Dropout
-    scale (ops.relu_bwd_bias); neither (e.g. the 21-channel fc8 outputs): the column sums alone"""
+class _GradLink:
+    """side channel between two adjacent nodes of a conv chain: when the upper node's data gradient was taken with the lower
+    node's ReLU (+ Dropout) backward folded into its store (ops.conv_igemm_dgrad), it leaves that here — with the lower node's
+    bias gradient where the store summed one — and the lower node's backward takes the incoming gradient as already masked.
+    Only wired where the model declares the lower node's output to have this one consumer (GemmConv2d(chain_input=True);
+    VGG16ASPP's fc6 -> fc7; retrain.py's bottlenecks)."""
+    __slots__ = ("scale", "gb", "ptr", "version")
+
+    def __init__(self):
+        self.arm(1.0)
+
+    def arm(self, scale):
+        """lower node's forward: its Dropout scale (1.0 without Dropout), which the upper node's store applies with the mask;
+        whatever an earlier step left is discarded"""
+        self.scale, self.gb, self.ptr, self.version = scale, None, None, -1
+
+    def leave(self, gx, gb=None):
+        """upper node: gx is the masked (and scaled) data gradient it returns for the lower node's output, gb that node's bias
+        gradient (None: the lower node has none, retrain.py's folded convolutions)"""
+        self.gb, self.ptr, self.version = gb, gx.data_ptr(), gx._version
+
+    def take(self, g):
+        """lower node -> (accepted, bias gradient): accepted iff g is exactly the tensor the upper node left (autograd hands a lone
+        gradient through untouched; had the output a second consumer after all, the sum would be another tensor or a later
+        version of this one).  Declined: the caller runs its own ReLU backward, which is still right on a masked gradient unless
+        a Dropout scale was applied with it.  Either way nothing stays left"""
+        gb, ptr, self.gb, self.ptr = self.gb, self.ptr, None, None
+        if ptr is None:
+            return False, None
+        if g.data_ptr() == ptr and g._version == self.version:
+            return True, gb
+        if self.scale != 1.0:
+            raise RuntimeError("chain_input: the output of a conv + ReLU + Dropout node declared to have one consumer has several")
+        return False, None
+
+
+def _forward_tail(ctx, outs, relu, pool, links_out, scale):
+    """the end of a conv node's forward, outs its n convolution outputs (+ bias (+ ReLU (+ Dropout))) -> (what the node returns, the
+    outputs it saves for backward, the pool's window codes or None).  pool = (stride, ceil_mode): conv + ReLU + 3x3 max pool as
+    one node (n = 1: conv1_2, conv2_2, conv3_3) — the pool's backward then masks with this ReLU and sums the bias gradient in the
+    same pass (ops.maxpool3x3_bwd_relu); the window codes carry the ReLU's mask (relu_input), so the backward never reads the
+    full-resolution output and the node does not keep it.  links_out: this node's _GradLinks (or None), armed where a consumer
+    can mask for it — behind a ReLU without a pool.  Leaves out_shape, relu, pool, scale and links_out on ctx for _backward_head"""
+    code, kept = None, outs if (relu and pool is None) else ()
     if pool is not None:
-        return ops.maxpool3x3_bwd_relu(g, code, out_shape, pool[0])
-    if relu:
-        return ops.relu_bwd_bias(g, y, scale)
-    g = g.contiguous(memory_format=torch.channels_last)
+        pooled, code = ops.maxpool3x3_fwd(outs[0], pool[0], pool[1], relu_input=True)
+    ctx.out_shape, ctx.relu, ctx.pool, ctx.scale = tuple(outs[0].shape), relu, pool, scale
+    ctx.links_out = links_out if (relu and pool is None) else None
+    for lk in ctx.links_out or ():
+        lk.arm(scale)
+    return (tuple(outs) if pool is None else (pooled,)), kept, code
+
+
+def _backward_head(ctx, g, y, code, i=0, fallback=True):
+    """the start of a conv node's backward for its i-th output, g the incoming bf16 gradient -> (gradient of the pre-activation,
+    channels_last; bias gradient): g itself when the consumer left it masked in the link, the bias gradient beside it; else one
+    fused HIP pass of this node's own — or None where the caller says those passes do not take g (fallback=False)"""
+    if ctx.links_out is not None:
+        accepted, gb = ctx.links_out[i].take(g)
+        if accepted:
+            return g, gb
+    if not fallback:
+        return None
+    if ctx.pool is not None:     # the pool's backward masks with the ReLU the window codes carry
+        return ops.maxpool3x3_bwd_relu(g, code, ctx.out_shape, ctx.pool[0])
+    if ctx.relu:                 # mask by the sign of the output y, times the Dropout scale
+        return ops.relu_bwd_bias(g, y, ctx.scale)
+    g = g.contiguous(memory_format=torch.channels_last)      # (e.g. the 21-channel fc8 outputs): the column sums alone
     return g, ops.bias_grad(g)
 
 
+def _landed(g, slot):
+    """the gradient a backward returns for a parameter: when the kernel wrote it into the reducer's slot, a FRESH alias of the slot
+    (autograd adopts a gradient as `.grad` without a copy only if nobody else holds the tensor object)"""
+    return g.detach() if (slot is not None and g is slot) else g
+
+
 class _ConvFn(torch.autograd.Function):
-    """3x3 / 1x1 stride-1 'same' convolution (+ ReLU (+ Dropout)).  Forward: explicit NHWC im2col + one hipBLASLt GEMM
-    when `gemm` (at the 41x41 stages, 76 % of the backbone flops, MIOpen's forward kernels reach ~180 TFLOP/s on MI355X,
-    the GEMM route 300-1200: tools/conv_probe.py), MIOpen otherwise.  Backward: the ReLU mask, the dropout mask and scale
-    and the bias gradient come from one fused HIP pass (ops.relu_bwd_bias: the output of ReLU + Dropout is positive
-    exactly where both masks pass); data and weight gradients go to hipBLASLt GEMMs where that beats MIOpen/CK (the 41x41
-    stages, see the comments in backward) and to MIOpen/CK otherwise."""
+    """3x3 / 1x1 stride-1 'same' convolution (+ ReLU (+ Dropout) (+ the stride-2 max pool)) on bf16 or float32 COPIES of the
+    parameters (autocast's casts).  What is left to this node since _DirectConvFn and _IgemmConvFn took the default bf16 step:
+      * the float32 leg (no autocast) of every layer;
+      * launches below _IGEMM_MIN_TILES output tiles (batch-1 test-time forwards, small crops);
+      * 1x1 layers outside VGG16ASPP's grouped route (fc7_k then, the fc8 classifiers outside the heads kernels);
+      * parameters that are not float32 channels_last masters (a model never converted, or cast to bf16);
+      * retrain.py's convolutions with trained BatchNorm affine maps or shapes the folded implicit-GEMM node does not take;
+      * the DSRG_IGEMM=0 reference of the route comparisons (tests/test_gpu_igemm.py, tools/igemm_route_diag.py).
+    Forward: the direct MFMA kernel for bf16 64 / 128-channel 3x3 layers, else NHWC im2col + one hipBLASLt GEMM when `gemm`
+    (tools/conv_probe.py: 300-1200 TFLOP/s at the 41x41 stages against MIOpen's ~180), MIOpen otherwise.  Backward: ReLU mask,
+    Dropout mask and scale and the bias gradient in one fused HIP pass (ops.relu_bwd_bias: the output of ReLU + Dropout is
+    positive exactly where both masks pass); data and weight gradients by hipBLASLt GEMMs where that beats MIOpen/CK (the 41x41
+    stages, see the comments in backward) and by MIOpen/CK otherwise."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
@@ -119,40 +199,30 @@ class _ConvFn(torch.autograd.Function):
                 out.relu_()
         if drop_p > 0.0:
             out = torch.ops.aten.native_dropout(out, drop_p, True)[0]    # out = relu * mask / (1 - p)
-        code, pooled = None, None
-        if pool is not None:
-            # conv + ReLU + 3x3 max pool as one autograd node (conv1_2, conv2_2, conv3_3): the pool's backward then masks with
-            # this ReLU and sums the bias gradient in the same pass (ops.maxpool3x3_bwd_relu) instead of handing an unmasked
-            # gradient to a separate relu_bwd_bias pass — three fewer passes over the largest activations of the net
-            # (relu_input: the window codes carry this ReLU's mask, so the backward never reads the full-resolution output again
-            # and the node does not keep it)
-            pooled, code = ops.maxpool3x3_fwd(out, pool[0], pool[1], relu_input=True)
-        ctx.save_for_backward(x, weight, out if (relu and pool is None) else None, cols, code)
-        ctx.out_shape = tuple(out.shape)
-        ctx.dilation, ctx.k, ctx.relu, ctx.scale, ctx.gemm = dilation, k, relu, 1.0 / (1.0 - drop_p), gemm
-        ctx.direct, ctx.pool = direct, pool
-        # _GradLink (see below): link_in — x is the ReLU output of the node in front and feeds nothing else; link_out — ours
+        # link_in — x is the ReLU output of the node in front and feeds nothing else; link_out — ours, without Dropout only (the
+        # Dropout mask of this node is torch's: a consumer's store could not apply it)
+        (ret,), kept, code = _forward_tail(ctx, [out], relu, pool, [link_out] if (link_out is not None and drop_p == 0.0) else None,
+                                           1.0 / (1.0 - drop_p))
+        ctx.save_for_backward(x, weight, cols, code, *kept)
+        ctx.dilation, ctx.k, ctx.gemm, ctx.direct = dilation, k, gemm, direct
         ctx.link_in = link_in if (direct and link_in is not None and link_in.scale == 1.0 and x.shape[1] in (64, 128) and
                                   x.is_contiguous(memory_format=torch.channels_last)) else None
-        ctx.link_out = link_out if (relu and pool is None and drop_p == 0.0) else None
-        if ctx.link_out is not None:
-            ctx.link_out.scale, ctx.link_out.gb = 1.0, None
-        return out if pool is None else pooled
+        return ret
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g):
-        x, weight, y, cols, code = ctx.saved_tensors
+        x, weight, cols, code, *y = ctx.saved_tensors
+        y = y[0] if y else None                        # the output: kept for a ReLU without a pool only
         pad = ctx.dilation * (ctx.k // 2)
         cout = weight.shape[0]
-        # do the fused passes take g: always behind a link or a pool (forward guaranteed bf16, ReLU, no dropout, cout | 2048)
-        gb = ctx.link_out.take(g) if ctx.link_out is not None else None
-        fused = gb is not None or ctx.pool is not None or (
-            g.dtype == torch.bfloat16 and ((cout % 8 == 0 and cout <= 2048) or (not ctx.relu and cout <= 256)))
-        if gb is not None:
-            pass                                       # g came masked by this node's ReLU, its bias gradient beside it
-        elif fused:
-            g, gb = _relu_bias_backward(g, ctx.pool, code, ctx.out_shape, ctx.relu, y, ctx.scale)
+        # the fused passes take g: always behind a pool (forward guaranteed bf16, ReLU, no dropout, cout | 2048); a link's masked g
+        # needs none
+        head = _backward_head(ctx, g, y, code, 0, ctx.pool is not None or (
+            g.dtype == torch.bfloat16 and ((cout % 8 == 0 and cout <= 2048) or (not ctx.relu and cout <= 256))))
+        fused = head is not None
+        if fused:
+            g, gb = head
         else:
             if ctx.relu:
                 g = g * (y > 0) * ctx.scale
@@ -188,11 +258,8 @@ class _ConvFn(torch.autograd.Function):
             gx = ops.col2im3x3_nhwc(torch.mm(g.permute(0, 2, 3, 1).reshape(-1, cout), wmat.t()), B_, H_, W_, cin, ctx.dilation)
         elif gemm_dgrad:
             gx = _im2col_gemm(g, weight.flip(2, 3).transpose(0, 1), None, ctx.dilation, False)
-        # weight gradient = im2col(x)^T @ g, taken as its transpose g^T @ im2col(x), again one hipBLASLt GEMM (K = B*H*W), for the
-        # 41x41 layers with >= 512 output channels: the 512 -> 1024 dilated fc6 layers (MIOpen's wrw 650 TFLOP/s there; 883 -> 902 images/s in round 1) and,
-        # since the hipBLASLt solutions are picked by TunableOp, the 512 -> 512 / 256 -> 512 layers too (round 2, A/B on one
-        # box: 932.8 / 931.4 images/s with the 1024 threshold, 939.9 / 938.9 with 512, 934.1 / 932.4 with 256; the transposed
-        # product g^T @ im2col(x) another +0.6 %)
+        # weight gradient = im2col(x)^T @ g, taken as its transpose g^T @ im2col(x) (+0.6 %), again one hipBLASLt GEMM (K = B*H*W), for
+        # the 41x41 layers from _WGRAD_MIN_COUT output channels (MIOpen's wrw runs fc6 at 650 TFLOP/s there)
         gemm_wgrad = gemm_dgrad and x.shape[2] * x.shape[3] <= _GEMM_WGRAD_MAX_MAP and x.shape[1] % 8 == 0 and cout >= _WGRAD_MIN_COUT
         gw = None
         if gemm_1x1:
@@ -219,60 +286,18 @@ class _ConvFn(torch.autograd.Function):
         return (gx if gemm_dgrad else gx2), (gw if gemm_wgrad else gw2), (gb if fused else gb2), None, None, None, None, None, None, None
 
 
-class _GradLink:
-    """side channel between two adjacent nodes of a conv chain: when the upper node's data gradient was taken with the lower
-    node's ReLU (+ Dropout) backward and bias gradient folded into its store (ops.conv_igemm_dgrad), it leaves the bias gradient
-    here and the lower node's backward takes the incoming gradient as already masked.  Only wired where the model declares the
-    lower node's output to have this one consumer (GemmConv2d(chain_input=True); VGG16ASPP's fc6 -> fc7)."""
-    __slots__ = ("scale", "gb", "ptr", "version")
-
-    def __init__(self):
-        self.scale, self.gb, self.ptr, self.version = 1.0, None, 0, -1
-
-    def leave(self, gx, gb):
-        """upper node: gx is the masked (and scaled) data gradient it returns for the lower node's output, gb that node's bias gradient"""
-        self.gb, self.ptr, self.version = gb, gx.data_ptr(), gx._version
-
-    def take(self, g):
-        """lower node: the bias gradient if g is exactly the tensor the upper node left (autograd hands a lone gradient through
-        untouched; had the output a second consumer after all, the sum would be another tensor or a later version of this one),
-        else None — the caller then runs its own ReLU backward, which is still right on a masked gradient unless a Dropout
-        scale was applied with it"""
-        gb, self.gb = self.gb, None
-        if gb is None:
-            return None
-        if g.data_ptr() == self.ptr and g._version == self.version:
-            return gb
-        if self.scale != 1.0:
-            raise RuntimeError("chain_input: the output of a conv + ReLU + Dropout node declared to have one consumer has several")
-        return None
-
-
-_FUSE_CHAIN = _os.environ.get("DSRG_FUSE_CHAIN", "1") != "0"
-# (measured and dropped in round 5: packing every wide layer's kernels on a second stream at the start of the step, under the
-# HBM-bound conv1_x / conv2_x — 1 822 -> 1 798 images/s: the packs then compete with those kernels for the same HBM)
-# (measured and dropped in round 5: the weight gradient of an implicit-GEMM layer on a second stream beside its data gradient,
-# to fill the sixth of the chip a 212-tile data-gradient launch leaves idle — 1 761 -> 1 715 images/s, the two 139 KB-LDS kernels
-# only take CUs from each other; profiles/r05_wgrad_side_stream_ab.txt)
-
-
-def _landed(g, slot):
-    """the gradient a backward returns for a parameter: when the kernel wrote it into the reducer's slot, a FRESH alias of the slot
-    (autograd adopts a gradient as `.grad` without a copy only if nobody else holds the tensor object)"""
-    return g.detach() if (slot is not None and g is slot) else g
-
-
 class _IgemmConvFn(torch.autograd.Function):
     """n convolutions of one geometry (n = 1, or the four ASPP branches) + bias (+ ReLU (+ Dropout) (+ the stride-2 max pool)):
     apply(k, dils, relu, drop_p, pool, n, links_in, links_out, x_1..x_n, w_1..w_n, b_1..b_n) (links: lists of _GradLink or None —
-    links_in[i] says x_i is the sole-consumer output of a ReLU node whose backward this node's data gradient absorbs).  k = 3 (conv3_x .. fc6_k): forward, data and weight
-    gradient by the implicit-GEMM kernels; k = 1 (fc7_k): forward and data gradient are plain hipBLASLt GEMMs over the NHWC
-    matrices (nothing to gather), the weight gradients of all branches one implicit-GEMM launch.
+    links_in[i] says x_i is the sole-consumer output of a ReLU node whose backward this node's data gradient absorbs).
+    k = 3 (conv3_x .. fc6_k): forward, data and weight gradient by the implicit-GEMM kernels; k = 1 (fc7_k): the same with Dropout
+    behind it, else forward and data gradient are plain hipBLASLt GEMMs over the NHWC matrices (nothing to gather) and the weight
+    gradients of all branches one implicit-GEMM launch.
     x: bf16 channels_last; w, b: the float32 master parameters — the kernel is cast to bf16 by the same copy that packs it
     for the kernel, and the weight gradient comes back in float32, so autocast's per-layer casts both ways disappear.
-    Backward: ReLU / dropout mask + bias gradient in one fused pass (as _ConvFn); data and weight gradients in ONE grid
-    (ops.conv_igemm_backward for n = 1, ops.conv_igemm_backward_groups for the four branches) when all inputs need gradients, else
-    data gradients of all branches in one launch (the same kernel on the flipped, transposed kernels), weight gradients in one."""
+    Backward: _backward_head, then data and weight gradients in ONE grid where all inputs need gradients and the kernels tile the
+    shape, else the data gradients of all branches in one launch and the weight gradients in one."""
+    LEAD = 8                                           # arguments of apply in front of the 3 n tensors
 
     @staticmethod
     def forward(ctx, k, dils, relu, drop_p, pool, n, links_in, links_out, *t):
@@ -296,117 +321,90 @@ class _IgemmConvFn(torch.autograd.Function):
         seed = ops.dropout_seed() if fused_drop else 0
         if links_in is not None and not all(lk is not None for lk in links_in):
             links_in = None
-        if k == 3:
-            # both packed forms of every kernel from the float32 master in one pass each; the data-gradient form waits for backward
-            need_d = any(ctx.needs_input_grad[8:8 + n]) and ops.conv_igemm_supported(ws[0].shape[0], ws[0].shape[1], 3)
+        if k == 3 or fused_drop:
+            # (fc7_k with Dropout behind it: one 1x1 implicit-GEMM launch for all branches with the mask in its epilogue beats four
+            # hipBLASLt GEMMs + four dropout passes.)  Both packed forms of every kernel from the float32 master in one pass each,
+            # the data-gradient form, which waits for backward, only where backward is sure to launch with it
+            lead = _IgemmConvFn.LEAD
+            need_d = (any(ctx.needs_input_grad[lead:lead + n]) and ops.conv_igemm_supported(ws[0].shape[0], ws[0].shape[1], 3)) \
+                if k == 3 else (links_in is not None and _FUSE_CHAIN)
             packs = [ops.pack_conv_weight_pair(w, True, need_d) for w in ws]
             packs_d = [p[1] for p in packs]
-            outs = ops.conv_igemm(xs, [p[0] for p in packs], fb, dils, 3, relu, drop_p, seed)
-        elif fused_drop:
-            # fc7_k with Dropout behind it: one 1x1 implicit-GEMM launch for all branches with the mask in its epilogue beats four
-            # hipBLASLt GEMMs + four dropout passes
-            packs = [ops.pack_conv_weight_pair(w, True, links_in is not None and _FUSE_CHAIN) for w in ws]
-            packs_d = [p[1] for p in packs]
-            outs = ops.conv_igemm(xs, [p[0] for p in packs], fb, dils, 1, relu, drop_p, seed)
+            outs = ops.conv_igemm(xs, [p[0] for p in packs], fb, dils, k, relu, drop_p, seed)
         else:
             outs = [_im2col_gemm(x, w.to(torch.bfloat16), b.to(torch.bfloat16), 1, relu) for x, w, b in zip(xs, ws, bs)]
-        code, pooled = None, None
-        if pool is not None:                                                             # n == 1 (conv3_3)
-            pooled, code = ops.maxpool3x3_fwd(outs[0], pool[0], pool[1], relu_input=True)       # the codes carry the ReLU mask
-        ctx.save_for_backward(code, *xs, *ws, *(outs if (relu and pool is None) else ()))
-        ctx.out_shape = tuple(outs[0].shape)
+        ret, kept, code = _forward_tail(ctx, outs, relu, pool, links_out, scale)          # (a pool: n == 1, conv3_3)
+        ctx.save_for_backward(code, *xs, *ws, *kept)
         # where a data-parallel reducer wants the weight gradients written (dsrg_amd/reducer.py: the parameters' bucket slots)
         ctx.gw_out = [getattr(w, "_dsrg_grad_out", None) for w in ws]
         ctx.packs_d = packs_d                  # not an input or output of the node: kept outside save_for_backward
-        ctx.dils, ctx.relu, ctx.scale, ctx.pool, ctx.n, ctx.k = dils, relu, scale, pool, n, k
-        ctx.links_in = links_in
-        ctx.links_out = links_out if (relu and pool is None) else None
-        if ctx.links_out is not None:
-            for lk in ctx.links_out:
-                lk.scale, lk.gb = scale, None
-        return tuple(outs) if pool is None else (pooled,)
+        ctx.dils, ctx.n, ctx.k, ctx.links_in = dils, n, k, links_in
+        return ret
 
     @staticmethod
     def backward(ctx, *gs):
-        n = ctx.n
+        n, k, lead = ctx.n, ctx.k, _IgemmConvFn.LEAD
         code, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         xs, ws, ys = saved[:n], saved[n:2 * n], saved[2 * n:] or (None,) * n      # outputs: kept for a ReLU without a pool only
         cout, cin = ws[0].shape[0], ws[0].shape[1]
-        gms, gbs = [], []
-        cl = torch.channels_last
-        for i, g in enumerate(gs):
-            gm, gb = g, ctx.links_out[i].take(g) if ctx.links_out is not None else None
-            if gb is None:        # else the consumer's data gradient came masked by this node's ReLU (+ Dropout), the bias gradient beside it
-                gm, gb = _relu_bias_backward(g, ctx.pool, code, ctx.out_shape, ctx.relu, ys[i], ctx.scale)
-            gms.append(gm); gbs.append(gb)
-        need_x = [ctx.needs_input_grad[8 + i] for i in range(n)]
-        gxs = [None] * n
+        gms, gbs = map(list, zip(*[_backward_head(ctx, g, ys[i], code, i) for i, g in enumerate(gs)]))
+        need_x = list(ctx.needs_input_grad[lead:lead + n])
+        # do the data-gradient launches that share a grid or a store with other work take this node
+        takes = all(need_x) and ops.conv_igemm_supported(cout, cin, k) and all(x.is_contiguous(memory_format=torch.channels_last) for x in xs)
         # inputs that are another node's ReLU outputs with no other consumer: that node's backward rides in this data gradient
-        absorb = _FUSE_CHAIN and ctx.links_in is not None and all(need_x) and ops.conv_igemm_supported(cout, cin, ctx.k) and \
-            cin >= 256 and all(x.is_contiguous(memory_format=cl) for x in xs)
-        if n == 1 and ctx.k == 3 and need_x[0] and ops.conv_igemm_supported(cout, cin, 3) and \
-                ops.conv_igemm_wgrad_supported(cin, cout, 3) and xs[0].is_contiguous(memory_format=cl):
-            # one launch for both gradients of the layer (ops.conv_igemm_backward): the data gradient's tiles and the weight gradient's
-            # workgroups share a grid, so the CUs a 212-tile data gradient leaves idle do weight-gradient work
-            pd = ctx.packs_d[0] if ctx.packs_d[0] is not None else ops.pack_conv_weight(ws[0], for_dgrad=True)
-            gx, gw, gb_below = ops.conv_igemm_backward(gms[0], pd, xs[0], ctx.dils[0], xs[0] if absorb else None,
-                                                       ctx.links_in[0].scale if absorb else 1.0, gw_out=ctx.gw_out[0])
-            if absorb:
-                ctx.links_in[0].leave(gx, gb_below)
-            return (None,) * 8 + (gx, _landed(gw, ctx.gw_out[0])) + tuple(gbs)
-        if n > 1 and all(need_x) and ops.conv_igemm_supported(cout, cin, ctx.k) and \
-                ops.conv_igemm_wgrad_supported(cin, cout, ctx.k) and all(x.is_contiguous(memory_format=cl) for x in xs):
+        absorb = takes and _FUSE_CHAIN and ctx.links_in is not None and cin >= 256
+        masks, mask_scale = (list(xs), ctx.links_in[0].scale) if absorb else (None, 1.0)
+        # both gradients in one grid: a single 3x3 layer, or the branches of one level
+        merged = takes and ops.conv_igemm_wgrad_supported(cin, cout, k) and (n > 1 or k == 3)
+
+        def packs_d():           # the forward's data-gradient packings, made now where it had no reason to (one route at most asks)
+            return [p if p is not None else ops.pack_conv_weight(w, for_dgrad=True) for p, w in zip(ctx.packs_d, ws)]
+
+        def library(i, which):   # shapes the kernels do not tile (input channels not a multiple of 128, ...): MIOpen / CK
+            d = ctx.dils[i]
+            return torch.ops.aten.convolution_backward(gms[i], xs[i], ws[i].to(torch.bfloat16), None, [1, 1], [d, d], [d, d], False,
+                                                       [0, 0], 1, [which == 0, which == 1, False])[which]
+
+        def wgrads():            # the weight gradients of all branches in a launch of their own: float32, the parameters' own layout
+            if k == 1 or ops.conv_igemm_wgrad_supported(cin, cout, 3):
+                return ops.conv_igemm_wgrad(list(xs), gms, ctx.dils, k, outs=ctx.gw_out)
+            return [library(i, 1).float() for i in range(n)]
+
+        gb_below = None
+        if merged and n == 1:
+            # ops.conv_igemm_backward: the data gradient's tiles and the weight gradient's workgroups share a grid, so the CUs a
+            # 212-tile data gradient leaves idle do weight-gradient work
+            gx, gw, gb = ops.conv_igemm_backward(gms[0], packs_d()[0], xs[0], ctx.dils[0], xs[0] if absorb else None, mask_scale,
+                                                 gw_out=ctx.gw_out[0])
+            gxs, gws, gb_below = [gx], [gw], [gb]
+        elif merged:
             # the four ASPP branches (fc7_k: 1x1 with the mask and bias gradients of fc6_k in the store; fc6_k: 3x3, dilations 6 - 24):
-            # the same one grid for both gradients, in the grouped forms of both halves (ops.conv_igemm_backward_groups).  With or
-            # without the masks: the weight gradient's pixel split belongs to the grid, so fc7_k's weight gradients are the same
-            # bits whether or not fc6_k's ReLU backward rides along (DSRG_FUSE_CHAIN)
-            packs_d = [p if p is not None else ops.pack_conv_weight(w, for_dgrad=True) for p, w in zip(ctx.packs_d, ws)]
-            gxs, gws, gb_below = ops.conv_igemm_backward_groups(gms, packs_d, list(xs), ctx.dils, ctx.k, list(xs) if absorb else None,
-                                                                ctx.links_in[0].scale if absorb else 1.0, gw_outs=ctx.gw_out)
-            if absorb:
-                for lk, gx_, gb_ in zip(ctx.links_in, gxs, gb_below):
-                    lk.leave(gx_, gb_)
-            gws = [_landed(gw, o) for gw, o in zip(gws, ctx.gw_out)]
-            if ctx.same_x and _sum_takes(gxs):
-                gxs = [ops.sum_bf16(list(gxs))] + [None] * (n - 1)      # (see below)
-            return (None,) * 8 + tuple(gxs) + tuple(gws) + tuple(gbs)
+            # the same one grid in the grouped forms of both halves.  With or without the masks: the weight gradient's pixel split
+            # belongs to the grid, so fc7_k's weight gradients are the same bits whether or not fc6_k's ReLU backward rides along
+            gxs, gws, gb_below = ops.conv_igemm_backward_groups(gms, packs_d(), list(xs), ctx.dils, k, masks, mask_scale,
+                                                                gw_outs=ctx.gw_out)
+        elif absorb:
+            gxs, gb_below = ops.conv_igemm_dgrad(gms, packs_d(), masks, ctx.dils, k, mask_scale)
+            gws = wgrads()
+        elif k == 1:             # plain hipBLASLt GEMMs over the NHWC matrices
+            gxs = [torch.mm(gm.permute(0, 2, 3, 1).reshape(-1, cout), w.to(torch.bfloat16).reshape(cout, cin)).view(
+                x.shape[0], x.shape[2], x.shape[3], cin).permute(0, 3, 1, 2) if nx else None for gm, w, x, nx in zip(gms, ws, xs, need_x)]
+            gws = wgrads()
+        else:                    # the forward kernel on the flipped, transposed kernels
+            gxs = [None] * n
+            if any(need_x):
+                gxs = ops.conv_igemm(gms, packs_d(), None, ctx.dils, 3, False) if ops.conv_igemm_supported(cout, cin, 3) else \
+                    [library(i, 0) for i in range(n)]
+            gws = wgrads()
         if absorb:
-            packs_d = [p if p is not None else ops.pack_conv_weight(w, for_dgrad=True) for p, w in zip(ctx.packs_d, ws)]
-            gxs, gb_below = ops.conv_igemm_dgrad(gms, packs_d, list(xs), ctx.dils, ctx.k, ctx.links_in[0].scale)
-            for lk, gx_, gb_ in zip(ctx.links_in, gxs, gb_below):
-                lk.leave(gx_, gb_)
-        if ctx.k == 1:
-            for i in range(n):
-                if absorb:
-                    break
-                if need_x[i]:
-                    g2d = gms[i].permute(0, 2, 3, 1).reshape(-1, cout)
-                    B_, _, H_, W_ = xs[i].shape
-                    gxs[i] = torch.mm(g2d, ws[i].to(torch.bfloat16).reshape(cout, cin)).view(B_, H_, W_, cin).permute(0, 3, 1, 2)
-            gws = [_landed(gw, o) for gw, o in zip(ops.conv_igemm_wgrad(list(xs), gms, ctx.dils, 1, outs=ctx.gw_out), ctx.gw_out)]
-            return (None,) * 8 + tuple(gxs) + tuple(gws) + tuple(gbs)
-        if any(need_x) and not absorb:
-            if ops.conv_igemm_supported(cout, cin, 3):
-                packs_d = [p if p is not None else ops.pack_conv_weight(w, for_dgrad=True) for p, w in zip(ctx.packs_d, ws)]
-                gxs = ops.conv_igemm(gms, packs_d, None, ctx.dils, 3, False)
-            else:                                                                        # input channels not a multiple of 128
-                for i in range(n):
-                    d = ctx.dils[i]
-                    gxs[i] = torch.ops.aten.convolution_backward(gms[i], xs[i], ws[i].to(torch.bfloat16), None, [1, 1], [d, d], [d, d],
-                                                                 False, [0, 0], 1, [True, False, False])[0]
-        if ops.conv_igemm_wgrad_supported(cin, cout, 3):
-            gws = ops.conv_igemm_wgrad(list(xs), gms, ctx.dils, 3, outs=ctx.gw_out)      # float32, the parameters' own layout
-            gws = [_landed(gw, o) for gw, o in zip(gws, ctx.gw_out)]
-        else:
-            gws = []
-            for i in range(n):
-                d = ctx.dils[i]
-                gws.append(torch.ops.aten.convolution_backward(gms[i], xs[i], ws[i].to(torch.bfloat16), None, [1, 1], [d, d], [d, d],
-                                                               False, [0, 0], 1, [False, True, False])[1].float())
-        if ctx.same_x and all(need_x) and _sum_takes(gxs):
-            # rne(rne(rne(g_1 + g_2) + g_3) + g_4): the bits the engine's accumulation of the n gradients of one tensor has
+            for lk, gx, gb in zip(ctx.links_in, gxs, gb_below):
+                lk.leave(gx, gb)
+        # one tensor fed n times: rne(rne(rne(g_1 + g_2) + g_3) + g_4), the bits the engine's accumulation of its n gradients has
+        # (the separate 1x1 launches never formed this sum, and no model feeds one tensor to several 1x1 layers: left to the engine)
+        if ctx.same_x and all(need_x) and (merged or k == 3) and _sum_takes(gxs):
             gxs = [ops.sum_bf16(list(gxs))] + [None] * (n - 1)
-        return (None,) * 8 + tuple(gx if nx else None for gx, nx in zip(gxs, need_x)) + tuple(gws) + tuple(gbs)
+        return (None,) * lead + tuple(gx if nx else None for gx, nx in zip(gxs, need_x)) + \
+            tuple(_landed(gw, o) for gw, o in zip(gws, ctx.gw_out)) + tuple(gbs)
 
 
 def _sum_takes(gs):
@@ -436,26 +434,17 @@ class _DirectConvFn(torch.autograd.Function):
         else:
             w16, wd = ops.pack_direct_weight_pair(weight, ctx.needs_input_grad[0])
         out = ops.conv3x3_direct(x, w16, bias.detach(), relu)
-        code, pooled = None, None
-        if pool is not None:
-            pooled, code = ops.maxpool3x3_fwd(out, pool[0], pool[1], relu_input=True)     # the codes carry the ReLU mask
-        ctx.save_for_backward(x, out if (relu and pool is None) else None, code)
-        ctx.out_shape = tuple(out.shape)
+        (ret,), kept, code = _forward_tail(ctx, [out], relu, pool, [link_out] if link_out is not None else None, 1.0)
+        ctx.save_for_backward(x, code, *kept)
         ctx.wd = wd                                    # not an input or output of the node: kept outside save_for_backward
         ctx.gw_out = getattr(weight, "_dsrg_grad_out", None)      # a reducer's slot for the weight gradient (dsrg_amd/reducer.py)
-        ctx.relu, ctx.pool = relu, pool
         ctx.link_in = link_in if (link_in is not None and link_in.scale == 1.0 and wd is not None) else None
-        ctx.link_out = link_out if (relu and pool is None) else None
-        if ctx.link_out is not None:
-            ctx.link_out.scale, ctx.link_out.gb = 1.0, None
-        return out if pool is None else pooled
+        return ret
 
     @staticmethod
     def backward(ctx, g):
-        x, y, code = ctx.saved_tensors
-        gb = ctx.link_out.take(g) if ctx.link_out is not None else None
-        if gb is None:            # else g came masked by this node's ReLU, its bias gradient beside it
-            g, gb = _relu_bias_backward(g, ctx.pool, code, ctx.out_shape, ctx.relu, y, 1.0)
+        x, code, *y = ctx.saved_tensors
+        g, gb = _backward_head(ctx, g, y[0] if y else None, code)
         gx = None
         if ctx.needs_input_grad[0]:
             if _FUSE_CHAIN and ctx.link_in is not None:
@@ -492,9 +481,8 @@ def _direct_route(conv, x, p, pool):
 
 def _igemm_route(conv, x, groups=1):
     """does this GemmConv2d call take the implicit-GEMM kernels: a 3x3 'same' convolution with bias on bf16 activations
-    (autocast), 64 | input channels, 256 | output channels — and enough 256 x 256 output tiles to occupy the chip: one image
-    at 41x41 is 14 tiles of 72 K-steps for 256 CUs, where the library GEMM's small-M kernels win (batch-1 inference 740 against
-    970 images/s); `groups` problems share the launch (the four fc6_k)"""
+    (autocast), 64 | input channels, 256 | output channels — and enough 256 x 256 output tiles to occupy the chip
+    (_IGEMM_MIN_TILES); `groups` problems share the launch (the four fc6_k)"""
     if not (_IGEMM and x.is_cuda and conv.gemm and conv.kernel_size == (3, 3) and conv.bias is not None and conv.groups == 1):
         return False
     if not _bf16_run(x):
@@ -508,9 +496,12 @@ def _igemm_route(conv, x, groups=1):
 
 
 class GemmConv2d(nn.Conv2d):
-    """nn.Conv2d (same parameters, same init, same state_dict) whose CUDA forward is im2col + GEMM, optionally
-    with the following ReLU (`fuse_relu`) and Dropout (`fuse_dropout` = p, needs fuse_relu) fused; on the CPU it is the
-    plain convolution (+ ReLU (+ Dropout)).
+    """nn.Conv2d (same parameters, same init, same state_dict) with the following ReLU (`fuse_relu`), Dropout (`fuse_dropout` = p,
+    needs fuse_relu) and stride-2 max pool (`fuse_pool`) in the same autograd node.  A stride-1 'same' 3x3 / 1x1 call on the GPU
+    picks its node from what it observes: _IgemmConvFn (_igemm_route: bf16 run, >= 256 output channels, >= _IGEMM_MIN_TILES
+    tiles), else _DirectConvFn (_direct_route: the four narrow layers with float32 channels_last masters under bf16 autocast),
+    else _ConvFn (its docstring lists what that leaves; `gemm` there chooses im2col + GEMM over MIOpen).  Any other call, and the
+    CPU, is the plain convolution (+ ReLU (+ Dropout) (+ pool)).
 
     Contract of the fused forms (what a user of these modules may and may not rely on):
       * `fuse_dropout` = p is realised in steps of 1/256 on the implicit-GEMM route (keep a value iff its random byte >= round(256 p);
@@ -688,6 +679,7 @@ class _HeadsPtrFn(torch.autograd.Function):
     """_HeadsFn with the n classifier kernels and biases read where the parameters lie (ops.heads_forward_ptrs: no stacked copy
     of either per step) and every kernel's gradient written to a tensor of its own with the parameter's strides — a reducer's slot
     (`_dsrg_grad_out`) where the parameter names one.  apply(links, n, w_1..w_n, b_1..b_n, x_1..x_n); the same bits as _HeadsFn."""
+    LEAD = 2                                           # arguments of apply in front of the 3 n tensors
 
     @staticmethod
     def forward(ctx, links, n, *t):
@@ -706,7 +698,7 @@ class _HeadsPtrFn(torch.autograd.Function):
         n = ctx.n
         ws, xs = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
         O = ws[0].shape[0]
-        need_x = ctx.needs_input_grad[2 + 2 * n:]
+        need_x = ctx.needs_input_grad[_HeadsPtrFn.LEAD + 2 * n:]
         if _FUSE_CHAIN and ctx.links is not None and all(need_x):
             gxs, gws, gb_below = ops.heads_backward_ptrs(xs, ws, g, True, ctx.links[0].scale, gw_outs=ctx.gw_out)
             for i, lk in enumerate(ctx.links):
@@ -715,7 +707,7 @@ class _HeadsPtrFn(torch.autograd.Function):
             gxs, gws = ops.heads_backward_ptrs(xs, ws, g, need_gx=any(need_x), gw_outs=ctx.gw_out)
         gb = g.sum((0, 2, 3)).unsqueeze(0).expand(n, O).contiguous()      # fp32, the same for every branch (torch's sum, as _HeadsFn)
         gws = [_landed(gw, o) for gw, o in zip(gws, ctx.gw_out)]
-        return (None, None) + tuple(gws) + tuple(gb[i] for i in range(n)) + (tuple(gxs) if gxs is not None else (None,) * n)
+        return (None,) * _HeadsPtrFn.LEAD + tuple(gws) + tuple(gb[i] for i in range(n)) + (tuple(gxs) if gxs is not None else (None,) * n)
 
 
 class _StackKernels(torch.autograd.Function):
@@ -771,53 +763,61 @@ class VGG16ASPP(nn.Module):
         (Softmax + 1e-4, the CRF, the 0.85 / 0.99 SRG thresholds, the 0.05 / 20 clip of the constrain loss), and a bf16
         score of magnitude 8-16 has a step of 0.06-0.125."""
         f = self.features(x)
-        hs = []
-        fc6 = [br[0] for br in self.branches]
-        if len(fc6) <= 4 and all(_igemm_route(m, f, len(fc6)) and m.stride == (1, 1) and m.padding == m.dilation for m in fc6):
-            # the four fc6_k (same input, own dilation) in one launch each way: 1696 tiles fill the chip where 424 leave a sixth idle
-            p = fc6[0].fuse_dropout if self.training else 0.0
-            n = len(fc6)
-            links = [_GradLink() for _ in range(n)] if torch.is_grad_enabled() else None
-            hs = list(_IgemmConvFn.apply(3, [m.dilation[0] for m in fc6], True, p, None, n, None, links, *([f] * n),
-                                         *[m.weight for m in fc6], *[m.bias for m in fc6]))
-            fc7 = [br[3] for br in self.branches]
-            if all(isinstance(m, GemmConv2d) and m.kernel_size == (1, 1) and m.fuse_relu and m.bias is not None and m.gemm
-                   and m.in_channels % 256 == 0 and m.out_channels % 256 == 0 for m in fc7):
-                # fc7_k: own input each, one launch for the four weight gradients
-                p7 = fc7[0].fuse_dropout if self.training else 0.0
-                # (fc6_k's output feeds fc7_k only: its ReLU / Dropout backward and bias gradient ride in fc7_k's data gradient)
-                links7 = [_GradLink() for _ in range(n)] if torch.is_grad_enabled() else None
-                hs = list(_IgemmConvFn.apply(1, [1] * n, True, p7, None, n, links, links7, *hs, *[m.weight for m in fc7],
-                                             *[m.bias for m in fc7]))
-                for h, lk in zip(hs, links7 or []):
-                    h._dsrg_grad_link = lk
-            else:
-                for i, br in enumerate(self.branches):
-                    for m in list(br)[1:-1]:
-                        hs[i] = m(hs[i])
-        else:
-            for br in self.branches:
-                h = f
+        hs = self._grouped_branches(f)
+        if hs is None:
+            hs = [f] * len(self.branches)
+            for i, br in enumerate(self.branches):
                 for m in list(br)[:-1]:
-                    h = m(h)
-                hs.append(h)
+                    hs[i] = m(hs[i])
         heads = [br[-1] for br in self.branches]
-        if hs[0].is_cuda and hs[0].dtype == torch.bfloat16 and len(hs) <= 4 and heads[0].out_channels <= 32 \
-                and heads[0].in_channels % 256 == 0:
-            # (on the grouped route the fc7_k outputs feed these classifiers and nothing else)
-            links = [getattr(h, "_dsrg_grad_link", None) for h in hs]
-            if all(m.bias is not None for m in heads) and ops.heads_kernels_in_place([m.weight for m in heads], [m.bias for m in heads]):
-                # the kernels and biases read where they lie, every weight gradient written to its own tensor
-                return _HeadsPtrFn.apply(links, len(heads), *[m.weight for m in heads], *[m.bias for m in heads], *hs)
-            w = _StackKernels.apply(*[m.weight for m in heads])       # the fallback (another dtype / layout): stacked copies
-            b = torch.stack([m.bias for m in heads])
-            return _HeadsFn.apply(links, w.float(), b.float(), *hs)
-        out = None
-        with torch.autocast(device_type=hs[0].device.type, enabled=False):
-            for m, h in zip(heads, hs):
-                s = m(h.float())
-                out = s if out is None else out + s
+        out = self._fused_heads(heads, hs)
+        if out is None:
+            with torch.autocast(device_type=hs[0].device.type, enabled=False):
+                for m, h in zip(heads, hs):
+                    s = m(h.float())
+                    out = s if out is None else out + s
         return out
+
+    def _grouped_branches(self, f):
+        """pool5a's output -> the fc7_k outputs with the four fc6_k (same input, own dilation) in one launch each way: 1696 tiles fill
+        the chip where 424 leave a sixth idle; None where the launch does not take them (_igemm_route)"""
+        fc6 = [br[0] for br in self.branches]
+        n = len(fc6)
+        if not (n <= 4 and all(_igemm_route(m, f, n) and m.stride == (1, 1) and m.padding == m.dilation for m in fc6)):
+            return None
+        p = fc6[0].fuse_dropout if self.training else 0.0
+        links = [_GradLink() for _ in range(n)] if torch.is_grad_enabled() else None
+        hs = list(_IgemmConvFn.apply(3, [m.dilation[0] for m in fc6], True, p, None, n, None, links, *([f] * n),
+                                     *[m.weight for m in fc6], *[m.bias for m in fc6]))
+        fc7 = [br[3] for br in self.branches]
+        if not all(isinstance(m, GemmConv2d) and m.kernel_size == (1, 1) and m.fuse_relu and m.bias is not None and m.gemm
+                   and m.in_channels % 256 == 0 and m.out_channels % 256 == 0 for m in fc7):
+            for i, br in enumerate(self.branches):
+                for m in list(br)[1:-1]:
+                    hs[i] = m(hs[i])
+            return hs
+        # fc7_k: own input each, one launch for the four weight gradients; fc6_k's output feeds fc7_k only, so its ReLU / Dropout
+        # backward and bias gradient ride in fc7_k's data gradient (links), as fc7_k's ride in the classifiers' (links7)
+        p7 = fc7[0].fuse_dropout if self.training else 0.0
+        links7 = [_GradLink() for _ in range(n)] if torch.is_grad_enabled() else None
+        hs = list(_IgemmConvFn.apply(1, [1] * n, True, p7, None, n, links, links7, *hs, *[m.weight for m in fc7], *[m.bias for m in fc7]))
+        for h, lk in zip(hs, links7 or []):
+            h._dsrg_grad_link = lk
+        return hs
+
+    def _fused_heads(self, heads, hs):
+        """the four classifiers and their sum in one HIP pass each way over bf16 fc7_k outputs; None where the kernels do not take them"""
+        if not (hs[0].is_cuda and hs[0].dtype == torch.bfloat16 and len(hs) <= 4 and heads[0].out_channels <= 32
+                and heads[0].in_channels % 256 == 0):
+            return None
+        # (on the grouped route the fc7_k outputs feed these classifiers and nothing else)
+        links = [getattr(h, "_dsrg_grad_link", None) for h in hs]
+        if all(m.bias is not None for m in heads) and ops.heads_kernels_in_place([m.weight for m in heads], [m.bias for m in heads]):
+            # the kernels and biases read where they lie, every weight gradient written to its own tensor
+            return _HeadsPtrFn.apply(links, len(heads), *[m.weight for m in heads], *[m.bias for m in heads], *hs)
+        w = _StackKernels.apply(*[m.weight for m in heads])       # the fallback (another dtype / layout): stacked copies
+        b = torch.stack([m.bias for m in heads])
+        return _HeadsFn.apply(links, w.float(), b.float(), *hs)
 
     def caffe_param_groups(self):
         """lr_mult / decay_mult of the prototxt: weights (1,1), biases (2,0); fc8-SEC (10,1)/(20,0)."""

@@ -15,7 +15,7 @@ import torch.nn.functional as F
 
 import os as _os
 
-from .backbone import VGG16ASPP, GemmConv2d, _ConvFn, _bf16_run
+from .backbone import VGG16ASPP, GemmConv2d, _ConvFn, _bf16_run, _landed
 from .trainer import CaffeSGD
 
 _FUSE_RES = _os.environ.get("DSRG_RESNET_FUSE_RES", "1") == "1"   # tools / tests: 0 = the shortcut's add + ReLU and its backward as passes of their own
@@ -84,6 +84,7 @@ class _FoldedIgemmFn(torch.autograd.Function):
     mask, data gradient by the same kernel, weight gradient by the implicit-GEMM weight-gradient kernel where its tiling takes the
     shape (both sides multiples of 256 channels) and by the library otherwise; d/dw = scale * d/d(w * scale).
     x: bf16 channels_last; w: the float32 master parameter (channels_last); scale, shift: float32 (cout), no gradient."""
+    RES = 8                                            # where `res` stands among forward's arguments (and backward's results)
 
     @staticmethod
     def forward(ctx, x, w, scale, shift, dil, relu, link_in=None, link_out=None, res=None, res_link=None):
@@ -107,7 +108,7 @@ class _FoldedIgemmFn(torch.autograd.Function):
         ctx.link_in = link_in if (need_d and x.is_contiguous(memory_format=torch.channels_last)) else None
         ctx.link_out = link_out if relu else None
         if ctx.link_out is not None:
-            ctx.link_out.scale, ctx.link_out.gb = 1.0, None
+            ctx.link_out.arm(1.0)
         ctx.has_res, ctx.res_link = res is not None, res_link
         if res_link is not None and res is None:
             res_link.armed, res_link.gm = bool(need_d), None     # the block's first node: it will add the shortcut's gradient itself
@@ -120,11 +121,11 @@ class _FoldedIgemmFn(torch.autograd.Function):
         cout, cin, k, d = w.shape[0], w.shape[1], ctx.k, ctx.dil
         cl = torch.channels_last
         g = g if g.dtype == torch.bfloat16 else g.bfloat16()
-        masked = ctx.link_out.take(g) is not None if ctx.link_out is not None else False      # the consumer's data gradient came masked
+        masked = ctx.link_out is not None and ctx.link_out.take(g)[0]                   # the consumer's data gradient came masked
         gm = (g if masked else relu_mask(g, y)) if ctx.relu else g
         gm = gm if gm.is_contiguous(memory_format=cl) else gm.contiguous(memory_format=cl)
         gres = None
-        if ctx.has_res and ctx.needs_input_grad[8]:
+        if ctx.has_res and ctx.needs_input_grad[_FoldedIgemmFn.RES]:
             if ctx.res_link is not None and ctx.res_link.armed:
                 ctx.res_link.gm = gm                                                    # the block's first node adds it in its store
             else:
@@ -132,44 +133,39 @@ class _FoldedIgemmFn(torch.autograd.Function):
         shortcut = None
         if not ctx.has_res and ctx.res_link is not None:
             shortcut, ctx.res_link.gm = ctx.res_link.gm, None
-        gx = None
+        # x = relu(...) of the node in front, read by this node only: that ReLU's backward is a mask in this node's data-gradient store
+        mask = x if ctx.link_in is not None else None
+        gx = gw = None
         if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and conv_igemm_wgrad_launchable(cin, cout, k) and \
                 x.is_contiguous(memory_format=cl):
             # the whole backward in one grid (the weight gradient's workgroups take the CUs the data gradient's tiles leave idle: a
             # 65 x 65 x 10 map is 166 pixel tiles), the scale on the weight gradient in its reduction, written into the reducer's slot
-            from .backbone import _landed
             from .ops import conv_igemm_backward_residual
             from .reducer import grad_destination
             slot = grad_destination(w, w.shape)
-            gx, gw = conv_igemm_backward_residual(gm, ctx.pd, x, d, k, x if ctx.link_in is not None else None, shortcut, scale, slot)
-            if ctx.link_in is not None:
-                ctx.link_in.leave(gx, True)
-            return gx, _landed(gw, slot), None, None, None, None, None, None, gres, None
-        if ctx.needs_input_grad[0]:
-            if shortcut is not None:
-                # the block's first convolution: data gradient + the gradient along the shortcut, and (x a block output with this
-                # block as its one reader) the ReLU backward of the block in front — one store
-                gx = conv_igemm_residual(gm, ctx.pd, None, shortcut, x if ctx.link_in is not None else None, d, k, False)
-                if ctx.link_in is not None:
-                    ctx.link_in.leave(gx, True)
-            elif ctx.link_in is not None:
-                # x = relu(...) of the node in front, read by this node only: its backward is a mask in this launch's store
+            gx, gw = conv_igemm_backward_residual(gm, ctx.pd, x, d, k, mask, shortcut, scale, slot)
+            gw = _landed(gw, slot)
+        else:
+            if ctx.needs_input_grad[0] and shortcut is not None:
+                # the block's first convolution: data gradient + the gradient along the shortcut (and the mask) — one store
+                gx = conv_igemm_residual(gm, ctx.pd, None, shortcut, mask, d, k, False)
+            elif ctx.needs_input_grad[0] and mask is not None:
                 (gx,), _ = conv_igemm_dgrad([gm], [ctx.pd], [x], [d], k, 1.0, bias_grad=False)
-                ctx.link_in.leave(gx, True)
-            else:
+            elif ctx.needs_input_grad[0]:
                 gx = conv_igemm([gm], [ctx.pd], None, [d], k, False)[0]
-        gw = None
-        if ctx.needs_input_grad[1]:
-            if conv_igemm_wgrad_launchable(cin, cout, k):
-                (gwf,) = conv_igemm_wgrad([x], [gm], [d], k)                    # float32, channels_last
-            else:
-                p = d * (k // 2)
-                gwf = torch.ops.aten.convolution_backward(gm, x, w.to(torch.bfloat16), None, [1, 1], [p, p], [d, d], False, [0, 0], 1,
-                                                          [False, True, False])[1].float()
-            gw = gwf * scale.view(-1, 1, 1, 1)
-        if shortcut is not None and gx is None:                                         # (cannot happen: the link is armed only by a node that computes one)
-            raise RuntimeError("a shortcut gradient was left for a node that computes no data gradient")
-        return gx, gw, None, None, None, None, None, None, gres, None
+            if ctx.needs_input_grad[1]:
+                if conv_igemm_wgrad_launchable(cin, cout, k):
+                    (gwf,) = conv_igemm_wgrad([x], [gm], [d], k)                    # float32, channels_last
+                else:
+                    p = d * (k // 2)
+                    gwf = torch.ops.aten.convolution_backward(gm, x, w.to(torch.bfloat16), None, [1, 1], [p, p], [d, d], False, [0, 0],
+                                                              1, [False, True, False])[1].float()
+                gw = gwf * scale.view(-1, 1, 1, 1)
+            if shortcut is not None and gx is None:                                     # (cannot happen: the link is armed only by a node that computes one)
+                raise RuntimeError("a shortcut gradient was left for a node that computes no data gradient")
+        if mask is not None:
+            ctx.link_in.leave(gx)                        # masked, and the node in front has no bias to sum a gradient for
+        return (gx, gw) + (None,) * (_FoldedIgemmFn.RES - 2) + (gres, None)
 
 
 class _ResLink:
