@@ -39,6 +39,7 @@ def test_srg_golden_vectors_bit_exact(ops, golden_srg):
 
 
 def test_srg_random_batches_vs_oracle(ops, O):
+    """sides 3..69, so mostly the 64-bit one-row form: the other growth forms and their seams are in tests/test_srg_paths.py"""
     rng = np.random.default_rng(5)
     for trial in range(8):
         B, C = 5, (21 if trial < 6 else 81 + 15 * (trial - 6))              # 81 = COCO (pylayers.py:389-512), 96 = the cap
