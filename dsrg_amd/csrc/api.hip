@@ -582,8 +582,13 @@ extern "C" int dsrg_avgpool3x3_s1_bf16(const void *in, void *out, int B, int H, 
 extern "C" int dsrg_conv_igemm_residual_bf16(const void *x_dev, const void *w_dev, const float *bias_dev, const void *res_dev, const void *mask_dev,
                                              void *y_dev, int dilation, int B, int H, int W, int cin, int cout, int ksize, int relu, void *stream) {
     if (!x_dev || !w_dev || !res_dev || !y_dev || B < 1 || H < 1 || W < 1) return set_error(DSRG_ERR_INVALID, "conv_igemm_residual: bad arguments");
-    return launch_conv_igemm_residual(x_dev, w_dev, bias_dev, res_dev, mask_dev, y_dev, dilation, B, H, W, cin, cout, ksize, relu,
-                                      static_cast<hipStream_t>(stream));
+    IgemmRequest r;
+    r.x[0] = x_dev; r.w[0] = w_dev; r.bias[0] = bias_dev; r.y[0] = y_dev; r.dil[0] = dilation;
+    r.mask[0] = mask_dev; r.masked = mask_dev != nullptr;
+    r.res = res_dev;
+    r.s = {B, H, W, cin, cout, ksize};
+    r.relu = relu;
+    return launch_conv_igemm(r, static_cast<hipStream_t>(stream));
 }
 extern "C" int dsrg_aspp_shift_sum_f32(const void *y_dev, const float *bias_dev, float *out_dev, const int *offsets, int npairs, int outputs,
                                        int channels, int B, int H, int W, void *stream) {
@@ -598,7 +603,7 @@ extern "C" int dsrg_aspp_shift_gather_bf16(const float *g_dev, void *gp_dev, con
 extern "C" int dsrg_conv_igemm_split_f32(const void *x3_dev, const void *w_dev, const float *bias_dev, float *y_dev, int dilation, int B, int H,
                                          int W, int cin, int cout, int ksize, int relu, void *stream) {
     if (!x3_dev || !w_dev || !y_dev) return set_error(DSRG_ERR_INVALID, "NULL argument");
-    return launch_conv_igemm_split(x3_dev, w_dev, bias_dev, y_dev, dilation, B, H, W, cin, cout, ksize, relu, static_cast<hipStream_t>(stream));
+    return launch_conv_igemm_split(x3_dev, w_dev, bias_dev, y_dev, dilation, {B, H, W, cin, cout, ksize}, relu, static_cast<hipStream_t>(stream));
 }
 extern "C" int dsrg_add_relu_bf16(const void *a, const void *b, void *y, size_t n, void *stream) {
     if (!a || !b || !y) return set_error(DSRG_ERR_INVALID, "NULL argument");
@@ -639,8 +644,14 @@ extern "C" int dsrg_conv_igemm_bf16(const void *const *x_dev, const void *const 
                                     int ksize, int relu, float dropout_p, unsigned long long dropout_seed, void *workspace_dev,
                                     size_t workspace_bytes, void *stream) {
     if (!x_dev || !w_dev || !y_dev || B < 1 || H < 1 || W < 1) return set_error(DSRG_ERR_INVALID, "conv_igemm: bad arguments");
-    return launch_conv_igemm(x_dev, w_dev, bias_dev, y_dev, dilation, ngroups, B, H, W, cin, cout, ksize, relu, dropout_p,
-                             dropout_seed, workspace_dev, workspace_bytes, static_cast<hipStream_t>(stream));
+    IgemmRequest r;
+    put_groups(r.x, x_dev, ngroups); put_groups(r.w, w_dev, ngroups); put_groups(r.bias, bias_dev, ngroups); put_groups(r.y, y_dev, ngroups);
+    put_groups(r.dil, dilation, ngroups);
+    r.ngroups = ngroups;
+    r.s = {B, H, W, cin, cout, ksize};
+    r.relu = relu; r.drop_p = dropout_p; r.seed = dropout_seed;
+    r.workspace = workspace_dev; r.workspace_bytes = workspace_bytes;
+    return launch_conv_igemm(r, static_cast<hipStream_t>(stream));
 }
 extern "C" size_t dsrg_conv_igemm_dgrad_workspace(int ngroups, int B, int H, int W, int cout) {
     return conv_igemm_colsum_workspace(ngroups, B, H, W, cout);
@@ -651,8 +662,15 @@ extern "C" int dsrg_conv_igemm_dgrad_bf16(const void *const *g_dev, const void *
                                           size_t workspace_bytes, void *stream) {
     if (!g_dev || !w_dev || !gx_dev || !mask_dev || B < 1 || H < 1 || W < 1)
         return set_error(DSRG_ERR_INVALID, "conv_igemm_dgrad: bad arguments");
-    return launch_conv_igemm(g_dev, w_dev, nullptr, gx_dev, dilation, ngroups, B, H, W, cin, cout, ksize, 0, 0.0f, 0ull, nullptr, 0,
-                             static_cast<hipStream_t>(stream), mask_dev, mask_scale, bias_grad_dev, workspace_dev, workspace_bytes);
+    IgemmRequest r;      // (cin: the gradient's channels — the data gradient is a convolution with the flipped kernel)
+    put_groups(r.x, g_dev, ngroups); put_groups(r.w, w_dev, ngroups); put_groups(r.y, gx_dev, ngroups); put_groups(r.dil, dilation, ngroups);
+    r.masked = put_groups(r.mask, mask_dev, ngroups);
+    r.colsums = put_groups(r.colsum, bias_grad_dev, ngroups);
+    r.ngroups = ngroups;
+    r.s = {B, H, W, cin, cout, ksize};
+    r.out_scale = mask_scale;
+    r.colsum_ws = workspace_dev; r.colsum_ws_bytes = workspace_bytes;
+    return launch_conv_igemm(r, static_cast<hipStream_t>(stream));
 }
 extern "C" size_t dsrg_conv_igemm_workspace(void) { return conv_igemm_workspace(); }
 extern "C" int dsrg_conv_igemm_workspace_status(const void *workspace_dev, void *stream, int *status_host) {
@@ -692,13 +710,22 @@ extern "C" int dsrg_conv_igemm_wgrad_bf16(const void *const *x_dev, const void *
                                           int ngroups, void *workspace_dev, size_t workspace_bytes, int B, int H, int W, int cin,
                                           int cout, int ksize, int out_bf16, void *stream) {
     if (!x_dev || !g_dev || !gw_dev || B < 1 || H < 1 || W < 1) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: bad arguments");
-    return launch_conv_igemm_wgrad(x_dev, g_dev, gw_dev, dilation, ngroups, workspace_dev, workspace_bytes, B, H, W, cin, cout, ksize,
-                                   out_bf16, static_cast<hipStream_t>(stream));
+    WgradRequest r;
+    put_groups(r.x, x_dev, ngroups); put_groups(r.g, g_dev, ngroups); put_groups(r.gw, gw_dev, ngroups); put_groups(r.dil, dilation, ngroups);
+    r.ngroups = ngroups;
+    r.workspace = workspace_dev; r.workspace_bytes = workspace_bytes;
+    r.s = {B, H, W, cin, cout, ksize};
+    return launch_conv_igemm_wgrad(r, out_bf16, static_cast<hipStream_t>(stream));
 }
-namespace dsrg {
-int launch_conv_igemm_backward(const void *g, const void *wd, const void *x, const void *mask, void *gx, void *gw, int dil, float *bias_grad,
-                               float mask_scale, void *colsum_ws, size_t colsum_ws_bytes, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H,
-                               int W, int cin, int cout, int k, hipStream_t stream);
+// the request of one convolution's whole backward (dsrg_conv_igemm_backward_bf16 and its residual form)
+static BackwardRequest backward_request(const void *g, const void *wd, const void *x, const void *mask, void *gx, float *gw, int dilation,
+                                        void *wgrad_ws, size_t wgrad_ws_bytes, const ConvGeom &s) {
+    BackwardRequest r;
+    r.g[0] = g; r.wd[0] = wd; r.x[0] = x; r.gx[0] = gx; r.gw[0] = gw; r.dil[0] = dilation;
+    r.mask[0] = mask; r.masked = mask != nullptr;
+    r.wgrad_ws = wgrad_ws; r.wgrad_ws_bytes = wgrad_ws_bytes;
+    r.s = s;
+    return r;
 }
 extern "C" int dsrg_conv_igemm_backward_bf16(const void *g_dev, const void *w_dgrad_dev, const void *x_dev, const void *mask_dev, void *gx_dev,
                                              float *gw_dev, int dilation, float *bias_grad_dev, float mask_scale, void *colsum_workspace_dev,
@@ -706,9 +733,12 @@ extern "C" int dsrg_conv_igemm_backward_bf16(const void *g_dev, const void *w_dg
                                              int H, int W, int cin, int cout, int ksize, void *stream) {
     if (!g_dev || !w_dgrad_dev || !x_dev || !gx_dev || !gw_dev || B < 1 || H < 1 || W < 1 || (bias_grad_dev && !mask_dev))
         return set_error(DSRG_ERR_INVALID, "conv_igemm_backward: bad arguments");
-    return dsrg::launch_conv_igemm_backward(g_dev, w_dgrad_dev, x_dev, mask_dev, gx_dev, gw_dev, dilation, bias_grad_dev, mask_scale,
-                                            colsum_workspace_dev, colsum_workspace_bytes, wgrad_workspace_dev, wgrad_workspace_bytes, B, H,
-                                            W, cin, cout, ksize, static_cast<hipStream_t>(stream));
+    BackwardRequest r = backward_request(g_dev, w_dgrad_dev, x_dev, mask_dev, gx_dev, gw_dev, dilation, wgrad_workspace_dev, wgrad_workspace_bytes,
+                                         {B, H, W, cin, cout, ksize});
+    r.bias_grad[0] = bias_grad_dev; r.bias_grads = bias_grad_dev != nullptr;
+    r.mask_scale = mask_scale;
+    r.colsum_ws = colsum_workspace_dev; r.colsum_ws_bytes = colsum_workspace_bytes;
+    return launch_conv_igemm_backward(r, static_cast<hipStream_t>(stream));
 }
 extern "C" int dsrg_conv_igemm_backward_residual_bf16(const void *g_dev, const void *w_dgrad_dev, const void *x_dev, const void *mask_dev,
                                                       const void *res_dev, void *gx_dev, float *gw_dev, const float *gw_scale_dev, int dilation,
@@ -716,9 +746,10 @@ extern "C" int dsrg_conv_igemm_backward_residual_bf16(const void *g_dev, const v
                                                       int cout, int ksize, void *stream) {
     if (!g_dev || !w_dgrad_dev || !x_dev || !gx_dev || !gw_dev || B < 1 || H < 1 || W < 1)
         return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_residual: bad arguments");
-    return launch_conv_igemm_backward_residual(g_dev, w_dgrad_dev, x_dev, mask_dev, res_dev, gx_dev, gw_dev, gw_scale_dev, dilation,
-                                               wgrad_workspace_dev, wgrad_workspace_bytes, B, H, W, cin, cout, ksize,
-                                               static_cast<hipStream_t>(stream));
+    BackwardRequest r = backward_request(g_dev, w_dgrad_dev, x_dev, mask_dev, gx_dev, gw_dev, dilation, wgrad_workspace_dev, wgrad_workspace_bytes,
+                                         {B, H, W, cin, cout, ksize});
+    r.res = res_dev; r.gw_scale = gw_scale_dev;
+    return launch_conv_igemm_backward(r, static_cast<hipStream_t>(stream));
 }
 extern "C" int dsrg_conv_igemm_backward_groups_bf16(const void *const *g_dev, const void *const *w_dgrad_dev, const void *const *x_dev,
                                                     const void *const *mask_dev, void *const *gx_dev, void *const *gw_dev, const int *dilation,
@@ -728,14 +759,23 @@ extern "C" int dsrg_conv_igemm_backward_groups_bf16(const void *const *g_dev, co
                                                     void *stream) {
     if (!g_dev || !w_dgrad_dev || !x_dev || !gx_dev || !gw_dev || B < 1 || H < 1 || W < 1 || (bias_grad_dev && !mask_dev))
         return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups: bad arguments");
-    return launch_conv_igemm_backward_groups(g_dev, w_dgrad_dev, x_dev, mask_dev, gx_dev, gw_dev, dilation, ngroups, bias_grad_dev, mask_scale,
-                                             colsum_workspace_dev, colsum_workspace_bytes, wgrad_workspace_dev, wgrad_workspace_bytes, B, H,
-                                             W, cin, cout, ksize, force_ksplit, force_order, static_cast<hipStream_t>(stream));
+    BackwardRequest r;
+    put_groups(r.g, g_dev, ngroups); put_groups(r.wd, w_dgrad_dev, ngroups); put_groups(r.x, x_dev, ngroups); put_groups(r.gx, gx_dev, ngroups);
+    put_groups(r.gw, gw_dev, ngroups); put_groups(r.dil, dilation, ngroups);
+    r.masked = put_groups(r.mask, mask_dev, ngroups);
+    r.bias_grads = put_groups(r.bias_grad, bias_grad_dev, ngroups);
+    r.ngroups = ngroups;
+    r.mask_scale = mask_scale;
+    r.colsum_ws = colsum_workspace_dev; r.colsum_ws_bytes = colsum_workspace_bytes;
+    r.wgrad_ws = wgrad_workspace_dev; r.wgrad_ws_bytes = wgrad_workspace_bytes;
+    r.s = {B, H, W, cin, cout, ksize};
+    r.forced_ksplit = force_ksplit; r.forced_order = force_order;
+    return launch_conv_igemm_backward_groups(r, static_cast<hipStream_t>(stream));
 }
 extern "C" int dsrg_conv_igemm_backward_groups_plan(int ngroups, int B, int H, int W, int cin, int cout, int ksize, const int *dilation,
                                                     int with_mask, int force_ksplit, int force_order, int *plan_out, double *us_out) {
     if (B < 1 || H < 1 || W < 1) return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups_plan: bad arguments");
-    return conv_igemm_backward_groups_plan(ngroups, B, H, W, cin, cout, ksize, dilation, with_mask, force_ksplit, force_order, plan_out, us_out);
+    return conv_igemm_backward_groups_plan(ngroups, {B, H, W, cin, cout, ksize}, dilation, with_mask, force_ksplit, force_order, plan_out, us_out);
 }
 extern "C" int dsrg_pack_conv_weight_scaled_f32(const float *w_dev, const float *scale_dev, void *fwd_dev, void *dgrad_dev, int cout, int cin,
                                                 int ksize, void *stream) {

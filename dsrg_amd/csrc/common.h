@@ -301,32 +301,74 @@ int launch_conv3x3_direct(const void *x, const void *w, const float *bias, void 
                           void *colsum_ws = nullptr, size_t colsum_ws_bytes = 0);
 size_t conv3x3_direct_colsum_workspace(int cout);
 bool conv_igemm_supported(int cin, int cout, int k);
-int launch_conv_igemm_residual(const void *x, const void *w, const float *bias, const void *res, const void *mask, void *y, int dil, int B,
-                               int H, int W, int cin, int cout, int k, int relu, hipStream_t stream);
-int launch_conv_igemm_split(const void *x3, const void *w, const float *bias, float *y, int dil, int B, int H, int W, int cin, int cout, int k,
-                            int relu, hipStream_t stream);
-int launch_conv_igemm(const void *const *x, const void *const *w, const float *const *bias, void *const *y, const int *dil,
-                      int ngroups, int B, int H, int W, int cin, int cout, int k, int relu, float drop_p, unsigned long long seed,
-                      void *workspace, size_t workspace_bytes, hipStream_t stream, const void *const *mask = nullptr,
-                      float out_scale = 1.0f, float *const *colsum = nullptr, void *colsum_ws = nullptr, size_t colsum_ws_bytes = 0);
+// ---- implicit-GEMM convolutions (conv_igemm.hip).  A launch is asked for with a request: an aggregate whose defaults mean "not
+// used", filled field by field.  Per-group pointers are held by value; put_groups copies a caller's array (false: there is none)
+struct ConvGeom { int B, H, W, cin, cout, k; };     // the FORWARD convolution's: cin -> cout channels, k x k taps
+template <class T> bool put_groups(T (&dst)[4], T const *src, int ngroups) {
+    for (int g = 0; src && g < ngroups && g < 4; g++) dst[g] = src[g];
+    return src != nullptr;
+}
+// One grid of conv_igemm_kernel_64x2 (or its stream-K form): a forward, or a data gradient on the flipped kernel (then s.cin counts
+// the gradient's channels).  masked: zero the output where mask <= 0, one mask per group; colsums: bias gradients of the layer
+// below into colsum[], one per group, through colsum_ws (conv_igemm_colsum_workspace)
+struct IgemmRequest {
+    const void *x[4] = {}, *w[4] = {}, *mask[4] = {};
+    const float *bias[4] = {};
+    void *y[4] = {};
+    float *colsum[4] = {};
+    bool masked = false, colsums = false;
+    int dil[4] = {1, 1, 1, 1}, ngroups = 1;
+    ConvGeom s = {};
+    int relu = 0;
+    float drop_p = 0.0f;
+    unsigned long long seed = 0;
+    void *workspace = nullptr;          // stream-K (conv_igemm_workspace); none: whole tiles
+    size_t workspace_bytes = 0;
+    float out_scale = 1.0f;
+    void *colsum_ws = nullptr;
+    size_t colsum_ws_bytes = 0;
+    const void *res = nullptr;          // the residual in the single group's store (IgemmGroup::res)
+    int split_cin = 0;                  // split mode: the real input channel count (s.cin is then the VIRTUAL count 6 * real)
+    bool may_stream_k = true;           // false: whole tiles whatever the shape (the halves of a backward)
+};
+struct WgradRequest {
+    const void *x[4] = {}, *g[4] = {};
+    void *gw[4] = {};
+    int dil[4] = {1, 1, 1, 1}, ngroups = 1;
+    void *workspace = nullptr;          // conv_igemm_wgrad_workspace
+    size_t workspace_bytes = 0;
+    ConvGeom s = {};
+    int forced_ksplit = 0;              // > 0: the half of a merged backward grid, on the uniform pixel split picked for that grid
+};
+// The whole backward of one convolution, or of 1 - 4 of one geometry (launch_conv_igemm_backward_groups)
+struct BackwardRequest {
+    const void *g[4] = {}, *wd[4] = {}, *x[4] = {}, *mask[4] = {};
+    void *gx[4] = {}, *gw[4] = {};
+    float *bias_grad[4] = {};
+    bool masked = false, bias_grads = false;
+    int dil[4] = {1, 1, 1, 1}, ngroups = 1;
+    float mask_scale = 1.0f;
+    void *colsum_ws = nullptr, *wgrad_ws = nullptr;
+    size_t colsum_ws_bytes = 0, wgrad_ws_bytes = 0;
+    ConvGeom s = {};
+    const void *res = nullptr;          // one convolution: a residual in the data gradient's store,
+    const float *gw_scale = nullptr;    // a per-output factor on the weight gradient
+    int forced_ksplit = 0, forced_order = 0;      // groups (tests): that uniform split; 1 / 2: the data / weight gradient's blocks first
+};
+int launch_conv_igemm(const IgemmRequest &r, hipStream_t stream);
+int launch_conv_igemm_split(const void *x3, const void *w, const float *bias, float *y, int dil, const ConvGeom &s, int relu, hipStream_t stream);
 size_t conv_igemm_colsum_workspace(int ngroups, int B, int H, int W, int cout);
 size_t conv_igemm_workspace();
 int conv_igemm_workspace_status(const void *workspace, hipStream_t stream, int *status);
 size_t conv_igemm_wgrad_workspace(int ngroups, int B, int H, int W, int cin, int cout, int k);
 int conv_igemm_wgrad_splits(int ngroups, int B, int H, int W, int cin, int cout, int k, const int *dil, int *splits);
-int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *const *gw, const int *dil, int ngroups, void *workspace,
-                            size_t workspace_bytes, int B, int H, int W, int cin, int cout, int k, int out_bf16, hipStream_t stream);
+int launch_conv_igemm_wgrad(const WgradRequest &r, int out_bf16, hipStream_t stream);
 int launch_pack_conv_weight(const float *w, void *fwd, void *dgrad, int cout, int cin, int k, hipStream_t stream, int plain = 0,
                             const float *scale = nullptr);
-int launch_conv_igemm_backward_residual(const void *g, const void *wd, const void *x, const void *mask, const void *res, void *gx, void *gw,
-                                        const float *gw_scale, int dil, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W, int cin,
-                                        int cout, int k, hipStream_t stream);
-int launch_conv_igemm_backward_groups(const void *const *g, const void *const *wd, const void *const *x, const void *const *mask,
-                                      void *const *gx, void *const *gw, const int *dil, int ngroups, float *const *bias_grad, float mask_scale,
-                                      void *colsum_ws, size_t colsum_ws_bytes, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W,
-                                      int cin, int cout, int k, int forced_ksplit, int forced_order, hipStream_t stream);
-int conv_igemm_backward_groups_plan(int ngroups, int B, int H, int W, int cin, int cout, int k, const int *dil, int with_mask, int forced_ksplit,
-                                    int forced_order, int *out, double *us);
+int launch_conv_igemm_backward(const BackwardRequest &r, hipStream_t stream);
+int launch_conv_igemm_backward_groups(const BackwardRequest &r, hipStream_t stream);
+int conv_igemm_backward_groups_plan(int ngroups, const ConvGeom &s, const int *dil, int with_mask, int forced_ksplit, int forced_order, int *out,
+                                    double *us);
 int heads_bwd_chunks(int M);
 int launch_heads_bwd(const void *const *x, int nbr, const float *w, const float *g, void *gx, size_t gx_branch_stride,
                      float *gw, float *partial, int B, int HW, int K, int O, hipStream_t stream, float relu_scale = 0.0f,

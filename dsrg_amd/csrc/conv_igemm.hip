@@ -1245,15 +1245,12 @@ struct IgemmLaunch {
     bool stream_k;          // conv_igemm_sk_kernel instead of conv_igemm_kernel_64x2
 };
 
-// Besides launch_conv_igemm's public arguments: res — the residual of the single group (IgemmGroup::res) or nullptr; split_cin — split
-// mode: the real input channel count (cin is then the VIRTUAL count 6 * real), 0: an ordinary launch; may_stream_k — false: whole
-// tiles whatever the shape (the halves of a backward).  Launches nothing, enqueues nothing
-int prepare_igemm(const void *const *x, const void *const *w, const float *const *bias, void *const *y, const int *dil, int ngroups, int B, int H,
-                  int W, int cin, int cout, int k, int relu, float drop_p, unsigned long long seed, void *workspace, size_t workspace_bytes,
-                  const void *const *mask, float out_scale, float *const *colsum, void *colsum_ws, size_t colsum_ws_bytes, const void *res,
-                  int split_cin, bool may_stream_k, const IgemmVariant &v, IgemmLaunch &L) {
+// The request's fields: IgemmRequest (common.h).  Launches nothing, enqueues nothing
+int prepare_igemm(const IgemmRequest &r, const IgemmVariant &v, IgemmLaunch &L) {
+    const int ngroups = r.ngroups, B = r.s.B, H = r.s.H, W = r.s.W, cin = r.s.cin, cout = r.s.cout, k = r.s.k, split_cin = r.split_cin;
+    const float drop_p = r.drop_p;
     if (ngroups < 1 || ngroups > 4) return set_error(DSRG_ERR_INVALID, "conv_igemm: 1..4 groups");
-    if (colsum && (!colsum_ws || colsum_ws_bytes < conv_igemm_colsum_workspace(ngroups, B, H, W, cout)))
+    if (r.colsums && (!r.colsum_ws || r.colsum_ws_bytes < conv_igemm_colsum_workspace(ngroups, B, H, W, cout)))
         return set_error(DSRG_ERR_INVALID, "conv_igemm: column-sum scratch missing or too small");
     if (!conv_igemm_launchable(cin, cout, k))
         return set_error(DSRG_ERR_UNSUPPORTED, "conv_igemm: cin %% 64 == 0, cout %% 128 == 0 (or cout = 64), k in (1, 3) required (got %d, %d, %d)",
@@ -1264,18 +1261,18 @@ int prepare_igemm(const void *const *x, const void *const *w, const float *const
     memset(&L, 0, sizeof(L));
     IgemmArgs &a = L.sk.base;
     for (int g = 0; g < ngroups; g++) {
-        a.g[g].x = static_cast<const uint16_t *>(x[g]);
-        a.g[g].w = static_cast<const uint16_t *>(w[g]);
-        a.g[g].bias = bias ? bias[g] : nullptr;
-        a.g[g].y = static_cast<uint16_t *>(y[g]);
-        a.g[g].dil = dil ? dil[g] : 1;
-        a.g[g].mask = mask ? static_cast<const uint16_t *>(mask[g]) : nullptr;
-        a.g[g].colsum = colsum ? static_cast<float *>(colsum_ws) + (size_t)g * conv_igemm_pixel_tiles(B, H, W) * cout : nullptr;
-        a.g[g].res = static_cast<const uint16_t *>(res);
-        if (!a.g[g].x || !a.g[g].w || !a.g[g].y || (mask && !mask[g]) || (colsum && !colsum[g]))
+        a.g[g].x = static_cast<const uint16_t *>(r.x[g]);
+        a.g[g].w = static_cast<const uint16_t *>(r.w[g]);
+        a.g[g].bias = r.bias[g];
+        a.g[g].y = static_cast<uint16_t *>(r.y[g]);
+        a.g[g].dil = r.dil[g];
+        a.g[g].mask = r.masked ? static_cast<const uint16_t *>(r.mask[g]) : nullptr;
+        a.g[g].colsum = r.colsums ? static_cast<float *>(r.colsum_ws) + (size_t)g * conv_igemm_pixel_tiles(B, H, W) * cout : nullptr;
+        a.g[g].res = static_cast<const uint16_t *>(r.res);
+        if (!a.g[g].x || !a.g[g].w || !a.g[g].y || (r.masked && !r.mask[g]) || (r.colsums && !r.colsum[g]))
             return set_error(DSRG_ERR_INVALID, "conv_igemm: null pointer");
     }
-    a.out_scale = out_scale;
+    a.out_scale = r.out_scale;
     a.xrow = cin * 2;
     if (split_cin > 0) {
         a.xrow = 3 * split_cin * 2;
@@ -1283,10 +1280,10 @@ int prepare_igemm(const void *const *x, const void *const *w, const float *const
         a.out_f32 = 1;
     }
     a.skip_taps = v.skip_dead_steps;
-    const bool fused_bwd = mask || colsum || res;
-    if (res && (colsum || ngroups != 1 || drop_p != 0.0f || split_cin))
+    const bool fused_bwd = r.masked || r.colsums || r.res;
+    if (r.res && (r.colsums || ngroups != 1 || drop_p != 0.0f || split_cin))
         return set_error(DSRG_ERR_UNSUPPORTED, "conv_igemm: a residual goes with one group, no column sums, no dropout");
-    a.ngroups = ngroups; a.B = B; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.taps = k * k; a.relu = relu; a.M = (int)M;
+    a.ngroups = ngroups; a.B = B; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.taps = k * k; a.relu = r.relu; a.M = (int)M;
     a.tiles_m = (int)((M + kBM - 1) / kBM);
     a.tiles_n = (cout + kBN - 1) / kBN;
     a.tiles_per_group = a.tiles_m * a.tiles_n;
@@ -1294,7 +1291,7 @@ int prepare_igemm(const void *const *x, const void *const *w, const float *const
     a.drop_thresh = (uint32_t)(drop_p * 256.0f + 0.5f);       // p is realised in steps of 1 / 256 (0.5 exactly)
     if (a.drop_thresh > 255) a.drop_thresh = 255;
     a.drop_scale = 256.0f / (float)(256 - (int)a.drop_thresh);
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+    a.seed_lo = (uint32_t)r.seed; a.seed_hi = (uint32_t)(r.seed >> 32);
     a.stagger = v.stagger;
     // stream-K only where it was measured to win (profiles/r04_igemm_stream_k.txt): a single round that fills at most 60 % of
     // the chip (conv4_1's data gradient: 106 tiles, 115 -> 88 us).  A cut tile costs its workgroups ~25 us (256 KB of
@@ -1303,13 +1300,13 @@ int prepare_igemm(const void *const *x, const void *const *w, const float *const
     // different rounds overlap: fc6 x 4, 6.6 rounds, 810 us whole against 902 us dealt out).
     const int units = igemm_cus(), tiles_total = a.tiles_per_group * ngroups, nsteps = (cin / 64) * k * k;
     const bool sk_wins = tiles_total * 100 <= units * 60;
-    if (may_stream_k && !fused_bwd && split_cin == 0 && cout % 128 == 0 && workspace && workspace_bytes >= conv_igemm_workspace() &&
+    if (r.may_stream_k && !fused_bwd && split_cin == 0 && cout % 128 == 0 && r.workspace && r.workspace_bytes >= conv_igemm_workspace() &&
         ((v.stream_k_where_it_wins && sk_wins) || v.stream_k_forced) && (long long)tiles_total * nsteps >= (long long)units * 8 &&
         tiles_total * 3 >= units) {
         L.stream_k = true; L.grid = units;
         a.stagger = 1;
-        L.sk.ws = static_cast<float *>(workspace);
-        L.sk.flags = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(workspace) + (size_t)units * (32 * 512 * 16));
+        L.sk.ws = static_cast<float *>(r.workspace);
+        L.sk.flags = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(r.workspace) + (size_t)units * (32 * 512 * 16));
         L.sk.units = units; L.sk.tiles_total = tiles_total;
         return DSRG_OK;
     }
@@ -1349,7 +1346,15 @@ int prepare_igemm(const void *const *x, const void *const *w, const float *const
     return DSRG_OK;
 }
 
-// the prepared launch, then the column-sum pass into colsum (nullptr: the launch kept no column sums)
+// the column sums a data gradient's grid left per tile, summed into colsum (nullptr: it kept none)
+int run_colsum(const IgemmArgs &a, float *const *colsum, hipStream_t stream) {
+    if (!colsum) return DSRG_OK;
+    const float *parts[4];
+    for (int g = 0; g < a.ngroups; g++) parts[g] = a.g[g].colsum;
+    return launch_igemm_colsum(parts, colsum, a.ngroups, a.tiles_m, a.Cout, stream);
+}
+
+// the prepared launch, then its column-sum pass
 int run_igemm(const IgemmLaunch &L, float *const *colsum, hipStream_t stream) {
     static LdsGrant grant[2];
     constexpr size_t lds = ICfg<64, 2>::LDS;
@@ -1364,53 +1369,31 @@ int run_igemm(const IgemmLaunch &L, float *const *colsum, hipStream_t stream) {
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(&conv_igemm_kernel_64x2), lds, grant[0])) return rc;
     hipLaunchKernelGGL(conv_igemm_kernel_64x2, dim3(L.grid), dim3(512), lds, stream, a);
     DSRG_LAUNCH_CHECK();
-    if (colsum) {
-        const float *parts[4];
-        for (int g = 0; g < a.ngroups; g++) parts[g] = a.g[g].colsum;
-        if (int rc = launch_igemm_colsum(parts, colsum, a.ngroups, a.tiles_m, a.Cout, stream)) return rc;
-    }
-    return DSRG_OK;
+    return run_colsum(a, colsum, stream);
 }
 }  // namespace
 
-int launch_conv_igemm(const void *const *x, const void *const *w, const float *const *bias, void *const *y, const int *dil,
-                      int ngroups, int B, int H, int W, int cin, int cout, int k, int relu, float drop_p, unsigned long long seed,
-                      void *workspace, size_t workspace_bytes, hipStream_t stream, const void *const *mask, float out_scale,
-                      float *const *colsum, void *colsum_ws, size_t colsum_ws_bytes) {
+// A forward, a data gradient (the request's mask / colsum fields), or either with a residual in the single group's store: y =
+// post(bf16(conv(x, w) + bias) + res), post = ReLU (relu) and / or zero where mask <= 0 — the forward of a residual block's last
+// convolution, the data gradient of its first
+int launch_conv_igemm(const IgemmRequest &r, hipStream_t stream) {
     IgemmLaunch L;
-    if (int rc = prepare_igemm(x, w, bias, y, dil, ngroups, B, H, W, cin, cout, k, relu, drop_p, seed, workspace, workspace_bytes, mask, out_scale,
-                               colsum, colsum_ws, colsum_ws_bytes, nullptr, 0, true, igemm_variant(), L)) return rc;
-    return run_igemm(L, colsum, stream);
+    if (int rc = prepare_igemm(r, igemm_variant(), L)) return rc;
+    return run_igemm(L, r.colsums ? r.colsum : nullptr, stream);
 }
 
 // A float32 convolution on the bf16 MFMA (forward, one group; layer-level prototype of round 6): x3 = the three bf16 planes of the
 // float32 activation, (B, H, W, 3 cin) with channel index plane * cin + c; w = the packed kernel over 6 cin VIRTUAL channels,
 // (cout, 6 cin / 64, k k, 64), virtual chunk block q holding plane {0, 1, 0, 2, 0, 1}[q] of the split kernel; y float32 (B, H, W, cout)
-int launch_conv_igemm_split(const void *x3, const void *w, const float *bias, float *y, int dil, int B, int H, int W, int cin, int cout, int k,
-                            int relu, hipStream_t stream) {
-    if (!conv_igemm_supported(cin, cout, k) || (long long)B * H * W * 3 * cin * 2 >= 0x7fffffffLL)
+int launch_conv_igemm_split(const void *x3, const void *w, const float *bias, float *y, int dil, const ConvGeom &s, int relu, hipStream_t stream) {
+    if (!conv_igemm_supported(s.cin, s.cout, s.k) || (long long)s.B * s.H * s.W * 3 * s.cin * 2 >= 0x7fffffffLL)
         return set_error(DSRG_ERR_UNSUPPORTED, "conv_igemm_split: shape not supported");
-    const void *xp[1] = {x3}, *wp[1] = {w};
-    const float *bp[1] = {bias};
-    void *yp[1] = {y};
-    IgemmLaunch L;
-    if (int rc = prepare_igemm(xp, wp, bias ? bp : nullptr, yp, &dil, 1, B, H, W, 6 * cin, cout, k, relu, 0.0f, 0ull, nullptr, 0, nullptr, 1.0f,
-                               nullptr, nullptr, 0, nullptr, cin, true, igemm_variant(), L)) return rc;
-    return run_igemm(L, nullptr, stream);
-}
-
-// One group with a residual in the store (IgemmGroup::res): y = post(bf16(conv(x, w) + bias) + res), post = ReLU (relu) and / or
-// zero where mask <= 0 (mask may be nullptr).  Forward of a residual block's last convolution; data gradient of its first.
-int launch_conv_igemm_residual(const void *x, const void *w, const float *bias, const void *res, const void *mask, void *y, int dil, int B,
-                               int H, int W, int cin, int cout, int k, int relu, hipStream_t stream) {
-    if (!res) return set_error(DSRG_ERR_INVALID, "conv_igemm_residual: null residual");
-    const void *xp[1] = {x}, *wp[1] = {w}, *mp[1] = {mask};
-    const float *bp[1] = {bias};
-    void *yp[1] = {y};
-    IgemmLaunch L;
-    if (int rc = prepare_igemm(xp, wp, bias ? bp : nullptr, yp, &dil, 1, B, H, W, cin, cout, k, relu, 0.0f, 0ull, nullptr, 0, mask ? mp : nullptr,
-                               1.0f, nullptr, nullptr, 0, res, 0, true, igemm_variant(), L)) return rc;
-    return run_igemm(L, nullptr, stream);
+    IgemmRequest r;
+    r.x[0] = x3; r.w[0] = w; r.bias[0] = bias; r.y[0] = y; r.dil[0] = dil;
+    r.s = {s.B, s.H, s.W, 6 * s.cin, s.cout, s.k};
+    r.relu = relu;
+    r.split_cin = s.cin;
+    return launch_conv_igemm(r, stream);
 }
 
 bool conv_igemm_wgrad_supported(int cin, int cout, int k) {
@@ -1452,10 +1435,12 @@ struct WgradLaunch {
     int grid;
 };
 
-// forced_ksplit > 0: the weight-gradient half of a merged backward grid, with the pixel split picked for that grid (a uniform split:
-// such a launch takes no work list).  Launches nothing, enqueues nothing
-int prepare_wgrad(const void *const *x, const void *const *g, void *const *gw, const int *dil, int ngroups, void *workspace, size_t workspace_bytes,
-                  int B, int H, int W, int cin, int cout, int k, const IgemmVariant &v, int forced_ksplit, WgradLaunch &L) {
+// The request's fields: WgradRequest (common.h); a forced split is a uniform one: such a launch takes no work list.  Launches
+// nothing, enqueues nothing
+int prepare_wgrad(const WgradRequest &r, const IgemmVariant &v, WgradLaunch &L) {
+    const int ngroups = r.ngroups, B = r.s.B, H = r.s.H, W = r.s.W, cin = r.s.cin, cout = r.s.cout, k = r.s.k, forced_ksplit = r.forced_ksplit;
+    const int *const dil = r.dil;
+    void *const workspace = r.workspace;
     if (ngroups < 1 || ngroups > 4) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: 1..4 groups");
     if (!conv_igemm_wgrad_launchable(cin, cout, k))
         return set_error(DSRG_ERR_UNSUPPORTED, "conv_igemm_wgrad: cin %% 64 == 0, cout %% 64 == 0, k in (1, 3) required (got %d, %d, %d)", cin, cout, k);
@@ -1463,7 +1448,7 @@ int prepare_wgrad(const void *const *x, const void *const *g, void *const *gw, c
     if (M <= 0 || M * cin * 2 >= 0x7fffffffLL || M * cout * 2 >= 0x7fffffffLL)
         return set_error(DSRG_ERR_UNSUPPORTED, "conv_igemm_wgrad: tensor too large for 32-bit buffer offsets");
     const size_t need = wgrad_workspace_bytes(ngroups, B, H, W, cin, cout, k);
-    if (!workspace || workspace_bytes < need) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: workspace of %zu bytes needed", need);
+    if (!workspace || r.workspace_bytes < need) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: workspace of %zu bytes needed", need);
     memset(&L, 0, sizeof(L));
     IgemmWgradArgs &a = L.a;
     a.ngroups = ngroups; a.B = B; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout; a.taps = k * k; a.M = (int)M;
@@ -1477,11 +1462,11 @@ int prepare_wgrad(const void *const *x, const void *const *g, void *const *gw, c
     a.skip_rows = v.skip_dead_steps;
     const size_t per_group = (size_t)a.ksplit * cout * k * k * cin;
     for (int q = 0; q < ngroups; q++) {
-        a.g[q].x = static_cast<const uint16_t *>(x[q]);
-        a.g[q].g = static_cast<const uint16_t *>(g[q]);
+        a.g[q].x = static_cast<const uint16_t *>(r.x[q]);
+        a.g[q].g = static_cast<const uint16_t *>(r.g[q]);
         a.g[q].part = static_cast<float *>(workspace) + (L.plan ? 0 : (size_t)q * per_group);
-        a.g[q].dil = dil ? dil[q] : 1;
-        if (!a.g[q].x || !a.g[q].g || !gw[q]) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: null pointer");
+        a.g[q].dil = dil[q];
+        if (!a.g[q].x || !a.g[q].g || !r.gw[q]) return set_error(DSRG_ERR_INVALID, "conv_igemm_wgrad: null pointer");
     }
     // (compact pixel order for every 3x3 layer, not the dilated ones only: 1 800-1 807 against 1 776-1 782 images/s)
     for (int q = 0; q < ngroups; q++) {
@@ -1551,11 +1536,10 @@ int run_wgrad(const WgradLaunch &L, void *const *gw, const float *scale, int out
 }
 }  // namespace
 
-int launch_conv_igemm_wgrad(const void *const *x, const void *const *g, void *const *gw, const int *dil, int ngroups, void *workspace,
-                            size_t workspace_bytes, int B, int H, int W, int cin, int cout, int k, int out_bf16, hipStream_t stream) {
+int launch_conv_igemm_wgrad(const WgradRequest &r, int out_bf16, hipStream_t stream) {
     WgradLaunch L;
-    if (int rc = prepare_wgrad(x, g, gw, dil, ngroups, workspace, workspace_bytes, B, H, W, cin, cout, k, igemm_variant(), 0, L)) return rc;
-    return run_wgrad(L, gw, nullptr, out_bf16, stream);
+    if (int rc = prepare_wgrad(r, igemm_variant(), L)) return rc;
+    return run_wgrad(L, r.gw, nullptr, out_bf16, stream);
 }
 
 // the merged grid of two prepared halves (a.nd / a.nw blocks, padded to multiples of 8; a.w_first: the order)
@@ -1568,108 +1552,92 @@ static int launch_bwd_grid(const IgemmBwdArgs &a, hipStream_t stream) {
     return DSRG_OK;
 }
 
-// The backward of ONE convolution as one launch (conv_igemm_bwd_kernel): data gradient of g with the flipped kernel `wd` (+ the
-// ReLU / Dropout backward and bias gradient of the layer below when `mask` is given, as launch_conv_igemm's fused form; + a residual in
-// its store, IgemmGroup::res, when `res` is given) and the weight gradient from (x, g), times gw_scale per output when that is given.
-// Both halves are prepared — whole tiles, no stream-K — and the split and block order of the merged grid come from
-// merged_backward_split (igemm_plan.h).  Where the merged kernel does not apply (a dilation >= 3: the XCD-interleaved forms; the
-// variants without it) the two prepared halves run as two launches: same results either way — the two halves of the merged kernel
-// run the very code of the separate kernels on the very argument blocks.
-static int conv_igemm_backward(const void *g, const void *wd, const void *x, const void *mask, const void *res, void *gx, void *gw,
-                               const float *gw_scale, int dil, float *bias_grad, float mask_scale, void *colsum_ws, size_t colsum_ws_bytes,
-                               void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W, int cin, int cout, int k, hipStream_t stream) {
-    // (forward convolution: cin -> cout; g has cout channels, gx and x have cin, gw is (cout, cin, k, k) in float32)
-    const void *gp[1] = {g}, *wp[1] = {wd}, *xp[1] = {x}, *mp[1] = {mask};
-    void *gxp[1] = {gx}, *gwp[1] = {gw};
-    float *bgp[1] = {bias_grad};
-    float *const *colsum = bias_grad ? bgp : nullptr;
-    const IgemmVariant v = igemm_variant();
-    IgemmLaunch d;
-    if (int rc = prepare_igemm(gp, wp, nullptr, gxp, &dil, 1, B, H, W, cout, cin, k, 0, 0.0f, 0ull, nullptr, 0, mask ? mp : nullptr, mask_scale,
-                               colsum, colsum_ws, colsum_ws_bytes, res, 0, false, v, d)) return rc;
-    const bool merge = ((k == 3 && dil < 3) || k == 1) && v.merged_backward && !d.sk.base.xcd_mix && d.grid >= 1;
-    const std::pair<int, int> pick = merge ? merged_backward_split(B, H, W, cin, cout, k, d.grid, igemm_cus()) : std::make_pair(0, 0);
-    WgradLaunch w;
-    if (int rc = prepare_wgrad(xp, gp, gwp, &dil, 1, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout, k, v, pick.first, w)) return rc;
-    if (!merge || w.grid < 1) {
-        if (int rc = run_igemm(d, colsum, stream)) return rc;
-        return run_wgrad(w, gwp, gw_scale, 0, stream);
-    }
-    IgemmBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.d = d.sk.base;
-    a.w = w.a;
-    a.nd = d.grid; a.nd_pad = (a.nd + 7) & ~7; a.nw = w.grid; a.nw_pad = (a.nw + 7) & ~7;
-    a.w_first = pick.second;
-    if (int rc = launch_bwd_grid(a, stream)) return rc;
-    if (bias_grad) {
-        const float *parts[1] = {a.d.g[0].colsum};
-        if (int rc = launch_igemm_colsum(parts, bgp, 1, a.d.tiles_m, cin, stream)) return rc;
-    }
-    return reduce_wgrad(a.w, gwp, gw_scale, 0, stream);
-}
-
-int launch_conv_igemm_backward(const void *g, const void *wd, const void *x, const void *mask, void *gx, void *gw, int dil, float *bias_grad,
-                               float mask_scale, void *colsum_ws, size_t colsum_ws_bytes, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H,
-                               int W, int cin, int cout, int k, hipStream_t stream) {
-    return conv_igemm_backward(g, wd, x, mask, nullptr, gx, gw, nullptr, dil, bias_grad, mask_scale, colsum_ws, colsum_ws_bytes, wgrad_ws,
-                               wgrad_ws_bytes, B, H, W, cin, cout, k, stream);
-}
-
-// The backward of 1 - 4 convolutions of one geometry (the four ASPP branches) as one launch: conv_igemm_backward's merged grid with
-// both halves in their GROUPED forms — the data gradient with its XCD-interleaved map and class-ordered or row tiles where the
-// kernels are dilated (fc6 x4), mask and bias sums in its store where `mask` is given (fc7 x4); the weight gradient on its uniform
-// split (fc7 x4: searched for this grid) or on its per-tap work list (fc6 x4: the list of the launch alone, so its bits are that
-// launch's; the list is stored in front of the grid as in front of every launch that reads it).  Both bodies decode group, tile
-// and list entry from (arguments, block id, blocks of their half), so the kernel is conv_igemm_bwd_kernel as it is; what is new
-// is the planner, which prices both halves block by block (merged_groups_plan, igemm_plan.h).  Where it declines, or the variant
-// has no merged backward, the same prepared halves run as two launches: the same bits.
+// ---- a whole backward: prepare_backward (one convolution) or prepare_backward_groups decides, run_backward launches
 namespace {
-struct GroupsBackward {
+// Both halves prepared — whole tiles, no stream-K — and how they run: as one grid (conv_igemm_bwd_kernel) in the order w_first, or
+// as two launches.  Same results either way: the two halves of the merged kernel run the very code of the separate kernels on the
+// very argument blocks
+struct Backward {
     IgemmLaunch d;
     WgradLaunch w;
-    MergedGroupsPlan plan;
+    bool merge;
+    int w_first;
 };
-// forced_ksplit > 0 (tests): that uniform split instead of the planner's; forced_order 1 / 2 (tests): a merged grid with the data /
-// weight gradient's blocks first, whichever the planner prices lower.  Launches nothing, enqueues nothing
-int prepare_backward_groups(const void *const *g, const void *const *wd, const void *const *x, const void *const *mask, void *const *gx,
-                            void *const *gw, const int *dil, int ngroups, float *const *bias_grad, float mask_scale, void *colsum_ws,
-                            size_t colsum_ws_bytes, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W, int cin, int cout, int k,
-                            int forced_ksplit, int forced_order, const IgemmVariant &v, GroupsBackward &P) {
-    if (int rc = prepare_igemm(g, wd, nullptr, gx, dil, ngroups, B, H, W, cout, cin, k, 0, 0.0f, 0ull, nullptr, 0, mask, mask_scale, bias_grad,
-                               colsum_ws, colsum_ws_bytes, nullptr, 0, false, v, P.d)) return rc;
-    if (int rc = prepare_wgrad(x, g, gw, dil, ngroups, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout, k, v, 0, P.w)) return rc;
+
+// the data gradient of g with the flipped kernels wd (cout -> cin channels), with the ReLU / Dropout backward and the bias gradients
+// of the layer below where masks are given, as launch_conv_igemm's fused form
+IgemmRequest dgrad_half(const BackwardRequest &r) {
+    IgemmRequest q;
+    put_groups(q.x, r.g, 4); put_groups(q.w, r.wd, 4); put_groups(q.y, r.gx, 4); put_groups(q.mask, r.mask, 4);
+    put_groups(q.colsum, r.bias_grad, 4); put_groups(q.dil, r.dil, 4);
+    q.masked = r.masked; q.colsums = r.bias_grads; q.ngroups = r.ngroups;
+    q.s = {r.s.B, r.s.H, r.s.W, r.s.cout, r.s.cin, r.s.k};
+    q.out_scale = r.mask_scale;
+    q.colsum_ws = r.colsum_ws; q.colsum_ws_bytes = r.colsum_ws_bytes;
+    q.res = r.res;
+    q.may_stream_k = false;
+    return q;
+}
+// the weight gradient from (x, g): gw is (cout, cin, k, k) in float32
+WgradRequest wgrad_half(const BackwardRequest &r, int forced_ksplit) {
+    WgradRequest q;
+    put_groups(q.x, r.x, 4); put_groups(q.g, r.g, 4); put_groups(q.gw, r.gw, 4); put_groups(q.dil, r.dil, 4);
+    q.ngroups = r.ngroups;
+    q.workspace = r.wgrad_ws; q.workspace_bytes = r.wgrad_ws_bytes;
+    q.s = r.s;
+    q.forced_ksplit = forced_ksplit;
+    return q;
+}
+
+// ONE convolution: the split and block order of the merged grid come from merged_backward_split (igemm_plan.h).  Two launches where
+// the merged kernel does not apply (a dilation >= 3: the XCD-interleaved forms; the variants without it).  Launches nothing
+int prepare_backward(const BackwardRequest &r, const IgemmVariant &v, Backward &P) {
+    if (int rc = prepare_igemm(dgrad_half(r), v, P.d)) return rc;
+    const int dil = r.dil[0], k = r.s.k;
+    const bool merge = ((k == 3 && dil < 3) || k == 1) && v.merged_backward && !P.d.sk.base.xcd_mix && P.d.grid >= 1;
+    const std::pair<int, int> pick = merge ? merged_backward_split(r.s.B, r.s.H, r.s.W, r.s.cin, r.s.cout, k, P.d.grid, igemm_cus()) : std::make_pair(0, 0);
+    if (int rc = prepare_wgrad(wgrad_half(r, pick.first), v, P.w)) return rc;
+    P.merge = merge && P.w.grid >= 1;
+    P.w_first = pick.second;
+    return DSRG_OK;
+}
+
+// 1 - 4 convolutions of one geometry (the four ASPP branches), both halves in their GROUPED forms — the data gradient with its
+// XCD-interleaved map and class-ordered or row tiles where the kernels are dilated (fc6 x4), mask and bias sums in its store where
+// masks are given (fc7 x4); the weight gradient on its uniform split (fc7 x4: searched for this grid) or on its per-tap work list
+// (fc6 x4: the list of the launch alone, so its bits are that launch's).  Both bodies decode group, tile and list entry from
+// (arguments, block id, blocks of their half), so the kernel is conv_igemm_bwd_kernel as it is; the planner prices both halves block
+// by block (merged_groups_plan, igemm_plan.h).  Where it declines, or the variant has no merged backward: two launches.
+// r.forced_ksplit / r.forced_order: BackwardRequest.  Launches nothing
+int prepare_backward_groups(const BackwardRequest &r, const IgemmVariant &v, Backward &P, MergedGroupsPlan &plan) {
+    const int ngroups = r.ngroups, B = r.s.B, H = r.s.H, W = r.s.W, cin = r.s.cin, cout = r.s.cout, k = r.s.k;
+    if (int rc = prepare_igemm(dgrad_half(r), v, P.d)) return rc;
+    if (int rc = prepare_wgrad(wgrad_half(r, 0), v, P.w)) return rc;
     const IgemmArgs &a = P.d.sk.base;
     // the planner's own reading of the geometry must be what was prepared: its block costs follow the kernels' id decode
-    const DgradShape ds = dgrad_shape_for(ngroups, B, H, W, cin, cout, k, dil, v);
-    const WgradShape ws = wgrad_shape_for(ngroups, B, H, W, cin, cout, k, dil, v, 0, igemm_cus());
+    const DgradShape ds = dgrad_shape_for(ngroups, B, H, W, cin, cout, k, r.dil, v);
+    const WgradShape ws = wgrad_shape_for(ngroups, B, H, W, cin, cout, k, r.dil, v, 0, igemm_cus());
     if (ds.grid != P.d.grid || ds.tiles_m != a.tiles_m || ds.tiles_n != a.tiles_n || ds.xcd_mix != a.xcd_mix || ds.row_tiles != a.row_tiles ||
         ds.cls_tiles != a.cls_tiles || ws.grid != P.w.grid || ws.ksplit != P.w.a.ksplit || ws.xcd_mix != P.w.a.xcd_mix ||
         ws.compact != P.w.a.compact || ws.nent != P.w.a.nent || (ws.plan != nullptr) != (P.w.plan != nullptr))
         return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups: the planner and the launcher disagree on the grid");
-    if (!v.merged_backward || P.d.grid < 1 || P.w.grid < 1) {
-        P.plan = MergedGroupsPlan{false, 0, P.w.plan ? 0 : P.w.a.ksplit, 0.0, 0.0};
-        return DSRG_OK;
+    plan = MergedGroupsPlan{false, 0, P.w.plan ? 0 : P.w.a.ksplit, 0.0, 0.0};
+    if (v.merged_backward && P.d.grid >= 1 && P.w.grid >= 1) {
+        plan = merged_groups_plan(ds, cin, cout, k, v, P.w.plan ? 0 : r.forced_ksplit, igemm_cus());
+        if (plan.merge && r.forced_order > 0) plan.w_first = r.forced_order == 2;
+        if (plan.ksplit > 0 && plan.ksplit != P.w.a.ksplit)
+            if (int rc = prepare_wgrad(wgrad_half(r, plan.ksplit), v, P.w)) return rc;
     }
-    P.plan = merged_groups_plan(ds, cin, cout, k, v, P.w.plan ? 0 : forced_ksplit, igemm_cus());
-    if (P.plan.merge && forced_order > 0) P.plan.w_first = forced_order == 2;
-    if (P.plan.ksplit > 0 && P.plan.ksplit != P.w.a.ksplit)
-        if (int rc = prepare_wgrad(x, g, gw, dil, ngroups, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout, k, v, P.plan.ksplit, P.w)) return rc;
+    P.merge = plan.merge;
+    P.w_first = plan.w_first;
     return DSRG_OK;
 }
-}  // namespace
 
-int launch_conv_igemm_backward_groups(const void *const *g, const void *const *wd, const void *const *x, const void *const *mask,
-                                      void *const *gx, void *const *gw, const int *dil, int ngroups, float *const *bias_grad, float mask_scale,
-                                      void *colsum_ws, size_t colsum_ws_bytes, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W,
-                                      int cin, int cout, int k, int forced_ksplit, int forced_order, hipStream_t stream) {
-    if (bias_grad && !mask) return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups: bias gradients come with the masks");
-    GroupsBackward P;
-    if (int rc = prepare_backward_groups(g, wd, x, mask, gx, gw, dil, ngroups, bias_grad, mask_scale, colsum_ws, colsum_ws_bytes, wgrad_ws,
-                                         wgrad_ws_bytes, B, H, W, cin, cout, k, forced_ksplit, forced_order, igemm_variant(), P)) return rc;
-    if (!P.plan.merge) {
+// Merged: the work list (if the weight gradient runs one) is stored in front of the grid as in front of every launch that reads it
+int run_backward(const Backward &P, void *const *gw, const float *gw_scale, float *const *bias_grad, hipStream_t stream) {
+    if (!P.merge) {
         if (int rc = run_igemm(P.d, bias_grad, stream)) return rc;
-        return run_wgrad(P.w, gw, nullptr, 0, stream);
+        return run_wgrad(P.w, gw, gw_scale, 0, stream);
     }
     if (int rc = upload_wgrad_plan(P.w, stream)) return rc;
     IgemmBwdArgs a;
@@ -1677,44 +1645,56 @@ int launch_conv_igemm_backward_groups(const void *const *g, const void *const *w
     a.d = P.d.sk.base;
     a.w = P.w.a;
     a.nd = P.d.grid; a.nd_pad = merged_second_half_start(a.nd); a.nw = P.w.grid; a.nw_pad = merged_second_half_start(a.nw);
-    a.w_first = P.plan.w_first;
+    a.w_first = P.w_first;
     if (int rc = launch_bwd_grid(a, stream)) return rc;
-    if (bias_grad) {
-        const float *parts[4];
-        for (int q = 0; q < ngroups; q++) parts[q] = a.d.g[q].colsum;
-        if (int rc = launch_igemm_colsum(parts, bias_grad, ngroups, a.d.tiles_m, cin, stream)) return rc;
-    }
-    return reduce_wgrad(a.w, gw, nullptr, 0, stream);
+    if (int rc = run_colsum(a.d, bias_grad, stream)) return rc;
+    return reduce_wgrad(a.w, gw, gw_scale, 0, stream);
+}
+}  // namespace
+
+// The backward of one convolution: r.ngroups = 1, r.res and r.gw_scale as a ResNet bottleneck convolution wants them
+int launch_conv_igemm_backward(const BackwardRequest &r, hipStream_t stream) {
+    Backward P;
+    if (int rc = prepare_backward(r, igemm_variant(), P)) return rc;
+    return run_backward(P, r.gw, r.gw_scale, r.bias_grads ? r.bias_grad : nullptr, stream);
+}
+
+int launch_conv_igemm_backward_groups(const BackwardRequest &r, hipStream_t stream) {
+    if (r.bias_grads && !r.masked) return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups: bias gradients come with the masks");
+    Backward P;
+    MergedGroupsPlan plan;
+    if (int rc = prepare_backward_groups(r, igemm_variant(), P, plan)) return rc;
+    return run_backward(P, r.gw, nullptr, r.bias_grads ? r.bias_grad : nullptr, stream);
 }
 
 // host only: what launch_conv_igemm_backward_groups would do for this geometry under the current variant — out[0] merged grid or two
 // launches, out[1] w_first, out[2] the weight gradient's uniform split (0: its work list), out[3] / out[4] blocks of the data /
 // weight gradient half; us[0] / us[1] the model's price of the choice and of the two launches (0 where nothing was priced)
-int conv_igemm_backward_groups_plan(int ngroups, int B, int H, int W, int cin, int cout, int k, const int *dil, int with_mask, int forced_ksplit,
-                                    int forced_order, int *out, double *us) {
+int conv_igemm_backward_groups_plan(int ngroups, const ConvGeom &s, const int *dil, int with_mask, int forced_ksplit, int forced_order, int *out,
+                                    double *us) {
     if (ngroups < 1 || ngroups > 4 || !out || !us) return set_error(DSRG_ERR_INVALID, "conv_igemm_backward_groups_plan: 1..4 groups");
-    const size_t need = wgrad_workspace_bytes(ngroups, B, H, W, cin, cout, k), cneed = conv_igemm_colsum_workspace(ngroups, B, H, W, cin);
     // (nothing is launched: the prepared argument blocks only ever hold these stand-in addresses)
     void *const fake = reinterpret_cast<void *>(uintptr_t(256));
-    const void *cp[4] = {fake, fake, fake, fake};
-    void *vp[4] = {fake, fake, fake, fake};
-    float *fp[4] = {static_cast<float *>(fake), static_cast<float *>(fake), static_cast<float *>(fake), static_cast<float *>(fake)};
-    GroupsBackward P;
-    if (int rc = prepare_backward_groups(cp, cp, cp, with_mask ? cp : nullptr, vp, vp, dil, ngroups, with_mask ? fp : nullptr, 1.0f,
-                                         with_mask ? fake : nullptr, cneed, fake, need, B, H, W, cin, cout, k, forced_ksplit, forced_order, igemm_variant(), P))
-        return rc;
-    out[0] = P.plan.merge; out[1] = P.plan.w_first; out[2] = P.plan.ksplit; out[3] = P.d.grid; out[4] = P.w.grid;
-    us[0] = P.plan.merged_us; us[1] = P.plan.separate_us;
+    BackwardRequest r;
+    for (int q = 0; q < ngroups; q++) {
+        r.g[q] = r.wd[q] = r.x[q] = r.gx[q] = r.gw[q] = fake;
+        if (with_mask) { r.mask[q] = fake; r.bias_grad[q] = static_cast<float *>(fake); }
+    }
+    r.masked = r.bias_grads = with_mask != 0;
+    put_groups(r.dil, dil, ngroups);
+    r.ngroups = ngroups;
+    r.s = s;
+    r.colsum_ws = with_mask ? fake : nullptr;
+    r.colsum_ws_bytes = conv_igemm_colsum_workspace(ngroups, s.B, s.H, s.W, s.cin);
+    r.wgrad_ws = fake;
+    r.wgrad_ws_bytes = wgrad_workspace_bytes(ngroups, s.B, s.H, s.W, s.cin, s.cout, s.k);
+    r.forced_ksplit = forced_ksplit; r.forced_order = forced_order;
+    Backward P;
+    MergedGroupsPlan plan;
+    if (int rc = prepare_backward_groups(r, igemm_variant(), P, plan)) return rc;
+    out[0] = plan.merge; out[1] = plan.w_first; out[2] = plan.ksplit; out[3] = P.d.grid; out[4] = P.w.grid;
+    us[0] = plan.merged_us; us[1] = plan.separate_us;
     return DSRG_OK;
-}
-
-// launch_conv_igemm_backward with a residual in the data gradient's store (res may be nullptr) and a per-output-channel factor on the
-// weight gradient (gw_scale may be nullptr); no bias gradient.  A ResNet bottleneck convolution's whole backward.
-int launch_conv_igemm_backward_residual(const void *g, const void *wd, const void *x, const void *mask, const void *res, void *gx, void *gw,
-                                        const float *gw_scale, int dil, void *wgrad_ws, size_t wgrad_ws_bytes, int B, int H, int W, int cin,
-                                        int cout, int k, hipStream_t stream) {
-    return conv_igemm_backward(g, wd, x, mask, res, gx, gw, gw_scale, dil, nullptr, 1.0f, nullptr, 0, wgrad_ws, wgrad_ws_bytes, B, H, W, cin, cout,
-                               k, stream);
 }
 
 int launch_pack_conv_weight(const float *w, void *fwd, void *dgrad, int cout, int cin, int k, hipStream_t stream, int plain, const float *scale) {

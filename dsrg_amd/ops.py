@@ -444,8 +444,11 @@ def _want_outputs(names, shapes, C, device):
                             device=device) for H, W in shapes] for n in names}
 
 
-def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors]) if tensors is not None else None
+def _ptrs(tensors):
+    """host array of one device pointer per entry (null for a None entry); None: no array"""
+    if tensors is None:
+        return None
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
 def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",)):
@@ -499,8 +502,8 @@ def multiscale_unary_batch(scores, shapes, eps=1e-5, want=("unary",)):
     ws = (ctypes.c_int32 * K)(*[s.shape[3] for s in scores])
     Hs = (ctypes.c_int32 * G)(*[H for H, _ in shapes])
     Ws = (ctypes.c_int32 * G)(*[W for _, W in shapes])
-    check(_lib.lib().dsrg_multiscale_unary_batch(G, K, int(C), ptrs, hs, ws, Hs, Ws, float(eps), _ptr_array(out.get("unary")),
-                                                 _ptr_array(out.get("argmax")), _ptr_array(out.get("sum")), _stream()))
+    check(_lib.lib().dsrg_multiscale_unary_batch(G, K, int(C), ptrs, hs, ws, Hs, Ws, float(eps), _ptrs(out.get("unary")),
+                                                 _ptrs(out.get("argmax")), _ptrs(out.get("sum")), _stream()))
     if single:
         return out[names[0]]
     return [tuple(out[n][g] for n in names) for g in range(G)]
@@ -538,8 +541,8 @@ def train_gt_unary_batch(scores, shapes, eps=1e-5, want=("unary",), select=None,
     Hs = (ctypes.c_int32 * G)(*[H for H, _ in shapes])
     Ws = (ctypes.c_int32 * G)(*[W for _, W in shapes])
     check(_lib.lib().dsrg_train_gt_unary_batch(G, int(C), _ptr(scores), int(h), int(w), Hs, Ws, float(eps), sel, nsel, int(stride),
-                                               float(ignore_below or 0.0), _ptr(workspace), _ptr_array(out.get("unary")),
-                                               _ptr_array(out.get("probs")), _ptr_array(out.get("labels")), _stream()))
+                                               float(ignore_below or 0.0), _ptr(workspace), _ptrs(out.get("unary")),
+                                               _ptrs(out.get("probs")), _ptrs(out.get("labels")), _stream()))
     if single:
         return out[names[0]]
     return [tuple(out[n][g] for n in names) for g in range(G)]
@@ -1149,6 +1152,17 @@ def conv_igemm_split(x, weight, bias, dilation, relu):
     return y
 
 
+def _is_bf16(t, shape, channels_last=False):
+    """a bf16 CUDA tensor of this shape (channels_last: and in that layout, not merely convertible to it)"""
+    return (t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == tuple(shape)
+            and (not channels_last or t.is_contiguous(memory_format=torch.channels_last)))
+
+
+def _is_packed(p, rows, chunk_channels, ksize):
+    """a kernel as pack_conv_weight lays it out: (rows, chunk_channels / 64, ksize * ksize, 64) bf16, contiguous"""
+    return p.dtype == torch.bfloat16 and tuple(p.shape) == (rows, chunk_channels // 64, ksize * ksize, 64) and p.is_contiguous()
+
+
 def conv_igemm(xs, packed, biases, dilations, ksize, relu, dropout_p=0.0, seed=0, stream_k=True):
     """1 .. 4 convolutions of one geometry in one launch (the four ASPP branches): xs[g] (B,cin,H,W) bf16 channels_last,
     packed[g] = pack_conv_weight(w_g), biases[g] (cout) f32 or None -> list of (B,cout,H,W) bf16 channels_last; fp32
@@ -1161,20 +1175,15 @@ def conv_igemm(xs, packed, biases, dilations, ksize, relu, dropout_p=0.0, seed=0
     cl = torch.channels_last
     if not (1 <= n <= 4 and len(packed) == n and len(dilations) == n):
         raise ValueError("conv_igemm: 1..4 groups")
-    for x, p in zip(xs, packed):
-        if not (x.is_cuda and x.dtype == torch.bfloat16 and tuple(x.shape) == (B, cin, H, W) and p.dtype == torch.bfloat16
-                and tuple(p.shape) == (cout, cin // 64, ksize * ksize, 64) and p.is_contiguous()):
-            raise ValueError("conv_igemm needs bf16 CUDA inputs of one shape and kernels packed by pack_conv_weight")
+    if not all(_is_bf16(x, (B, cin, H, W)) and _is_packed(p, cout, cin, ksize) for x, p in zip(xs, packed)):
+        raise ValueError("conv_igemm needs bf16 CUDA inputs of one shape and kernels packed by pack_conv_weight")
     xs = [x.contiguous(memory_format=cl) for x in xs]
     bs = [None if b is None else _f32c(b, "bias") for b in (biases or [None] * n)]
     ys = [torch.empty((B, cout, H, W), dtype=torch.bfloat16, device=xs[0].device, memory_format=cl) for _ in range(n)]
-    vp = ctypes.c_void_p * n
     ws = _igemm_sk_workspace(xs[0].device) if stream_k else None
-    check(_lib.lib().dsrg_conv_igemm_bf16(vp(*[x.data_ptr() for x in xs]), vp(*[p.data_ptr() for p in packed]),
-                                          vp(*[None if b is None else b.data_ptr() for b in bs]),
-                                          vp(*[y.data_ptr() for y in ys]), (ctypes.c_int * n)(*[int(d) for d in dilations]),
-                                          n, B, H, W, cin, cout, ksize, int(bool(relu)), float(dropout_p),
-                                          int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ws), ws.numel() if ws is not None else 0, _stream()))
+    check(_lib.lib().dsrg_conv_igemm_bf16(_ptrs(xs), _ptrs(packed), _ptrs(bs), _ptrs(ys), _i32s(dilations), n, B, H, W, cin, cout, ksize,
+                                          int(bool(relu)), float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ws),
+                                          ws.numel() if ws is not None else 0, _stream()))
     return ys
 
 
@@ -1186,9 +1195,8 @@ def conv_igemm_residual(x, packed, bias, res, mask, dilation, ksize, relu):
     B, cin, H, W = x.shape
     cout = packed.shape[0]
     cl = torch.channels_last
-    ok = lambda t: t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == (B, cout, H, W) and t.is_contiguous(memory_format=cl)   # noqa: E731
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and packed.dtype == torch.bfloat16 and packed.is_contiguous()
-            and tuple(packed.shape) == (cout, cin // 64, ksize * ksize, 64) and ok(res) and (mask is None or ok(mask))):
+    if not (_is_bf16(x, x.shape) and _is_packed(packed, cout, cin, ksize) and _is_bf16(res, (B, cout, H, W), True)
+            and (mask is None or _is_bf16(mask, (B, cout, H, W), True))):
         raise ValueError("conv_igemm_residual needs bf16 channels_last tensors of matching shapes and a kernel packed by pack_conv_weight")
     x = x.contiguous(memory_format=cl)
     b = None if bias is None else _f32c(bias, "bias")
@@ -1239,25 +1247,39 @@ def conv_igemm_dgrad(gs, packed_t, masks, dilations, ksize, mask_scale=1.0, bias
     cl = torch.channels_last
     if not (1 <= n <= 4 and len(packed_t) == n and len(dilations) == n and len(masks) == n):
         raise ValueError("conv_igemm_dgrad: 1..4 groups")
-    for g, p, m in zip(gs, packed_t, masks):
-        if not (g.is_cuda and g.dtype == torch.bfloat16 and tuple(g.shape) == (B, cin, H, W) and p.dtype == torch.bfloat16
-                and tuple(p.shape) == (cout, cin // 64, ksize * ksize, 64) and p.is_contiguous() and m.dtype == torch.bfloat16
-                and tuple(m.shape) == (B, cout, H, W) and m.is_contiguous(memory_format=cl)):
-            raise ValueError("conv_igemm_dgrad needs bf16 channels_last gradients / masks of one shape and packed kernels")
+    if not all(_is_bf16(g, (B, cin, H, W)) and _is_packed(p, cout, cin, ksize) and _is_bf16(m, (B, cout, H, W), True)
+               for g, p, m in zip(gs, packed_t, masks)):
+        raise ValueError("conv_igemm_dgrad needs bf16 channels_last gradients / masks of one shape and packed kernels")
     gs = [g.contiguous(memory_format=cl) for g in gs]
     outs = [torch.empty((B, cout, H, W), dtype=torch.bfloat16, device=gs[0].device, memory_format=cl) for _ in range(n)]
-    vp = ctypes.c_void_p * n
     L = _lib.lib()
     gb = ws = None
     if bias_grad:
         gb = [_bias_grad_dest(gb_outs[i] if gb_outs is not None else None, (cout,), gs[0].device) for i in range(n)]
         ws = _reduction_scratch(gs[0].device, L.dsrg_conv_igemm_dgrad_workspace(n, B, H, W, cout))
-    check(L.dsrg_conv_igemm_dgrad_bf16(vp(*[g.data_ptr() for g in gs]), vp(*[p.data_ptr() for p in packed_t]),
-                                       vp(*[m.data_ptr() for m in masks]), vp(*[o.data_ptr() for o in outs]),
-                                       vp(*[b.data_ptr() for b in gb]) if gb else None,
-                                       (ctypes.c_int * n)(*[int(d) for d in dilations]), n, B, H, W, cin, cout, ksize,
-                                       float(mask_scale), _ptr(ws), ws.numel() if ws is not None else 0, _stream()))
+    check(L.dsrg_conv_igemm_dgrad_bf16(_ptrs(gs), _ptrs(packed_t), _ptrs(masks), _ptrs(outs), _ptrs(gb), _i32s(dilations), n, B, H, W, cin,
+                                       cout, ksize, float(mask_scale), _ptr(ws), ws.numel() if ws is not None else 0, _stream()))
     return outs, gb
+
+
+def _conv_igemm_backward_args(name, g, packed_d, x, ksize, gw_out, **like_x):
+    """what conv_igemm_backward and conv_igemm_backward_residual share: the checks (like_x: named tensors of x's shape and layout, or
+    None), the weight gradient's scratch and the two results -> (library, g channels_last, scratch, gx, gw, (B, H, W, cin, cout, ksize))"""
+    B, cout, H, W = g.shape
+    cin = x.shape[1]
+    cl = torch.channels_last
+    if not (_is_bf16(g, g.shape) and _is_bf16(x, (B, cin, H, W), True) and _is_packed(packed_d, cin, cout, ksize)
+            and all(t is None or _is_bf16(t, (B, cin, H, W), True) for t in like_x.values())):
+        raise ValueError("%s needs bf16 channels_last g / x (/ %s) of one geometry and the data-gradient packing" % (name, " / ".join(like_x)))
+    g = g.contiguous(memory_format=cl)
+    L = _lib.lib()
+    need = L.dsrg_conv_igemm_wgrad_workspace(1, B, H, W, cin, cout, ksize)
+    if need == 0:
+        raise ValueError("%s: 256 | cin (or cin = 128 with a 3x3 kernel), 256 | cout required (got %d, %d)" % (name, cin, cout))
+    ws = _stream_scratch("igemm_wgrad", g.device, need)              # shared with conv_igemm_wgrad
+    gx = torch.empty((B, cin, H, W), dtype=torch.bfloat16, device=g.device, memory_format=cl)
+    gw = _dest(gw_out, (cout, cin, ksize, ksize), torch.float32, g.device, True)
+    return L, g, ws, gx, gw, (B, H, W, cin, cout, ksize)
 
 
 def conv_igemm_backward(g, packed_d, x, dilation, mask=None, mask_scale=1.0, ksize=3, gw_out=None, gb_out=None):
@@ -1267,29 +1289,15 @@ def conv_igemm_backward(g, packed_d, x, dilation, mask=None, mask_scale=1.0, ksi
     the data gradient, as conv_igemm_dgrad) -> (gx (B,cin,H,W) bf16 channels_last, gw (cout,cin,k,k) float32 channels_last, bias
     gradient of the layer below (cin) f32 or None).  gx and the bias gradient equal conv_igemm(_dgrad)'s bit for bit, gw equals
     conv_igemm_wgrad's up to fp32 reassociation (another pixel split)."""
-    B, cout, H, W = g.shape
-    cin = x.shape[1]
-    cl = torch.channels_last
-    if not (g.is_cuda and g.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and tuple(x.shape) == (B, cin, H, W)
-            and packed_d.dtype == torch.bfloat16 and tuple(packed_d.shape) == (cin, cout // 64, ksize * ksize, 64)
-            and packed_d.is_contiguous() and x.is_contiguous(memory_format=cl)
-            and (mask is None or (mask.dtype == torch.bfloat16 and tuple(mask.shape) == (B, cin, H, W) and mask.is_contiguous(memory_format=cl)))):
-        raise ValueError("conv_igemm_backward needs bf16 channels_last g / x (/ mask) of one geometry and the data-gradient packing")
-    g = g.contiguous(memory_format=cl)
-    L = _lib.lib()
-    need = L.dsrg_conv_igemm_wgrad_workspace(1, B, H, W, cin, cout, ksize)
-    if need == 0:
-        raise ValueError("conv_igemm_backward: 256 | cin (or cin = 128), 256 | cout required (got %d, %d)" % (cin, cout))
-    ws = _stream_scratch("igemm_wgrad", g.device, need)              # shared with conv_igemm_wgrad
-    gx = torch.empty((B, cin, H, W), dtype=torch.bfloat16, device=g.device, memory_format=cl)
-    gw = _dest(gw_out, (cout, cin, ksize, ksize), torch.float32, g.device, True)
+    L, g, ws, gx, gw, geom = _conv_igemm_backward_args("conv_igemm_backward", g, packed_d, x, ksize, gw_out, mask=mask)
+    B, H, W, cin = geom[:4]
     gb = cws = None
     if mask is not None:
         gb = _bias_grad_dest(gb_out, (cin,), g.device)
         cws = _reduction_scratch(g.device, L.dsrg_conv_igemm_dgrad_workspace(1, B, H, W, cin))
     check(L.dsrg_conv_igemm_backward_bf16(_ptr(g), _ptr(packed_d), _ptr(x), _ptr(mask), _ptr(gx), _ptr(gw), int(dilation), _ptr(gb),
                                           float(mask_scale), _ptr(cws), cws.numel() if cws is not None else 0, _ptr(ws), ws.numel(),
-                                          B, H, W, cin, cout, ksize, _stream()))
+                                          *geom, _stream()))
     return gx, gw, gb
 
 
@@ -1298,24 +1306,10 @@ def conv_igemm_backward_residual(g, packed_d, x, dilation, ksize, mask=None, res
     (B,cin,H,W) bf16 channels_last or None is added to the bf16-rounded data gradient before the mask (the gradient along the
     block's shortcut); gw_scale (cout) f32 or None multiplies the weight gradient per output channel (the constant scale the
     forward's kernel was packed with); no bias gradient -> (gx, gw)"""
-    B, cout, H, W = g.shape
-    cin = x.shape[1]
-    cl = torch.channels_last
-    ok = lambda t: t.dtype == torch.bfloat16 and tuple(t.shape) == (B, cin, H, W) and t.is_contiguous(memory_format=cl)      # noqa: E731
-    if not (g.is_cuda and g.dtype == torch.bfloat16 and ok(x) and packed_d.dtype == torch.bfloat16 and packed_d.is_contiguous()
-            and tuple(packed_d.shape) == (cin, cout // 64, ksize * ksize, 64) and (mask is None or ok(mask)) and (res is None or ok(res))):
-        raise ValueError("conv_igemm_backward_residual needs bf16 channels_last g / x (/ mask / res) of one geometry and the data-gradient packing")
-    g = g.contiguous(memory_format=cl)
-    L = _lib.lib()
-    need = L.dsrg_conv_igemm_wgrad_workspace(1, B, H, W, cin, cout, ksize)
-    if need == 0:
-        raise ValueError("conv_igemm_backward_residual: 256 | cin (or cin = 128 with a 3x3 kernel), 256 | cout required (got %d, %d)" % (cin, cout))
-    ws = _stream_scratch("igemm_wgrad", g.device, need)              # shared with conv_igemm_wgrad
-    gx = torch.empty((B, cin, H, W), dtype=torch.bfloat16, device=g.device, memory_format=cl)
-    gw = _dest(gw_out, (cout, cin, ksize, ksize), torch.float32, g.device, True)
+    L, g, ws, gx, gw, geom = _conv_igemm_backward_args("conv_igemm_backward_residual", g, packed_d, x, ksize, gw_out, mask=mask, res=res)
     sc = None if gw_scale is None else _f32c(gw_scale, "gw_scale")
     check(L.dsrg_conv_igemm_backward_residual_bf16(_ptr(g), _ptr(packed_d), _ptr(x), _ptr(mask), _ptr(res), _ptr(gx), _ptr(gw), _ptr(sc),
-                                                   int(dilation), _ptr(ws), ws.numel(), B, H, W, cin, cout, ksize, _stream()))
+                                                   int(dilation), _ptr(ws), ws.numel(), *geom, _stream()))
     return gx, gw
 
 
@@ -1336,12 +1330,9 @@ def conv_igemm_backward_groups(gs, packed_d, xs, dilations, ksize, masks=None, m
     cl = torch.channels_last
     if not (1 <= n <= 4 and len(packed_d) == n and len(xs) == n and len(dilations) == n and (masks is None or len(masks) == n)):
         raise ValueError("conv_igemm_backward_groups: 1..4 groups")
-    ok = lambda t: t.dtype == torch.bfloat16 and tuple(t.shape) == (B, cin, H, W) and t.is_contiguous(memory_format=cl)      # noqa: E731
-    for i in range(n):
-        if not (gs[i].is_cuda and gs[i].dtype == torch.bfloat16 and tuple(gs[i].shape) == (B, cout, H, W) and ok(xs[i])
-                and packed_d[i].dtype == torch.bfloat16 and tuple(packed_d[i].shape) == (cin, cout // 64, ksize * ksize, 64)
-                and packed_d[i].is_contiguous() and (masks is None or ok(masks[i]))):
-            raise ValueError("conv_igemm_backward_groups needs bf16 channels_last g / x (/ mask) of one geometry and the data-gradient packing")
+    if not all(_is_bf16(gs[i], (B, cout, H, W)) and _is_bf16(xs[i], (B, cin, H, W), True) and _is_packed(packed_d[i], cin, cout, ksize)
+               and (masks is None or _is_bf16(masks[i], (B, cin, H, W), True)) for i in range(n)):
+        raise ValueError("conv_igemm_backward_groups needs bf16 channels_last g / x (/ mask) of one geometry and the data-gradient packing")
     gs = [g.contiguous(memory_format=cl) for g in gs]
     dev = gs[0].device
     L = _lib.lib()
@@ -1355,13 +1346,9 @@ def conv_igemm_backward_groups(gs, packed_d, xs, dilations, ksize, masks=None, m
     if masks is not None:
         gbs = [_bias_grad_dest(gb_outs[i] if gb_outs is not None else None, (cin,), dev) for i in range(n)]
         cws = _reduction_scratch(dev, L.dsrg_conv_igemm_dgrad_workspace(n, B, H, W, cin))
-    vp = ctypes.c_void_p * n
-    ptrs = lambda ts: vp(*[t.data_ptr() for t in ts])      # noqa: E731
-    check(L.dsrg_conv_igemm_backward_groups_bf16(ptrs(gs), ptrs(packed_d), ptrs(xs), ptrs(masks) if masks is not None else None, ptrs(gxs),
-                                                 ptrs(gws), (ctypes.c_int * n)(*[int(d) for d in dilations]), n,
-                                                 ptrs(gbs) if gbs is not None else None, float(mask_scale), _ptr(cws),
-                                                 cws.numel() if cws is not None else 0, _ptr(ws), ws.numel(), B, H, W, cin, cout, ksize,
-                                                 int(force_ksplit), int(force_order), _stream()))
+    check(L.dsrg_conv_igemm_backward_groups_bf16(_ptrs(gs), _ptrs(packed_d), _ptrs(xs), _ptrs(masks), _ptrs(gxs), _ptrs(gws), _i32s(dilations), n,
+                                                 _ptrs(gbs), float(mask_scale), _ptr(cws), cws.numel() if cws is not None else 0, _ptr(ws),
+                                                 ws.numel(), B, H, W, cin, cout, ksize, int(force_ksplit), int(force_order), _stream()))
     return gxs, gws, gbs
 
 
@@ -1420,10 +1407,8 @@ def conv_igemm_wgrad(xs, gs, dilations, ksize, out_dtype=torch.float32, outs=Non
     cl = torch.channels_last
     if not (1 <= n <= 4 and len(gs) == n and len(dilations) == n) or out_dtype not in (torch.float32, torch.bfloat16):
         raise ValueError("conv_igemm_wgrad: 1..4 groups, float32 or bfloat16 result")
-    for x, g in zip(xs, gs):
-        if not (x.is_cuda and x.dtype == torch.bfloat16 and g.dtype == torch.bfloat16 and tuple(x.shape) == (B, cin, H, W)
-                and tuple(g.shape) == (B, cout, H, W)):
-            raise ValueError("conv_igemm_wgrad needs bf16 CUDA tensors of one geometry")
+    if not all(_is_bf16(x, (B, cin, H, W)) and _is_bf16(g, (B, cout, H, W)) for x, g in zip(xs, gs)):
+        raise ValueError("conv_igemm_wgrad needs bf16 CUDA tensors of one geometry")
     xs = [x.contiguous(memory_format=cl) for x in xs]
     gs = [g.contiguous(memory_format=cl) for g in gs]
     L = _lib.lib()
@@ -1432,10 +1417,8 @@ def conv_igemm_wgrad(xs, gs, dilations, ksize, out_dtype=torch.float32, outs=Non
         raise ValueError("conv_igemm_wgrad: 64 | cin, 64 | cout, k in (1, 3) required (got %d, %d, %d)" % (cin, cout, ksize))
     ws = _stream_scratch("igemm_wgrad", xs[0].device, need)          # reused across layers and steps
     gws = [_dest(outs[i] if outs is not None else None, (cout, cin, ksize, ksize), out_dtype, xs[0].device, True) for i in range(n)]
-    vp = ctypes.c_void_p * n
-    check(L.dsrg_conv_igemm_wgrad_bf16(vp(*[x.data_ptr() for x in xs]), vp(*[g.data_ptr() for g in gs]),
-                                       vp(*[w.data_ptr() for w in gws]), (ctypes.c_int * n)(*[int(d) for d in dilations]), n,
-                                       _ptr(ws), ws.numel(), B, H, W, cin, cout, ksize, int(out_dtype == torch.bfloat16), _stream()))
+    check(L.dsrg_conv_igemm_wgrad_bf16(_ptrs(xs), _ptrs(gs), _ptrs(gws), _i32s(dilations), n, _ptr(ws), ws.numel(), B, H, W, cin, cout, ksize,
+                                       int(out_dtype == torch.bfloat16), _stream()))
     return gws
 
 
