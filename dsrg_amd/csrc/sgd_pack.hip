@@ -11,8 +11,9 @@
 // there.  With lr = 0 momentum = 1 and no gradient the same kernel only packs (first step, weights loaded from a file).
 //
 // Layouts (see conv_igemm.hip, pack_conv_weight_kernel, which this kernel's packing half restates): parameter [o][tap][c]
-// (channels_last (cout, cin, k, k)); igemm forward fwd[o][c / 64][tap][64], igemm data gradient dg[c][o / 64][T - tap][64]; plain
-// (direct kernels): fwd[o][tap][c], dg[c][T - tap][o].
+// (channels_last (cout, cin, k, k)), tap = ky * k + kx in 0 .. T - 1, T = k * k; igemm forward fwd[o][c / 64][tap][c % 64], igemm
+// data gradient dg[c][o / 64][T - 1 - tap][o % 64] (the kernel flipped: tap 0 lands at T - 1, tap T - 1 at 0); plain (direct
+// kernels): fwd[o][tap][c], dg[c][T - 1 - tap][o].  tests/sgd_pack_cases.py restates all four in numpy.
 #include "common.h"
 #include <cstring>
 

@@ -361,7 +361,10 @@ def test_sgd_pack_kernel_equals_torch_fused_sgd_and_the_pack_kernel(ops):
     kernel, a kernel that is not packed, biases, a 21 x 1024 classifier — sizes off every multiple of 4096) against
     torch._fused_sgd_ with the same rates per group, two steps (momentum history in play): parameters and history agree to the last
     bit or the one before it (torch's kernel may contract a*b+c), and the packed bf16 forms it leaves are bit for bit those of
-    dsrg_pack_conv_weight_f32 on the updated parameter"""
+    dsrg_pack_conv_weight_f32 on the updated parameter.
+    What this does not reach — bit patterns against a reference that is no GPU kernel, sizes around the block seams at every
+    alignment, memory beyond a tensor's ends, each packed form alone, pack only, the launch seam, refusals — is in
+    tests/test_gpu_sgd_pack.py"""
     from dsrg_amd import _lib
     dev_ = torch.device("cuda", 0)
     g = torch.Generator(device="cpu").manual_seed(5)
