@@ -507,6 +507,18 @@ extern "C" int dsrg_multiscale_unary_batch(int G, int K, int C, const float *con
     // every argument is checked before the first device call
     return launch_multiscale_unary_batch(G, K, C, scores, h, w, H, W, eps, unary, amax, sum, static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_multiscale_unary_mirror(int K, int C, const float *const *scores, const int32_t *mirror, const int32_t *h,
+                                            const int32_t *w, int H, int W, float eps, float *unary, int32_t *amax, float *sum,
+                                            void *stream) {
+    // every argument is checked before the first device call
+    return launch_multiscale_unary_mirror(K, C, scores, mirror, h, w, H, W, eps, unary, amax, sum, static_cast<hipStream_t>(stream));
+}
+extern "C" int dsrg_multiscale_unary_mirror_batch(int G, int K, int C, const float *const *scores, const int32_t *h, const int32_t *w,
+                                                  const int32_t *H, const int32_t *W, float eps, float *const *unary,
+                                                  int32_t *const *amax, float *const *sum, void *stream) {
+    // every argument is checked before the first device call
+    return launch_multiscale_unary_mirror_batch(G, K, C, scores, h, w, H, W, eps, unary, amax, sum, static_cast<hipStream_t>(stream));
+}
 extern "C" int dsrg_train_gt_unary_batch(int G, int C, const float *scores, int h, int w, const int32_t *H, const int32_t *W, float eps,
                                          const int32_t *select, const int32_t *nselect, int select_stride, float ignore_below,
                                          float *workspace, float *const *unary, float *const *probs, int32_t *const *labels,
@@ -526,6 +538,13 @@ extern "C" int dsrg_preprocess_rect_batch(int G, int capacity, int K, const unsi
                                           float *const *out, void *stream) {
     // every argument is checked before the first device call
     return launch_preprocess_rect_batch(G, capacity, K, images, H, W, out_h, out_w, mean, out, static_cast<hipStream_t>(stream));
+}
+extern "C" int dsrg_preprocess_rect_mirror_batch(int G, int capacity, int K, const unsigned char *const *images, const int32_t *H,
+                                                 const int32_t *W, const int32_t *out_h, const int32_t *out_w, const float *mean,
+                                                 float *const *out, void *stream) {
+    // every argument is checked before the first device call
+    return launch_preprocess_rect_mirror_batch(G, capacity, K, images, H, W, out_h, out_w, mean, out,
+                                               static_cast<hipStream_t>(stream));
 }
 extern "C" int dsrg_train_s_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off,
                                         const int32_t *H, const int32_t *W, const int32_t *cue_off, const int32_t *ncues,

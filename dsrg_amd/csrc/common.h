@@ -265,10 +265,18 @@ int launch_multiscale_unary(int K, int C, const float *const *scores, const int3
 int launch_multiscale_unary_batch(int G, int K, int C, const float *const *scores, const int32_t *h, const int32_t *w,
                                   const int32_t *H, const int32_t *W, float eps, float *const *unary, int32_t *const *amax,
                                   float *const *sum_out, hipStream_t stream);
+int launch_multiscale_unary_mirror(int K, int C, const float *const *scores, const int32_t *mirror, const int32_t *h, const int32_t *w,
+                                   int H, int W, float eps, float *unary, int32_t *amax, float *sum_out, hipStream_t stream);
+int launch_multiscale_unary_mirror_batch(int G, int K, int C, const float *const *scores, const int32_t *h, const int32_t *w,
+                                         const int32_t *H, const int32_t *W, float eps, float *const *unary, int32_t *const *amax,
+                                         float *const *sum_out, hipStream_t stream);
 int launch_preprocess_ms_batch(int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H, const int32_t *W,
                                const int32_t *sizes, const float *mean, float *const *out, hipStream_t stream);
 int launch_preprocess_rect_batch(int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H, const int32_t *W,
                                  const int32_t *oh, const int32_t *ow, const float *mean, float *const *out, hipStream_t stream);
+int launch_preprocess_rect_mirror_batch(int G, int Gcap, int K, const unsigned char *const *images, const int32_t *H, const int32_t *W,
+                                        const int32_t *oh, const int32_t *ow, const float *mean, float *const *out,
+                                        hipStream_t stream);
 int launch_train_s_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *H,
                                const int32_t *W, const int32_t *cue_off, const int32_t *ncues, const int32_t *label_off,
                                const int32_t *nlabels, const int32_t *mirror, int S, int C, int Hm, int Wm, const float *mean,

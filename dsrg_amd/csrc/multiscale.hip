@@ -15,6 +15,12 @@
 //
 // Two front ends share the body: multiscale_unary_kernel (one image) and multiscale_unary_batch_kernel (G images whose score maps
 // are the slices of K batched maps, test-ms.py's fixed sizes: blockIdx.x -> (image, block) through per-image block prefix sums).
+//
+// Mirrored test-time augmentation (the scores of a mirrored input, mirrored back and summed with the plain ones) is the body's
+// MIRROR instantiation behind two front ends of its own, multiscale_unary_mirror_kernel and multiscale_unary_mirror_batch_kernel:
+// a map whose bit of `mirror` is set is read as flip(map, last axis).  y0, y1, x0, x1 and the blend weights of step 1 come from
+// the output pixel exactly as for a plain map; only the four loads move, to columns w - 1 - x0 and w - 1 - x1.  The MIRROR = false
+// instantiations are the kernels as they were.
 #include <math.h>
 #include <string.h>
 #include "common.h"
@@ -25,6 +31,7 @@ constexpr int kMsPix = 64;        // output pixels per workgroup
 constexpr int kMsThreads = 256;
 constexpr int kMsMaxScales = 8;
 constexpr int kMsMaxBatch = 16;   // images per batched launch (multiscale_unary_batch_kernel, preprocess_rect_batch_kernel)
+constexpr int kMsMaxMirrorBatch = 8;   // ... of the mirror forms: two slices per image in a batch of at most 16
 
 struct MsArgs {
     const float *s[kMsMaxScales];  // (C, h_k, w_k) score maps
@@ -33,8 +40,9 @@ struct MsArgs {
 };
 
 // block `blk` of one image: output pixels [64 blk, 64 blk + 64) of the H x W map
-template <int K>
-__device__ __forceinline__ void multiscale_unary_body(const MsArgs &a, int C, int H, int W, float eps, int blk,
+// (mirror: bit k set = map k is read with its columns reversed; MIRROR = false ignores it)
+template <int K, bool MIRROR>
+__device__ __forceinline__ void multiscale_unary_body(const MsArgs &a, unsigned mirror, int C, int H, int W, float eps, int blk,
                                                       float *__restrict__ unary, int32_t *__restrict__ amax,
                                                       float *__restrict__ sum_out) {
     __shared__ float s_tile[kMsPix * (kMaxLabels + 1)];     // [pixel][label], row stride Cs (odd: conflict-free columns)
@@ -59,10 +67,12 @@ __device__ __forceinline__ void multiscale_unary_body(const MsArgs &a, int C, in
         const double sy = a.sh[k] * (double)y, sx = a.sw[k] * (double)x;
         const int y0 = (int)sy, x0 = (int)sx;
         const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-        o00[k] = y0 * w + x0;
-        o01[k] = y0 * w + x1;
-        o10[k] = y1 * w + x0;
-        o11[k] = y1 * w + x1;
+        const bool rev = MIRROR && ((mirror >> k) & 1u);
+        const int c0x = rev ? w - 1 - x0 : x0, c1x = rev ? w - 1 - x1 : x1;      // the columns the two taps are loaded from
+        o00[k] = y0 * w + c0x;
+        o01[k] = y0 * w + c1x;
+        o10[k] = y1 * w + c0x;
+        o11[k] = y1 * w + c1x;
         hw[k] = h * w;
         l1h[k] = sy - (double)y0;
         l1w[k] = sx - (double)x0;
@@ -149,7 +159,14 @@ template <int K>
 __global__ __launch_bounds__(kMsThreads) void multiscale_unary_kernel(MsArgs a, int C, int H, int W, float eps,
                                                                       float *__restrict__ unary, int32_t *__restrict__ amax,
                                                                       float *__restrict__ sum_out) {
-    multiscale_unary_body<K>(a, C, H, W, eps, (int)blockIdx.x, unary, amax, sum_out);
+    multiscale_unary_body<K, false>(a, 0u, C, H, W, eps, (int)blockIdx.x, unary, amax, sum_out);
+}
+
+template <int K>
+__global__ __launch_bounds__(kMsThreads) void multiscale_unary_mirror_kernel(MsArgs a, unsigned mirror, int C, int H, int W, float eps,
+                                                                             float *__restrict__ unary, int32_t *__restrict__ amax,
+                                                                             float *__restrict__ sum_out) {
+    multiscale_unary_body<K, true>(a, mirror, C, H, W, eps, (int)blockIdx.x, unary, amax, sum_out);
 }
 
 // G images in one launch.  s[k]: (Gcap, C, h_k, w_k) batched maps, image g reads slice g; blk0[g]: the first block of image g
@@ -181,7 +198,31 @@ __global__ __launch_bounds__(kMsThreads) void multiscale_unary_batch_kernel(MsBa
         a.sh[k] = H > 1 ? (double)(h - 1) / (double)(H - 1) : 0.0;
         a.sw[k] = W > 1 ? (double)(w - 1) / (double)(W - 1) : 0.0;
     }
-    multiscale_unary_body<K>(a, C, H, W, eps, blk - b.blk0[g], b.unary[g], b.amax[g], b.sum[g]);
+    multiscale_unary_body<K, false>(a, 0u, C, H, W, eps, blk - b.blk0[g], b.unary[g], b.amax[g], b.sum[g]);
+}
+
+// G images at K scales, each with its mirror: s[k] is (Gcap >= 2 G, C, h_k, w_k), image g reads slice 2 g plain and slice 2 g + 1
+// mirrored back.  The body runs on the 2 K maps in the order scale 0 plain, scale 0 mirror, scale 1 plain, ..., which is the
+// list multiscale_unary_mirror_kernel<2 K> gets for those slices with the flags 0, 1, 0, 1, ...: bit for bit its outputs.
+template <int K>
+__global__ __launch_bounds__(kMsThreads) void multiscale_unary_mirror_batch_kernel(MsBatchArgs b, int G, int C, float eps) {
+    const int blk = (int)blockIdx.x;
+    int g = 0;
+    while (g + 1 < G && blk >= b.blk0[g + 1]) ++g;          // (uniform over the block)
+    const int H = b.H[g], W = b.W[g];
+    MsArgs a;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int h = b.h[k], w = b.w[k];
+        const size_t slice = (size_t)C * h * w;
+        a.s[2 * k] = b.s[k] + (size_t)(2 * g) * slice;
+        a.s[2 * k + 1] = b.s[k] + (size_t)(2 * g + 1) * slice;
+        a.h[2 * k] = a.h[2 * k + 1] = h;
+        a.w[2 * k] = a.w[2 * k + 1] = w;
+        a.sh[2 * k] = a.sh[2 * k + 1] = H > 1 ? (double)(h - 1) / (double)(H - 1) : 0.0;
+        a.sw[2 * k] = a.sw[2 * k + 1] = W > 1 ? (double)(w - 1) / (double)(W - 1) : 0.0;
+    }
+    multiscale_unary_body<2 * K, true>(a, 0xAAu, C, H, W, eps, blk - b.blk0[g], b.unary[g], b.amax[g], b.sum[g]);
 }
 
 int check_multiscale_unary(int K, int C, const float *const *scores, const int32_t *h, const int32_t *w, int H, int W,
@@ -205,29 +246,51 @@ int check_multiscale_unary(int K, int C, const float *const *scores, const int32
     return DSRG_OK;
 }
 
-int launch_multiscale_unary(int K, int C, const float *const *scores, const int32_t *h, const int32_t *w, int H, int W, float eps,
-                            float *unary, int32_t *amax, float *sum_out, hipStream_t stream) {
+// mirrored: dsrg_multiscale_unary_mirror (mirror: K flags, non-zero = map k is read with its columns reversed), else
+// dsrg_multiscale_unary (mirror unused)
+static int launch_multiscale_unary_any(bool mirrored, int K, int C, const float *const *scores, const int32_t *mirror, const int32_t *h,
+                                       const int32_t *w, int H, int W, float eps, float *unary, int32_t *amax, float *sum_out,
+                                       hipStream_t stream) {
     int rc = check_multiscale_unary(K, C, scores, h, w, H, W, unary, amax, sum_out);
     if (rc) return rc;
+    if (mirrored && !mirror) return set_error(DSRG_ERR_INVALID, "multiscale unary mirror: NULL mirror flag array");
     MsArgs a;
     memset(&a, 0, sizeof(a));
+    unsigned mask = 0;
     for (int k = 0; k < K; ++k) {
         a.s[k] = scores[k];
         a.h[k] = h[k];
         a.w[k] = w[k];
         a.sh[k] = H > 1 ? (double)(h[k] - 1) / (double)(H - 1) : 0.0;
         a.sw[k] = W > 1 ? (double)(w[k] - 1) / (double)(W - 1) : 0.0;
+        if (mirrored && mirror[k]) mask |= 1u << k;
     }
     const dim3 grid((unsigned)((H * W + kMsPix - 1) / kMsPix)), block(kMsThreads);
     switch (K) {
-#define DSRG_MS_CASE(k) \
-    case k: hipLaunchKernelGGL(multiscale_unary_kernel<k>, grid, block, 0, stream, a, C, H, W, eps, unary, amax, sum_out); break;
+#define DSRG_MS_CASE(k)                                                                                                          \
+    case k:                                                                                                                      \
+        if (mirrored)                                                                                                            \
+            hipLaunchKernelGGL(multiscale_unary_mirror_kernel<k>, grid, block, 0, stream, a, mask, C, H, W, eps, unary, amax,    \
+                               sum_out);                                                                                         \
+        else                                                                                                                     \
+            hipLaunchKernelGGL(multiscale_unary_kernel<k>, grid, block, 0, stream, a, C, H, W, eps, unary, amax, sum_out);       \
+        break;
         DSRG_MS_CASE(1) DSRG_MS_CASE(2) DSRG_MS_CASE(3) DSRG_MS_CASE(4) DSRG_MS_CASE(5) DSRG_MS_CASE(6) DSRG_MS_CASE(7)
         DSRG_MS_CASE(8)
 #undef DSRG_MS_CASE
     }
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
+}
+
+int launch_multiscale_unary(int K, int C, const float *const *scores, const int32_t *h, const int32_t *w, int H, int W, float eps,
+                            float *unary, int32_t *amax, float *sum_out, hipStream_t stream) {
+    return launch_multiscale_unary_any(false, K, C, scores, nullptr, h, w, H, W, eps, unary, amax, sum_out, stream);
+}
+
+int launch_multiscale_unary_mirror(int K, int C, const float *const *scores, const int32_t *mirror, const int32_t *h, const int32_t *w,
+                                   int H, int W, float eps, float *unary, int32_t *amax, float *sum_out, hipStream_t stream) {
+    return launch_multiscale_unary_any(true, K, C, scores, mirror, h, w, H, W, eps, unary, amax, sum_out, stream);
 }
 
 // all-NULL (-> 0) or all-set (-> 1) host array of G device pointers; -1: mixed
@@ -238,16 +301,20 @@ static int output_class(const void *const *p, int G) {
     return set == 0 ? 0 : set == G ? 1 : -1;
 }
 
-int launch_multiscale_unary_batch(int G, int K, int C, const float *const *scores, const int32_t *h, const int32_t *w,
-                                  const int32_t *H, const int32_t *W, float eps, float *const *unary, int32_t *const *amax,
-                                  float *const *sum_out, hipStream_t stream) {
-    if (G < 1 || G > kMsMaxBatch)
-        return set_error(DSRG_ERR_INVALID, "multiscale unary batch: 1..%d images, got %d", kMsMaxBatch, G);
-    if (!H || !W) return set_error(DSRG_ERR_INVALID, "multiscale unary batch: NULL image size array");
+// mirrored: dsrg_multiscale_unary_mirror_batch (at most kMsMaxMirrorBatch images and kMsMaxScales / 2 scales, each scale's map
+// holding two slices per image), else dsrg_multiscale_unary_batch; `what` names the entry point in the messages
+static int launch_multiscale_unary_batch_any(bool mirrored, const char *what, int G, int K, int C, const float *const *scores,
+                                             const int32_t *h, const int32_t *w, const int32_t *H, const int32_t *W, float eps,
+                                             float *const *unary, int32_t *const *amax, float *const *sum_out, hipStream_t stream) {
+    const int maxG = mirrored ? kMsMaxMirrorBatch : kMsMaxBatch;
+    if (G < 1 || G > maxG) return set_error(DSRG_ERR_INVALID, "%s: 1..%d images, got %d", what, maxG, G);
+    if (mirrored && (K < 1 || K > kMsMaxScales / 2))
+        return set_error(DSRG_ERR_INVALID, "%s: 1..%d scales (each with its mirror), got %d", what, kMsMaxScales / 2, K);
+    if (!H || !W) return set_error(DSRG_ERR_INVALID, "%s: NULL image size array", what);
     const int cu = output_class((const void *const *)unary, G), ca = output_class((const void *const *)amax, G),
               cs = output_class((const void *const *)sum_out, G);
     if (cu < 0 || ca < 0 || cs < 0)
-        return set_error(DSRG_ERR_INVALID, "multiscale unary batch: an output class must be NULL or set for every image");
+        return set_error(DSRG_ERR_INVALID, "%s: an output class must be NULL or set for every image", what);
     MsBatchArgs b;
     memset(&b, 0, sizeof(b));
     for (int g = 0; g < G; ++g) {
@@ -268,15 +335,38 @@ int launch_multiscale_unary_batch(int G, int K, int C, const float *const *score
         b.w[k] = w[k];
     }
     const dim3 grid((unsigned)b.blk0[G]), block(kMsThreads);
-    switch (K) {
+    if (mirrored) {
+        switch (K) {
+#define DSRG_MS_CASE(k) \
+    case k: hipLaunchKernelGGL(multiscale_unary_mirror_batch_kernel<k>, grid, block, 0, stream, b, G, C, eps); break;
+            DSRG_MS_CASE(1) DSRG_MS_CASE(2) DSRG_MS_CASE(3) DSRG_MS_CASE(4)
+#undef DSRG_MS_CASE
+        }
+    } else {
+        switch (K) {
 #define DSRG_MS_CASE(k) \
     case k: hipLaunchKernelGGL(multiscale_unary_batch_kernel<k>, grid, block, 0, stream, b, G, C, eps); break;
-        DSRG_MS_CASE(1) DSRG_MS_CASE(2) DSRG_MS_CASE(3) DSRG_MS_CASE(4) DSRG_MS_CASE(5) DSRG_MS_CASE(6) DSRG_MS_CASE(7)
-        DSRG_MS_CASE(8)
+            DSRG_MS_CASE(1) DSRG_MS_CASE(2) DSRG_MS_CASE(3) DSRG_MS_CASE(4) DSRG_MS_CASE(5) DSRG_MS_CASE(6) DSRG_MS_CASE(7)
+            DSRG_MS_CASE(8)
 #undef DSRG_MS_CASE
+        }
     }
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
+}
+
+int launch_multiscale_unary_batch(int G, int K, int C, const float *const *scores, const int32_t *h, const int32_t *w,
+                                  const int32_t *H, const int32_t *W, float eps, float *const *unary, int32_t *const *amax,
+                                  float *const *sum_out, hipStream_t stream) {
+    return launch_multiscale_unary_batch_any(false, "multiscale unary batch", G, K, C, scores, h, w, H, W, eps, unary, amax, sum_out,
+                                             stream);
+}
+
+int launch_multiscale_unary_mirror_batch(int G, int K, int C, const float *const *scores, const int32_t *h, const int32_t *w,
+                                         const int32_t *H, const int32_t *W, float eps, float *const *unary, int32_t *const *amax,
+                                         float *const *sum_out, hipStream_t stream) {
+    return launch_multiscale_unary_batch_any(true, "multiscale unary mirror batch", G, K, C, scores, h, w, H, W, eps, unary, amax,
+                                             sum_out, stream);
 }
 
 }  // namespace dsrg

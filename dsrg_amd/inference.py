@@ -9,6 +9,8 @@ full-resolution dense CRF on log-probabilities, pseudo-label generation, and the
   predict_train_gt      <-> training/tools/generate_train_gt.py:78-106
   predict_train_gt_many <-> the loop of generate_train_gt.py:117-123 over train_aug (batched forwards, fused HIP tail)
   ConfusionMatrix       <-> training/tools/evaluate.py:17-68
+  flip=True             (no counterpart in the reference) mirrored test-time augmentation of the ms / ms-f functions: every scale
+                        runs on the image and on its mirror image, the mirror's scores are mirrored back, all 2K maps are summed
 
 The network runs in PyTorch-ROCm; resampling uses align-corners bilinear interpolation, which is the
 sampling scipy.ndimage.zoom(order=1) performs ((in-1)/(out-1) mapping); the CRF is
@@ -35,6 +37,29 @@ def _zoom(x, h, w):
     # once; with float32 weights the result is off by up to 4e-5 of the value range (measured against scipy.ndimage.zoom,
     # tests/test_inference.py), in float64 by the final rounding only
     return F.interpolate(x.double(), size=(h, w), mode="bilinear", align_corners=True).to(x.dtype)
+
+
+def _zoom_steps(x, h, w):
+    """_zoom's arithmetic (align-corners order-1 zoom: coordinate o * (in - 1) / (out - 1), the two-tap blend
+    l0h * (l0w * v00 + l1w * v01) + l1h * (l0w * v10 + l1w * v11) in float64, rounded once to x.dtype) issued as separate torch
+    ops, so that every product and sum is rounded on its own.  _zoom's single GPU kernel (upsample_bilinear2d on float64) is
+    compiled with products contracted into FMAs and differs from this in the last bit of about one value in a thousand; this form
+    is what csrc/multiscale.hip computes (-ffp-contract=off), bit for bit, on the GPU and on the CPU"""
+    def axis(n_in, n_out):
+        scale = (n_in - 1) / (n_out - 1) if n_out > 1 else 0.0
+        src = torch.arange(n_out, dtype=torch.float64, device=x.device) * scale
+        i0 = src.to(torch.int64)
+        return i0, i0 + (i0 < n_in - 1).to(torch.int64), src - i0.to(torch.float64)
+
+    y0, y1, l1h = axis(x.shape[2], h)
+    x0, x1, l1w = axis(x.shape[3], w)
+    l0h, l1h = (1.0 - l1h).view(-1, 1), l1h.view(-1, 1)
+    l0w = 1.0 - l1w
+    v = x.double()
+    r0, r1 = v.index_select(2, y0), v.index_select(2, y1)
+    top = l0w * r0.index_select(3, x0) + l1w * r0.index_select(3, x1)
+    bottom = l0w * r1.index_select(3, x0) + l1w * r1.index_select(3, x1)
+    return (l0h * top + l1h * bottom).to(x.dtype)
 
 
 @contextlib.contextmanager
@@ -131,9 +156,57 @@ def _probs_from_scores(scores, eps=0.00001):
     return torch.clamp(probs, min=eps)                       # probs[probs < eps] = eps (test-ms.py:102-103)
 
 
+MAX_FLIP_SCALES = 4         # scales with flip=True: 2 K <= 8 maps in one dsrg_multiscale_unary_mirror launch
+MAX_FLIP_BATCH = 8          # images per group with flip=True: two slots each in the batched forwards
+
+
+def _check_flip(nscales, group=1):
+    """the limits of flip=True, checked before any launch"""
+    if nscales > MAX_FLIP_SCALES:
+        raise ValueError("flip=True takes at most %d scales (each runs twice), got %d" % (MAX_FLIP_SCALES, nscales))
+    if int(group) > MAX_FLIP_BATCH:
+        raise ValueError("flip=True takes groups of at most %d images (two slots each), got %d" % (MAX_FLIP_BATCH, int(group)))
+
+
+def _flip_pair_scores(net, inputs, forward):
+    """flip=True, one image: every (1,3,h,w) network input runs with its mirror image as one batch-2 forward,
+    cat([x, x.flip(-1)]) (a GraphedForward holds batch-2 graphs) -> the 2K (1,C,h',w') float32 score maps in the order of the
+    sum: scale 0 plain, scale 0 mirror, scale 1 plain, ...  The mirror maps are NOT mirrored back here: ops.multiscale_unary
+    (mirror=[0, 1, 0, 1, ...]) reads them reversed, the torch composition flips them"""
+    inputs = list(inputs)
+    shapes = [tuple(x.shape) for x in inputs]
+    maps = []
+    with _eval_mode(net):
+        for k, x in enumerate(inputs):
+            sc = (forward or net)(torch.cat([x, x.flip(-1)])).float()
+            if forward is not None and shapes[k] in shapes[k + 1:]:
+                sc = sc.clone()                  # a graph's static output: the later replay of the same shape would overwrite it
+            sc = sc.contiguous()
+            maps += [sc[0:1], sc[1:2]]
+    return maps
+
+
+def _ms_flip_result(net, image, sizes, device, forward, want):
+    """test-ms.py:89-103 with flip=True for one image: len(sizes) batch-2 forwards and one dsrg_multiscale_unary_mirror launch"""
+    from . import ops
+    maps = _flip_pair_scores(net, [preprocess(image, size, device) for size in sizes], forward)
+    return ops.multiscale_unary(maps, image.shape[0], image.shape[1], eps=0.00001, want=want, mirror=[0, 1] * len(sizes))
+
+
 @torch.no_grad()
-def predict_mask_ms(net, image, smooth=True, sizes=(241, 321, 401), device="cuda", forward=None):
-    """test-ms.py:84-111 -> (H,W) int64 label mask.  forward: see multiscale_scores"""
+def predict_mask_ms(net, image, smooth=True, sizes=(241, 321, 401), device="cuda", forward=None, flip=False):
+    """test-ms.py:84-111 -> (H,W) int64 label mask.  forward: see multiscale_scores.  flip=True (at most 4 sizes): every size
+    runs on the image and its mirror image as one batch-2 forward, and the tail is the fused kernel (one
+    dsrg_multiscale_unary_mirror launch on the 2K maps: zoom, the mirrors read reversed, sum, softmax, clamp, log) instead of the
+    torch composition this function runs without flip"""
+    if flip:
+        sizes = tuple(sizes)
+        _check_flip(len(sizes))
+        out = _ms_flip_result(net, image, sizes, device, forward, "unary" if smooth else "argmax")
+        if smooth:
+            img = torch.as_tensor(np.asarray(image).astype('ubyte'), device=out.device)
+            return CRF_device(img, out, scale_factor=1.0, want="map").cpu().numpy().astype(np.int64)
+        return out.cpu().numpy().astype(np.int64)
     probs = _probs_from_scores(multiscale_scores(net, image, sizes, device, forward))
     if smooth:
         # scores, log-probabilities, CRF and arg-max all stay on the GPU; only the (H,W) mask crosses PCIe
@@ -162,38 +235,51 @@ def _forward_groups(items, G):
         yield group + [None] * (G - len(group))
 
 
-def _batched_inputs(group, sizes, device, forward):
+def _with_mirrors(slots):
+    """per-image network inputs -> each followed by its mirror image (the slot pairs of the batched flip forwards)"""
+    return [t for x in slots for t in (x, x.flip(-1))]
+
+
+def _batched_inputs(group, sizes, device, forward, flip=False):
     """one padded group of _forward_groups -> (the images on the device, list of (G, 3, S, S) network inputs, one per size).
     uint8 images go through one dsrg_preprocess_ms_batch launch, written straight into the static inputs of `forward`'s graphs
-    where those exist; a group with other dtypes takes `preprocess` for those slots"""
+    where those exist; a group with other dtypes takes `preprocess` for those slots.  flip: the inputs are (2 G, 3, S, S), image g
+    in slot 2g and its mirror image in slot 2g+1 (one dsrg_preprocess_rect_mirror_batch launch), the padding slots behind them"""
     from . import ops
     G = len(group)
+    B = 2 * G if flip else G                                # the batch of the forwards
     images = [im for im in group if im is not None]
     arrays = [np.ascontiguousarray(np.asarray(im)) for im in images]
     if all(a.dtype == np.uint8 for a in arrays):
         dev_images = [torch.from_numpy(a).to(device) for a in arrays]
         out = None
         if isinstance(forward, GraphedForward):
-            out = [forward.static_input((G, 3, S, S)) for S in sizes]
+            out = [forward.static_input((B, 3, S, S)) for S in sizes]
             if len(set(sizes)) != len(sizes) or any(o is None for o in out):
                 out = None                                  # (first group: the graphs are captured from fresh tensors)
+        if flip:
+            return dev_images, ops.preprocess_rect_mirror_batch(dev_images, [(S, S) for S in sizes], capacity=B, mean=MEAN_PIXEL,
+                                                                out=out)
         return dev_images, ops.preprocess_ms_batch(dev_images, sizes, capacity=G, mean=MEAN_PIXEL, out=out)
     dev_images = [torch.as_tensor(a.astype('ubyte'), device=device) for a in arrays]
     xs = []
     for S in sizes:
         slots = [ops.preprocess_ms_batch([d], [S], mean=MEAN_PIXEL)[0] if a.dtype == np.uint8 else preprocess(a, S, device)
                  for a, d in zip(arrays, dev_images)]
-        if len(slots) < G:
-            slots.append(torch.zeros((G - len(slots), 3, S, S), dtype=torch.float32, device=device))
+        if flip:
+            slots = _with_mirrors(slots)
+        if len(slots) < B:
+            slots.append(torch.zeros((B - len(slots), 3, S, S), dtype=torch.float32, device=device))
         xs.append(torch.cat(slots))
     return dev_images, xs
 
 
-def _batched_unaries(net, group, sizes, device, forward, want):
+def _batched_unaries(net, group, sizes, device, forward, want, flip=False):
     """test-ms.py:89-103 for one padded group: K batched forwards and one dsrg_multiscale_unary_batch launch -> (the images on the
-    device, the `want` output of ops.multiscale_unary per image); the padding slots' results are dropped"""
+    device, the `want` output of ops.multiscale_unary per image); the padding slots' results are dropped.  flip: batch-2G forwards
+    on _batched_inputs' slot pairs and one dsrg_multiscale_unary_mirror_batch launch"""
     from . import ops
-    dev_images, xs = _batched_inputs(group, sizes, device, forward)
+    dev_images, xs = _batched_inputs(group, sizes, device, forward, flip)
     scores = []
     with _eval_mode(net):
         for k, x in enumerate(xs):
@@ -202,11 +288,14 @@ def _batched_unaries(net, group, sizes, device, forward, want):
                 sc = sc.clone()                  # a graph's static output: the later replay of the same shape would overwrite it
             scores.append(sc.contiguous())
     shapes = [(im.shape[0], im.shape[1]) for im in dev_images]
+    if flip:
+        return dev_images, ops.multiscale_unary_mirror_batch(scores, shapes, eps=0.00001, want=want)
     return dev_images, ops.multiscale_unary_batch(scores, shapes, eps=0.00001, want=want)
 
 
 @torch.no_grad()
-def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", forward=None, in_flight=3, batch=1, forward_batch=1):
+def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", forward=None, in_flight=3, batch=1, forward_batch=1,
+                          flip=False):
     """predict_mask_ms over many images (the loop of test-ms.py over a split's 1 449 / 10 582 images), as a generator of (H,W) int64
     masks in order: the forwards of image i + 1 (on the caller's stream; `forward`: a GraphedForward) run while the CRFs of the images
     before it are in flight on `in_flight` worker streams (crf.CRF_device_many; batch > 1: consecutive same-sized images share one
@@ -215,12 +304,19 @@ def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", for
     forward_batch = G > 1: the images are taken G at a time.  test-ms.py resizes every image to the same `sizes`, so a group's
     forwards are len(sizes) batch-G forwards (a GraphedForward holds one batch-G graph per size; the tail group is padded with
     zero inputs) between one dsrg_preprocess_ms_batch launch and one dsrg_multiscale_unary_batch launch.  A batch-G forward need
-    not round as a batch-1 forward does: the masks are predict_mask_ms's except where two labels all but tie."""
+    not round as a batch-1 forward does: the masks are predict_mask_ms's except where two labels all but tie.
+
+    flip=True: predict_mask_ms(flip=True) image by image; with forward_batch = G (at most 8, and at most 4 sizes: ValueError
+    before any stream or worker exists) a group is one dsrg_preprocess_rect_mirror_batch launch, len(sizes) batch-2G forwards
+    (image g in slot 2g, its mirror image in slot 2g+1, the padding slots zero) and one dsrg_multiscale_unary_mirror_batch
+    launch."""
     sizes = tuple(sizes)
+    if flip:
+        _check_flip(len(sizes), forward_batch)
     if int(forward_batch) != 1:
         def batched_pairs():
             for group in _forward_groups(images, forward_batch):
-                for pair in zip(*_batched_unaries(net, group, sizes, device, forward, "unary")):
+                for pair in zip(*_batched_unaries(net, group, sizes, device, forward, "unary", flip)):
                     yield pair
 
         yield from _crf_in_flight(batched_pairs(), device, in_flight, batch)
@@ -228,6 +324,10 @@ def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", for
 
     def pairs():
         for image in images:
+            if flip:
+                unary = _ms_flip_result(net, image, sizes, device, forward, "unary")
+                yield torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device), unary
+                continue
             probs = _probs_from_scores(multiscale_scores(net, image, sizes, device, forward))
             unary = torch.log(probs).permute(1, 2, 0).contiguous()
             yield torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device), unary
@@ -237,20 +337,23 @@ def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", for
 
 @torch.no_grad()
 def predict_masks_ms_batched(net, images, smooth=True, sizes=(241, 321, 401), device="cuda", forward=None, in_flight=3, batch=1,
-                             capacity=None):
+                             capacity=None, flip=False):
     """predict_masks_ms_many(forward_batch=capacity) for ONE group of 1..16 images, as a list of (H,W) int64 masks.
     smooth=False: the arg-max of the summed scores (dsrg_multiscale_unary_batch's), no CRF.  capacity (default: the number of
-    images): the batch size of the forwards, the slots beyond the images run on zeros (a tail group on the full groups' graphs)"""
+    images): the batch size of the forwards, the slots beyond the images run on zeros (a tail group on the full groups' graphs).
+    flip=True: as predict_masks_ms_many(flip=True); at most 8 images in the capacity, the forwards' batch is twice the capacity"""
     images = list(images)
     capacity = len(images) if capacity is None else int(capacity)
+    sizes = tuple(sizes)
+    if flip:
+        _check_flip(len(sizes), capacity)
     if not 1 <= len(images) <= capacity <= MAX_FORWARD_BATCH:
         raise ValueError("one group holds 1..%d images within its capacity, got %d in %d" % (MAX_FORWARD_BATCH, len(images), capacity))
     images = images + [None] * (capacity - len(images))
-    sizes = tuple(sizes)
     if smooth:
-        dev_images, unaries = _batched_unaries(net, images, sizes, device, forward, "unary")
+        dev_images, unaries = _batched_unaries(net, images, sizes, device, forward, "unary", flip)
         return list(_crf_in_flight(zip(dev_images, unaries), device, in_flight, batch))
-    _, labels = _batched_unaries(net, images, sizes, device, forward, "argmax")
+    _, labels = _batched_unaries(net, images, sizes, device, forward, "argmax", flip)
     return [lab.cpu().numpy().astype(np.int64) for lab in labels]
 
 
@@ -317,30 +420,45 @@ def _relative_scores(net, image, scales, device, forward):
     return out
 
 
-def _relative_unary(net, image, scales, device, forward, fused, smooth):
+def _relative_unary(net, image, scales, device, forward, fused, smooth, flip=False, want=None):
     """test-ms-f.py:121-134 -> (H,W,C) float32 log-probabilities (smooth) or (H,W) arg-max labels.  fused: one
-    dsrg_multiscale_unary launch after the forwards; otherwise the torch composition (_zoom, sum, softmax, clamp, log)"""
+    dsrg_multiscale_unary launch after the forwards; otherwise the torch composition (_zoom, sum, softmax, clamp, log).
+    flip: batch-2 forwards (_flip_pair_scores); fused, one dsrg_multiscale_unary_mirror launch on the 2K maps, otherwise
+    torch.flip of the mirrors' scores, the zoom and the sum in the same order — the zoom as _zoom_steps, _zoom's arithmetic
+    without contracted products, so that the composition's sum is the fused kernel's bit for bit.  want="sum": the (H,W,C)
+    summed scores of either route instead (parity checks)"""
     d1, d2 = image.shape[0], image.shape[1]
-    scores = _relative_scores(net, image, scales, device, forward)
+    want = want or ("unary" if smooth else "argmax")
+    if flip:
+        _check_flip(len(scales))
+        scores = _flip_pair_scores(net, [preprocess_relative(image, s, device) for s in scales], forward)
+    else:
+        scores = _relative_scores(net, image, scales, device, forward)
     if fused:
         from . import ops
-        return ops.multiscale_unary(scores, d1, d2, eps=0.00001, want="unary" if smooth else "argmax")
+        return ops.multiscale_unary(scores, d1, d2, eps=0.00001, want=want, mirror=[0, 1] * len(scales) if flip else None)
     total = None
-    for sc in scores:
-        z = _zoom(sc, d1, d2)
+    for k, sc in enumerate(scores):
+        z = _zoom_steps(torch.flip(sc, [-1]) if k % 2 else sc, d1, d2) if flip else _zoom(sc, d1, d2)
         total = z if total is None else total + z
+    if want == "sum":
+        return total[0].permute(1, 2, 0).contiguous()
     probs = _probs_from_scores(total[0])
-    if smooth:
+    if want == "unary":
         return torch.log(probs).permute(1, 2, 0).contiguous()
     return probs.argmax(0)
 
 
 @torch.no_grad()
-def predict_mask_ms_f(net, image, scales=(0.75, 1.0, 1.25), smooth=True, device="cuda", forward=None, fused=True):
+def predict_mask_ms_f(net, image, scales=(0.75, 1.0, 1.25), smooth=True, device="cuda", forward=None, fused=True, flip=False):
     """test-ms-f.py:115-142 -> (H,W) int64 label mask: forwards at `scales` relative to the image's own size, the fused
     multi-scale unary, then the full-resolution CRF (smooth) or the arg-max.  forward: see multiscale_scores (a GraphedForward,
-    best bounded: GraphedForward(net, max_shapes=..., capture_after=2)); fused=False: the torch composition, for A/B runs"""
-    out = _relative_unary(net, image, scales, device, forward, fused, smooth)
+    best bounded: GraphedForward(net, max_shapes=..., capture_after=2)); fused=False: the torch composition, for A/B runs.
+    flip=True (at most 4 scales): every scale runs on the image and its mirror image as one batch-2 forward, the mirror's scores
+    are mirrored back and all 2K maps summed (scale 0 plain, scale 0 mirror, scale 1 plain, ...) before the softmax: one
+    dsrg_multiscale_unary_mirror launch, or with fused=False torch.flip of the mirrors' scores in the torch composition (zoomed
+    by _zoom_steps: its summed scores are the kernel's bit for bit)"""
+    out = _relative_unary(net, image, tuple(scales), device, forward, fused, smooth, flip)
     if smooth:
         img = torch.as_tensor(np.asarray(image).astype('ubyte'), device=out.device)
         return CRF_device(img, out, scale_factor=1.0, want="map").cpu().numpy().astype(np.int64)
@@ -384,13 +502,15 @@ def plan_size_groups(keys, G, window):
     return groups()
 
 
-def _relative_group_results(net, group, scales, device, forward, want):
+def _relative_group_results(net, group, scales, device, forward, want, flip=False):
     """test-ms-f.py:121-134 for a group of n same-sized images (not padded): one dsrg_preprocess_rect_batch launch for all scales
     (written straight into the static inputs of `forward`'s graphs where those exist; non-uint8 images take preprocess_relative
     for their slot), len(scales) batch-n forwards and one dsrg_multiscale_unary_batch launch -> (the images on the device, the
-    `want` output of ops.multiscale_unary per image)"""
+    `want` output of ops.multiscale_unary per image).  flip: one dsrg_preprocess_rect_mirror_batch launch (image g in slot 2g, its
+    mirror image in slot 2g+1), batch-2n forwards and one dsrg_multiscale_unary_mirror_batch launch"""
     from . import ops
     n = len(group)
+    B = 2 * n if flip else n                                # the batch of the forwards
     H, W = group[0].shape[0], group[0].shape[1]
     shapes = [(relative_size(H, s), relative_size(W, s)) for s in scales]
     if any(h < 1 or w < 1 for h, w in shapes):
@@ -400,15 +520,17 @@ def _relative_group_results(net, group, scales, device, forward, want):
         dev_images = [torch.from_numpy(a).to(device) for a in arrays]
         out = None
         if isinstance(forward, GraphedForward):
-            out = [forward.static_input((n, 3, h, w)) for h, w in shapes]
+            out = [forward.static_input((B, 3, h, w)) for h, w in shapes]
             if len(set(shapes)) != len(shapes) or any(o is None for o in out):
                 out = None                                  # (not captured yet: GraphedForward copies a fresh tensor in)
-        xs = ops.preprocess_rect_batch(dev_images, shapes, mean=MEAN_PIXEL, out=out)
+        xs = (ops.preprocess_rect_mirror_batch if flip else ops.preprocess_rect_batch)(dev_images, shapes, mean=MEAN_PIXEL, out=out)
     else:
         dev_images = [torch.as_tensor(a.astype('ubyte'), device=device) for a in arrays]
-        xs = [torch.cat([ops.preprocess_rect_batch([d], [hw], mean=MEAN_PIXEL)[0] if a.dtype == np.uint8
-                         else preprocess_relative(a, s, device) for a, d in zip(arrays, dev_images)])
-              for s, hw in zip(scales, shapes)]
+        xs = []
+        for s, hw in zip(scales, shapes):
+            slots = [ops.preprocess_rect_batch([d], [hw], mean=MEAN_PIXEL)[0] if a.dtype == np.uint8
+                     else preprocess_relative(a, s, device) for a, d in zip(arrays, dev_images)]
+            xs.append(torch.cat(_with_mirrors(slots) if flip else slots))
     scores = []
     with _eval_mode(net):
         for k, x in enumerate(xs):
@@ -416,12 +538,14 @@ def _relative_group_results(net, group, scales, device, forward, want):
             if forward is not None and shapes[k] in shapes[k + 1:]:
                 sc = sc.clone()                  # a graph's static output: the later replay of the same shape would overwrite it
             scores.append(sc.contiguous())
+    if flip:
+        return dev_images, ops.multiscale_unary_mirror_batch(scores, [(H, W)] * n, eps=0.00001, want=want)
     return dev_images, ops.multiscale_unary_batch(scores, [(H, W)] * n, eps=0.00001, want=want)
 
 
 @torch.no_grad()
 def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda", forward=None, in_flight=3, batch=1, fused=True,
-                            same_size_batch=1, window=64, smooth=True):
+                            same_size_batch=1, window=64, smooth=True, flip=False):
     """predict_mask_ms_f over many images, as predict_masks_ms_many does it for test-ms.py: a generator of (H,W) int64 masks
     in order, the forwards of the next image running while the CRFs of the images before it are in flight (smooth=False: the
     arg-max, no CRF).  Same masks as predict_mask_ms_f image by image.
@@ -435,8 +559,15 @@ def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda"
     fewer than `window` images and masks are held (window = 64 is a judgement, not a measurement).  A batch-n forward need not
     round as a batch-1 forward does: the masks are predict_mask_ms_f's except where two labels all but tie, and there they
     depend on the grouping (G, window and the order of the images).  A relative size below one pixel: ValueError before any
-    launch of that group.  These groups run the fused kernels only (fused=False: ValueError)."""
+    launch of that group.  These groups run the fused kernels only (fused=False: ValueError).
+
+    flip=True: predict_mask_ms_f(flip=True) image by image; with same_size_batch = G (at most 8, and at most 4 scales:
+    ValueError before any stream or worker exists) a group of n images is one dsrg_preprocess_rect_mirror_batch launch,
+    len(scales) batch-2n forwards and one dsrg_multiscale_unary_mirror_batch launch."""
     G = int(same_size_batch)
+    scales = tuple(scales)
+    if flip:
+        _check_flip(len(scales), G)
     if G != 1:
         if not fused:
             raise ValueError("same_size_batch > 1 runs the fused kernels only")
@@ -452,7 +583,8 @@ def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda"
         def results():
             for idx in groups:
                 group = [held_images.pop(i) for i in idx]
-                dev_images, outs = _relative_group_results(net, group, scales, device, forward, "unary" if smooth else "argmax")
+                dev_images, outs = _relative_group_results(net, group, scales, device, forward, "unary" if smooth else "argmax",
+                                                           flip)
                 for i, im, out in zip(idx, dev_images, outs):
                     order.append(i)
                     yield (im, out) if smooth else out
@@ -470,12 +602,12 @@ def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda"
         return
     if not smooth:
         for image in images:
-            yield predict_mask_ms_f(net, image, scales, False, device, forward, fused)
+            yield predict_mask_ms_f(net, image, scales, False, device, forward, fused, flip)
         return
 
     def pairs():
         for image in images:
-            unary = _relative_unary(net, image, scales, device, forward, fused, True)
+            unary = _relative_unary(net, image, scales, device, forward, fused, True, flip)
             yield torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device), unary
 
     yield from _crf_in_flight(pairs(), device, in_flight, batch)

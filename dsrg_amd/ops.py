@@ -451,16 +451,22 @@ def _ptrs(tensors):
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
-def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",)):
+def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",), mirror=None):
     """test-ms.py:90-103 / test-ms-f.py:121-134 after the forwards, in one launch (dsrg_multiscale_unary): the K score maps
     zoomed to H x W, summed in scale order, softmax over labels clamped at eps.  scores: list of (1, C, h_k, w_k) float32 CUDA
     tensors (sizes may differ).  want: names among "unary" ((H, W, C) f32 log-probabilities, the layout CRF_device takes),
     "argmax" ((H, W) int32, the first maximum) and "sum" ((H, W, C) f32 summed scores, for parity checks).  A string returns
-    that one tensor, a sequence a tuple in its order.  Runs on torch's current stream."""
+    that one tensor, a sequence a tuple in its order.  mirror: one flag per map (dsrg_multiscale_unary_mirror): a map whose flag
+    is set is read with its columns reversed, the result being that of this call on torch.flip(map, [-1]) bit for bit (the
+    scores of a mirrored network input, mirrored back); None: today's kernel.  Runs on torch's current stream."""
     names, single = _want_names(want, _MS_OUTPUTS)
     scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
     if not scores:
         raise ValueError("no score maps")
+    if mirror is not None:
+        mirror = [int(bool(m)) for m in mirror]
+        if len(mirror) != len(scores):
+            raise ValueError("mirror must hold one flag per score map: %d flags for %d maps" % (len(mirror), len(scores)))
     C = scores[0].shape[1]
     for s in scores:
         if s.dim() != 4 or s.shape[0] != 1 or s.shape[1] != C:
@@ -470,8 +476,13 @@ def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",)):
     ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scores])
     hs = (ctypes.c_int32 * K)(*[s.shape[2] for s in scores])
     ws = (ctypes.c_int32 * K)(*[s.shape[3] for s in scores])
-    check(_lib.lib().dsrg_multiscale_unary(K, int(C), ptrs, hs, ws, int(H), int(W), float(eps), _ptr(out.get("unary")),
-                                           _ptr(out.get("argmax")), _ptr(out.get("sum")), _stream()))
+    if mirror is None:
+        check(_lib.lib().dsrg_multiscale_unary(K, int(C), ptrs, hs, ws, int(H), int(W), float(eps), _ptr(out.get("unary")),
+                                               _ptr(out.get("argmax")), _ptr(out.get("sum")), _stream()))
+    else:
+        check(_lib.lib().dsrg_multiscale_unary_mirror(K, int(C), ptrs, (ctypes.c_int32 * K)(*mirror), hs, ws, int(H), int(W),
+                                                      float(eps), _ptr(out.get("unary")), _ptr(out.get("argmax")),
+                                                      _ptr(out.get("sum")), _stream()))
     res = tuple(out[n] for n in names)
     return res[0] if single else res
 
@@ -482,6 +493,11 @@ def multiscale_unary_batch(scores, shapes, eps=1e-5, want=("unary",)):
     tensors, image g reads slice g; shapes: the G <= min(Gcap, 16) output sizes (H_g, W_g).  want: as multiscale_unary.  Returns a
     list of G entries, each what multiscale_unary(slices g, H_g, W_g, eps, want) returns, bit for bit.  Runs on torch's current
     stream."""
+    return _multiscale_unary_batch(scores, shapes, eps, want, False)
+
+
+def _multiscale_unary_batch(scores, shapes, eps, want, mirror):
+    """multiscale_unary_batch (one slice per image) / multiscale_unary_mirror_batch (mirror: two)"""
     names, single = _want_names(want, _MS_OUTPUTS)
     scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
     if not scores:
@@ -494,19 +510,30 @@ def multiscale_unary_batch(scores, shapes, eps=1e-5, want=("unary",)):
     for s in scores:
         if s.dim() != 4 or s.shape[0] != Gcap or s.shape[1] != C:
             raise ValueError("score maps must be (Gcap, C, h, w) with one Gcap and one C; got %s" % (tuple(s.shape),))
-    if not 1 <= G <= Gcap:
-        raise ValueError("%d output shapes for score maps of %d images" % (G, Gcap))
+    if not 1 <= G * (2 if mirror else 1) <= Gcap:
+        raise ValueError("%d output shapes for score maps of %d %s" % (G, Gcap, "slices, two per image" if mirror else "images"))
     out = _want_outputs(names, shapes, C, scores[0].device)
     ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scores])
     hs = (ctypes.c_int32 * K)(*[s.shape[2] for s in scores])
     ws = (ctypes.c_int32 * K)(*[s.shape[3] for s in scores])
     Hs = (ctypes.c_int32 * G)(*[H for H, _ in shapes])
     Ws = (ctypes.c_int32 * G)(*[W for _, W in shapes])
-    check(_lib.lib().dsrg_multiscale_unary_batch(G, K, int(C), ptrs, hs, ws, Hs, Ws, float(eps), _ptrs(out.get("unary")),
-                                                 _ptrs(out.get("argmax")), _ptrs(out.get("sum")), _stream()))
+    entry = _lib.lib().dsrg_multiscale_unary_mirror_batch if mirror else _lib.lib().dsrg_multiscale_unary_batch
+    check(entry(G, K, int(C), ptrs, hs, ws, Hs, Ws, float(eps), _ptrs(out.get("unary")), _ptrs(out.get("argmax")),
+                _ptrs(out.get("sum")), _stream()))
     if single:
         return out[names[0]]
     return [tuple(out[n][g] for n in names) for g in range(G)]
+
+
+def multiscale_unary_mirror_batch(scores, shapes, eps=1e-5, want=("unary",)):
+    """multiscale_unary_batch for mirrored test-time augmentation, in one launch (dsrg_multiscale_unary_mirror_batch).  scores: list
+    of K <= 4 (Gcap, C, h_k, w_k) float32 CUDA tensors, the outputs of batched forwards on preprocess_rect_mirror_batch's inputs:
+    image g reads slice 2g plain and slice 2g+1 mirrored back; shapes: the G <= min(Gcap // 2, 8) output sizes (H_g, W_g).  Per
+    pixel the sum runs scale 0 plain, scale 0 mirror, scale 1 plain, ...  Returns a list of G entries, each what
+    multiscale_unary([s_0[2g], s_0[2g+1], s_1[2g], ...], H_g, W_g, eps, want, mirror=[0, 1, 0, 1, ...]) returns, bit for bit.
+    Runs on torch's current stream."""
+    return _multiscale_unary_batch(scores, shapes, eps, want, True)
 
 
 def train_gt_unary_batch(scores, shapes, eps=1e-5, want=("unary",), select=None, ignore_below=None):
@@ -548,9 +575,10 @@ def train_gt_unary_batch(scores, shapes, eps=1e-5, want=("unary",), select=None,
     return [tuple(out[n][g] for n in names) for g in range(G)]
 
 
-def _preprocess_group(images, out_shapes, capacity, mean, out):
-    """the shared front end of preprocess_ms_batch / preprocess_rect_batch: checks, output tensors and the launch's host arrays
-    -> (G, capacity, K, image pointers, H, W, mean, output pointers, outputs)"""
+def _preprocess_group(images, out_shapes, capacity, mean, out, per_image=1):
+    """the shared front end of preprocess_ms_batch / preprocess_rect_batch / preprocess_rect_mirror_batch (per_image = 2 slots per
+    image): checks, output tensors and the launch's host arrays -> (G, capacity, K, image pointers, H, W, mean, output pointers,
+    outputs)"""
     images = list(images)
     G, K = len(images), len(out_shapes)
     if G < 1 or K < 1:
@@ -561,9 +589,9 @@ def _preprocess_group(images, out_shapes, capacity, mean, out):
         if not (torch.is_tensor(im) and im.is_cuda and im.dtype == torch.uint8 and im.is_contiguous() and im.dim() == 3
                 and im.shape[2] == 3):
             raise ValueError("images[%d] must be a contiguous (H, W, 3) uint8 CUDA tensor" % g)
-    cap = G if capacity is None else int(capacity)
-    if cap < G:
-        raise ValueError("capacity %d is below the %d images" % (cap, G))
+    cap = per_image * G if capacity is None else int(capacity)
+    if cap < per_image * G:
+        raise ValueError("capacity %d is below the %d slots of %d images" % (cap, per_image * G, G))
     if len(mean) != 3:
         raise ValueError("mean must hold 3 values")
     dev = images[0].device
@@ -608,6 +636,23 @@ def preprocess_rect_batch(images, out_shapes, capacity=None, mean=MEAN_PIXEL, ou
     G, cap, K, ims, Hs, Ws, mean3, optrs, out = _preprocess_group(images, out_shapes, capacity, mean, out)
     check(_lib.lib().dsrg_preprocess_rect_batch(G, cap, K, ims, Hs, Ws, (ctypes.c_int32 * K)(*[h for h, _ in out_shapes]),
                                                 (ctypes.c_int32 * K)(*[w for _, w in out_shapes]), mean3, optrs, _stream()))
+    return out
+
+
+def preprocess_rect_mirror_batch(images, out_shapes, capacity=None, mean=MEAN_PIXEL, out=None):
+    """preprocess_rect_batch for mirrored test-time augmentation, in one launch (dsrg_preprocess_rect_mirror_batch): image g fills
+    the slots 2g (what preprocess_rect_batch writes for it, bit for bit) and 2g+1 (the same tensor with its last axis reversed:
+    the mirrored network input).  images: G <= 8 contiguous (H_g, W_g, 3) RGB uint8 CUDA tensors; out_shapes: the K <= 8 targets
+    (h_k, w_k), (S, S) pairs for the fixed sizes of test-ms.py; capacity >= 2G (default 2G): the batch size of the outputs, slots
+    2G.. are written as zeros; mean, out as there.  Returns a list of K (capacity, 3, h_k, w_k) float32 tensors.  Runs on torch's
+    current stream."""
+    try:
+        out_shapes = [(int(h), int(w)) for h, w in out_shapes]
+    except TypeError:
+        raise ValueError("out_shapes must hold (h, w) pairs")
+    G, cap, K, ims, Hs, Ws, mean3, optrs, out = _preprocess_group(images, out_shapes, capacity, mean, out, per_image=2)
+    check(_lib.lib().dsrg_preprocess_rect_mirror_batch(G, cap, K, ims, Hs, Ws, (ctypes.c_int32 * K)(*[h for h, _ in out_shapes]),
+                                                       (ctypes.c_int32 * K)(*[w for _, w in out_shapes]), mean3, optrs, _stream()))
     return out
 
 

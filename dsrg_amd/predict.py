@@ -15,6 +15,8 @@ CRFs of earlier images are in flight (inference.predict_masks_ms_many / predict_
 takes the images N at a time through batch-N forwards (the absolute sizes are the same for every image); so does --mode gt
 (inference.predict_train_gt_many).  --mode ms-f --same-size-batch N collects same-sized images (up to N, out of a window of
 --window images) into batch-n forwards (inference.plan_size_groups); the masks are still written per image, in input order.
+--flip (ms, ms-f; no counterpart in the reference): mirrored test-time augmentation, every scale runs on the image and on its
+mirror image and all the score maps are summed before the softmax (at most 4 scales, batches of at most 8 images).
 """
 import argparse
 import os
@@ -48,6 +50,9 @@ def parse_args(argv=None):
                    help="ms-f: same-sized images per batched forward (1..16; default 1: one image per forward)")
     p.add_argument("--window", type=int, default=64,
                    help="ms-f with --same-size-batch: an image waits for at most N - 1 later images for its group (default 64)")
+    p.add_argument("--flip", action="store_true",
+                   help="ms, ms-f: mirrored test-time augmentation: every scale also runs on the mirror image, whose scores are "
+                        "mirrored back and summed with the others (at most 4 scales; --forward-batch / --same-size-batch at most 8)")
     a = p.parse_args(argv)
     if a.mode == "gt":
         if not a.cues:
@@ -66,6 +71,13 @@ def parse_args(argv=None):
         p.error("--same-size-batch must be 1..16")
     if a.window < 1:
         p.error("--window must be at least 1")
+    if a.flip:
+        if a.mode == "gt":
+            p.error("--flip is for --mode ms and --mode ms-f only: the softmax-before-zoom tail of --mode gt has no mirror form")
+        if a.forward_batch > 8 or a.same_size_batch > 8:
+            p.error("--flip takes --forward-batch / --same-size-batch of at most 8: every image fills two slots of a batch")
+        if a.scales is not None and len(a.scales.split(",")) > 4:
+            p.error("--flip takes at most 4 scales: every scale runs twice")
     return a
 
 
@@ -148,21 +160,22 @@ def main(argv=None):
             from .crf import MAX_BATCH
             masks = I.predict_masks_ms_f_many(net, images, scales=scales, device=dev, forward=fwd, in_flight=a.in_flight,
                                               batch=min(a.same_size_batch, MAX_BATCH), same_size_batch=a.same_size_batch,
-                                              window=a.window, smooth=a.smooth)
+                                              window=a.window, smooth=a.smooth, flip=a.flip)
         elif a.smooth:
             if a.mode == "ms":
                 masks = I.predict_masks_ms_many(net, images, sizes=scales, device=dev, forward=fwd, in_flight=a.in_flight,
-                                                forward_batch=a.forward_batch)
+                                                forward_batch=a.forward_batch, flip=a.flip)
             else:
-                masks = I.predict_masks_ms_f_many(net, images, scales=scales, device=dev, forward=fwd, in_flight=a.in_flight)
+                masks = I.predict_masks_ms_f_many(net, images, scales=scales, device=dev, forward=fwd, in_flight=a.in_flight,
+                                                  flip=a.flip)
         elif a.mode == "ms" and a.forward_batch > 1:
             masks = (m for group in I._forward_groups(images, a.forward_batch)
                      for m in I.predict_masks_ms_batched(net, [im for im in group if im is not None], smooth=False, sizes=scales,
-                                                         device=dev, forward=fwd, capacity=a.forward_batch))
+                                                         device=dev, forward=fwd, capacity=a.forward_batch, flip=a.flip))
         elif a.mode == "ms":
-            masks = (I.predict_mask_ms(net, im, smooth=False, sizes=scales, device=dev, forward=fwd) for im in images)
+            masks = (I.predict_mask_ms(net, im, smooth=False, sizes=scales, device=dev, forward=fwd, flip=a.flip) for im in images)
         else:
-            masks = (I.predict_mask_ms_f(net, im, scales=scales, smooth=False, device=dev, forward=fwd) for im in images)
+            masks = (I.predict_mask_ms_f(net, im, scales=scales, smooth=False, device=dev, forward=fwd, flip=a.flip) for im in images)
         n = 0
         for img_id, mask in zip(ids, masks):
             write_mask(os.path.join(a.output, img_id + ".png"), mask)

@@ -302,6 +302,26 @@ int dsrg_multiscale_unary(int K, int C, const float *const *scores_dev, const in
 int dsrg_multiscale_unary_batch(int G, int K, int C, const float *const *scores_dev, const int32_t *h_host, const int32_t *w_host,
                                 const int32_t *H_host, const int32_t *W_host, float eps, float *const *unary_dev,
                                 int32_t *const *argmax_dev, float *const *sum_dev, void *stream);
+/* dsrg_multiscale_unary with mirrored maps (horizontal-flip test-time augmentation: the scores of a mirrored network input are
+ * mirrored back and summed with the plain ones): mirror_host is a HOST array of K flags, and a map whose flag is non-zero is read
+ * with its columns reversed.  The result is defined as dsrg_multiscale_unary's on flip(map, last axis): the sampling
+ * coordinates, x0, x1 and the blend weights come from the output pixel as there, only the four loads address columns w-1-x0
+ * and w-1-x1; the f32 sum runs in list order.  All flags zero gives dsrg_multiscale_unary's outputs bit for bit.  Limits and
+ * checks as there (K <= 8 maps: up to four scales with their mirrors), mirror_host must not be NULL.  Stream-ordered, no host
+ * synchronisation, no handle; bit-reproducible (no atomics). */
+int dsrg_multiscale_unary_mirror(int K, int C, const float *const *scores_dev, const int32_t *mirror_host, const int32_t *h_host,
+                                 const int32_t *w_host, int H, int W, float eps, float *unary_dev, int32_t *argmax_dev,
+                                 float *sum_dev, void *stream);
+/* dsrg_multiscale_unary_mirror for G images at K scales in one launch: scores_dev is a HOST array of K device pointers to batched
+ * maps (Gcap, C, h_k, w_k) f32 NCHW with Gcap >= 2 G (the outputs of batch-2G forwards on dsrg_preprocess_rect_mirror_batch's
+ * inputs); image g reads slice 2g plain and slice 2g+1 mirrored back.  Per pixel the f32 sum runs scale-major: scale 0 plain,
+ * scale 0 mirror, scale 1 plain, ...  Image g's outputs equal dsrg_multiscale_unary_mirror's on those 2K slices in that order
+ * (flags 0, 1, 0, 1, ...) and (H_g, W_g) bit for bit.  H_host / W_host and the output arrays as dsrg_multiscale_unary_batch
+ * takes them.  1 <= G <= 8, 1 <= K <= 4; otherwise the limits of dsrg_multiscale_unary, per image; every argument is checked
+ * before the first device call.  Stream-ordered, no host synchronisation, no handle; bit-reproducible (no atomics). */
+int dsrg_multiscale_unary_mirror_batch(int G, int K, int C, const float *const *scores_dev, const int32_t *h_host,
+                                       const int32_t *w_host, const int32_t *H_host, const int32_t *W_host, float eps,
+                                       float *const *unary_dev, int32_t *const *argmax_dev, float *const *sum_dev, void *stream);
 /* The full-resolution tail of the weakly supervised pseudo-label pass (training/tools/generate_train_gt.py:85-104) for G images
  * whose score maps are the slices of one batched forward: scores_dev (Gcap >= G, C, h, w) f32 NCHW, image g reads slice g.  First
  * the softmax over labels per MAP pixel in f32 (s - max, expf, sum in label order, divide) into workspace_dev (G * C * h * w
@@ -342,6 +362,15 @@ int dsrg_preprocess_ms_batch(int G, int capacity, int K, const unsigned char *co
 int dsrg_preprocess_rect_batch(int G, int capacity, int K, const unsigned char *const *images_dev, const int32_t *H_host,
                                const int32_t *W_host, const int32_t *out_h_host, const int32_t *out_w_host, const float *mean_host,
                                float *const *out_dev, void *stream);
+/* dsrg_preprocess_rect_batch for mirrored test-time augmentation: every image fills two slots.  Slot 2g of output k is what
+ * dsrg_preprocess_rect_batch writes for image g, bit for bit; slot 2g+1 is the same tensor with its last axis reversed (the
+ * mirrored network input, not a second zoom of a mirrored image: each value is computed once and stored twice); slots
+ * 2G..capacity-1 are written as zeros.  With h_k = w_k = S_k this serves the fixed sizes of test-ms.py as well.  1 <= G <= 8,
+ * 2G <= capacity; the other arguments, limits and checks as there.  Nothing is allocated.  Stream-ordered, no host
+ * synchronisation, no handle; bit-reproducible (no atomics). */
+int dsrg_preprocess_rect_mirror_batch(int G, int capacity, int K, const unsigned char *const *images_dev, const int32_t *H_host,
+                                      const int32_t *W_host, const int32_t *out_h_host, const int32_t *out_w_host,
+                                      const float *mean_host, float *const *out_dev, void *stream);
 /* The stage-1 training batch in one launch: Caffe's ImageData layer (training/experiment/seed_mc/train-s.prototxt:3-22: read,
  * cv::resize to S x S, mean 104/117/123) followed by AnnotationLayer (pylayers/pylayers/pylayers.py:346-387), for B images.
  * stage_dev: ONE device buffer of stage_bytes raw bytes (uploaded by the caller with one copy per batch); the HOST arrays
