@@ -108,6 +108,7 @@ SIGNATURES = {
                                       _vp, _vp, _vp]),
     "dsrg_train_f_input_scaled_batch": (_i, [_i, _vp, _sz] + [ctypes.POINTER(ctypes.c_int32)] * 9 + [_i, _i, ctypes.POINTER(_f), _f, _f,
                                              _vp, _vp, _vp]),
+    "dsrg_eval_confusion_batch": (_i, [_i, _i, _vp, _i, _i, _vp, _i, _i, _f, _i, _vp, _vp]),
     "dsrg_resnet_stem_packed_bytes": (_sz, []),
     "dsrg_pack_resnet_stem_f32": (_i, [_vp, _vp, _vp, _vp]),
     "dsrg_resnet_stem_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -571,6 +571,11 @@ extern "C" int dsrg_train_f_input_scaled_batch(int B, const unsigned char *stage
     return launch_train_f_input_scaled_batch(B, stage, stage_bytes, image_off, label_off, H, W, Hs, Ws, top, left, mirror, ch, cw, mean,
                                              scale, ignore_label, data, label, static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_eval_confusion_batch(int B, int C, const float *scores, int h, int w, const float *labels, int Hz, int Wz,
+                                         float ignore_label, int rule_lt, unsigned long long *hist, void *stream) {
+    // every argument is checked before the first device call
+    return launch_eval_confusion_batch(B, C, scores, h, w, labels, Hz, Wz, ignore_label, rule_lt, hist, static_cast<hipStream_t>(stream));
+}
 extern "C" size_t dsrg_resnet_stem_packed_bytes(void) { return resnet_stem_packed_bytes(); }
 extern "C" int dsrg_pack_resnet_stem_f32(const float *w, const float *scale, void *packed, void *stream) {
     if (!w || !scale || !packed) return set_error(DSRG_ERR_INVALID, "resnet stem pack: NULL argument");

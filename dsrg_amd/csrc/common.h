@@ -289,6 +289,8 @@ int launch_train_f_input_scaled_batch(int B, const unsigned char *stage, size_t 
                                       const int32_t *label_off, const int32_t *H, const int32_t *W, const int32_t *Hs, const int32_t *Ws,
                                       const int32_t *top, const int32_t *left, const int32_t *mirror, int ch, int cw, const float *mean,
                                       float scale, float ignore_label, float *data, float *label, hipStream_t stream);
+int launch_eval_confusion_batch(int B, int C, const float *scores, int h, int w, const float *labels, int Hz, int Wz,
+                                float ignore_label, int rule_lt, unsigned long long *hist, hipStream_t stream);
 size_t resnet_stem_packed_bytes();
 int launch_pack_resnet_stem(const float *w, const float *scale, void *packed, hipStream_t stream);
 int launch_resnet_stem(const float *x, const void *packed, const float *shift, void *y, int B, int H, int W, hipStream_t stream);

@@ -702,6 +702,18 @@ class ConfusionMatrix(object):
         assert h[-1] == 0, "labels or predictions outside [0, nclass)"
         self.M += h[:-1].reshape(self.nclass, self.nclass).astype(np.float64)
 
+    def add_counts(self, hist):
+        """add nclass*nclass + 1 counters as ops.confusion_matrix / ops.eval_confusion_batch return them (a tensor or an array):
+        the first nclass*nclass go to M; a non-zero last counter — labels outside [0, nclass) that the rule kept — raises, as
+        `add` would (the reference asserts there are none)"""
+        h = hist.detach().cpu().numpy() if hasattr(hist, "detach") else np.asarray(hist)
+        h = h.reshape(-1)
+        if h.size != self.nclass ** 2 + 1:
+            raise ValueError("expected %d counters, got %d" % (self.nclass ** 2 + 1, h.size))
+        if h[-1] != 0:
+            raise ValueError("%d kept pixels carry a label outside [0, %d)" % (int(h[-1]), self.nclass))
+        self.M += h[:-1].reshape(self.nclass, self.nclass).astype(np.float64)
+
     def generateM(self, item):
         """evaluate.py:61-68: the matrix of one (gt, pred) pair, keeping ground truth < nclass"""
         gt, pred = np.asarray(item[0]).ravel(), np.asarray(item[1]).ravel()

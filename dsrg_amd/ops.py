@@ -421,6 +421,33 @@ def confusion_matrix(gt, pred, nclass, rule_lt=False, hist=None):
     return hist
 
 
+def eval_confusion_batch(scores, labels, nclass, ignore_label=255, rule_lt=False, hist=None):
+    """Validation scoring of a batch in one launch (dsrg_eval_confusion_batch): scores (>= B, nclass, h, w) and labels (B, 1, Hz, Wz),
+    contiguous float32 CUDA tensors — the network's score maps and the label maps train_f_input_batch returns (ignore_label off the
+    image).  The first B slices of scores are zoomed to Hz x Wz with multiscale_unary's arithmetic, their first maximum over the
+    labels is the prediction, and the pixels whose label passes the rule (rule_lt False: label != ignore_label; True: label <
+    nclass) are counted.  Returns the (nclass*nclass + 1) int64 counters of confusion_matrix (added to `hist` when given); the last
+    counts kept labels that are not one of 0..nclass-1.  Nothing else is written.  Runs on torch's current stream."""
+    for t, name in ((scores, "scores"), (labels, "labels")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 CUDA tensor" % name)
+    nclass = int(nclass)
+    if scores.dim() != 4 or scores.shape[1] != nclass:
+        raise ValueError("scores must be (>= B, %d, h, w), got %s" % (nclass, tuple(scores.shape)))
+    if labels.dim() != 4 or labels.shape[1] != 1:
+        raise ValueError("labels must be (B, 1, Hz, Wz), got %s" % (tuple(labels.shape),))
+    B, _, Hz, Wz = labels.shape
+    if B > scores.shape[0]:
+        raise ValueError("%d label maps for %d score maps" % (B, scores.shape[0]))
+    if hist is None:
+        hist = torch.zeros(nclass * nclass + 1, dtype=torch.int64, device=scores.device)
+    elif not (hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.numel() == nclass * nclass + 1):
+        raise ValueError("hist must be a contiguous int64 CUDA tensor of %d counters" % (nclass * nclass + 1))
+    check(_lib.lib().dsrg_eval_confusion_batch(int(B), nclass, _ptr(scores), int(scores.shape[2]), int(scores.shape[3]), _ptr(labels),
+                                               int(Hz), int(Wz), float(ignore_label), int(bool(rule_lt)), _ptr(hist), _stream()))
+    return hist
+
+
 _MS_OUTPUTS = ("unary", "argmax", "sum")
 _TG_OUTPUTS = ("unary", "probs", "labels")
 _INT_OUTPUTS = ("argmax", "labels")                  # (H, W) int32 maps; every other output is (H, W, C) float32

@@ -12,6 +12,13 @@ before runs.  Every --display steps the mean of the last --display losses is pri
 (<prefix>_iter_N.caffemodel + .solverstate.pt) are written every --snapshot-every steps and at the end; --snapshot resumes at the
 snapshot's iteration count.  Under a launcher (torch.distributed.run: RANK / WORLD_SIZE set) every rank takes its shard of each
 epoch and --batch / WORLD_SIZE images per step.
+
+--val-list ('image_path label_path' lines, --val-root prefixed to both; ground-truth label PNGs) turns on validation: every
+--val-every steps (default: whenever a snapshot is written) and at the last iteration the network is scored over the list by
+dsrg_amd.validate.Validator — single scale, every image padded to --val-crop, no CRF — and rank 0 prints the mean IoU and the pixel
+accuracy (and rewrites --val-result in evaluate's three-line format).  Every rank scores its share of the list; the pass is
+collective and leaves the run's weights, momentum and random streams as it found them: a run with validation ends with the
+weights of the same run without.
 """
 import argparse
 import os
@@ -23,6 +30,12 @@ STAGE_DEFAULTS = {
     "f": dict(iters=20000, snapshot_every=10000, display=20, prefix="models/model-f", batch=10),
 }
 F_DEFAULTS = dict(crop=321, mean=(104.0, 117.0, 123.0))
+VAL_CROP = 513                                   # no VOC image is larger
+
+
+def val_batch(a, world):
+    """validation images per forward on one rank: --val-batch, else the per-rank training batch"""
+    return a.val_batch if a.val_batch is not None else a.batch // world
 
 
 def parse_args(argv=None):
@@ -47,10 +60,26 @@ def parse_args(argv=None):
     p.add_argument("--scale-factors", default=None,
                    help="f: rescale every image by one of these factors, drawn per image, before the crop, e.g. 0.5,0.75,1,1.25,1.5 "
                         "(bilinear for the image, nearest neighbour for the label, done on the GPU; default: none)")
+    p.add_argument("--val-list", default=None, help="validate on these 'image_path label_path' lines (ground-truth label PNGs)")
+    p.add_argument("--val-root", default=None, help="prefix of both paths of a --val-list line (default: --root)")
+    p.add_argument("--val-every", type=int, default=None, help="validate every N steps (default: whenever a snapshot is written)")
+    p.add_argument("--val-crop", type=int, default=None, help="every validation image is padded to this size (513)")
+    p.add_argument("--val-batch", type=int, default=None, help="validation images per forward and rank (default: the per-rank batch)")
+    p.add_argument("--val-result", default=None, help="file rewritten at each validation: meanIOU / per-class IoU / matrix")
     a = p.parse_args(argv)
     for key, value in STAGE_DEFAULTS[a.stage].items():
         if getattr(a, key) is None:
             setattr(a, key, value)
+    if a.val_list is None:
+        given = [o for o in ("val_root", "val_every", "val_crop", "val_batch", "val_result") if getattr(a, o) is not None]
+        if given:
+            p.error("%s need%s --val-list" % (", ".join("--" + o.replace("_", "-") for o in given), "s" if len(given) == 1 else ""))
+    else:
+        a.val_root = a.root if a.val_root is None else a.val_root
+        a.val_every = a.snapshot_every if a.val_every is None else a.val_every
+        a.val_crop = VAL_CROP if a.val_crop is None else a.val_crop
+        if min(a.val_every, a.val_crop) < 1 or (a.val_batch is not None and not 1 <= a.val_batch <= 32):
+            p.error("--val-every and --val-crop must be >= 1, --val-batch 1..32")
     if a.stage == "s":
         if not a.cues:
             p.error("--stage s needs --cues (the localisation-cue pickle)")
@@ -125,6 +154,13 @@ def main(argv=None):
     if trainer.opt.iter:
         say("resumed from %s at iteration %d" % (a.snapshot, trainer.opt.iter), flush=True)
 
+    validator = None
+    if a.val_list is not None:
+        from .validate import Validator, write_result
+        validator = Validator(trainer.net, a.val_list, a.val_root, crop=a.val_crop, batch=val_batch(a, world),
+                              mean=a.mean if a.stage == "f" else TrainSInput.mean, device=device, rank=rank, world_size=world,
+                              amp_dtype=trainer.amp_dtype, workers=a.workers)
+
     window, saved_at = [], None
     with loader:
         while trainer.opt.iter < a.iters:
@@ -139,6 +175,12 @@ def main(argv=None):
                 paths = trainer.save(a.prefix)                           # (collective: every rank calls it)
                 saved_at = it
                 say("snapshot %s %s" % paths, flush=True)
+            if validator is not None and (it % a.val_every == 0 or it == a.iters):
+                res = validator.run()                                    # (collective: every rank scores its share of the list)
+                say("Iteration %d, validation: meanIOU = %.6f, pixel accuracy = %.6f (%d images)"
+                    % (it, res["miou"], res["pixel_accuracy"], res["images"]), flush=True)
+                if a.val_result and rank == 0:
+                    write_result(a.val_result, res)
     if saved_at != trainer.opt.iter:                                     # (a run that had nothing left to do still leaves its model)
         say("snapshot %s %s" % trainer.save(a.prefix), flush=True)
     words = params_checksum(list(trainer.net.parameters()) + [b for g in trainer.opt.groups for b in g["bufs"]])

@@ -424,6 +424,26 @@ int dsrg_train_f_input_scaled_batch(int B, const unsigned char *stage_dev, size_
                                     const int32_t *Hs_host, const int32_t *Ws_host, const int32_t *top_host, const int32_t *left_host,
                                     const int32_t *mirror_host, int ch, int cw, const float *mean_host, float scale,
                                     float ignore_label, float *data_dev, float *label_dev, void *stream);
+/* Validation scoring of a batch in one launch: the confusion counters of the network's score maps against full-resolution label
+ * maps, with nothing else written (no zoomed scores, no argmax map).
+ *   scores_dev (>= B, C, h, w) f32 contiguous NCHW: the first B slices are scored (the scores of B inputs of extent Hz x Wz)
+ *   labels_dev (B, 1, Hz, Wz) f32: what dsrg_train_f_input_batch writes as label_dev (the label byte as a float on the image,
+ *              ignore_label off it)
+ *   hist_dev   C*C + 1 unsigned 64-bit counters that are ADDED to, dsrg_confusion_matrix's layout: row = ground truth, column =
+ *              prediction, the last one the overflow counter
+ * A pixel (b, y, x) is kept iff label != ignore_label (rule_lt = 0, ConfusionMatrix.add) or label < (float)C (rule_lt = 1,
+ * generateM).  Its prediction is the value dsrg_multiscale_unary(K = 1, C, slice b, h, w, Hz, Wz) writes to
+ * argmax_dev[y * Wz + x], bit for bit: scale (in-1)/(out-1) in double (0 when out == 1), i0 = (int)src, i1 = i0 + (i0 < in-1),
+ * the two-tap blend l0h*(l0w*v00 + l1w*v01) + l1h*(l0w*v10 + l1w*v11) in double rounded once to f32, the first maximum over the
+ * labels.  A kept label that is one of 0..C-1 exactly adds 1 to hist[label * C + pred]; any other kept label (negative, >= C,
+ * non-integral) adds 1 to hist[C*C].  The prediction is always in [0, C): scores are assumed finite, non-finite ones may give
+ * any label in range and never index outside the counters.
+ * 1 <= B <= 32, 1 <= C <= 96 (above: DSRG_ERR_UNSUPPORTED), h, w, Hz, Wz >= 1, B*C*h*w < 2^31, B*Hz*Wz < 2^31; every argument is
+ * checked before the first device call (NULL pointers and bad shapes: DSRG_ERR_INVALID).  Nothing is allocated.  Stream-ordered,
+ * no host synchronisation, no handle.  The counters are integers added with atomics: the result does not depend on the order in
+ * which workgroups finish, and repeated calls give identical counters. */
+int dsrg_eval_confusion_batch(int B, int C, const float *scores_dev, int h, int w, const float *labels_dev, int Hz, int Wz,
+                              float ignore_label, int rule_lt, unsigned long long *hist_dev, void *stream);
 /* The stem of the DeepLab-v2 ResNet-101 at test time in one launch (backbone plumbing; the reference's networks are Caffe
  * prototxts): conv 7x7 / stride 2 / zero pad 3, 3 -> 64, with a frozen BatchNorm folded in -> ReLU -> max pool 3x3 / stride 2 /
  * pad 1, ceil mode.  The convolution map never reaches memory.
