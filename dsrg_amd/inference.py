@@ -74,14 +74,29 @@ def _eval_mode(net):
         net.train(was_training)
 
 
-def preprocess(image, size, device="cuda"):
-    """image: (H,W,3) RGB uint8/float -> (1,3,size,size) float32 BGR, mean-subtracted (test-ms.py:68-81)"""
+def _preprocess_to(image, h, w, device):
+    """image: (H,W,3) RGB uint8/float zoomed to h x w (order 1, float64 blend: _zoom) -> (1,3,h,w) float32 BGR, mean-subtracted"""
     # (uploaded in the image's own dtype and converted on the device: a float32 conversion on the host is a multi-threaded torch op,
     # and the idle spin of its ~100 worker threads after every call eats a container's CPU quota — 7 ms per image became 95)
     x = torch.from_numpy(np.ascontiguousarray(np.asarray(image))).to(device).to(torch.float32).permute(2, 0, 1)[None]
-    x = _zoom(x, size, size)
+    x = _zoom(x, h, w)
     x = x[:, [2, 1, 0]]
     return x - torch.tensor(MEAN_PIXEL, dtype=torch.float32, device=device).view(1, 3, 1, 1)
+
+
+def preprocess(image, size, device="cuda"):
+    """image: (H,W,3) RGB uint8/float -> (1,3,size,size) float32 BGR, mean-subtracted (test-ms.py:68-81)"""
+    return _preprocess_to(image, size, size, device)
+
+
+def _device_image(image, device):
+    """image (H,W,3) -> the uint8 tensor on the device that the CRF reads"""
+    return torch.as_tensor(np.asarray(image).astype('ubyte'), device=device)
+
+
+def _host_mask(labels):
+    """a label map on the device -> (H,W) int64 array, the only thing that crosses PCIe"""
+    return labels.cpu().numpy().astype(np.int64)
 
 
 class GraphedForward(object):
@@ -168,22 +183,34 @@ def _check_flip(nscales, group=1):
         raise ValueError("flip=True takes groups of at most %d images (two slots each), got %d" % (MAX_FLIP_BATCH, int(group)))
 
 
+def _forwards(net, forward, xs):
+    """the forwards of every test-time function: net (in eval mode for the call), or `forward` in its place (a GraphedForward of
+    the same net), on each network input of xs -> list of contiguous float32 score maps.  A graph's output is its static buffer,
+    which the replay for a later input of the same shape would overwrite: such a map is cloned; every other map is what the
+    forward returned"""
+    xs = list(xs)
+    shapes = [tuple(x.shape) for x in xs]
+    maps = []
+    with _eval_mode(net):
+        for k, x in enumerate(xs):
+            sc = (forward or net)(x).float()
+            if forward is not None and shapes[k] in shapes[k + 1:]:
+                sc = sc.clone()
+            maps.append(sc.contiguous())
+    return maps
+
+
+def _with_mirrors(slots):
+    """per-image network inputs -> each followed by its mirror image (the slot pairs of the flip forwards)"""
+    return [t for x in slots for t in (x, x.flip(-1))]
+
+
 def _flip_pair_scores(net, inputs, forward):
     """flip=True, one image: every (1,3,h,w) network input runs with its mirror image as one batch-2 forward,
     cat([x, x.flip(-1)]) (a GraphedForward holds batch-2 graphs) -> the 2K (1,C,h',w') float32 score maps in the order of the
     sum: scale 0 plain, scale 0 mirror, scale 1 plain, ...  The mirror maps are NOT mirrored back here: ops.multiscale_unary
     (mirror=[0, 1, 0, 1, ...]) reads them reversed, the torch composition flips them"""
-    inputs = list(inputs)
-    shapes = [tuple(x.shape) for x in inputs]
-    maps = []
-    with _eval_mode(net):
-        for k, x in enumerate(inputs):
-            sc = (forward or net)(torch.cat([x, x.flip(-1)])).float()
-            if forward is not None and shapes[k] in shapes[k + 1:]:
-                sc = sc.clone()                  # a graph's static output: the later replay of the same shape would overwrite it
-            sc = sc.contiguous()
-            maps += [sc[0:1], sc[1:2]]
-    return maps
+    return [half for sc in _forwards(net, forward, [torch.cat(_with_mirrors([x])) for x in inputs]) for half in (sc[0:1], sc[1:2])]
 
 
 def _ms_flip_result(net, image, sizes, device, forward, want):
@@ -193,27 +220,30 @@ def _ms_flip_result(net, image, sizes, device, forward, want):
     return ops.multiscale_unary(maps, image.shape[0], image.shape[1], eps=0.00001, want=want, mirror=[0, 1] * len(sizes))
 
 
+def _ms_unary(net, image, sizes, device, forward, flip):
+    """test-ms.py:89-103 for one image -> (H,W,C) float32 log-probabilities: the torch composition, or with flip the fused tail"""
+    if flip:
+        return _ms_flip_result(net, image, sizes, device, forward, "unary")
+    probs = _probs_from_scores(multiscale_scores(net, image, sizes, device, forward))
+    return torch.log(probs).permute(1, 2, 0).contiguous()
+
+
 @torch.no_grad()
 def predict_mask_ms(net, image, smooth=True, sizes=(241, 321, 401), device="cuda", forward=None, flip=False):
     """test-ms.py:84-111 -> (H,W) int64 label mask.  forward: see multiscale_scores.  flip=True (at most 4 sizes): every size
     runs on the image and its mirror image as one batch-2 forward, and the tail is the fused kernel (one
     dsrg_multiscale_unary_mirror launch on the 2K maps: zoom, the mirrors read reversed, sum, softmax, clamp, log) instead of the
     torch composition this function runs without flip"""
+    sizes = tuple(sizes)
     if flip:
-        sizes = tuple(sizes)
         _check_flip(len(sizes))
-        out = _ms_flip_result(net, image, sizes, device, forward, "unary" if smooth else "argmax")
-        if smooth:
-            img = torch.as_tensor(np.asarray(image).astype('ubyte'), device=out.device)
-            return CRF_device(img, out, scale_factor=1.0, want="map").cpu().numpy().astype(np.int64)
-        return out.cpu().numpy().astype(np.int64)
-    probs = _probs_from_scores(multiscale_scores(net, image, sizes, device, forward))
     if smooth:
         # scores, log-probabilities, CRF and arg-max all stay on the GPU; only the (H,W) mask crosses PCIe
-        unary = torch.log(probs).permute(1, 2, 0).contiguous()
-        img = torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device)
-        return CRF_device(img, unary, scale_factor=1.0, want="map").cpu().numpy().astype(np.int64)
-    return probs.argmax(0).cpu().numpy()
+        unary = _ms_unary(net, image, sizes, device, forward, flip)
+        return _host_mask(CRF_device(_device_image(image, unary.device), unary, scale_factor=1.0, want="map"))
+    if flip:
+        return _host_mask(_ms_flip_result(net, image, sizes, device, forward, "argmax"))
+    return _probs_from_scores(multiscale_scores(net, image, sizes, device, forward)).argmax(0).cpu().numpy()
 
 
 MAX_FORWARD_BATCH = 16      # images per group of the batched path (the limit of the two batched kernels)
@@ -235,71 +265,64 @@ def _forward_groups(items, G):
         yield group + [None] * (G - len(group))
 
 
-def _with_mirrors(slots):
-    """per-image network inputs -> each followed by its mirror image (the slot pairs of the batched flip forwards)"""
-    return [t for x in slots for t in (x, x.flip(-1))]
-
-
-def _batched_inputs(group, sizes, device, forward, flip=False):
-    """one padded group of _forward_groups -> (the images on the device, list of (G, 3, S, S) network inputs, one per size).
-    uint8 images go through one dsrg_preprocess_ms_batch launch, written straight into the static inputs of `forward`'s graphs
-    where those exist; a group with other dtypes takes `preprocess` for those slots.  flip: the inputs are (2 G, 3, S, S), image g
-    in slot 2g and its mirror image in slot 2g+1 (one dsrg_preprocess_rect_mirror_batch launch), the padding slots behind them"""
+# ---- one group of images: inputs, K batched forwards, one tail launch (the batched forms of ms, ms-f and gt) -----------------------
+def _preprocess_square_batch(images, shapes, **kw):
+    """ops.preprocess_ms_batch on (S, S) targets: the launch of the fixed sizes (preprocess_rect_batch's bits under its own name)"""
     from . import ops
-    G = len(group)
-    B = 2 * G if flip else G                                # the batch of the forwards
-    images = [im for im in group if im is not None]
-    arrays = [np.ascontiguousarray(np.asarray(im)) for im in images]
+    return ops.preprocess_ms_batch(images, [h for h, _ in shapes], **kw)
+
+
+def _group_inputs(images, shapes, device, forward, flip, square=False):
+    """one group -> (its images on the device, the K network inputs (B, 3, h_k, w_k) for the targets `shapes`).  images may end in
+    None, the padding slots of _forward_groups, which run on zeros; B = len(images), with flip twice that: image g in slot 2g, its
+    mirror image in slot 2g+1, the padding behind them.  uint8 images take ONE launch — dsrg_preprocess_rect_batch, with
+    square=True (every target (S, S): the fixed sizes of test-ms.py) dsrg_preprocess_ms_batch, with flip
+    dsrg_preprocess_rect_mirror_batch — written straight into the static inputs of `forward`'s graphs where those exist; in a
+    group with other dtypes every slot is made on its own, those images by _preprocess_to"""
+    from . import ops
+    B = (2 if flip else 1) * len(images)                    # the batch of the forwards
+    arrays = [np.ascontiguousarray(np.asarray(im)) for im in images if im is not None]
+    plain = _preprocess_square_batch if square else ops.preprocess_rect_batch
     if all(a.dtype == np.uint8 for a in arrays):
         dev_images = [torch.from_numpy(a).to(device) for a in arrays]
         out = None
         if isinstance(forward, GraphedForward):
-            out = [forward.static_input((B, 3, S, S)) for S in sizes]
-            if len(set(sizes)) != len(sizes) or any(o is None for o in out):
-                out = None                                  # (first group: the graphs are captured from fresh tensors)
-        if flip:
-            return dev_images, ops.preprocess_rect_mirror_batch(dev_images, [(S, S) for S in sizes], capacity=B, mean=MEAN_PIXEL,
-                                                                out=out)
-        return dev_images, ops.preprocess_ms_batch(dev_images, sizes, capacity=G, mean=MEAN_PIXEL, out=out)
-    dev_images = [torch.as_tensor(a.astype('ubyte'), device=device) for a in arrays]
+            out = [forward.static_input((B, 3, h, w)) for h, w in shapes]
+            if len(set(shapes)) != len(shapes) or any(o is None for o in out):
+                out = None                                  # (not captured yet: GraphedForward copies a fresh tensor in)
+        return dev_images, (ops.preprocess_rect_mirror_batch if flip else plain)(dev_images, shapes, capacity=B, mean=MEAN_PIXEL,
+                                                                                  out=out)
+    dev_images = [_device_image(a, device) for a in arrays]
     xs = []
-    for S in sizes:
-        slots = [ops.preprocess_ms_batch([d], [S], mean=MEAN_PIXEL)[0] if a.dtype == np.uint8 else preprocess(a, S, device)
+    for h, w in shapes:
+        slots = [plain([d], [(h, w)], mean=MEAN_PIXEL)[0] if a.dtype == np.uint8 else _preprocess_to(a, h, w, device)
                  for a, d in zip(arrays, dev_images)]
         if flip:
             slots = _with_mirrors(slots)
         if len(slots) < B:
-            slots.append(torch.zeros((B - len(slots), 3, S, S), dtype=torch.float32, device=device))
+            slots.append(torch.zeros((B - len(slots), 3, h, w), dtype=torch.float32, device=device))
         xs.append(torch.cat(slots))
     return dev_images, xs
 
 
-def _batched_unaries(net, group, sizes, device, forward, want, flip=False):
-    """test-ms.py:89-103 for one padded group: K batched forwards and one dsrg_multiscale_unary_batch launch -> (the images on the
-    device, the `want` output of ops.multiscale_unary per image); the padding slots' results are dropped.  flip: batch-2G forwards
-    on _batched_inputs' slot pairs and one dsrg_multiscale_unary_mirror_batch launch"""
+def _group_results(net, images, shapes, device, forward, want, flip, square=False):
+    """test-ms.py:89-103 / test-ms-f.py:121-134 for one group: _group_inputs, len(shapes) batched forwards and one
+    dsrg_multiscale_unary_batch launch (flip: dsrg_multiscale_unary_mirror_batch on the slot pairs) -> (the images on the device,
+    the `want` output of ops.multiscale_unary per image); the padding slots' results are dropped"""
     from . import ops
-    dev_images, xs = _batched_inputs(group, sizes, device, forward, flip)
-    scores = []
-    with _eval_mode(net):
-        for k, x in enumerate(xs):
-            sc = (forward or net)(x).float()
-            if forward is not None and sizes[k] in sizes[k + 1:]:
-                sc = sc.clone()                  # a graph's static output: the later replay of the same shape would overwrite it
-            scores.append(sc.contiguous())
-    shapes = [(im.shape[0], im.shape[1]) for im in dev_images]
-    if flip:
-        return dev_images, ops.multiscale_unary_mirror_batch(scores, shapes, eps=0.00001, want=want)
-    return dev_images, ops.multiscale_unary_batch(scores, shapes, eps=0.00001, want=want)
+    dev_images, xs = _group_inputs(images, shapes, device, forward, flip, square)
+    scores = _forwards(net, forward, xs)
+    tail = ops.multiscale_unary_mirror_batch if flip else ops.multiscale_unary_batch
+    return dev_images, tail(scores, [(im.shape[0], im.shape[1]) for im in dev_images], eps=0.00001, want=want)
 
 
 @torch.no_grad()
 def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", forward=None, in_flight=3, batch=1, forward_batch=1,
-                          flip=False):
+                          flip=False, smooth=True):
     """predict_mask_ms over many images (the loop of test-ms.py over a split's 1 449 / 10 582 images), as a generator of (H,W) int64
     masks in order: the forwards of image i + 1 (on the caller's stream; `forward`: a GraphedForward) run while the CRFs of the images
     before it are in flight on `in_flight` worker streams (crf.CRF_device_many; batch > 1: consecutive same-sized images share one
-    batched CRF call).  Same masks as predict_mask_ms image by image.
+    batched CRF call).  Same masks as predict_mask_ms image by image.  smooth=False: the arg-max, no CRF (and no stream or worker).
 
     forward_batch = G > 1: the images are taken G at a time.  test-ms.py resizes every image to the same `sizes`, so a group's
     forwards are len(sizes) batch-G forwards (a GraphedForward holds one batch-G graph per size; the tail group is padded with
@@ -314,25 +337,24 @@ def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", for
     if flip:
         _check_flip(len(sizes), forward_batch)
     if int(forward_batch) != 1:
-        def batched_pairs():
+        def results():
             for group in _forward_groups(images, forward_batch):
-                for pair in zip(*_batched_unaries(net, group, sizes, device, forward, "unary", flip)):
-                    yield pair
-
-        yield from _crf_in_flight(batched_pairs(), device, in_flight, batch)
-        return
-
-    def pairs():
+                yield from zip(*_group_results(net, group, [(S, S) for S in sizes], device, forward,
+                                               "unary" if smooth else "argmax", flip, square=True))
+    elif smooth:
+        def results():
+            for image in images:
+                unary = _ms_unary(net, image, sizes, device, forward, flip)
+                yield _device_image(image, unary.device), unary
+    else:
         for image in images:
-            if flip:
-                unary = _ms_flip_result(net, image, sizes, device, forward, "unary")
-                yield torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device), unary
-                continue
-            probs = _probs_from_scores(multiscale_scores(net, image, sizes, device, forward))
-            unary = torch.log(probs).permute(1, 2, 0).contiguous()
-            yield torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device), unary
-
-    yield from _crf_in_flight(pairs(), device, in_flight, batch)
+            yield predict_mask_ms(net, image, False, sizes, device, forward, flip)
+        return
+    if smooth:
+        yield from _crf_in_flight(results(), device, in_flight, batch)
+    else:
+        for _, labels in results():
+            yield _host_mask(labels)
 
 
 @torch.no_grad()
@@ -349,12 +371,11 @@ def predict_masks_ms_batched(net, images, smooth=True, sizes=(241, 321, 401), de
         _check_flip(len(sizes), capacity)
     if not 1 <= len(images) <= capacity <= MAX_FORWARD_BATCH:
         raise ValueError("one group holds 1..%d images within its capacity, got %d in %d" % (MAX_FORWARD_BATCH, len(images), capacity))
-    images = images + [None] * (capacity - len(images))
+    dev_images, outs = _group_results(net, images + [None] * (capacity - len(images)), [(S, S) for S in sizes], device, forward,
+                                      "unary" if smooth else "argmax", flip, square=True)
     if smooth:
-        dev_images, unaries = _batched_unaries(net, images, sizes, device, forward, "unary", flip)
-        return list(_crf_in_flight(zip(dev_images, unaries), device, in_flight, batch))
-    _, labels = _batched_unaries(net, images, sizes, device, forward, "argmax", flip)
-    return [lab.cpu().numpy().astype(np.int64) for lab in labels]
+        return list(_crf_in_flight(zip(dev_images, outs), device, in_flight, batch))
+    return [_host_mask(labels) for labels in outs]
 
 
 def _crf_in_flight(pairs, device, in_flight, batch, ignore_below=None):
@@ -377,7 +398,7 @@ def _crf_in_flight(pairs, device, in_flight, batch, ignore_below=None):
         with torch.cuda.stream(fstream):
             for lab in CRF_device_many(pairs, scale_factor=1.0, want="map", in_flight=in_flight, batch=batch,
                                        ignore_below=ignore_below):
-                yield lab.cpu().numpy().astype(np.int64)
+                yield _host_mask(lab)
     finally:
         sys.setswitchinterval(interval)
         # what the forward stream still holds (a forward issued ahead of a generator that was closed early, writes into a graph's
@@ -399,25 +420,7 @@ def relative_size(n, factor):
 def preprocess_relative(image, factor, device="cuda"):
     """test-ms-f.py:100-112: image (H,W,3) RGB uint8/float zoomed by `factor` (order 1, float64 blend as in _zoom) to
     (relative_size(H), relative_size(W)), BGR, mean-subtracted -> (1,3,h,w) float32"""
-    H, W = image.shape[0], image.shape[1]
-    x = torch.from_numpy(np.ascontiguousarray(np.asarray(image))).to(device).to(torch.float32).permute(2, 0, 1)[None]
-    x = _zoom(x, relative_size(H, factor), relative_size(W, factor))
-    x = x[:, [2, 1, 0]]
-    return x - torch.tensor(MEAN_PIXEL, dtype=torch.float32, device=device).view(1, 3, 1, 1)
-
-
-def _relative_scores(net, image, scales, device, forward):
-    """the forwards of test-ms-f.py:121-126 -> list of (1,C,h,w) float32 score maps, one per scale"""
-    out, shapes = [], set()
-    with _eval_mode(net):
-        for s in scales:
-            x = preprocess_relative(image, s, device)
-            sc = (forward or net)(x).float()
-            if forward is not None and tuple(x.shape) in shapes:
-                sc = sc.clone()                  # a graph's static output: a later replay of the same shape would overwrite it
-            shapes.add(tuple(x.shape))
-            out.append(sc.contiguous())
-    return out
+    return _preprocess_to(image, relative_size(image.shape[0], factor), relative_size(image.shape[1], factor), device)
 
 
 def _relative_unary(net, image, scales, device, forward, fused, smooth, flip=False, want=None):
@@ -431,9 +434,8 @@ def _relative_unary(net, image, scales, device, forward, fused, smooth, flip=Fal
     want = want or ("unary" if smooth else "argmax")
     if flip:
         _check_flip(len(scales))
-        scores = _flip_pair_scores(net, [preprocess_relative(image, s, device) for s in scales], forward)
-    else:
-        scores = _relative_scores(net, image, scales, device, forward)
+    xs = [preprocess_relative(image, s, device) for s in scales]
+    scores = _flip_pair_scores(net, xs, forward) if flip else _forwards(net, forward, xs)
     if fused:
         from . import ops
         return ops.multiscale_unary(scores, d1, d2, eps=0.00001, want=want, mirror=[0, 1] * len(scales) if flip else None)
@@ -460,9 +462,8 @@ def predict_mask_ms_f(net, image, scales=(0.75, 1.0, 1.25), smooth=True, device=
     by _zoom_steps: its summed scores are the kernel's bit for bit)"""
     out = _relative_unary(net, image, tuple(scales), device, forward, fused, smooth, flip)
     if smooth:
-        img = torch.as_tensor(np.asarray(image).astype('ubyte'), device=out.device)
-        return CRF_device(img, out, scale_factor=1.0, want="map").cpu().numpy().astype(np.int64)
-    return out.cpu().numpy().astype(np.int64)
+        out = CRF_device(_device_image(image, out.device), out, scale_factor=1.0, want="map")
+    return _host_mask(out)
 
 
 def plan_size_groups(keys, G, window):
@@ -502,45 +503,12 @@ def plan_size_groups(keys, G, window):
     return groups()
 
 
-def _relative_group_results(net, group, scales, device, forward, want, flip=False):
-    """test-ms-f.py:121-134 for a group of n same-sized images (not padded): one dsrg_preprocess_rect_batch launch for all scales
-    (written straight into the static inputs of `forward`'s graphs where those exist; non-uint8 images take preprocess_relative
-    for their slot), len(scales) batch-n forwards and one dsrg_multiscale_unary_batch launch -> (the images on the device, the
-    `want` output of ops.multiscale_unary per image).  flip: one dsrg_preprocess_rect_mirror_batch launch (image g in slot 2g, its
-    mirror image in slot 2g+1), batch-2n forwards and one dsrg_multiscale_unary_mirror_batch launch"""
-    from . import ops
-    n = len(group)
-    B = 2 * n if flip else n                                # the batch of the forwards
-    H, W = group[0].shape[0], group[0].shape[1]
+def _relative_shapes(H, W, scales):
+    """the network input sizes of an H x W image at the relative scales; one below one pixel: ValueError"""
     shapes = [(relative_size(H, s), relative_size(W, s)) for s in scales]
     if any(h < 1 or w < 1 for h, w in shapes):
         raise ValueError("a %d x %d image at the scales %s gives an input below one pixel: %s" % (H, W, tuple(scales), shapes))
-    arrays = [np.ascontiguousarray(np.asarray(im)) for im in group]
-    if all(a.dtype == np.uint8 for a in arrays):
-        dev_images = [torch.from_numpy(a).to(device) for a in arrays]
-        out = None
-        if isinstance(forward, GraphedForward):
-            out = [forward.static_input((B, 3, h, w)) for h, w in shapes]
-            if len(set(shapes)) != len(shapes) or any(o is None for o in out):
-                out = None                                  # (not captured yet: GraphedForward copies a fresh tensor in)
-        xs = (ops.preprocess_rect_mirror_batch if flip else ops.preprocess_rect_batch)(dev_images, shapes, mean=MEAN_PIXEL, out=out)
-    else:
-        dev_images = [torch.as_tensor(a.astype('ubyte'), device=device) for a in arrays]
-        xs = []
-        for s, hw in zip(scales, shapes):
-            slots = [ops.preprocess_rect_batch([d], [hw], mean=MEAN_PIXEL)[0] if a.dtype == np.uint8
-                     else preprocess_relative(a, s, device) for a, d in zip(arrays, dev_images)]
-            xs.append(torch.cat(_with_mirrors(slots) if flip else slots))
-    scores = []
-    with _eval_mode(net):
-        for k, x in enumerate(xs):
-            sc = (forward or net)(x).float()
-            if forward is not None and shapes[k] in shapes[k + 1:]:
-                sc = sc.clone()                  # a graph's static output: the later replay of the same shape would overwrite it
-            scores.append(sc.contiguous())
-    if flip:
-        return dev_images, ops.multiscale_unary_mirror_batch(scores, [(H, W)] * n, eps=0.00001, want=want)
-    return dev_images, ops.multiscale_unary_batch(scores, [(H, W)] * n, eps=0.00001, want=want)
+    return shapes
 
 
 @torch.no_grad()
@@ -583,16 +551,16 @@ def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda"
         def results():
             for idx in groups:
                 group = [held_images.pop(i) for i in idx]
-                dev_images, outs = _relative_group_results(net, group, scales, device, forward, "unary" if smooth else "argmax",
-                                                           flip)
+                shapes = _relative_shapes(group[0].shape[0], group[0].shape[1], scales)     # (checked ahead of any launch)
+                dev_images, outs = _group_results(net, group, shapes, device, forward, "unary" if smooth else "argmax", flip)
                 for i, im, out in zip(idx, dev_images, outs):
                     order.append(i)
-                    yield (im, out) if smooth else out
+                    yield im, out
 
         if smooth:
             masks = _crf_in_flight(results(), device, in_flight, batch)
         else:
-            masks = (lab.cpu().numpy().astype(np.int64) for lab in results())
+            masks = (_host_mask(lab) for _, lab in results())
         held_masks, nxt = {}, 0
         for mask in masks:
             held_masks[order.popleft()] = mask
@@ -608,7 +576,7 @@ def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda"
     def pairs():
         for image in images:
             unary = _relative_unary(net, image, scales, device, forward, fused, True, flip)
-            yield torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device), unary
+            yield _device_image(image, unary.device), unary
 
     yield from _crf_in_flight(pairs(), device, in_flight, batch)
 
@@ -624,8 +592,7 @@ def predict_train_gt(net, image, labels, smooth=True, device="cuda"):
     probs = torch.clamp(probs, min=0.00001)
     if smooth:
         unary = torch.log(probs).permute(1, 2, 0).contiguous()
-        img = torch.as_tensor(np.asarray(image).astype('ubyte'), device=unary.device)
-        p = CRF_device(img, unary, scale_factor=1.0)
+        p = CRF_device(_device_image(image, unary.device), unary, scale_factor=1.0)
     else:
         p = probs.permute(1, 2, 0)
     sel = torch.as_tensor([0] + [int(l) for l in labels], device=p.device)
@@ -658,9 +625,9 @@ def predict_train_gt_many(net, items, smooth=True, size=321, device="cuda", forw
     def group_results():
         for group in _forward_groups(items, forward_batch):
             real = [it for it in group if it is not None]
-            dev_images, xs = _batched_inputs([None if it is None else it[0] for it in group], (size,), device, forward)
-            with _eval_mode(net):
-                scores = (forward or net)(xs[0]).float().contiguous()
+            dev_images, xs = _group_inputs([None if it is None else it[0] for it in group], [(size, size)], device, forward,
+                                           flip=False, square=True)
+            scores, = _forwards(net, forward, xs)
             shapes = [(im.shape[0], im.shape[1]) for im in dev_images]
             select = [train_gt_selection(labels) for _, labels in real]
             if smooth:
@@ -676,7 +643,7 @@ def predict_train_gt_many(net, items, smooth=True, size=321, device="cuda", forw
         yield from _crf_in_flight(group_results(), device, in_flight, batch, ignore_below)
         return
     for lab in group_results():
-        yield lab.cpu().numpy().astype(np.int64)
+        yield _host_mask(lab)
 
 
 class ConfusionMatrix(object):

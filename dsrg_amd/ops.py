@@ -478,6 +478,26 @@ def _ptrs(tensors):
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
+def _multiscale_args(scores, want, batched):
+    """the shared front end of multiscale_unary and its batched forms: the `want` names, the checks of the score maps ((1, C, h, w)
+    each, batched: one leading extent Gcap) and the launch's host arrays -> (names, single, scores, Gcap, C, (K, C, map pointers,
+    map heights, map widths))"""
+    names, single = _want_names(want, _MS_OUTPUTS)
+    scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
+    if not scores:
+        raise ValueError("no score maps")
+    if batched and scores[0].dim() != 4:
+        raise ValueError("score maps must be (Gcap, C, h, w); got %s" % (tuple(scores[0].shape),))
+    Gcap, C = scores[0].shape[0] if batched else 1, scores[0].shape[1]
+    for s in scores:
+        if s.dim() != 4 or s.shape[0] != Gcap or s.shape[1] != C:
+            raise ValueError("score maps must be %s; got %s" % ("(Gcap, C, h, w) with one Gcap and one C" if batched
+                                                                else "(1, C, h, w) with one C", tuple(s.shape)))
+    K = len(scores)
+    return names, single, scores, Gcap, C, (K, int(C), (ctypes.c_void_p * K)(*[s.data_ptr() for s in scores]),
+                                            _i32s([s.shape[2] for s in scores]), _i32s([s.shape[3] for s in scores]))
+
+
 def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",), mirror=None):
     """test-ms.py:90-103 / test-ms-f.py:121-134 after the forwards, in one launch (dsrg_multiscale_unary): the K score maps
     zoomed to H x W, summed in scale order, softmax over labels clamped at eps.  scores: list of (1, C, h_k, w_k) float32 CUDA
@@ -486,30 +506,16 @@ def multiscale_unary(scores, H, W, eps=1e-5, want=("unary",), mirror=None):
     that one tensor, a sequence a tuple in its order.  mirror: one flag per map (dsrg_multiscale_unary_mirror): a map whose flag
     is set is read with its columns reversed, the result being that of this call on torch.flip(map, [-1]) bit for bit (the
     scores of a mirrored network input, mirrored back); None: today's kernel.  Runs on torch's current stream."""
-    names, single = _want_names(want, _MS_OUTPUTS)
-    scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
-    if not scores:
-        raise ValueError("no score maps")
-    if mirror is not None:
-        mirror = [int(bool(m)) for m in mirror]
-        if len(mirror) != len(scores):
-            raise ValueError("mirror must hold one flag per score map: %d flags for %d maps" % (len(mirror), len(scores)))
-    C = scores[0].shape[1]
-    for s in scores:
-        if s.dim() != 4 or s.shape[0] != 1 or s.shape[1] != C:
-            raise ValueError("score maps must be (1, C, h, w) with one C; got %s" % (tuple(s.shape),))
-    K = len(scores)
+    names, single, scores, _, C, (K, C, ptrs, hs, ws) = _multiscale_args(scores, want, False)
     out = {n: ts[0] for n, ts in _want_outputs(names, [(H, W)], C, scores[0].device).items()}
-    ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scores])
-    hs = (ctypes.c_int32 * K)(*[s.shape[2] for s in scores])
-    ws = (ctypes.c_int32 * K)(*[s.shape[3] for s in scores])
+    tail = (hs, ws, int(H), int(W), float(eps), _ptr(out.get("unary")), _ptr(out.get("argmax")), _ptr(out.get("sum")), _stream())
     if mirror is None:
-        check(_lib.lib().dsrg_multiscale_unary(K, int(C), ptrs, hs, ws, int(H), int(W), float(eps), _ptr(out.get("unary")),
-                                               _ptr(out.get("argmax")), _ptr(out.get("sum")), _stream()))
+        check(_lib.lib().dsrg_multiscale_unary(K, C, ptrs, *tail))
     else:
-        check(_lib.lib().dsrg_multiscale_unary_mirror(K, int(C), ptrs, (ctypes.c_int32 * K)(*mirror), hs, ws, int(H), int(W),
-                                                      float(eps), _ptr(out.get("unary")), _ptr(out.get("argmax")),
-                                                      _ptr(out.get("sum")), _stream()))
+        mirror = [int(bool(m)) for m in mirror]
+        if len(mirror) != K:
+            raise ValueError("mirror must hold one flag per score map: %d flags for %d maps" % (len(mirror), K))
+        check(_lib.lib().dsrg_multiscale_unary_mirror(K, C, ptrs, _i32s(mirror), *tail))
     res = tuple(out[n] for n in names)
     return res[0] if single else res
 
@@ -525,29 +531,15 @@ def multiscale_unary_batch(scores, shapes, eps=1e-5, want=("unary",)):
 
 def _multiscale_unary_batch(scores, shapes, eps, want, mirror):
     """multiscale_unary_batch (one slice per image) / multiscale_unary_mirror_batch (mirror: two)"""
-    names, single = _want_names(want, _MS_OUTPUTS)
-    scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
-    if not scores:
-        raise ValueError("no score maps")
+    names, single, scores, Gcap, C, arrays = _multiscale_args(scores, want, True)
     shapes = [(int(H), int(W)) for H, W in shapes]
-    G, K = len(shapes), len(scores)
-    if scores[0].dim() != 4:
-        raise ValueError("score maps must be (Gcap, C, h, w); got %s" % (tuple(scores[0].shape),))
-    Gcap, C = scores[0].shape[0], scores[0].shape[1]
-    for s in scores:
-        if s.dim() != 4 or s.shape[0] != Gcap or s.shape[1] != C:
-            raise ValueError("score maps must be (Gcap, C, h, w) with one Gcap and one C; got %s" % (tuple(s.shape),))
+    G = len(shapes)
     if not 1 <= G * (2 if mirror else 1) <= Gcap:
         raise ValueError("%d output shapes for score maps of %d %s" % (G, Gcap, "slices, two per image" if mirror else "images"))
     out = _want_outputs(names, shapes, C, scores[0].device)
-    ptrs = (ctypes.c_void_p * K)(*[s.data_ptr() for s in scores])
-    hs = (ctypes.c_int32 * K)(*[s.shape[2] for s in scores])
-    ws = (ctypes.c_int32 * K)(*[s.shape[3] for s in scores])
-    Hs = (ctypes.c_int32 * G)(*[H for H, _ in shapes])
-    Ws = (ctypes.c_int32 * G)(*[W for _, W in shapes])
     entry = _lib.lib().dsrg_multiscale_unary_mirror_batch if mirror else _lib.lib().dsrg_multiscale_unary_batch
-    check(entry(G, K, int(C), ptrs, hs, ws, Hs, Ws, float(eps), _ptrs(out.get("unary")), _ptrs(out.get("argmax")),
-                _ptrs(out.get("sum")), _stream()))
+    check(entry(G, *arrays, _i32s([H for H, _ in shapes]), _i32s([W for _, W in shapes]), float(eps), _ptrs(out.get("unary")),
+                _ptrs(out.get("argmax")), _ptrs(out.get("sum")), _stream()))
     if single:
         return out[names[0]]
     return [tuple(out[n][g] for n in names) for g in range(G)]
@@ -650,19 +642,24 @@ def preprocess_ms_batch(images, sizes, capacity=None, mean=MEAN_PIXEL, out=None)
     return out
 
 
+def _rect_targets(out_shapes):
+    """the out_shapes of the rectangular preprocess wrappers -> ([(h_k, w_k)] as ints, the launch's height and width arrays)"""
+    try:
+        out_shapes = [(int(h), int(w)) for h, w in out_shapes]
+    except TypeError:
+        raise ValueError("out_shapes must hold (h, w) pairs")
+    return out_shapes, _i32s([h for h, _ in out_shapes]), _i32s([w for _, w in out_shapes])
+
+
 def preprocess_rect_batch(images, out_shapes, capacity=None, mean=MEAN_PIXEL, out=None):
     """preprocess_ms_batch with a target (h_k, w_k) per scale, in one launch (dsrg_preprocess_rect_batch): what
     inference.preprocess_relative (test-ms-f.py:100-112) makes of a group of same-sized images at every relative scale.  images: G
     <= 16 contiguous (H_g, W_g, 3) RGB uint8 CUDA tensors; out_shapes: the K <= 8 targets (h_k, w_k); capacity, mean, out as
     there.  Returns a list of K (capacity, 3, h_k, w_k) float32 tensors, BGR, mean-subtracted; with h_k = w_k they are
     preprocess_ms_batch's bit for bit.  Runs on torch's current stream."""
-    try:
-        out_shapes = [(int(h), int(w)) for h, w in out_shapes]
-    except TypeError:
-        raise ValueError("out_shapes must hold (h, w) pairs")
+    out_shapes, hs, ws = _rect_targets(out_shapes)
     G, cap, K, ims, Hs, Ws, mean3, optrs, out = _preprocess_group(images, out_shapes, capacity, mean, out)
-    check(_lib.lib().dsrg_preprocess_rect_batch(G, cap, K, ims, Hs, Ws, (ctypes.c_int32 * K)(*[h for h, _ in out_shapes]),
-                                                (ctypes.c_int32 * K)(*[w for _, w in out_shapes]), mean3, optrs, _stream()))
+    check(_lib.lib().dsrg_preprocess_rect_batch(G, cap, K, ims, Hs, Ws, hs, ws, mean3, optrs, _stream()))
     return out
 
 
@@ -673,13 +670,9 @@ def preprocess_rect_mirror_batch(images, out_shapes, capacity=None, mean=MEAN_PI
     (h_k, w_k), (S, S) pairs for the fixed sizes of test-ms.py; capacity >= 2G (default 2G): the batch size of the outputs, slots
     2G.. are written as zeros; mean, out as there.  Returns a list of K (capacity, 3, h_k, w_k) float32 tensors.  Runs on torch's
     current stream."""
-    try:
-        out_shapes = [(int(h), int(w)) for h, w in out_shapes]
-    except TypeError:
-        raise ValueError("out_shapes must hold (h, w) pairs")
+    out_shapes, hs, ws = _rect_targets(out_shapes)
     G, cap, K, ims, Hs, Ws, mean3, optrs, out = _preprocess_group(images, out_shapes, capacity, mean, out, per_image=2)
-    check(_lib.lib().dsrg_preprocess_rect_mirror_batch(G, cap, K, ims, Hs, Ws, (ctypes.c_int32 * K)(*[h for h, _ in out_shapes]),
-                                                       (ctypes.c_int32 * K)(*[w for _, w in out_shapes]), mean3, optrs, _stream()))
+    check(_lib.lib().dsrg_preprocess_rect_mirror_batch(G, cap, K, ims, Hs, Ws, hs, ws, mean3, optrs, _stream()))
     return out
 
 

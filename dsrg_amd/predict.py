@@ -156,26 +156,14 @@ def main(argv=None):
         if a.mode == "gt":
             masks = I.predict_train_gt_many(net, zip(images, gt_labels), smooth=a.smooth, size=scales[0], device=dev, forward=fwd,
                                             in_flight=a.in_flight, forward_batch=a.forward_batch)
-        elif a.mode == "ms-f" and a.same_size_batch > 1:
+        elif a.mode == "ms":
+            masks = I.predict_masks_ms_many(net, images, sizes=scales, device=dev, forward=fwd, in_flight=a.in_flight,
+                                            forward_batch=a.forward_batch, flip=a.flip, smooth=a.smooth)
+        else:
             from .crf import MAX_BATCH
             masks = I.predict_masks_ms_f_many(net, images, scales=scales, device=dev, forward=fwd, in_flight=a.in_flight,
                                               batch=min(a.same_size_batch, MAX_BATCH), same_size_batch=a.same_size_batch,
                                               window=a.window, smooth=a.smooth, flip=a.flip)
-        elif a.smooth:
-            if a.mode == "ms":
-                masks = I.predict_masks_ms_many(net, images, sizes=scales, device=dev, forward=fwd, in_flight=a.in_flight,
-                                                forward_batch=a.forward_batch, flip=a.flip)
-            else:
-                masks = I.predict_masks_ms_f_many(net, images, scales=scales, device=dev, forward=fwd, in_flight=a.in_flight,
-                                                  flip=a.flip)
-        elif a.mode == "ms" and a.forward_batch > 1:
-            masks = (m for group in I._forward_groups(images, a.forward_batch)
-                     for m in I.predict_masks_ms_batched(net, [im for im in group if im is not None], smooth=False, sizes=scales,
-                                                         device=dev, forward=fwd, capacity=a.forward_batch, flip=a.flip))
-        elif a.mode == "ms":
-            masks = (I.predict_mask_ms(net, im, smooth=False, sizes=scales, device=dev, forward=fwd, flip=a.flip) for im in images)
-        else:
-            masks = (I.predict_mask_ms_f(net, im, scales=scales, smooth=False, device=dev, forward=fwd, flip=a.flip) for im in images)
         n = 0
         for img_id, mask in zip(ids, masks):
             write_mask(os.path.join(a.output, img_id + ".png"), mask)
