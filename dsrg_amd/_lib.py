@@ -96,6 +96,8 @@ SIGNATURES = {
                                            [_f, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
     "dsrg_train_gt_unary_batch": (_i, [_i, _i, _vp, _i, _i] + [ctypes.POINTER(ctypes.c_int32)] * 2 + [_f] +
                                   [ctypes.POINTER(ctypes.c_int32)] * 2 + [_i, _f, _vp] + [ctypes.POINTER(_vp)] * 3 + [_vp]),
+    "dsrg_train_gt_ensemble_batch": (_i, [_i, _i, _i, _i, ctypes.POINTER(_vp)] + [ctypes.POINTER(ctypes.c_int32)] * 4 + [_f] +
+                                     [ctypes.POINTER(ctypes.c_int32)] * 2 + [_i, _f, _vp] + [ctypes.POINTER(_vp)] * 3 + [_vp]),
     "dsrg_preprocess_ms_batch": (_i, [_i, _i, _i, ctypes.POINTER(_vp)] + [ctypes.POINTER(ctypes.c_int32)] * 3 +
                                  [ctypes.POINTER(_f), ctypes.POINTER(_vp), _vp]),
     "dsrg_preprocess_rect_batch": (_i, [_i, _i, _i, ctypes.POINTER(_vp)] + [ctypes.POINTER(ctypes.c_int32)] * 4 +

@@ -137,6 +137,19 @@ __device__ __forceinline__ float max_label_value(const float *__restrict__ v, si
 }
 int check_select_list(const char *who, int image, const int32_t *sel, int n, int stride, int C);
 
+// ---- the pseudo-label tails (train_gt.hip: one map per image; train_gt_ms.hip: the ensemble of M maps) -----------------------------
+constexpr int kTgPix = 64;        // output pixels per workgroup
+constexpr int kTgThreads = 256;
+constexpr int kTgMaxBatch = 16;   // images per launch
+
+// all-NULL (-> 0) or all-set (-> 1) host array of G device pointers; -1: mixed
+inline int output_class(const void *const *p, int G) {
+    if (!p) return 0;
+    int set = 0;
+    for (int g = 0; g < G; ++g) set += p[g] != nullptr;
+    return set == 0 ? 0 : set == G ? 1 : -1;
+}
+
 // ---- permutohedral lattice, device-resident ----------------------------------
 // One lattice = one (image, kernel) pair.  All arrays are sized for the worst
 // case Mcap = Npad*(d+1) vertices so nothing depends on the data-dependent M.
@@ -255,6 +268,10 @@ int launch_train_gt_unary_batch(int G, int C, const float *scores, int h, int w,
                                 const int32_t *select, const int32_t *nselect, int select_stride, float ignore_below,
                                 float *workspace, float *const *unary, float *const *probs, int32_t *const *labels,
                                 hipStream_t stream);
+int launch_train_gt_ensemble_batch(int G, int K, int flip, int C, const float *const *scores, const int32_t *h, const int32_t *w,
+                                   const int32_t *H, const int32_t *W, float eps, const int32_t *select, const int32_t *nselect,
+                                   int select_stride, float ignore_below, float *workspace, float *const *unary,
+                                   float *const *probs, int32_t *const *labels, hipStream_t stream);
 int launch_seed_loss_plain(int B, int C, int HW, const float *p, const float *S, float *loss, float *grad, hipStream_t stream);
 int launch_expand_loss(int B, int C, int HW, const float *p, const float *stat, double q_fg, double q_bg, float *loss,
                        float *grad, double *terms, hipStream_t stream);

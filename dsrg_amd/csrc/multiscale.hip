@@ -293,14 +293,6 @@ int launch_multiscale_unary_mirror(int K, int C, const float *const *scores, con
     return launch_multiscale_unary_any(true, K, C, scores, mirror, h, w, H, W, eps, unary, amax, sum_out, stream);
 }
 
-// all-NULL (-> 0) or all-set (-> 1) host array of G device pointers; -1: mixed
-static int output_class(const void *const *p, int G) {
-    if (!p) return 0;
-    int set = 0;
-    for (int g = 0; g < G; ++g) set += p[g] != nullptr;
-    return set == 0 ? 0 : set == G ? 1 : -1;
-}
-
 // mirrored: dsrg_multiscale_unary_mirror_batch (at most kMsMaxMirrorBatch images and kMsMaxScales / 2 scales, each scale's map
 // holding two slices per image), else dsrg_multiscale_unary_batch; `what` names the entry point in the messages
 static int launch_multiscale_unary_batch_any(bool mirrored, const char *what, int G, int K, int C, const float *const *scores,

@@ -23,10 +23,6 @@
 
 namespace dsrg {
 
-constexpr int kTgPix = 64;        // output pixels per workgroup
-constexpr int kTgThreads = 256;
-constexpr int kTgMaxBatch = 16;   // images per launch
-
 struct TgBatchArgs {
     const float *planes;           // (G, C, h * w) probabilities of pass A
     int h, w;
@@ -144,14 +140,6 @@ int check_select_list(const char *who, int image, const int32_t *sel, int n, int
             return set_error(DSRG_ERR_INVALID, "%s: selection entry %d of image %d is label %d, outside [0, %d)", who, j, image,
                              (int)sel[j], C);
     return DSRG_OK;
-}
-
-// all-NULL (-> 0) or all-set (-> 1) host array of G device pointers; -1: mixed
-static int output_class(const void *const *p, int G) {
-    if (!p) return 0;
-    int set = 0;
-    for (int g = 0; g < G; ++g) set += p[g] != nullptr;
-    return set == 0 ? 0 : set == G ? 1 : -1;
 }
 
 int launch_train_gt_unary_batch(int G, int C, const float *scores, int h, int w, const int32_t *H, const int32_t *W, float eps,

@@ -8,6 +8,9 @@ full-resolution dense CRF on log-probabilities, pseudo-label generation, and the
   predict_masks_ms_f_many <-> the loop of test-ms-f.py:153-160 over the test list (same-sized images batched: plan_size_groups)
   predict_train_gt      <-> training/tools/generate_train_gt.py:78-106
   predict_train_gt_many <-> the loop of generate_train_gt.py:117-123 over train_aug (batched forwards, fused HIP tail)
+  predict_train_gt_ms / predict_train_gt_ms_many (no counterpart in the reference) the pseudo-label pass as a probability ensemble:
+                        the zoomed softmax of several sizes, optionally with their mirrors, averaged before the clamp; one size
+                        without flip is the reference's pass
   ConfusionMatrix       <-> training/tools/evaluate.py:17-68
   flip=True             (no counterpart in the reference) mirrored test-time augmentation of the ms / ms-f functions: every scale
                         runs on the image and on its mirror image, the mirror's scores are mirrored back, all 2K maps are summed
@@ -637,6 +640,96 @@ def predict_train_gt_many(net, items, smooth=True, size=321, device="cuda", forw
             else:
                 for lab in ops.train_gt_unary_batch(scores, shapes, eps=0.00001, want="labels", select=select,
                                                     ignore_below=ignore_below):
+                    yield lab
+
+    if smooth:
+        yield from _crf_in_flight(group_results(), device, in_flight, batch, ignore_below)
+        return
+    for lab in group_results():
+        yield _host_mask(lab)
+
+
+MAX_ENSEMBLE_MAPS = 8       # maps per image in one dsrg_train_gt_ensemble_batch: K sizes, with flip=True two maps each
+
+
+def _check_ensemble(nsizes, flip, group=1):
+    """the limits of the gt-ms functions (_check_flip's sibling), checked before any launch"""
+    per = 2 if flip else 1
+    if not 1 <= nsizes * per <= MAX_ENSEMBLE_MAPS:
+        raise ValueError("gt-ms takes 1..%d sizes%s, got %d" % (MAX_ENSEMBLE_MAPS // per, " with flip=True (each runs twice)" if flip else "",
+                                                             nsizes))
+    if flip and int(group) > MAX_FLIP_BATCH:
+        raise ValueError("flip=True takes groups of at most %d images (two slots each), got %d" % (MAX_FLIP_BATCH, int(group)))
+
+
+def _train_gt_ms_probs(net, image, sizes, flip, device):
+    """the ensemble of predict_train_gt_ms -> (C,H,W) float32 clamped probabilities: per size the softmax at map resolution zoomed
+    to the image (_zoom), with flip also that of the mirrored input's scores mirrored back (flip(-1)); the float32 sum in the order
+    size 0 plain, size 0 mirror, size 1 plain, ..., divided by the number of maps M (not at M = 1), clamped at 1e-5"""
+    d1, d2 = image.shape[0], image.shape[1]
+    acc = None
+    with _eval_mode(net):
+        for size in sizes:
+            x = preprocess(image, size, device)
+            maps = [net(x).float()] + ([net(x.flip(-1)).float().flip(-1)] if flip else [])
+            for sc in maps:
+                z = _zoom(torch.softmax(sc, dim=1), d1, d2)[0]
+                acc = z if acc is None else acc + z
+    M = len(sizes) * (2 if flip else 1)
+    return torch.clamp(acc / float(M) if M > 1 else acc, min=0.00001)
+
+
+@torch.no_grad()
+def predict_train_gt_ms(net, image, labels, sizes=(241, 321, 401), flip=False, smooth=True, device="cuda"):
+    """predict_train_gt as a probability ensemble over `sizes`, with flip=True each size also on the mirror image (no counterpart
+    in the reference; sizes=(321,) without flip is predict_train_gt): the mean of the zoomed softmax maps (_train_gt_ms_probs),
+    CRF on its log, arg-max restricted to background + the image-level labels -> (H,W) int64 pseudo-label mask.  The per-image torch
+    composition: the A/B route of predict_train_gt_ms_many"""
+    sizes = tuple(sizes)
+    _check_ensemble(len(sizes), flip)
+    probs = _train_gt_ms_probs(net, image, sizes, flip, device)
+    if smooth:
+        unary = torch.log(probs).permute(1, 2, 0).contiguous()
+        p = CRF_device(_device_image(image, unary.device), unary, scale_factor=1.0)
+    else:
+        p = probs.permute(1, 2, 0)
+    sel = torch.as_tensor(train_gt_selection(labels), device=p.device)
+    return sel[p[:, :, sel].argmax(2)].cpu().numpy()
+
+
+@torch.no_grad()
+def predict_train_gt_ms_many(net, items, sizes=(241, 321, 401), flip=False, smooth=True, device="cuda", forward=None, in_flight=3,
+                             batch=1, forward_batch=1, ignore_below=None):
+    """predict_train_gt_many as a probability ensemble over `sizes`, with flip=True each size also on the mirror image (no
+    counterpart in the reference): items and the generator of (H,W) int64 masks as there.  A group of forward_batch = G images
+    is one preprocessing launch (dsrg_preprocess_ms_batch; flip: dsrg_preprocess_rect_mirror_batch, image g in slot 2g, its mirror
+    image in slot 2g+1), len(sizes) batched forwards and one dsrg_train_gt_ensemble_batch (two launches: the softmax of every map
+    at map resolution; the zoom of the probabilities, their mean in the order size 0 plain, size 0 mirror, size 1 plain, ...,
+    clamp, log); then the CRFs with the restricted MAP (smooth) or the kernel's own restricted arg-max, as
+    predict_train_gt_many.  sizes=(S,) without flip gives predict_train_gt_many(size=S)'s masks.  At most 8 sizes; flip=True: at
+    most 4 sizes and forward_batch <= 8 (ValueError before any stream or worker exists).  The masks are predict_train_gt_ms's
+    except where two labels all but tie."""
+    from . import ops
+    sizes = tuple(int(S) for S in sizes)
+    _check_ensemble(len(sizes), flip, forward_batch)
+    if not 1 <= int(forward_batch) <= MAX_FORWARD_BATCH:
+        raise ValueError("forward_batch must be 1..%d, got %d" % (MAX_FORWARD_BATCH, int(forward_batch)))
+
+    def group_results():
+        for group in _forward_groups(items, forward_batch):
+            real = [it for it in group if it is not None]
+            dev_images, xs = _group_inputs([None if it is None else it[0] for it in group], [(S, S) for S in sizes], device, forward,
+                                           flip=flip, square=True)
+            scores = _forwards(net, forward, xs)
+            shapes = [(im.shape[0], im.shape[1]) for im in dev_images]
+            select = [train_gt_selection(labels) for _, labels in real]
+            if smooth:
+                unaries = ops.train_gt_ensemble_batch(scores, shapes, flip=flip, eps=0.00001, want="unary")
+                for triple in zip(dev_images, unaries, select):
+                    yield triple
+            else:
+                for lab in ops.train_gt_ensemble_batch(scores, shapes, flip=flip, eps=0.00001, want="labels", select=select,
+                                                       ignore_below=ignore_below):
                     yield lab
 
     if smooth:

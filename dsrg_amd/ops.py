@@ -594,6 +594,50 @@ def train_gt_unary_batch(scores, shapes, eps=1e-5, want=("unary",), select=None,
     return [tuple(out[n][g] for n in names) for g in range(G)]
 
 
+def train_gt_ensemble_batch(scores, shapes, flip=False, eps=1e-5, want=("unary",), select=None, ignore_below=None):
+    """train_gt_unary_batch as a probability ensemble over K sizes, with flip=True each also on the mirrored input
+    (dsrg_train_gt_ensemble_batch; no counterpart in the reference).  scores: list of K (Gcap, C, h_k, w_k) float32 CUDA tensors;
+    image g reads slice g, with flip slice 2g plain and slice 2g+1 mirrored (the outputs of batched forwards on
+    preprocess_rect_mirror_batch's inputs); K * (1 + flip) <= 8.  shapes: the G output sizes (H_g, W_g), G <= min(Gcap, 16), with
+    flip G <= min(Gcap // 2, 8).  Per map the softmax at map resolution and the zoom of the probabilities as train_gt_unary_batch
+    computes them (a mirror map read with its columns reversed), then in float32 and in the order scale 0 plain, scale 0 mirror,
+    scale 1 plain, ...: the sum, / M, the clamp at eps.  want / select / ignore_below and the return value: as
+    train_gt_unary_batch; one size without flip gives its results bit for bit.  Image g's results do not depend on the group.
+    Runs on torch's current stream; the workspace (the probability planes of every used slice) is a torch tensor."""
+    names, single = _want_names(want, _TG_OUTPUTS)
+    if torch.is_tensor(scores):
+        raise ValueError("scores must be a list of (Gcap, C, h, w) tensors, one per size")
+    scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
+    if not scores:
+        raise ValueError("no score maps")
+    if scores[0].dim() != 4:
+        raise ValueError("score maps must be (Gcap, C, h, w); got %s" % (tuple(scores[0].shape),))
+    Gcap, C = scores[0].shape[0], scores[0].shape[1]
+    for s in scores:
+        if s.dim() != 4 or s.shape[0] != Gcap or s.shape[1] != C:
+            raise ValueError("score maps must be (Gcap, C, h, w) with one Gcap and one C; got %s" % (tuple(s.shape),))
+    shapes = [(int(H), int(W)) for H, W in shapes]
+    K, G, per, dev = len(scores), len(shapes), 2 if flip else 1, scores[0].device
+    if not 1 <= G * per <= Gcap:
+        raise ValueError("%d output shapes for score maps of %d %s" % (G, Gcap, "slices, two per image" if flip else "images"))
+    sel = nsel = None
+    stride = 0
+    if "labels" in names:
+        if select is None:
+            raise ValueError('want="labels" needs one selection list per image (select=...)')
+        sel, nsel, stride = select_arrays(select, G, C)
+    out = _want_outputs(names, shapes, C, dev)
+    workspace = torch.empty(sum(G * per * C * s.shape[2] * s.shape[3] for s in scores), dtype=torch.float32, device=dev)
+    check(_lib.lib().dsrg_train_gt_ensemble_batch(G, K, int(bool(flip)), int(C), (ctypes.c_void_p * K)(*[s.data_ptr() for s in scores]),
+                                                  _i32s([s.shape[2] for s in scores]), _i32s([s.shape[3] for s in scores]),
+                                                  _i32s([H for H, _ in shapes]), _i32s([W for _, W in shapes]), float(eps), sel, nsel,
+                                                  int(stride), float(ignore_below or 0.0), _ptr(workspace), _ptrs(out.get("unary")),
+                                                  _ptrs(out.get("probs")), _ptrs(out.get("labels")), _stream()))
+    if single:
+        return out[names[0]]
+    return [tuple(out[n][g] for n in names) for g in range(G)]
+
+
 def _preprocess_group(images, out_shapes, capacity, mean, out, per_image=1):
     """the shared front end of preprocess_ms_batch / preprocess_rect_batch / preprocess_rect_mirror_batch (per_image = 2 slots per
     image): checks, output tensors and the launch's host arrays -> (G, capacity, K, image pointers, H, W, mean, output pointers,

@@ -5,6 +5,9 @@
   --mode ms --scales 481 --class 81  <-> training/tools/test-coco.py:108-135 (single-scale COCO test)
   --mode gt --cues PICKLE  <-> training/tools/generate_train_gt.py (one size, default 321; labels restricted to background + the
                image-level labels '<id>_labels' of the cue pickle; --images holds the reference's input_list.txt lines "name.jpg <id>")
+  --mode gt-ms --cues PICKLE  (no counterpart in the reference) --mode gt as a probability ensemble over several sizes (default
+               241,321,401; at most 8), with --flip each also on the mirror image: the zoomed softmax maps are averaged before the
+               clamp (inference.predict_train_gt_ms_many).  One size without --flip is --mode gt
 
 Reads DIR/JPEGImages/<id>.jpg for every id of --images, writes OUT/<id>.png: 8-bit grayscale class ids, what
 training/tools/evaluate.py reads (and `python -m dsrg_amd.evaluate`).  The network is VGG16-ASPP (--backbone resnet101: the DeepLab-v2
@@ -15,8 +18,9 @@ CRFs of earlier images are in flight (inference.predict_masks_ms_many / predict_
 takes the images N at a time through batch-N forwards (the absolute sizes are the same for every image); so does --mode gt
 (inference.predict_train_gt_many).  --mode ms-f --same-size-batch N collects same-sized images (up to N, out of a window of
 --window images) into batch-n forwards (inference.plan_size_groups); the masks are still written per image, in input order.
---flip (ms, ms-f; no counterpart in the reference): mirrored test-time augmentation, every scale runs on the image and on its
-mirror image and all the score maps are summed before the softmax (at most 4 scales, batches of at most 8 images).
+--flip (ms, ms-f, gt-ms; no counterpart in the reference): mirrored test-time augmentation, every scale runs on the image and on its
+mirror image and all the score maps are summed before the softmax (gt-ms: the probabilities averaged) (at most 4 scales, batches of at most 8
+images).
 """
 import argparse
 import os
@@ -25,18 +29,19 @@ import sys
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="multi-scale test: label PNGs for a list of images")
-    p.add_argument("--mode", choices=("ms", "ms-f", "gt"), required=True,
+    p.add_argument("--mode", choices=("ms", "ms-f", "gt", "gt-ms"), required=True,
                    help="ms: absolute sizes (test-ms.py); ms-f: sizes relative to each image (test-ms-f.py); "
-                        "gt: pseudo labels restricted to the image-level labels (generate_train_gt.py)")
+                        "gt: pseudo labels restricted to the image-level labels (generate_train_gt.py); gt-ms: gt as a "
+                        "probability ensemble over several sizes (and their mirrors with --flip)")
     p.add_argument("--model", required=True, help="weights (.caffemodel, .npz or torch file)")
     p.add_argument("--images", required=True, help="list of image ids, one per line (gt: lines 'name.jpg <id>')")
-    p.add_argument("--cues", default=None, help="gt: the localisation-cue pickle holding '<id>_labels' for every image")
+    p.add_argument("--cues", default=None, help="gt, gt-ms: the localisation-cue pickle holding '<id>_labels' for every image")
     p.add_argument("--dir", required=True, help="dataset root holding JPEGImages/")
     p.add_argument("--output", required=True, help="directory for the <id>.png label maps")
     p.add_argument("--smooth", action="store_true", help="dense-CRF post-processing (as the reference's --smooth)")
     p.add_argument("--scales", default=None,
                    help="comma-separated: sizes in pixels (ms; default 241,321,401) or factors (ms-f; default 0.75,1,1.25); "
-                        "gt: one size (default 321)")
+                        "gt: one size (default 321); gt-ms: up to 8 sizes (default 241,321,401)")
     p.add_argument("--class", dest="num_classes", type=int, default=21, help="number of classes including background")
     p.add_argument("--fp32", action="store_true", help="float32 forwards instead of bf16 autocast")
     p.add_argument("--backbone", choices=("vgg16", "resnet101"), default="vgg16",
@@ -45,22 +50,24 @@ def parse_args(argv=None):
     p.add_argument("--in-flight", type=int, default=3, help="CRFs in flight under the next image's forwards")
     p.add_argument("--max-graphs", type=int, default=12, help="ms-f: captured forward graphs kept (least recently used dropped)")
     p.add_argument("--forward-batch", type=int, default=1,
-                   help="ms, gt: images per batched forward (1..16; default 1: one image per forward)")
+                   help="ms, gt, gt-ms: images per batched forward (1..16; default 1: one image per forward)")
     p.add_argument("--same-size-batch", type=int, default=1,
                    help="ms-f: same-sized images per batched forward (1..16; default 1: one image per forward)")
     p.add_argument("--window", type=int, default=64,
                    help="ms-f with --same-size-batch: an image waits for at most N - 1 later images for its group (default 64)")
     p.add_argument("--flip", action="store_true",
-                   help="ms, ms-f: mirrored test-time augmentation: every scale also runs on the mirror image, whose scores are "
+                   help="ms, ms-f, gt-ms: mirrored test-time augmentation: every scale also runs on the mirror image, whose scores are "
                         "mirrored back and summed with the others (at most 4 scales; --forward-batch / --same-size-batch at most 8)")
     a = p.parse_args(argv)
-    if a.mode == "gt":
+    if a.mode in ("gt", "gt-ms"):
         if not a.cues:
-            p.error("--mode gt needs --cues (the pickle with the image-level labels)")
-        if a.scales is not None and len(a.scales.split(",")) != 1:
+            p.error("--mode %s needs --cues (the pickle with the image-level labels)" % a.mode)
+        if a.mode == "gt" and a.scales is not None and len(a.scales.split(",")) != 1:
             p.error("--mode gt takes one size in --scales")
+        if a.mode == "gt-ms" and a.scales is not None and len(a.scales.split(",")) > 8:
+            p.error("--mode gt-ms takes at most 8 sizes in --scales")
     elif a.cues:
-        p.error("--cues is for --mode gt only")
+        p.error("--cues is for --mode gt and --mode gt-ms only")
     if a.mode == "ms-f" and a.forward_batch != 1:
         p.error("--forward-batch is for --mode ms only: the relative scales of ms-f give every image size its own input shapes")
     if not 1 <= a.forward_batch <= 16:
@@ -120,11 +127,12 @@ def main(argv=None):
     from ._lib import require_gpu
 
     require_gpu()
-    if a.mode == "gt":
+    if a.mode in ("gt", "gt-ms"):
         from .layers import _open_cue_file
-        scales = (int(a.scales),) if a.scales else (321,)
         cues = _open_cue_file(os.path.abspath(a.cues))
-    elif a.mode == "ms":
+    if a.mode == "gt":
+        scales = (int(a.scales),) if a.scales else (321,)
+    elif a.mode in ("ms", "gt-ms"):
         scales = tuple(int(s) for s in a.scales.split(",")) if a.scales else (241, 321, 401)
     else:
         scales = tuple(float(s) for s in a.scales.split(",")) if a.scales else (0.75, 1.0, 1.25)
@@ -139,7 +147,7 @@ def main(argv=None):
     else:
         net = VGG16ASPP(num_classes=a.num_classes).to(dev).to(memory_format=torch.channels_last).eval()
         load_weights(net, a.model)
-    if a.mode == "gt":
+    if a.mode in ("gt", "gt-ms"):
         entries = read_gt_list(a.images)
         ids = [name for name, _ in entries]
         gt_labels = [cues['%i_labels' % num] for _, num in entries]
@@ -148,7 +156,7 @@ def main(argv=None):
     os.makedirs(a.output, exist_ok=True)
     images = (read_image(os.path.join(a.dir, "JPEGImages", i + ".jpg")) for i in ids)
 
-    if a.mode in ("ms", "gt"):
+    if a.mode in ("ms", "gt", "gt-ms"):
         fwd = I.GraphedForward(net)                         # one graph per fixed size
     else:                                                   # every image size has its own shapes: keep the common ones
         fwd = I.GraphedForward(net, max_shapes=a.max_graphs, capture_after=2)
@@ -156,6 +164,9 @@ def main(argv=None):
         if a.mode == "gt":
             masks = I.predict_train_gt_many(net, zip(images, gt_labels), smooth=a.smooth, size=scales[0], device=dev, forward=fwd,
                                             in_flight=a.in_flight, forward_batch=a.forward_batch)
+        elif a.mode == "gt-ms":
+            masks = I.predict_train_gt_ms_many(net, zip(images, gt_labels), sizes=scales, flip=a.flip, smooth=a.smooth, device=dev,
+                                               forward=fwd, in_flight=a.in_flight, forward_batch=a.forward_batch)
         elif a.mode == "ms":
             masks = I.predict_masks_ms_many(net, images, sizes=scales, device=dev, forward=fwd, in_flight=a.in_flight,
                                             forward_batch=a.forward_batch, flip=a.flip, smooth=a.smooth)
