@@ -532,7 +532,7 @@ extern "C" int dsrg_train_gt_ensemble_batch(int G, int K, int flip, int C, const
                                             const int32_t *nselect, int select_stride, float ignore_below, float *workspace,
                                             float *const *unary, float *const *probs, int32_t *const *labels, void *stream) {
     // every argument is checked before the first device call
-    return launch_train_gt_ensemble_batch(G, K, flip, C, scores, h, w, H, W, eps, select, nselect, select_stride, ignore_below,
+    return launch_train_gt_ensemble_batch("train-gt ensemble", G, K, flip, C, scores, h, w, H, W, eps, select, nselect, select_stride, ignore_below,
                                           workspace, unary, probs, labels, static_cast<hipStream_t>(stream));
 }
 extern "C" int dsrg_preprocess_ms_batch(int G, int capacity, int K, const unsigned char *const *images, const int32_t *H,

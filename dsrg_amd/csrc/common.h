@@ -108,8 +108,8 @@ constexpr float kMinProb = 0.0001f;
 
 // ---- label-restricted selection (generate_train_gt.py:98-104) -----------------
 // The result over an ordered list sel[0..n) of label indices is sel[j*], j* the FIRST j that maximises v[sel[j]] (np.argmax on
-// probs[:, :, labels]: strict > while walking the list; duplicates and any order allowed).  Shared by the unary kernel's
-// smooth=False route (train_gt.hip) and the two kernels that read a CRF object's final marginals (layers.hip, lattice_large.hip).
+// probs[:, :, labels]: strict > while walking the list; duplicates and any order allowed).  Shared by the pseudo-label
+// tail's smooth=False route (train_gt.hip) and the two kernels that read a CRF object's final marginals (layers.hip, lattice_large.hip).
 constexpr int kMaxSelect = 128;      // entries per list
 constexpr int kIgnoreLabel = 255;    // pixels whose maximum over ALL labels is below `ignore_below` (off at <= 0)
 constexpr int kSelectImages = 8;     // lists per CRF object: one per image of a batched object (kLargeBatchMax)
@@ -137,7 +137,7 @@ __device__ __forceinline__ float max_label_value(const float *__restrict__ v, si
 }
 int check_select_list(const char *who, int image, const int32_t *sel, int n, int stride, int C);
 
-// ---- the pseudo-label tails (train_gt.hip: one map per image; train_gt_ms.hip: the ensemble of M maps) -----------------------------
+// ---- the pseudo-label tail (train_gt.hip: the ensemble of M maps per image; one map is its K = 1, no-flip case) ---------------------
 constexpr int kTgPix = 64;        // output pixels per workgroup
 constexpr int kTgThreads = 256;
 constexpr int kTgMaxBatch = 16;   // images per launch
@@ -268,10 +268,10 @@ int launch_train_gt_unary_batch(int G, int C, const float *scores, int h, int w,
                                 const int32_t *select, const int32_t *nselect, int select_stride, float ignore_below,
                                 float *workspace, float *const *unary, float *const *probs, int32_t *const *labels,
                                 hipStream_t stream);
-int launch_train_gt_ensemble_batch(int G, int K, int flip, int C, const float *const *scores, const int32_t *h, const int32_t *w,
-                                   const int32_t *H, const int32_t *W, float eps, const int32_t *select, const int32_t *nselect,
-                                   int select_stride, float ignore_below, float *workspace, float *const *unary,
-                                   float *const *probs, int32_t *const *labels, hipStream_t stream);
+int launch_train_gt_ensemble_batch(const char *who, int G, int K, int flip, int C, const float *const *scores, const int32_t *h,
+                                   const int32_t *w, const int32_t *H, const int32_t *W, float eps, const int32_t *select,
+                                   const int32_t *nselect, int select_stride, float ignore_below, float *workspace,
+                                   float *const *unary, float *const *probs, int32_t *const *labels, hipStream_t stream);
 int launch_seed_loss_plain(int B, int C, int HW, const float *p, const float *S, float *loss, float *grad, hipStream_t stream);
 int launch_expand_loss(int B, int C, int HW, const float *p, const float *stat, double q_fg, double q_bg, float *loss,
                        float *grad, double *terms, hipStream_t stream);

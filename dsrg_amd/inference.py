@@ -587,19 +587,9 @@ def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda"
 @torch.no_grad()
 def predict_train_gt(net, image, labels, smooth=True, device="cuda"):
     """generate_train_gt.py:78-106: single-scale (321) softmax, zoomed to the image, CRF on log-probs,
-    argmax restricted to background + the image-level labels -> (H,W) int64 pseudo-label mask"""
-    d1, d2 = image.shape[0], image.shape[1]
-    with _eval_mode(net):
-        scores = net(preprocess(image, 321, device)).float()
-    probs = _zoom(torch.softmax(scores, dim=1), d1, d2)[0]
-    probs = torch.clamp(probs, min=0.00001)
-    if smooth:
-        unary = torch.log(probs).permute(1, 2, 0).contiguous()
-        p = CRF_device(_device_image(image, unary.device), unary, scale_factor=1.0)
-    else:
-        p = probs.permute(1, 2, 0)
-    sel = torch.as_tensor([0] + [int(l) for l in labels], device=p.device)
-    return sel[p[:, :, sel].argmax(2)].cpu().numpy()
+    argmax restricted to background + the image-level labels -> (H,W) int64 pseudo-label mask.  It is predict_train_gt_ms at the
+    one size 321 without flip: the same torch operations in the same order (one map: no sum, no division)"""
+    return predict_train_gt_ms(net, image, labels, sizes=(321,), flip=False, smooth=smooth, device=device)
 
 
 def train_gt_selection(labels):
@@ -608,45 +598,17 @@ def train_gt_selection(labels):
     return [0] + [int(l) for l in labels]
 
 
-@torch.no_grad()
 def predict_train_gt_many(net, items, smooth=True, size=321, device="cuda", forward=None, in_flight=3, batch=1, forward_batch=1,
                           ignore_below=None):
     """generate_train_gt.py:78-106 over many images (its loop over the 10 582 images of train_aug): items is an iterable of
     (image (H,W,3) RGB, image-level labels); a generator of (H,W) int64 masks in order, each restricted to background + the
-    image's labels.  The images are taken forward_batch = G at a time (the tail group is padded with zero inputs): one
-    dsrg_preprocess_ms_batch launch at `size` (into the static input of `forward`'s graph where `forward` is a GraphedForward), ONE
-    batch-G forward and one dsrg_train_gt_unary_batch (softmax at map resolution, zoom of the probabilities, clamp, log).
-    smooth: the full-resolution CRFs run on `in_flight` worker streams under the next group's forward (batch > 1: consecutive
-    same-sized images share one batched CRF call) and end in the restricted MAP of dsrg_crf_map_select; otherwise the labels are
-    the kernel's own restricted arg-max of the clamped probabilities.  ignore_below: pixels whose largest probability / marginal
-    over all labels is below it get 255 (the reference's commented-out line 104); None: off.  forward_batch=1 is the per-image
-    route on the same kernels.  A batch-G forward need not round as a batch-1 forward does: the masks are predict_train_gt's
-    except where two labels all but tie."""
-    from . import ops
-    size = int(size)
-
-    def group_results():
-        for group in _forward_groups(items, forward_batch):
-            real = [it for it in group if it is not None]
-            dev_images, xs = _group_inputs([None if it is None else it[0] for it in group], [(size, size)], device, forward,
-                                           flip=False, square=True)
-            scores, = _forwards(net, forward, xs)
-            shapes = [(im.shape[0], im.shape[1]) for im in dev_images]
-            select = [train_gt_selection(labels) for _, labels in real]
-            if smooth:
-                unaries = ops.train_gt_unary_batch(scores, shapes, eps=0.00001, want="unary")
-                for triple in zip(dev_images, unaries, select):
-                    yield triple
-            else:
-                for lab in ops.train_gt_unary_batch(scores, shapes, eps=0.00001, want="labels", select=select,
-                                                    ignore_below=ignore_below):
-                    yield lab
-
-    if smooth:
-        yield from _crf_in_flight(group_results(), device, in_flight, batch, ignore_below)
-        return
-    for lab in group_results():
-        yield _host_mask(lab)
+    image's labels.  It is predict_train_gt_ms_many at the one size `size` without flip, which see for the groups, the CRFs and
+    ignore_below: per group of forward_batch = G images one dsrg_preprocess_ms_batch launch at `size`, ONE batch-G forward and the
+    pseudo-label tail on its one map per image (softmax at map resolution, zoom of the probabilities, clamp, log).
+    forward_batch=1 is the per-image route on the same kernels; outside 1..16: ValueError before any launch.  A batch-G forward
+    need not round as a batch-1 forward does: the masks are predict_train_gt's except where two labels all but tie."""
+    return predict_train_gt_ms_many(net, items, sizes=(size,), flip=False, smooth=smooth, device=device, forward=forward,
+                                    in_flight=in_flight, batch=batch, forward_batch=forward_batch, ignore_below=ignore_below)
 
 
 MAX_ENSEMBLE_MAPS = 8       # maps per image in one dsrg_train_gt_ensemble_batch: K sizes, with flip=True two maps each
@@ -681,10 +643,10 @@ def _train_gt_ms_probs(net, image, sizes, flip, device):
 
 @torch.no_grad()
 def predict_train_gt_ms(net, image, labels, sizes=(241, 321, 401), flip=False, smooth=True, device="cuda"):
-    """predict_train_gt as a probability ensemble over `sizes`, with flip=True each size also on the mirror image (no counterpart
-    in the reference; sizes=(321,) without flip is predict_train_gt): the mean of the zoomed softmax maps (_train_gt_ms_probs),
-    CRF on its log, arg-max restricted to background + the image-level labels -> (H,W) int64 pseudo-label mask.  The per-image torch
-    composition: the A/B route of predict_train_gt_ms_many"""
+    """The pseudo-label mask of one image from a probability ensemble over `sizes`, with flip=True each size also on the mirror
+    image (no counterpart in the reference; sizes=(321,) without flip is predict_train_gt, generate_train_gt.py:78-106): the mean
+    of the zoomed softmax maps (_train_gt_ms_probs), CRF on its log, arg-max restricted to background + the image-level labels ->
+    (H,W) int64 pseudo-label mask.  The per-image torch composition: the A/B route of predict_train_gt_ms_many"""
     sizes = tuple(sizes)
     _check_ensemble(len(sizes), flip)
     probs = _train_gt_ms_probs(net, image, sizes, flip, device)
@@ -700,15 +662,20 @@ def predict_train_gt_ms(net, image, labels, sizes=(241, 321, 401), flip=False, s
 @torch.no_grad()
 def predict_train_gt_ms_many(net, items, sizes=(241, 321, 401), flip=False, smooth=True, device="cuda", forward=None, in_flight=3,
                              batch=1, forward_batch=1, ignore_below=None):
-    """predict_train_gt_many as a probability ensemble over `sizes`, with flip=True each size also on the mirror image (no
-    counterpart in the reference): items and the generator of (H,W) int64 masks as there.  A group of forward_batch = G images
-    is one preprocessing launch (dsrg_preprocess_ms_batch; flip: dsrg_preprocess_rect_mirror_batch, image g in slot 2g, its mirror
-    image in slot 2g+1), len(sizes) batched forwards and one dsrg_train_gt_ensemble_batch (two launches: the softmax of every map
-    at map resolution; the zoom of the probabilities, their mean in the order size 0 plain, size 0 mirror, size 1 plain, ...,
-    clamp, log); then the CRFs with the restricted MAP (smooth) or the kernel's own restricted arg-max, as
-    predict_train_gt_many.  sizes=(S,) without flip gives predict_train_gt_many(size=S)'s masks.  At most 8 sizes; flip=True: at
-    most 4 sizes and forward_batch <= 8 (ValueError before any stream or worker exists).  The masks are predict_train_gt_ms's
-    except where two labels all but tie."""
+    """The pseudo-label pass over many images as a probability ensemble over `sizes`, with flip=True each size also on the mirror
+    image (no counterpart in the reference; sizes=(S,) without flip is predict_train_gt_many(size=S)): items is an iterable of
+    (image (H,W,3) RGB, image-level labels); a generator of (H,W) int64 masks in order, each restricted to background + the
+    image's labels.  The images are taken forward_batch = G at a time (the tail group is padded with zero inputs): one
+    preprocessing launch (dsrg_preprocess_ms_batch, into the static inputs of `forward`'s graphs where `forward` is a
+    GraphedForward; flip: dsrg_preprocess_rect_mirror_batch, image g in slot 2g, its mirror image in slot 2g+1), len(sizes)
+    batched forwards and one dsrg_train_gt_ensemble_batch (two launches: the softmax of every map at map resolution; the zoom of
+    the probabilities, their mean in the order size 0 plain, size 0 mirror, size 1 plain, ..., clamp, log).  smooth: the
+    full-resolution CRFs run on `in_flight` worker streams under the next group's forwards (batch > 1: consecutive same-sized
+    images share one batched CRF call) and end in the restricted MAP of dsrg_crf_map_select; otherwise the labels are the kernel's
+    own restricted arg-max of the clamped probabilities.  ignore_below: pixels whose largest probability / marginal over all
+    labels is below it get 255 (the reference's commented-out line 104); None: off.  At most 8 sizes and forward_batch in 1..16;
+    flip=True: at most 4 sizes and forward_batch <= 8 (ValueError before any stream or worker exists).  The masks are
+    predict_train_gt_ms's except where two labels all but tie."""
     from . import ops
     sizes = tuple(int(S) for S in sizes)
     _check_ensemble(len(sizes), flip, forward_batch)

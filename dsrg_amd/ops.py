@@ -563,35 +563,13 @@ def train_gt_unary_batch(scores, shapes, eps=1e-5, want=("unary",), select=None,
     ((H, W) int32: per pixel the first maximum over the image's list select[g] — an ordered sequence of 1..128 labels, e.g.
     inference.train_gt_selection(labels) — or 255 where the largest probability over all labels is below ignore_below; None or
     <= 0: off).  A string returns the list of that one tensor per image, a sequence a list of tuples in its order.  Image g's
-    results equal those of a G = 1 call on slice g bit for bit.  Runs on torch's current stream; the workspace (G * C * h * w
-    floats) is a torch tensor."""
-    names, single = _want_names(want, _TG_OUTPUTS)
+    results equal those of a G = 1 call on slice g bit for bit.  It is train_gt_ensemble_batch([scores], flip=False): the same
+    kernels, one map per image, no sum and no division.  Runs on torch's current stream; the workspace (G * C * h * w floats) is a
+    torch tensor."""
+    names = _want_names(want, _TG_OUTPUTS)
     if not torch.is_tensor(scores):
         raise ValueError("scores must be one (Gcap, C, h, w) tensor")
-    scores = _f32c(scores, "scores")
-    if scores.dim() != 4:
-        raise ValueError("score maps must be (Gcap, C, h, w); got %s" % (tuple(scores.shape),))
-    shapes = [(int(H), int(W)) for H, W in shapes]
-    Gcap, C, h, w = scores.shape
-    G, dev = len(shapes), scores.device
-    if not 1 <= G <= Gcap:
-        raise ValueError("%d output shapes for score maps of %d images" % (G, Gcap))
-    sel = nsel = None
-    stride = 0
-    if "labels" in names:
-        if select is None:
-            raise ValueError('want="labels" needs one selection list per image (select=...)')
-        sel, nsel, stride = select_arrays(select, G, C)
-    out = _want_outputs(names, shapes, C, dev)
-    workspace = torch.empty((G, C, h, w), dtype=torch.float32, device=dev)
-    Hs = (ctypes.c_int32 * G)(*[H for H, _ in shapes])
-    Ws = (ctypes.c_int32 * G)(*[W for _, W in shapes])
-    check(_lib.lib().dsrg_train_gt_unary_batch(G, int(C), _ptr(scores), int(h), int(w), Hs, Ws, float(eps), sel, nsel, int(stride),
-                                               float(ignore_below or 0.0), _ptr(workspace), _ptrs(out.get("unary")),
-                                               _ptrs(out.get("probs")), _ptrs(out.get("labels")), _stream()))
-    if single:
-        return out[names[0]]
-    return [tuple(out[n][g] for n in names) for g in range(G)]
+    return _train_gt_batch([scores], shapes, False, eps, names, select, ignore_below)
 
 
 def train_gt_ensemble_batch(scores, shapes, flip=False, eps=1e-5, want=("unary",), select=None, ignore_below=None):
@@ -599,14 +577,21 @@ def train_gt_ensemble_batch(scores, shapes, flip=False, eps=1e-5, want=("unary",
     (dsrg_train_gt_ensemble_batch; no counterpart in the reference).  scores: list of K (Gcap, C, h_k, w_k) float32 CUDA tensors;
     image g reads slice g, with flip slice 2g plain and slice 2g+1 mirrored (the outputs of batched forwards on
     preprocess_rect_mirror_batch's inputs); K * (1 + flip) <= 8.  shapes: the G output sizes (H_g, W_g), G <= min(Gcap, 16), with
-    flip G <= min(Gcap // 2, 8).  Per map the softmax at map resolution and the zoom of the probabilities as train_gt_unary_batch
-    computes them (a mirror map read with its columns reversed), then in float32 and in the order scale 0 plain, scale 0 mirror,
-    scale 1 plain, ...: the sum, / M, the clamp at eps.  want / select / ignore_below and the return value: as
-    train_gt_unary_batch; one size without flip gives its results bit for bit.  Image g's results do not depend on the group.
-    Runs on torch's current stream; the workspace (the probability planes of every used slice) is a torch tensor."""
-    names, single = _want_names(want, _TG_OUTPUTS)
+    flip G <= min(Gcap // 2, 8).  Per map the softmax at map resolution and the zoom of the probabilities to the image (a mirror
+    map read with its columns reversed), then in float32 and in the order scale 0 plain, scale 0 mirror, scale 1 plain, ...: the
+    sum, / M (not at M = 1), the clamp at eps.  want / select / ignore_below and the return value: as train_gt_unary_batch, which
+    is the case of one size without flip.  Image g's results do not depend on the group.  Runs on torch's current stream; the
+    workspace (the probability planes of every used slice) is a torch tensor."""
+    names = _want_names(want, _TG_OUTPUTS)
     if torch.is_tensor(scores):
         raise ValueError("scores must be a list of (Gcap, C, h, w) tensors, one per size")
+    return _train_gt_batch(scores, shapes, flip, eps, names, select, ignore_below)
+
+
+def _train_gt_batch(scores, shapes, flip, eps, want, select, ignore_below):
+    """train_gt_unary_batch (one map, no flip) / train_gt_ensemble_batch after their `want` (parsed: _want_names) and type checks:
+    the shape checks, the outputs, the workspace and the one launch"""
+    names, single = want
     scores = [_f32c(s, "scores[%d]" % k) for k, s in enumerate(scores)]
     if not scores:
         raise ValueError("no score maps")

@@ -15,8 +15,9 @@ ResNet-101 of the stage-2 trainer, run through resnet_test.ResNetTestNet: fused 
 (checkpoint.load_weights: .caffemodel, .npz or a torch file), run under bf16 autocast (--fp32: float32, the reference's
 precision); forwards replay from captured HIP graphs (inference.GraphedForward, bounded for the relative scales) while the
 CRFs of earlier images are in flight (inference.predict_masks_ms_many / predict_masks_ms_f_many).  --mode ms --forward-batch N
-takes the images N at a time through batch-N forwards (the absolute sizes are the same for every image); so does --mode gt
-(inference.predict_train_gt_many).  --mode ms-f --same-size-batch N collects same-sized images (up to N, out of a window of
+takes the images N at a time through batch-N forwards (the absolute sizes are the same for every image); so do --mode gt and
+--mode gt-ms (one generator, inference.predict_train_gt_ms_many).
+--mode ms-f --same-size-batch N collects same-sized images (up to N, out of a window of
 --window images) into batch-n forwards (inference.plan_size_groups); the masks are still written per image, in input order.
 --flip (ms, ms-f, gt-ms; no counterpart in the reference): mirrored test-time augmentation, every scale runs on the image and on its
 mirror image and all the score maps are summed before the softmax (gt-ms: the probabilities averaged) (at most 4 scales, batches of at most 8
@@ -161,10 +162,7 @@ def main(argv=None):
     else:                                                   # every image size has its own shapes: keep the common ones
         fwd = I.GraphedForward(net, max_shapes=a.max_graphs, capture_after=2)
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=not a.fp32):
-        if a.mode == "gt":
-            masks = I.predict_train_gt_many(net, zip(images, gt_labels), smooth=a.smooth, size=scales[0], device=dev, forward=fwd,
-                                            in_flight=a.in_flight, forward_batch=a.forward_batch)
-        elif a.mode == "gt-ms":
+        if a.mode in ("gt", "gt-ms"):                       # gt: its one size, no flip (what predict_train_gt_many is)
             masks = I.predict_train_gt_ms_many(net, zip(images, gt_labels), sizes=scales, flip=a.flip, smooth=a.smooth, device=dev,
                                                forward=fwd, in_flight=a.in_flight, forward_batch=a.forward_batch)
         elif a.mode == "ms":

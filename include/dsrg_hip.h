@@ -334,7 +334,8 @@ int dsrg_multiscale_unary_mirror_batch(int G, int K, int C, const float *const *
  *              nselect_host / select_stride / ignore_below as there, one list per image; may be NULL when labels_dev is
  * 1 <= G <= 16, 1 <= C <= 96, H_g, W_g, h, w >= 1, H_g*W_g*C < 2^31, h*w*C < 2^31; every argument is checked before the first
  * device call.  Stream-ordered, no host synchronisation, no handle; bit-reproducible (no atomics), and image g's outputs do not
- * depend on the group. */
+ * depend on the group.  It is dsrg_train_gt_ensemble_batch at K = 1, flip = 0 on this one map: the same two kernels, the same
+ * workspace, the same return codes; its messages begin with "train-gt unary". */
 int dsrg_train_gt_unary_batch(int G, int C, const float *scores_dev, int h, int w, const int32_t *H_host, const int32_t *W_host,
                               float eps, const int32_t *select_host, const int32_t *nselect_host, int select_stride,
                               float ignore_below, float *workspace_dev, float *const *unary_dev, float *const *probs_dev,
@@ -344,12 +345,12 @@ int dsrg_train_gt_unary_batch(int G, int C, const float *scores_dev, int h, int 
  * arrays of their sizes).  flip = 0: Gcap >= G, image g reads slice g; flip != 0: Gcap >= 2 G, image g reads slice 2g plain and
  * slice 2g+1 mirrored (the slot layout of dsrg_preprocess_rect_mirror_batch).  The M = K * (1 + flip) maps of an image come in the
  * order scale 0 plain, scale 0 mirror, scale 1 plain, ...  Per map: the softmax over labels per MAP pixel and the order-1 zoom of
- * the probabilities to (H_g, W_g), both with the arithmetic of dsrg_train_gt_unary_batch (z_m: blended in double, rounded once to
- * f32); a mirror map is read as flip(map, last axis): coordinates and weights come from the output pixel as for a plain map, only
+ * the probabilities to (H_g, W_g), both with the arithmetic stated at dsrg_train_gt_unary_batch (z_m: blended in double, rounded
+ * once to f32); a mirror map is read as flip(map, last axis): coordinates and weights come from the output pixel as for a plain map, only
  * the four loads address columns w-1-x0 and w-1-x1.  Then in f32, in list order: acc = z_0, acc = acc + z_m; p = acc / (float)M
  * (no division at M = 1); p = max(p, eps).  workspace_dev: sum over k of G * (1 + flip) * C * h_k * w_k floats, the caller's
  * (nothing is allocated here).  Outputs (unary_dev = logf(p), probs_dev = p, labels_dev), their classes, alignment and the
- * selection lists as dsrg_train_gt_unary_batch takes them; K = 1 without flip gives its outputs bit for bit.
+ * selection lists as dsrg_train_gt_unary_batch takes them; K = 1 without flip is that entry point (one launcher, one kernel family).
  * 1 <= K, K * (1 + flip) <= 8; 1 <= G <= 16 without flip, <= 8 with it; 1 <= C <= 96; H_g, W_g, h_k, w_k >= 1, H_g*W_g*C < 2^31,
  * h_k*w_k*C < 2^31; every argument is checked before the first device call.  Two launches whatever K is.  Stream-ordered, no host
  * synchronisation, no handle; bit-reproducible (no atomics), and image g's outputs do not depend on the group. */

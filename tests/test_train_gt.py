@@ -2,7 +2,8 @@
 
 CPU: the argument checks of dsrg_train_gt_unary_batch / dsrg_crf_map_select, the selection helper and `--mode gt` of
 `python -m dsrg_amd.predict`.
-GPU: the softmax-then-zoom unary kernel (a group against single-image calls bit for bit; the probabilities against a float64
+GPU: the softmax-then-zoom unary kernel (a group against single-image calls bit for bit; the wrapper and the C entry point against
+the outputs recorded before the one-map form became the ensemble's K = 1 case, bit for bit; the probabilities against a float64
 restatement with scipy's zoom; the log against the kernel's own probabilities), the selection rule of the unary kernel and of the
 two CRF kernels against numpy on the returned probabilities / marginals (exact), predict_train_gt_many against its staged
 composition (exact), against predict_train_gt and against the reference restated in numpy / scipy (the project's agreement bar)."""
@@ -202,6 +203,37 @@ def test_train_gt_unary_batch_equals_single_image_calls(G):
             assert isinstance(only, list) and all(torch.equal(o, t3[1]) for o, t3 in zip(only, got))
             default = ops.train_gt_unary_batch(scores, shapes, eps=_EPS)                     # want=("unary",): 1-tuples
             assert all(len(o) == 1 and torch.equal(o[0], t3[1]) for o, t3 in zip(default, got))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("G", [1, 3, 16])
+def test_train_gt_unary_batch_gives_the_recorded_outputs(G):
+    """train_gt_unary_batch alone against the outputs its own kernels gave before it became the ensemble's K = 1 case
+    (train_gt_golden_cases; the cases are the loop of test_train_gt_ms.py's
+    test_one_size_without_flip_is_train_gt_unary_batch_bit_for_bit, with that file's shapes and lists)"""
+    import test_train_gt_ms as MS
+    import train_gt_golden_cases as golden
+    from dsrg_amd import _lib, ops
+    from dsrg_amd.crf import select_arrays
+    rng = np.random.default_rng(100 + G)
+    case = 0
+    for C in MS._CS:
+        for h, w in MS._MAPS:
+            case += 1
+            scores = _batched_scores(rng, G + case % 2, C, h, w, case % 3)
+            shapes = [MS._OUT[(case + g) % len(MS._OUT)] for g in range(G)]
+            select = MS._lists(rng, G, C)
+            t = (None, 0.5)[case % 2]
+            got = ops.train_gt_unary_batch(scores, shapes, eps=MS._EPS, want=golden.NAMES, select=select, ignore_below=t)
+            golden.assert_recorded("train_gt_unary_batch", G, case, scores, got)
+            # the C entry point of the one-map form, which the wrapper no longer goes through: G * C * h * w floats of workspace
+            out = ops._want_outputs(golden.NAMES, shapes, C, scores.device)
+            work = torch.empty(G * C * h * w, device="cuda")
+            sel, nsel, stride = select_arrays(select, G, C)
+            ops.check(_lib.lib().dsrg_train_gt_unary_batch(
+                G, C, ops._ptr(scores), h, w, _i32([H for H, _ in shapes]), _i32([W for _, W in shapes]), MS._EPS, sel, nsel, stride,
+                t or 0.0, ops._ptr(work), ops._ptrs(out["unary"]), ops._ptrs(out["probs"]), ops._ptrs(out["labels"]), ops._stream()))
+            golden.assert_recorded("dsrg_train_gt_unary_batch", G, case, scores, list(zip(*(out[n] for n in golden.NAMES))))
 
 
 @pytest.mark.gpu

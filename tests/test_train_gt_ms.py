@@ -3,8 +3,9 @@ generate_train_gt.py as a probability ensemble over K sizes, each optionally wit
 
 CPU: the argument checks of dsrg_train_gt_ensemble_batch, the limits of the gt-ms functions and `--mode gt-ms` of
 `python -m dsrg_amd.predict`.
-GPU: one size without flip against ops.train_gt_unary_batch (bit for bit); the definition restated from the existing kernel's exact
-zoomed probabilities and numpy float32 (bit for bit), the log against the kernel's own probabilities, the labels against the
+GPU: one size without flip against ops.train_gt_unary_batch and both against its outputs recorded before the two shared their
+kernels (bit for bit); the definition restated from the single-map case's exact zoomed probabilities (anchored by that record and
+by test_train_gt.py's float64 restatement) and numpy float32 (bit for bit), the log against the kernel's own probabilities, the labels against the
 selection rule in numpy (exact); a group against single-image calls with NaN in the unused slices; predict_train_gt_ms_many
 against its staged composition (exact), against predict_train_gt_many at one size (exact) and against the torch composition
 predict_train_gt_ms (the project's agreement bar)."""
@@ -134,6 +135,7 @@ def test_gt_ms_limits_raise_before_any_launch():
 
 
 # ---- GPU: the ensemble kernel ------------------------------------------------------------------------------------------------------
+import train_gt_golden_cases as golden                            # noqa: E402
 from test_ms_batched import TinyNet, _batched_scores, _image    # noqa: E402  (shared fixtures)
 
 # w odd, even and small; outputs below 64 pixels, no multiple of 64, several workgroups per image (391 = 6 * 64 + 7: the image
@@ -167,6 +169,8 @@ def _maps(rng, K, Gcap, C, case, kind):
 @pytest.mark.gpu
 @pytest.mark.parametrize("G", [1, 3, 16])
 def test_one_size_without_flip_is_train_gt_unary_batch_bit_for_bit(G):
+    """the two ops against each other, and both against the outputs that train_gt_unary_batch's own kernels gave before it became
+    the ensemble's K = 1 case (train_gt_golden_cases: sha256 of every output, the arrays at C = 5)"""
     from dsrg_amd import ops
     rng = np.random.default_rng(100 + G)
     case = 0
@@ -184,6 +188,8 @@ def test_one_size_without_flip_is_train_gt_unary_batch_bit_for_bit(G):
                 for n, a, b in zip(_NAMES, got[g], want[g]):
                     assert a.shape == b.shape and a.dtype == b.dtype, (n, G, C, g)
                     assert torch.equal(a, b), "%s of image %d differs from train_gt_unary_batch (G %d C %d map %dx%d)" % (n, g, G, C, h, w)
+            golden.assert_recorded("train_gt_ensemble_batch", G, case, scores, got)
+            golden.assert_recorded("train_gt_unary_batch", G, case, scores, want)
     only = ops.train_gt_ensemble_batch([scores], shapes, eps=_EPS, want="unary")                # string form, no lists needed
     assert isinstance(only, list) and all(torch.equal(o, t3[1]) for o, t3 in zip(only, got))
     default = ops.train_gt_ensemble_batch([scores], shapes, eps=_EPS)                          # want=("unary",): 1-tuples
@@ -191,9 +197,10 @@ def test_one_size_without_flip_is_train_gt_unary_batch_bit_for_bit(G):
 
 
 def _restated(scores, shapes, flip, eps):
-    """the definition from code that exists without the ensemble kernel: every z_m exactly, as ops.train_gt_unary_batch(eps=0.0,
-    want="probs") on the slices of map k (the mirror slices through torch.flip), then in numpy float32 and in list order the sum,
-    / M, the clamp -> one (H, W, C) float32 array per image"""
+    """the definition from the single-map case (held to its recorded outputs and to the float64 / scipy restatement of
+    test_train_gt.py): every z_m exactly, as ops.train_gt_unary_batch(eps=0.0, want="probs") on the slices of map k (the mirror
+    slices through torch.flip), then in numpy float32 and in list order the sum, / M, the clamp -> one (H, W, C) float32 array per
+    image"""
     from dsrg_amd import ops
     G, per = len(shapes), 2 if flip else 1
     zs = []                                                           # zs[m][g], m in list order

@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 WRAPPERS = ("multiscale_unary", "multiscale_unary_batch", "multiscale_unary_mirror_batch", "preprocess_ms_batch",
-            "preprocess_rect_batch", "preprocess_rect_mirror_batch", "train_gt_unary_batch")
+            "preprocess_rect_batch", "preprocess_rect_mirror_batch", "train_gt_unary_batch", "train_gt_ensemble_batch")
 
 
 def _count_calls(ops, counts):

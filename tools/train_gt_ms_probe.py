@@ -3,12 +3,12 @@
 
   (a) the fused tail (ops.train_gt_ensemble_batch, want="unary") against the composition it replaces, at the workload's shapes (21
       labels, 375 x 500 images, the fc8 maps of the sizes 241 / 321 / 401), with and without flip, for 1 and 8 images: the
-      composition is M calls of the existing kernel (ops.train_gt_unary_batch, eps = 0, want="probs"; the mirror slices through
-      torch.flip) plus the torch sum, divide, clamp and log per image.  Device-event medians, every shape warmed first, the two
+      composition is M calls of the one-map case (ops.train_gt_unary_batch, eps = 0, want="probs": the same kernels at K = 1; the
+      mirror slices through torch.flip) plus the torch sum, divide, clamp and log per image.  Device-event medians, every shape warmed first, the two
       sides alternating; the spread is (max - min) / median over the rounds.  The two sides' outputs are compared first.
   (b) images/s of the pass with --smooth on seeded synthetic 375 x 500 images, VGG16-ASPP under bf16 autocast, graphed forwards,
-      forward_batch 8, CRFs in flight: gt at 321 (predict_train_gt_many), gt-ms at 241,321,401 and the same with flip
-      (predict_train_gt_ms_many); the three alternate, three windows each, host clock around a window that ends in a device
+      forward_batch 8, CRFs in flight: gt at 321 (predict_train_gt_many: predict_train_gt_ms_many at that one size), gt-ms at
+      241,321,401 and the same with flip (predict_train_gt_ms_many); the three alternate, three windows each, host clock around a window that ends in a device
       synchronise.
 
 usage: python tools/train_gt_ms_probe.py [a|b ...] [--out FILE]     (default: both; FILE: profiles/train_gt_ms_probe.txt)

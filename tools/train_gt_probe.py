@@ -6,10 +6,12 @@
       indexing) alternating with inference.predict_train_gt_many(forward_batch=8, in_flight=3) at CRF batch = 1 and 8 (forwards
       replayed from one batch-8 graph).  Host clock around a window that ends in a device synchronise, every shape warmed first,
       three repeats each.
-  (b) device-event medians of one group's dsrg_train_gt_unary_batch (8 images of 375 x 500, 41 x 41 maps) against the torch
-      composition it replaces (softmax, fp64 zoom, clamp, log, permute per image), and of the restricted MAP
+  (b) device-event medians of one group's tail, ops.train_gt_unary_batch (8 images of 375 x 500, 41 x 41 maps: the pseudo-label
+      kernels of train_gt.hip at one map per image, train_gt_ms_softmax_kernel and train_gt_ms_zoom_kernel<1, false>) against the
+      torch composition it replaces (softmax, fp64 zoom, clamp, log, permute per image), and of the restricted MAP
       (CRF_device(want="map", select=...)) against marginals + torch indexing on one 375 x 500 image.
-  (k) a short run of both new kernels and nothing else, for `rocprofv3 --kernel-trace --stats -- python tools/train_gt_probe.py k`.
+  (k) a short run of the tail's two kernels and the selection kernels and nothing else, for `rocprofv3 --kernel-trace --stats --
+      python tools/train_gt_probe.py k`.
 
 usage: python tools/train_gt_probe.py [a|b|k ...]     (default: a b; one JSON line at the end)
 """
@@ -160,7 +162,7 @@ def probe_b(G=8, C=21):
 
 
 def probe_k(G=8, C=21):
-    """only the new kernels (and the CRF the selection kernel follows): for a kernel trace"""
+    """only the tail's kernels at one map per image (and the CRF the selection kernel follows): for a kernel trace"""
     from dsrg_amd import ops
     from dsrg_amd.crf import CRF_device
     scores, im, unary = _kernel_inputs(G, C)
