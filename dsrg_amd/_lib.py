@@ -106,6 +106,8 @@ SIGNATURES = {
                                           [ctypes.POINTER(_f), ctypes.POINTER(_vp), _vp]),
     "dsrg_train_s_input_batch": (_i, [_i, _vp, _sz] + [ctypes.POINTER(ctypes.c_int32)] * 8 + [_i, _i, _i, _i, ctypes.POINTER(_f),
                                       _vp, _vp, _vp, _vp]),
+    "dsrg_train_s_cuemap_input_batch": (_i, [_i, _vp, _sz] + [ctypes.POINTER(ctypes.c_int32)] * 5 + [_i, _i, _i, _i, _i,
+                                             ctypes.POINTER(_f), _i, _i, _vp, _vp, _vp, _vp]),
     "dsrg_train_f_input_batch": (_i, [_i, _vp, _sz] + [ctypes.POINTER(ctypes.c_int32)] * 7 + [_i, _i, ctypes.POINTER(_f), _f, _f,
                                       _vp, _vp, _vp]),
     "dsrg_train_f_input_scaled_batch": (_i, [_i, _vp, _sz] + [ctypes.POINTER(ctypes.c_int32)] * 9 + [_i, _i, ctypes.POINTER(_f), _f, _f,

@@ -562,6 +562,14 @@ extern "C" int dsrg_train_s_input_batch(int B, const unsigned char *stage, size_
     return launch_train_s_input_batch(B, stage, stage_bytes, image_off, H, W, cue_off, ncues, label_off, nlabels, mirror, S, C, Hm, Wm,
                                       mean, images, cues, labels, static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_train_s_cuemap_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off,
+                                               const int32_t *H, const int32_t *W, const int32_t *cue_off, const int32_t *mirror, int Sh,
+                                               int Sw, int C, int Hm, int Wm, const float *mean, int ignore_label, int bgr, float *images,
+                                               float *cues, float *labels, void *stream) {
+    // AnnotationLayerCOCO (pylayers.py:432-512); every argument is checked before the first device call
+    return launch_train_s_cuemap_input_batch(B, stage, stage_bytes, image_off, H, W, cue_off, mirror, Sh, Sw, C, Hm, Wm, mean, ignore_label,
+                                             bgr, images, cues, labels, static_cast<hipStream_t>(stream));
+}
 extern "C" int dsrg_train_f_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off,
                                         const int32_t *label_off, const int32_t *H, const int32_t *W, const int32_t *top,
                                         const int32_t *left, const int32_t *mirror, int ch, int cw, const float *mean, float scale,

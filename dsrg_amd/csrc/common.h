@@ -137,6 +137,37 @@ __device__ __forceinline__ float max_label_value(const float *__restrict__ v, si
 }
 int check_select_list(const char *who, int image, const int32_t *sel, int n, int stride, int C);
 
+// ---- the order-1 align-corners zoom of an (H, W, 3) uint8 image (scipy.ndimage.zoom(order=1); stated at the top of preprocess.hip) ----
+// Shared by preprocess_rect_batch_kernel (preprocess.hip) and train_s_cuemap_input_kernel (train_input.hip).
+// source coordinates per output coordinate on an axis of `in` source and `out` output samples: one IEEE double division, the same
+// bits from the host and from the device
+__host__ __device__ __forceinline__ double zoom_axis_scale(int in, int out) { return out > 1 ? (double)(in - 1) / (double)(out - 1) : 0.0; }
+// the four taps and the four weights of output pixel (y, x); the taps are inside the image whatever the coordinates' fractions.
+// Two steps, weights then pointers, so that a caller loads its image pointer where preprocess_rect_batch_kernel always has
+struct ZoomTaps {
+    int y0, x0, y1, x1;
+    double l0h, l1h, l0w, l1w;
+    const unsigned char *p00, *p01, *p10, *p11;
+};
+__device__ __forceinline__ ZoomTaps zoom_taps(int H, int W, double sh, double sw, int y, int x) {
+    ZoomTaps t;
+    const double sy = sh * (double)y, sx = sw * (double)x;
+    t.y0 = (int)sy, t.x0 = (int)sx;
+    t.y1 = t.y0 + (t.y0 < H - 1 ? 1 : 0), t.x1 = t.x0 + (t.x0 < W - 1 ? 1 : 0);
+    t.l1h = sy - (double)t.y0, t.l1w = sx - (double)t.x0;
+    t.l0h = 1.0 - t.l1h, t.l0w = 1.0 - t.l1w;
+    return t;
+}
+__device__ __forceinline__ void zoom_point(ZoomTaps &t, const unsigned char *im, int W) {
+    t.p00 = im + ((size_t)t.y0 * W + t.x0) * 3, t.p01 = im + ((size_t)t.y0 * W + t.x1) * 3;
+    t.p10 = im + ((size_t)t.y1 * W + t.x0) * 3, t.p11 = im + ((size_t)t.y1 * W + t.x1) * 3;
+}
+// source channel ch at the output pixel: the two-tap blend in double, rounded once to f32
+__device__ __forceinline__ float zoom_blend(const ZoomTaps &t, int ch) {
+    const double v00 = t.p00[ch], v01 = t.p01[ch], v10 = t.p10[ch], v11 = t.p11[ch];
+    return (float)(t.l0h * (t.l0w * v00 + t.l1w * v01) + t.l1h * (t.l0w * v10 + t.l1w * v11));
+}
+
 // ---- the pseudo-label tail (train_gt.hip: the ensemble of M maps per image; one map is its K = 1, no-flip case) ---------------------
 constexpr int kTgPix = 64;        // output pixels per workgroup
 constexpr int kTgThreads = 256;
@@ -298,6 +329,10 @@ int launch_train_s_input_batch(int B, const unsigned char *stage, size_t stage_b
                                const int32_t *W, const int32_t *cue_off, const int32_t *ncues, const int32_t *label_off,
                                const int32_t *nlabels, const int32_t *mirror, int S, int C, int Hm, int Wm, const float *mean,
                                float *images, float *cues, float *labels, hipStream_t stream);
+int launch_train_s_cuemap_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *H,
+                                      const int32_t *W, const int32_t *cue_off, const int32_t *mirror, int Sh, int Sw, int C, int Hm,
+                                      int Wm, const float *mean, int ignore_label, int bgr, float *images, float *cues, float *labels,
+                                      hipStream_t stream);
 int launch_train_f_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *label_off,
                                const int32_t *H, const int32_t *W, const int32_t *top, const int32_t *left, const int32_t *mirror,
                                int ch, int cw, const float *mean, float scale, float ignore_label, float *data, float *label,

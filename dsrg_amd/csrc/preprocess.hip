@@ -53,22 +53,11 @@ __global__ __launch_bounds__(kPpThreads) void preprocess_rect_batch_kernel(PpArg
         return;
     }
     const int H = a.H[g], W = a.W[g];
-    const double sh = h > 1 ? (double)(H - 1) / (double)(h - 1) : 0.0;
-    const double sw = w > 1 ? (double)(W - 1) / (double)(w - 1) : 0.0;
-    const double sy = sh * (double)y, sx = sw * (double)x;
-    const int y0 = (int)sy, x0 = (int)sx;
-    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    const double l1h = sy - (double)y0, l1w = sx - (double)x0;
-    const double l0h = 1.0 - l1h, l0w = 1.0 - l1w;
-    const unsigned char *im = a.im[g];
-    const unsigned char *p00 = im + ((size_t)y0 * W + x0) * 3, *p01 = im + ((size_t)y0 * W + x1) * 3;
-    const unsigned char *p10 = im + ((size_t)y1 * W + x0) * 3, *p11 = im + ((size_t)y1 * W + x1) * 3;
+    ZoomTaps t = zoom_taps(H, W, zoom_axis_scale(H, h), zoom_axis_scale(W, w), y, x);    // (common.h)
+    zoom_point(t, a.im[g], W);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {                           // output channel c = input channel 2 - c (BGR)
-        const double v00 = p00[2 - c], v01 = p01[2 - c], v10 = p10[2 - c], v11 = p11[2 - c];
-        const float z = (float)(l0h * (l0w * v00 + l1w * v01) + l1h * (l0w * v10 + l1w * v11));
-        o[c * hw] = z - a.mean[c];
-    }
+    for (int c = 0; c < 3; ++c)                             // output channel c = input channel 2 - c (BGR)
+        o[c * hw] = zoom_blend(t, 2 - c) - a.mean[c];
 }
 
 // The mirror form.  The index space is (image or zero slot, y, x) with Gcap - G entries on its first axis: the G images (entry g

@@ -27,9 +27,22 @@
 // mirror as in train_f_input_kernel.  Hs = H, Ws = W reproduces train_f_input_kernel bit for bit.  The two scales of an image ride
 // in the argument block beside Hs and Ws (the launcher divides once per image; the threads would each divide four times).
 //
-// All: loads are issued unconditionally on clamped indices and selected afterwards; no atomics, no scratch, no LDS, no dependence on
-// the order of workgroups (every output element has exactly one owner; duplicate cue triplets write the same value behind the
-// owner's barrier); -ffp-contract=off (Makefile).  Results are bit-reproducible.
+// train_s_cuemap_input_kernel (stage 1 fed by cue MAPS): AnnotationLayerCOCO (pylayers.py:432-512) for B images: per image an
+// (H, W, 3) RGB image and an (Hm, Wm) map of cue bytes, `ignore_label` = no cue.  One launch, three block ranges:
+//   blocks [0, cue0): one thread owns one output pixel of one image (its three channels): the order-1 align-corners zoom of
+//     preprocess_rect_batch_kernel to Sh x Sw (zoom_taps / zoom_blend of common.h, the code that kernel runs; the two scales of
+//     an image are divided once by the launcher and ride in the argument block), minus the mean in f32.  Output channel c reads
+//     source byte 2 - c with `bgr` (what every other pipeline of this project feeds the net) and byte c without (the layer's
+//     own order).
+//   blocks [cue0, lab0): one thread owns one map pixel of one image: it loads the byte v and walks the C planes, storing 1.0 to
+//     plane v and 0.0 to the others (all 0.0 where v == ignore_label or v >= C), so a wave's stores run along x within a plane.
+//   blocks [lab0, lab0 + B): one workgroup owns the image-level labels of one image: C flags in LDS, cleared, barrier, set by
+//     plain same-value stores for every kept byte of the map, barrier, written out as C floats.  Class 0 is not forced on.
+//   The mirror flag writes pixels and cue planes to the mirrored column; the labels do not depend on it.
+//
+// All: loads are issued unconditionally on clamped indices and selected afterwards; no atomics, no scratch, no dependence on the
+// order of workgroups (every output element has exactly one owner; duplicate cue triplets write the same value behind the owner's
+// barrier); LDS only for the C label flags of the cue-map kernel; -ffp-contract=off (Makefile).  Results are bit-reproducible.
 #include <string.h>
 #include "common.h"
 
@@ -245,6 +258,107 @@ int launch_train_s_input_batch(int B, const unsigned char *stage, size_t stage_b
         return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: %lld workgroups >= 2^24 (pixel blocks + B * C planes)", blocks);
     hipLaunchKernelGGL(train_s_input_kernel, dim3((unsigned)blocks), dim3(kTiThreads), 0, stream, stage, a, B, S, C, Hm, Wm, cue0, images,
                        cues, labels);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
+struct TcArgs {
+    int img_off[kTiMaxBatch], H[kTiMaxBatch], W[kTiMaxBatch];       // (H, W, 3) RGB uint8 at stage + img_off
+    int cue_off[kTiMaxBatch];                                       // (Hm, Wm) uint8 cue bytes at stage + cue_off
+    double sh[kTiMaxBatch], sw[kTiMaxBatch];                        // zoom_axis_scale(H, Sh), zoom_axis_scale(W, Sw): divided once, on the host
+    unsigned mirror;                                                // bit b: image b is mirrored
+    float mean[3];                                                  // of the OUTPUT channels
+};
+
+__global__ __launch_bounds__(kTiThreads) void train_s_cuemap_input_kernel(const unsigned char *__restrict__ stage, TcArgs a, int B, int Sh,
+                                                                          int Sw, int C, int Hm, int Wm, int ignore_label, int bgr,
+                                                                          int cue0, int lab0, float *__restrict__ images,
+                                                                          float *__restrict__ cues, float *__restrict__ labels) {
+    __shared__ int present[kMaxLabels];
+    const int blk = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int HW = Hm * Wm;
+    if (blk < cue0) {                                                                       // (uniform over the block)
+        const int SS = Sh * Sw;
+        const int idx = blk * kTiThreads + tid;                                             // (image, y, x) flattened: < B * Sh * Sw < 2^31 / 3
+        if (idx >= B * SS) return;
+        const int b = idx / SS, r = idx - b * SS;
+        const int y = r / Sw, x = r - y * Sw;
+        ZoomTaps t = zoom_taps(a.H[b], a.W[b], a.sh[b], a.sw[b], y, x);
+        zoom_point(t, stage + a.img_off[b], a.W[b]);
+        const int xo = ((a.mirror >> b) & 1u) ? Sw - 1 - x : x;
+        float *o = images + (size_t)b * 3 * SS + (size_t)y * Sw + xo;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c * SS] = zoom_blend(t, bgr ? 2 - c : c) - a.mean[c];
+        return;
+    }
+    if (blk < lab0) {
+        const int idx = (blk - cue0) * kTiThreads + tid;                                    // (image, y, x) flattened: < B * Hm * Wm
+        if (idx >= B * HW) return;
+        const int b = idx / HW, r = idx - b * HW;
+        const int y = r / Wm, x = r - y * Wm;
+        const int v = (int)stage[(size_t)a.cue_off[b] + r];
+        const int own = (v != ignore_label && v < C) ? v : -1;                              // the plane that takes this pixel's 1.0
+        const int xo = ((a.mirror >> b) & 1u) ? Wm - 1 - x : x;
+        float *o = cues + (size_t)b * C * HW + (size_t)y * Wm + xo;
+        for (int c = 0; c < C; ++c) o[(size_t)c * HW] = c == own ? 1.0f : 0.0f;
+        return;
+    }
+    const int b = blk - lab0;                                                               // < B
+    for (int c = tid; c < C; c += kTiThreads) present[c] = 0;                               // (C <= kMaxLabels: checked by the launcher)
+    __syncthreads();
+    const unsigned char *m = stage + a.cue_off[b];
+    for (int i = tid; i < HW; i += kTiThreads) {
+        const int v = (int)m[i];
+        if (v != ignore_label && v < C) present[v] = 1;                                     // same-value stores: any order gives the same flags
+    }
+    __syncthreads();
+    for (int c = tid; c < C; c += kTiThreads) labels[(size_t)b * C + c] = present[c] ? 1.0f : 0.0f;
+}
+
+int launch_train_s_cuemap_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *H,
+                                      const int32_t *W, const int32_t *cue_off, const int32_t *mirror, int Sh, int Sw, int C, int Hm,
+                                      int Wm, const float *mean, int ignore_label, int bgr, float *images, float *cues, float *labels,
+                                      hipStream_t stream) {
+    if (B < 1 || B > kTiMaxBatch) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: 1..%d images, got %d", kTiMaxBatch, B);
+    if (!stage) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL staging buffer");
+    if (!image_off || !H || !W) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL image offset / image size array");
+    if (!cue_off) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL cue offset array");
+    if (!mirror || !mean) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL mirror / mean array");
+    if (!images) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL images output");
+    if (!cues) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL cues output");
+    if (!labels) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL labels output");
+    if (((uintptr_t)images | (uintptr_t)cues | (uintptr_t)labels) & 3)
+        return set_error(DSRG_ERR_INVALID, "train-s cue-map input: an output is not aligned to a float");
+    if (Sh < 1 || Sw < 1 || C < 1 || Hm < 1 || Wm < 1)
+        return set_error(DSRG_ERR_INVALID, "train-s cue-map input: size %dx%d, %d classes, %dx%d maps", Sh, Sw, C, Hm, Wm);
+    if (C > kMaxLabels) return set_error(DSRG_ERR_UNSUPPORTED, "train-s cue-map input: %d classes, at most %d", C, kMaxLabels);
+    if (ignore_label < 0 || ignore_label > 255)
+        return set_error(DSRG_ERR_INVALID, "train-s cue-map input: ignore_label %d is no byte value", ignore_label);
+    if (bgr != 0 && bgr != 1) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: bgr must be 0 or 1, got %d", bgr);
+    if (stage_bytes >= ((size_t)1 << 31)) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: staging buffer holds >= 2^31 bytes");
+    if ((long long)Sh * Sw >= (1LL << 31) || (long long)B * 3 * Sh * Sw >= (1LL << 31))
+        return set_error(DSRG_ERR_INVALID, "train-s cue-map input: images hold >= 2^31 values (%d x 3 x %d x %d)", B, Sh, Sw);
+    if ((long long)Hm * Wm >= (1LL << 31) || (long long)B * C * Hm * Wm >= (1LL << 31))
+        return set_error(DSRG_ERR_INVALID, "train-s cue-map input: cues hold >= 2^31 values (%d x %d x %d x %d)", B, C, Hm, Wm);
+    TcArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int b = 0; b < B; ++b) {
+        if (H[b] < 1 || W[b] < 1) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: image %d is %dx%d", b, H[b], W[b]);
+        if ((long long)H[b] * W[b] * 3 >= (1LL << 31))
+            return set_error(DSRG_ERR_INVALID, "train-s cue-map input: image %d holds >= 2^31 values", b);
+        if (!inside(image_off[b], (long long)H[b] * W[b] * 3, stage_bytes))
+            return set_error(DSRG_ERR_INVALID, "train-s cue-map input: image %d lies outside the staging buffer", b);
+        if (!inside(cue_off[b], (long long)Hm * Wm, stage_bytes))
+            return set_error(DSRG_ERR_INVALID, "train-s cue-map input: cue map %d lies outside the staging buffer", b);
+        a.img_off[b] = image_off[b], a.H[b] = H[b], a.W[b] = W[b], a.cue_off[b] = cue_off[b];
+        a.sh[b] = zoom_axis_scale(H[b], Sh), a.sw[b] = zoom_axis_scale(W[b], Sw);
+        if (mirror[b]) a.mirror |= 1u << b;
+    }
+    for (int c = 0; c < 3; ++c) a.mean[c] = mean[c];
+    const int cue0 = (int)(((long long)B * Sh * Sw + kTiThreads - 1) / kTiThreads);          // < 2^23
+    const int lab0 = cue0 + (int)(((long long)B * Hm * Wm + kTiThreads - 1) / kTiThreads);   // < 2^24
+    hipLaunchKernelGGL(train_s_cuemap_input_kernel, dim3((unsigned)(lab0 + B)), dim3(kTiThreads), 0, stream, stage, a, B, Sh, Sw, C, Hm, Wm,
+                       ignore_label, bgr, cue0, lab0, images, cues, labels);
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
 }

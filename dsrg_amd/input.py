@@ -2,6 +2,9 @@
 
   TrainSInput  <-> Caffe's ImageData layer (train-s.prototxt:3-22) + AnnotationLayer (pylayers.py:346-387)
   TrainFInput  <-> ImageSegDataLayer (layer.py:17-251; train-f.prototxt:3-14)
+  TrainSCueMapInput <-> AnnotationLayerCOCO (pylayers.py:432-512): stage 1 fed by 'image_path cue_path' lists, the cue a small
+                   label map (255 = no cue) — any class count up to 96; assembled by ops.train_s_cuemap_input_batch
+                   (`layout_train_s_cuemap`, `pack_train_s_cuemap`, `check_cue_map`); order and mirror draws as TrainSInput's
 
 The host decodes files (PIL, on a thread pool), packs the raw bytes of a batch — uint8 pixels, uint8 labels, int32 cue triplets
 and class ids — into ONE pinned staging buffer and uploads it with one copy; the batch itself (resize, BGR, mean, cue planes,
@@ -29,6 +32,7 @@ import numpy as np
 from .data import SimpleTransformer, _Window, check_scale_factors, scaled_size
 
 MAX_BATCH = 32                                   # images per launch (dsrg_train_s_input_batch / dsrg_train_f_input_batch)
+MAX_CLASSES = 96                                 # kMaxLabels of the library: the layer and CRF kernels keep at most this many labels
 
 
 def _align(n):
@@ -141,6 +145,59 @@ def pack_train_s(buf, desc, images, cues, labels):
         buf[o:o + 12 * K].view(np.int32)[:] = np.asarray(cue, dtype=np.int32).reshape(-1)
         o, L = desc["label_off"][b], desc["nlabels"][b]
         buf[o:o + 4 * L].view(np.int32)[:] = np.asarray(lab, dtype=np.int32).reshape(-1)
+
+
+def check_cue_map(cue, num_classes, map_size, ignore_label=255, name="cue map"):
+    """a decoded cue map is what dsrg_train_s_cuemap_input_batch takes: (Hm, Wm) uint8 of exactly map_size (cue maps are never
+    resampled, as in AnnotationLayerCOCO) whose bytes are classes below num_classes or ignore_label (the layer's one-hot scatter
+    would raise IndexError on any other; the kernel's own guard only keeps bad data in bounds).  ValueError names `name`."""
+    if cue.dtype != np.uint8 or cue.ndim != 2:
+        raise ValueError("%s: a cue map must be a 2-d uint8 array, got %s %s" % (name, cue.dtype, cue.shape))
+    if tuple(cue.shape) != (int(map_size[0]), int(map_size[1])):
+        raise ValueError("%s: the cue map is %d x %d, the net's map is %d x %d (cue maps are not resampled)"
+                         % ((name,) + tuple(cue.shape) + (int(map_size[0]), int(map_size[1]))))
+    bad = (cue >= num_classes) & (cue != ignore_label)
+    if bad.any():
+        raise ValueError("%s: cue value %d is neither one of %d classes nor the ignore label %d"
+                         % (name, int(cue[bad].min()), num_classes, ignore_label))
+
+
+def layout_train_s_cuemap(shapes, map_size, mirror=None):
+    """where the pieces of a cue-map stage-1 batch lie in its staging buffer.  shapes: (H, W) per image; map_size: the (Hm, Wm)
+    every cue map has -> (bytes, desc): desc is the dict of per-image lists ops.train_s_cuemap_input_batch takes (and Hm, Wm)."""
+    n = len(shapes)
+    Hm, Wm = int(map_size[0]), int(map_size[1])
+    if Hm < 1 or Wm < 1:
+        raise ValueError("a cue map of %d x %d pixels" % (Hm, Wm))
+    desc = dict(image_off=[], H=[], W=[], cue_off=[], mirror=[0] * n if mirror is None else [int(bool(m)) for m in mirror],
+                Hm=Hm, Wm=Wm)
+    if len(desc["mirror"]) != n:
+        raise ValueError("one mirror flag per image, got %d for %d images" % (len(desc["mirror"]), n))
+    off = 0
+    for H, W in shapes:
+        if H < 1 or W < 1:
+            raise ValueError("an image of %d x %d pixels" % (H, W))
+        desc["image_off"].append(off), desc["H"].append(int(H)), desc["W"].append(int(W))
+        off = _align(off + H * W * 3)
+        desc["cue_off"].append(off)
+        off = _align(off + Hm * Wm)
+    _check_batch(n, off)
+    return off, desc
+
+
+def pack_train_s_cuemap(buf, desc, images, cue_maps):
+    """write the batch's raw bytes into buf: images (H, W, 3) uint8 RGB, cue maps (Hm, Wm) uint8"""
+    Hm, Wm = desc["Hm"], desc["Wm"]
+    for b, (im, cue) in enumerate(zip(images, cue_maps)):
+        H, W = desc["H"][b], desc["W"][b]
+        if im.dtype != np.uint8 or im.shape != (H, W, 3):
+            raise ValueError("image %d must be (%d, %d, 3) uint8" % (b, H, W))
+        if cue.dtype != np.uint8 or cue.shape != (Hm, Wm):
+            raise ValueError("cue map %d must be (%d, %d) uint8" % (b, Hm, Wm))
+        o = desc["image_off"][b]
+        buf[o:o + im.size] = im.reshape(-1)
+        o = desc["cue_off"][b]
+        buf[o:o + cue.size] = cue.reshape(-1)
 
 
 def layout_train_f(shapes, top, left, mirror, scaled=None):
@@ -398,6 +455,91 @@ class TrainSInput(_StagedLoader):
         from . import ops
         return ops.train_s_input_batch(slot.dev, slot.desc, self.size, self.num_classes, self.map_size, self.mean,
                                        out=slot.outputs, nbytes=slot.nbytes)
+
+
+def read_pair_list(path):
+    """'image_path cue_path' lines (AnnotationLayerCOCO's `source`) -> [(image_path, cue_path)]"""
+    out = []
+    with open(path) as f:
+        for line in f:
+            parts = line.split()
+            if parts:
+                if len(parts) < 2:
+                    raise ValueError("%s: expected 'image_path cue_path', got %r" % (path, line.strip()))
+                out.append((parts[0], parts[1]))
+    if not out:
+        raise ValueError("%s lists no image / cue map pair" % path)
+    return out
+
+
+class TrainSCueMapInput(_StagedLoader):
+    """Iterator of (images (B,3,Sh,Sw), labels (B,1,1,C), cues (B,C,Hm,Wm)) float32 device tensors for DSRGTrainer.step:
+    AnnotationLayerCOCO (pylayers.py:432-512), the feeder of the 81-class runs, assembled on the device by
+    ops.train_s_cuemap_input_batch.
+
+    list_file: 'image_path cue_path' lines; `root` is prefixed to both as it stands (as TrainFInput and the layer do).  A cue file
+    is a one-channel image of exactly map_size = (Sh // 8 + 1, Sw // 8 + 1) — the layer's top[1]; cue maps are never resampled —
+    whose bytes are classes below num_classes or ignore_label (no cue); the image-level labels are the classes the map names
+    (class 0 is not forced on; a map without a cue gives all zeros).  size: an int or (h, w): the images are zoomed to it
+    (scipy.ndimage.zoom, order 1).  bgr: the channel order of the network input — True, B G R with `mean` in that order, is what
+    every other pipeline of this project feeds the net; False is the layer's own R G B (`mean` is always in the OUTPUT order).
+    Epochs: file order first, reshuffled after each pass when `shuffle` (the layer's order, from a random.Random(seed) of the
+    loader's own); the list wraps mid-batch; with world_size > 1 every rank shuffles identically and takes items rank, rank +
+    world_size, ... of the epoch.  Mirror: one RandomState(seed).choice(2) per image in batch order, 0 = mirror (the layer's
+    choice(2) * 2 - 1).  A cue file of another size or with a byte that is neither a class nor ignore_label raises ValueError
+    naming the file when its batch is laid out, before any upload.  The tensors of batch n are valid until the __next__ call
+    after next (_StagedLoader)."""
+
+    def __init__(self, list_file, root, num_classes, batch_size=20, size=321, mean=(104.0, 117.0, 123.0), mirror=True,
+                 ignore_label=255, bgr=True, shuffle=True, seed=0, workers=8, rank=0, world_size=1, device=None):
+        _StagedLoader.__init__(self, batch_size, workers, device)
+        self.num_classes = int(num_classes)
+        if not 1 <= self.num_classes <= MAX_CLASSES:
+            raise ValueError("num_classes must be 1..%d, got %d" % (MAX_CLASSES, self.num_classes))
+        self.size = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+        if min(self.size) < 1:
+            raise ValueError("size %r" % (size,))
+        self.map_size = (self.size[0] // 8 + 1, self.size[1] // 8 + 1)
+        self.ignore_label = int(ignore_label)
+        if not 0 <= self.ignore_label <= 255:
+            raise ValueError("ignore_label must be a byte value, got %d" % self.ignore_label)
+        if len(mean) != 3:
+            raise ValueError("mean must hold 3 values")
+        self.mean, self.mirror, self.bgr, self.root = tuple(float(m) for m in mean), bool(mirror), bool(bgr), root
+        self.entries = read_pair_list(list_file)
+        self._items = epoch_items(self.entries, shuffle, random.Random(seed), rank, world_size)
+        self._mirror_rng = np.random.RandomState(seed)
+
+    def plan_batch(self):
+        plan = []
+        for _ in range(self.batch_size):
+            image_path, cue_path = next(self._items)
+            plan.append(dict(image=self.root + image_path, cue=self.root + cue_path,
+                             mirror=bool(self.mirror) and int(self._mirror_rng.choice(2)) == 0))
+        return plan
+
+    def _decode(self, item):
+        return read_rgb(item["image"]), read_gray(item["cue"])
+
+    def _layout(self, plan, arrays):
+        images, cue_maps = [a[0] for a in arrays], [a[1] for a in arrays]
+        for item, cue in zip(plan, cue_maps):                           # a bad cue file raises here, before any upload
+            check_cue_map(cue, self.num_classes, self.map_size, self.ignore_label, item["cue"])
+        nbytes, desc = layout_train_s_cuemap([a.shape[:2] for a in images], self.map_size, [item["mirror"] for item in plan])
+        return nbytes, desc, (images, cue_maps)
+
+    def _pack(self, buf, desc, pieces):
+        pack_train_s_cuemap(buf, desc, *pieces)
+
+    def _outputs(self, torch):
+        B, C, (Sh, Sw), (Hm, Wm) = self.batch_size, self.num_classes, self.size, self.map_size
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)      # noqa: E731
+        return mk(B, 3, Sh, Sw), mk(B, 1, 1, C), mk(B, C, Hm, Wm)
+
+    def _assemble(self, slot):
+        from . import ops
+        return ops.train_s_cuemap_input_batch(slot.dev, slot.desc, self.size, self.num_classes, self.map_size, self.mean,
+                                              self.ignore_label, self.bgr, out=slot.outputs, nbytes=slot.nbytes)
 
 
 class TrainFInput(_StagedLoader):

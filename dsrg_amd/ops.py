@@ -752,6 +752,34 @@ def train_s_input_batch(stage, desc, size=321, num_classes=21, map_size=(41, 41)
     return images, labels, cues
 
 
+def train_s_cuemap_input_batch(stage, desc, size, num_classes, map_size, mean, ignore_label=255, bgr=True, out=None, nbytes=None):
+    """The stage-1 training batch of a run fed by cue maps, in one launch (dsrg_train_s_cuemap_input_batch): AnnotationLayerCOCO
+    (pylayers.py:432-512).  stage: the batch's raw bytes as a 1-d uint8 CUDA tensor (input.pack_train_s_cuemap); desc: the dict of
+    per-image lists input.layout_train_s_cuemap returns — image_off, H, W, cue_off, mirror.  size: the (h, w) the images are zoomed
+    to (an int: square), as preprocess_rect_batch zooms; map_size: the (Hm, Wm) of every cue map; a cue byte counts unless it is
+    ignore_label or >= num_classes; bgr: output channel c is source byte 2 - c (the order of this project's other pipelines) or,
+    False, byte c (the layer's own).  Returns (images (B,3,h,w), labels (B,1,1,C), cues (B,C,Hm,Wm)), float32, every element
+    written: the arguments of DSRGTrainer.step.  out: three existing tensors of those shapes to write into.  The launch takes no
+    scratch.  Runs on torch's current stream."""
+    nbytes = _stage_arg(stage, nbytes)
+    B = len(desc["H"])
+    Sh, Sw = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    C, (Hm, Wm) = int(num_classes), (int(map_size[0]), int(map_size[1]))
+    if len(mean) != 3:
+        raise ValueError("mean must hold 3 values")
+    keys = ("image_off", "H", "W", "cue_off", "mirror")
+    if any(len(desc[k]) != B for k in keys):
+        raise ValueError("every descriptor list must hold one entry per image")
+    out = (None, None, None) if out is None else out
+    images = _out_arg(out[0], (B, 3, Sh, Sw), "out[0]", stage.device)
+    labels = _out_arg(out[1], (B, 1, 1, C), "out[1]", stage.device)
+    cues = _out_arg(out[2], (B, C, Hm, Wm), "out[2]", stage.device)
+    check(_lib.lib().dsrg_train_s_cuemap_input_batch(B, _ptr(stage), nbytes, *[_i32s(desc[k]) for k in keys], Sh, Sw, C, Hm, Wm,
+                                                     (ctypes.c_float * 3)(*[float(m) for m in mean]), int(ignore_label),
+                                                     int(bool(bgr)), _ptr(images), _ptr(cues), _ptr(labels), _stream()))
+    return images, labels, cues
+
+
 def train_f_input_batch(stage, desc, crop_size, mean, scale=1.0, ignore_label=255, out=None, nbytes=None):
     """The stage-2 training batch in one launch (dsrg_train_f_input_batch): data.SimpleTransformer.preprocess (layer.py:169-236) for
     every image of the batch.  stage: the batch's raw bytes as a 1-d uint8 CUDA tensor (input.pack_train_f); desc: the dict of

@@ -2,7 +2,12 @@
 
   --mode ms    <-> training/tools/test-ms.py    (absolute sizes, default 241,321,401; pseudo labels)
   --mode ms-f  <-> training/tools/test-ms-f.py  (sizes relative to each image, default 0.75,1,1.25; the final test)
-  --mode ms --scales 481 --class 81  <-> training/tools/test-coco.py:108-135 (single-scale COCO test)
+  --mode ms --scales 481 --class 81  <-> training/tools/test-coco.py:108-135 (single-scale COCO test).  Channel order: that script
+               reads with pylab.imread (RGB) and swaps [2, 1, 0] (test-coco.py:101, 110), so it feeds B G R, as every mode here
+               does.  The reference's COCO TRAINING layer feeds the other order (AnnotationLayerCOCO, pylayers.py:456, 489:
+               cv2.imread gives BGR, the same swap makes it RGB).  `python -m dsrg_amd.train --stage s --cue-maps --class 81`
+               feeds B G R by default, so a model trained here matches this command; one trained with --channel-order rgb (the
+               layer's own order) would need RGB here, which this command does not offer
   --mode gt --cues PICKLE  <-> training/tools/generate_train_gt.py (one size, default 321; labels restricted to background + the
                image-level labels '<id>_labels' of the cue pickle; --images holds the reference's input_list.txt lines "name.jpg <id>")
   --mode gt-ms --cues PICKLE  (no counterpart in the reference) --mode gt as a probability ensemble over several sizes (default

@@ -419,12 +419,17 @@ class RetrainTrainer(object):
     """one train-f step: backbone -> (logits, labels shrunk by 8) -> softmax loss -> SGD with poly LR"""
 
     def __init__(self, device, world_size=1, backbone="vgg16", base_lr=1e-3, max_iter=20000, seed=0,
-                 amp_dtype=torch.bfloat16, net=None, weights=None, snapshot=None, ddp=None):
+                 amp_dtype=torch.bfloat16, net=None, weights=None, snapshot=None, ddp=None, num_classes=21):
         """weights: run.sh:9 `--weights models/model-s_iter_8000.caffemodel` — stage 2 starts from the stage-1 model
-        (copied by layer name: .caffemodel / .npz / torch file); snapshot: a solverstate written by save()."""
+        (copied by layer name: .caffemodel / .npz / torch file); snapshot: a solverstate written by save().  num_classes: the
+        outputs of the classifiers of the net built here (21: VOC; 81: the COCO variant; at most 96); a `net` that is handed in
+        keeps its own."""
+        if not 1 <= int(num_classes) <= 96:
+            raise ValueError("num_classes must be 1..96, got %r" % (num_classes,))
         torch.manual_seed(seed)
         self.device, self.amp_dtype, self.max_iter, self.base_lr = device, amp_dtype, max_iter, base_lr
-        net = net if net is not None else (VGG16ASPP() if backbone == "vgg16" else ResNet101DeepLab())
+        net = net if net is not None else (VGG16ASPP(num_classes=int(num_classes)) if backbone == "vgg16"
+                                           else ResNet101DeepLab(num_classes=int(num_classes)))
         if weights is not None:
             from .checkpoint import load_weights
             self.loaded_layers = load_weights(net, weights)

@@ -6,7 +6,12 @@
 
 Stage s reads --list ('name.jpg <id>' lines, the reference's list/input_list.txt), the images under --root and the localisation
 cues of --cues; stage f reads --list ('image_path label_path' lines, list/train.txt) with --root prefixed to both paths.  The
-defaults are the solver files' values (STAGE_DEFAULTS).  Stage f's --scale-factors (not the reference's; DeepLab's augmentation for
+defaults are the solver files' values (STAGE_DEFAULTS).  --class N (1..96, default 21; 81: the reference's COCO variant) sets the
+outputs of the network's classifiers in both stages and reaches the loader and the validator.  Stage s with --cue-maps is fed as
+AnnotationLayerCOCO feeds the 81-class runs (pylayers.py:432-512; TrainSCueMapInput): --list then holds 'image_path cue_path'
+lines with --root prefixed to both, a cue file is a 41 x 41 one-channel image of classes with 255 = no cue, --cues is absent and
+the images are zoomed to 321 x 321; --channel-order rgb feeds the net R G B as that layer does (the default, bgr, is what this
+project's predict and validate — and the reference's test-coco.py — feed).  Stage f's --scale-factors (not the reference's; DeepLab's augmentation for
 --backbone resnet101 --crop 513, where no VOC image leaves the crop any slack) rescales each image by a drawn factor before the crop.  Batches are assembled on the GPU (dsrg_amd/input.py) while the step
 before runs.  Every --display steps the mean of the last --display losses is printed with the learning rate; snapshots
 (<prefix>_iter_N.caffemodel + .solverstate.pt) are written every --snapshot-every steps and at the end; --snapshot resumes at the
@@ -53,6 +58,14 @@ def parse_args(argv=None):
     p.add_argument("--display", type=int, default=None, help="print the mean loss every N steps (s: 10, f: 20)")
     p.add_argument("--workers", type=int, default=8, help="decoding threads")
     p.add_argument("--cues", default=None, help="s: the localisation-cue pickle")
+    p.add_argument("--class", dest="num_classes", type=int, default=21, metavar="N",
+                   help="outputs of the classifiers, labels 0..N-1 (1..96; default 21, the reference's COCO variant has 81)")
+    p.add_argument("--cue-maps", action="store_true",
+                   help="s: --list holds 'image_path cue_path' lines (--root prefixed to both); a cue file is a 41 x 41 map of classes, "
+                        "255 = no cue (AnnotationLayerCOCO's format); --cues is then absent")
+    p.add_argument("--channel-order", choices=("bgr", "rgb"), default=None,
+                   help="s with --cue-maps: the network input's channel order (default bgr, as predict and validate feed; rgb is "
+                        "AnnotationLayerCOCO's own)")
     p.add_argument("--backbone", choices=("vgg16", "resnet101"), default=None, help="f: the network (default vgg16)")
     p.add_argument("--crop", type=int, default=None, help="f: crop size (321)")
     p.add_argument("--mean", default=None, help="f: B,G,R mean (104,117,123)")
@@ -80,9 +93,20 @@ def parse_args(argv=None):
         a.val_crop = VAL_CROP if a.val_crop is None else a.val_crop
         if min(a.val_every, a.val_crop) < 1 or (a.val_batch is not None and not 1 <= a.val_batch <= 32):
             p.error("--val-every and --val-crop must be >= 1, --val-batch 1..32")
+    if not 1 <= a.num_classes <= 96:
+        p.error("--class takes 1..96, got %d" % a.num_classes)
+    if a.cue_maps and a.stage != "s":
+        p.error("--cue-maps is for --stage s")
+    if a.channel_order is not None and not a.cue_maps:
+        p.error("--channel-order needs --cue-maps")
+    a.channel_order = a.channel_order or "bgr"
     if a.stage == "s":
-        if not a.cues:
-            p.error("--stage s needs --cues (the localisation-cue pickle)")
+        if a.cue_maps and a.cues:
+            p.error("--cue-maps reads the cues from the files of --list: --cues must be absent")
+        if not a.cues and not a.cue_maps:
+            p.error("--stage s needs --cues (the localisation-cue pickle) or --cue-maps")
+        if a.cues and a.num_classes != 21:
+            p.error("--class %d: the cue pickle of --cues describes 21 classes; other class counts are fed by --cue-maps" % a.num_classes)
         if a.backbone or a.crop is not None or a.mean is not None or a.no_mirror or a.scale_factors is not None:
             p.error("--backbone, --crop, --mean, --no-mirror and --scale-factors are for --stage f")
     else:
@@ -125,7 +149,7 @@ def main(argv=None):
     a = parse_args(argv)
     import torch
     from ._lib import require_gpu
-    from .input import TrainFInput, TrainSInput
+    from .input import TrainFInput, TrainSCueMapInput, TrainSInput
     from .trainer import DSRGTrainer, params_checksum
 
     require_gpu()
@@ -138,15 +162,20 @@ def main(argv=None):
     say = print if rank == 0 else (lambda *args, **kw: None)
 
     if a.stage == "s":
-        trainer = DSRGTrainer(device, world_size=world, seed=a.seed, weights=a.weights, snapshot=a.snapshot)
-        loader = TrainSInput(a.list, a.root, a.cues, batch_size=batch, seed=a.seed, workers=a.workers, rank=rank,
-                             world_size=world, device=device)
+        trainer = DSRGTrainer(device, world_size=world, seed=a.seed, weights=a.weights, snapshot=a.snapshot, num_classes=a.num_classes)
+        if a.cue_maps:
+            loader = TrainSCueMapInput(a.list, a.root, a.num_classes, batch_size=batch, size=321, mean=TrainSInput.mean,
+                                       bgr=a.channel_order == "bgr", seed=a.seed, workers=a.workers, rank=rank, world_size=world,
+                                       device=device)
+        else:
+            loader = TrainSInput(a.list, a.root, a.cues, batch_size=batch, seed=a.seed, workers=a.workers, rank=rank,
+                                 world_size=world, device=device)
         names = ("loss-Seed", "loss-Constrain")
         rate = trainer.opt.lr
     else:
         from .retrain import RetrainTrainer, poly_lr
         trainer = RetrainTrainer(device, world_size=world, backbone=a.backbone, max_iter=a.iters, seed=a.seed, weights=a.weights,
-                                 snapshot=a.snapshot)
+                                 snapshot=a.snapshot, num_classes=a.num_classes)
         loader = TrainFInput(dict(source=a.list, root_folder=a.root, batch_size=batch, crop_size=(a.crop, a.crop), mean=a.mean,
                                   mirror=not a.no_mirror, scale_factors=a.scale_factors), seed=a.seed, workers=a.workers, rank=rank, world_size=world, device=device)
         names = ("loss",)
@@ -158,7 +187,7 @@ def main(argv=None):
     if a.val_list is not None:
         from .validate import Validator, write_result
         validator = Validator(trainer.net, a.val_list, a.val_root, crop=a.val_crop, batch=val_batch(a, world),
-                              mean=a.mean if a.stage == "f" else TrainSInput.mean, device=device, rank=rank, world_size=world,
+                              mean=a.mean if a.stage == "f" else TrainSInput.mean, num_classes=a.num_classes, device=device, rank=rank, world_size=world,
                               amp_dtype=trainer.amp_dtype, workers=a.workers)
 
     window, saved_at = [], None

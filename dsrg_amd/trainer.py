@@ -133,11 +133,15 @@ def distributed_rank():
 
 class DSRGTrainer(object):
     def __init__(self, device, world_size=1, seed=0, amp_dtype=torch.bfloat16, channels_last=True,
-                 loss_fn=None, net=None, ddp=None, weights=None, snapshot=None, bucket_cap_mb=32):
+                 loss_fn=None, net=None, ddp=None, weights=None, snapshot=None, bucket_cap_mb=32, num_classes=21):
         """loss_fn(logits, images, labels, cues) -> (total, losses); defaults to the HIP supervision
         path.  (Tests inject a torch loss to exercise the data-parallel plumbing on CPU/gloo.)
         weights: `train.py --weights` (run.sh:5: ../../vgg16_20M_mc.caffemodel) — a .caffemodel / .npz / torch file
-        copied by layer name before training; snapshot: `train.py --snapshot` — a solverstate written by save()."""
+        copied by layer name before training; snapshot: `train.py --snapshot` — a solverstate written by save().
+        num_classes: the outputs of the four classifiers of the net built here (21: VOC; 81: the COCO variant; at most 96, the
+        layer kernels' kMaxLabels); a `net` that is handed in keeps its own."""
+        if not 1 <= int(num_classes) <= 96:
+            raise ValueError("num_classes must be 1..96, got %r" % (num_classes,))
         torch.manual_seed(seed)            # same initial weights on every rank (the reducer also broadcasts)
         self.device = device
         self.amp_dtype = amp_dtype
@@ -147,7 +151,7 @@ class DSRGTrainer(object):
         # backbone forward runs (HIP path only)
         self.overlap_build = loss_fn is None and device.type == "cuda"
         self.side = torch.cuda.Stream(device=device) if self.overlap_build else None
-        net = net if net is not None else VGG16ASPP()
+        net = net if net is not None else VGG16ASPP(num_classes=int(num_classes))
         if weights is not None:
             from .checkpoint import load_weights
             self.loaded_layers = load_weights(net, weights)
@@ -215,7 +219,7 @@ class DSRGTrainer(object):
         return all(w == words[0] for w in words), words
 
     def step(self, images, labels, cues):
-        """images (B,3,321,321) f32 mean-subtracted, labels (B,1,1,21), cues (B,21,41,41) -> losses[2] (this rank's shard;
+        """images (B,3,321,321) f32 mean-subtracted, labels (B,1,1,C), cues (B,C,41,41), C = num_classes -> losses[2] (this rank's shard;
         reduce_losses() gives the global-batch figure for logging)"""
         if self.reducer is not None:
             self.reducer.prepare()                          # gradients unset, every large parameter knows its bucket slot

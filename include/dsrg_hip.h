@@ -410,6 +410,26 @@ int dsrg_train_s_input_batch(int B, const unsigned char *stage_dev, size_t stage
                              const int32_t *label_off_host, const int32_t *nlabels_host, const int32_t *mirror_host, int S, int C,
                              int Hm, int Wm, const float *mean_host, float *images_dev, float *cues_dev, float *labels_dev,
                              void *stream);
+/* The stage-1 training batch of a run fed by cue MAPS, in one launch: AnnotationLayerCOCO (pylayers/pylayers/pylayers.py:432-512,
+ * the feeder of the 81-class runs) for B images.  stage_dev / stage_bytes as above; image_off the (H_b, W_b, 3) RGB uint8 image,
+ * cue_off its (Hm, Wm) map of cue bytes (a class per pixel, ignore_label = no cue); mirror_host[b] != 0 reverses the last axis
+ * of image b's pixels and cue planes.  A byte v is KEPT iff v != ignore_label and v < C.  Outputs, every element written:
+ *   images_dev (B, 3, Sh, Sw) f32 NCHW: the image zoomed to Sh x Sw as dsrg_preprocess_rect_batch zooms (scipy.ndimage.zoom,
+ *              order 1: coordinate y*(H-1)/(Sh-1), 0 when Sh == 1, likewise x; i0 = (int)src, i1 = i0 + (i0 < in-1); the two-tap
+ *              blend l0h*(l0w*v00 + l1w*v01) + l1h*(l0w*v10 + l1w*v11) in double, rounded once to f32), minus mean_host[c] in
+ *              f32.  Output channel c reads source byte 2 - c with bgr = 1 (the order of every other entry of this library:
+ *              the values are then dsrg_preprocess_rect_batch's bit for bit) and byte c with bgr = 0 (the layer's own order)
+ *   cues_dev   (B, C, Hm, Wm) f32: 1.0 at (v, y, x) for every kept byte v at (y, x), 0.0 elsewhere
+ *   labels_dev (B, 1, 1, C) f32: 1.0 for every class some kept byte names, else 0.0 (class 0 is NOT forced on; a map without a
+ *              kept byte gives all zeros)
+ * 1 <= B <= 32, Sh, Sw, Hm, Wm >= 1, 1 <= C <= 96 (above: DSRG_ERR_UNSUPPORTED), 0 <= ignore_label <= 255, bgr 0 or 1, H_b, W_b
+ * >= 1, every offset + extent inside stage_bytes < 2^31, H_b*W_b*3, B*3*Sh*Sw and B*C*Hm*Wm < 2^31, outputs aligned to 4 bytes
+ * (otherwise DSRG_ERR_INVALID); every argument is checked before the first device call.  Nothing is allocated.  Stream-ordered, no
+ * host synchronisation, no handle; bit-reproducible (no atomics). */
+int dsrg_train_s_cuemap_input_batch(int B, const unsigned char *stage_dev, size_t stage_bytes, const int32_t *image_off_host,
+                                    const int32_t *H_host, const int32_t *W_host, const int32_t *cue_off_host,
+                                    const int32_t *mirror_host, int Sh, int Sw, int C, int Hm, int Wm, const float *mean_host,
+                                    int ignore_label, int bgr, float *images_dev, float *cues_dev, float *labels_dev, void *stream);
 /* The stage-2 training batch in one launch: SimpleTransformer.preprocess of ImageSegDataLayer (pylayers/pylayers/layer.py:17-251,
  * the arithmetic of layer.py:169-236; train-f.prototxt:3-14) for B images.  stage_dev / stage_bytes as above; image_off the
  * (H_b, W_b, 3) RGB uint8 image, label_off its (H_b, W_b) uint8 label; top_host / left_host: the crop's offsets on the image

@@ -19,7 +19,13 @@ alternating.
       summarises its database).
   (j) the same for the two stage-2 launches of (e).
 
-usage: python tools/train_input_probe.py [a|b|c|d|e|f|j|k ...]     (default: a b c d; one JSON line at the end)
+  (m) the cue-map feeder of the 81-class runs (TrainSCueMapInput, train_s_cuemap_input_kernel) at B = 20, C = 81, 321 / 41 x 41:
+      the launch alone as in (b); the host composition it replaces (layers.AnnotationLayerCOCO.load_next_image x 20 — decode, scipy
+      zoom, one-hot scatter — plus the three uploads; also with the files already decoded); DSRGTrainer.step at C = 81 fed by the
+      loader against the same step on resident tensors; the C = 81 step next to the C = 21 step, both on resident tensors.  The
+      sides of every comparison alternate within the one process.
+
+usage: python tools/train_input_probe.py [a|b|c|d|e|f|j|k|m ...]     (default: a b c d; one JSON line at the end)
 """
 import json
 import os
@@ -312,6 +318,104 @@ def probe_d(p):
     return r
 
 
+def _cuemap_files(p, C=81):
+    """a 41 x 41 cue PNG (classes below C, a third 255) per image of _files and the 'image_path cue_path' list"""
+    from PIL import Image
+    rng = np.random.default_rng(78)
+    lines = []
+    for k in range(N_FILES):
+        cue = rng.integers(0, C, (41, 41)).astype(np.uint8)
+        cue[rng.random((41, 41)) < 0.33] = 255
+        Image.fromarray(cue, mode="L").save(os.path.join(p["root"], "cue%d.png" % k))
+        lines.append("/im%d.jpg /cue%d.png\n" % (k, k))
+    path = os.path.join(p["root"], "cuemap.txt")
+    open(path, "w").write("".join(lines))
+    return path
+
+
+def probe_m(p, B=20, C=81, steps=30):
+    from dsrg_amd import input as I, layers, ops
+    from dsrg_amd.trainer import DSRGTrainer
+    lst = _cuemap_files(p, C)
+    out = {}
+    # the launch alone
+    images = [I.read_rgb(os.path.join(p["root"], "im%d.jpg" % k)) for k in range(B)]
+    maps = [I.read_gray(os.path.join(p["root"], "cue%d.png" % k)) for k in range(B)]
+    nbytes, desc = I.layout_train_s_cuemap([im.shape[:2] for im in images], (41, 41), [k % 2 for k in range(B)])
+    buf = np.zeros(nbytes, np.uint8)
+    I.pack_train_s_cuemap(buf, desc, images, maps)
+    stage = torch.from_numpy(buf).cuda()
+    res = ops.train_s_cuemap_input_batch(stage, desc, 321, C, (41, 41), MEAN)
+    call = lambda: ops.train_s_cuemap_input_batch(stage, desc, 321, C, (41, 41), MEAN, out=res)      # noqa: E731
+    us = [round(_median_us(call, reps=200), 2) for _ in range(3)]
+    out.update(cuemap_call_us=us, staging_bytes=nbytes, output_bytes=sum(o.numel() * 4 for o in res))
+    print("(m) back-to-back train_s_cuemap_input_batch calls, %d images, C = %d, device events (an UPPER BOUND on kernel time): %s us "
+          "(%d staging bytes -> %d output bytes)" % (B, C, us, nbytes, out["output_bytes"]), flush=True)
+
+    # the host composition the launch replaces
+    class Blob(object):
+        def reshape(self, *s):
+            self.data = np.zeros(s, np.float32)
+    lay = layers.AnnotationLayerCOCO()
+    lay.param_str = repr({'source': lst, 'root': p["root"], 'batch_size': B, 'mean': MEAN, 'new_size': (321, 321), 'mirror': True})
+    tops = [Blob(), Blob(), Blob()]
+    lay.setup([], tops)
+
+    def host_files():
+        lay.forward([], tops)                                            # load_next_image x B: decode, zoom, scatter
+        dev = [torch.from_numpy(t.data).cuda() for t in tops]
+        torch.cuda.synchronize()
+        return dev
+
+    def host_decoded():
+        parts = [lay.preprocess(im[:, :, ::-1], cue) for im, cue in zip(images, maps)]
+        dev = [torch.from_numpy(np.stack([np.asarray(q[i], dtype=np.float32) for q in parts])).cuda() for i in range(3)]
+        torch.cuda.synchronize()
+        return dev
+    for name, fn in (("host_composition_ms", host_files), ("host_composition_decoded_ms", host_decoded)):
+        fn()
+        t = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            fn()
+            t.append(round((time.perf_counter() - t0) * 1e3, 1))
+        out[name] = t
+    print("(m) host composition per batch of %d (AnnotationLayerCOCO.load_next_image x %d + 3 uploads): %s ms; files already decoded "
+          "(preprocess x %d + uploads): %s ms" % (B, B, out["host_composition_ms"], B, out["host_composition_decoded_ms"]), flush=True)
+
+    # the step at C = 81 fed by the loader against resident tensors; the C = 81 step next to the C = 21 step
+    dev = torch.device("cuda", torch.cuda.current_device())
+    tr81, tr21 = DSRGTrainer(dev, num_classes=C), DSRGTrainer(dev)
+    mk_s, _ = _loaders(p)
+    with I.TrainSCueMapInput(lst, p["root"], C, batch_size=B, workers=8) as ld, mk_s() as ld21:
+        resident = [t.clone() for t in next(ld)]
+        resident21 = [t.clone() for t in next(ld21)]
+        for _ in range(3):
+            tr81.step(*resident)
+            tr81.step(*next(ld))
+            tr21.step(*resident21)
+
+        def window(tr, feed):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                tr.step(*feed())
+            torch.cuda.synchronize()
+            return round(steps * B / (time.perf_counter() - t0), 1)
+        r81, fed, r21 = [], [], []
+        for _ in range(3):
+            r81.append(window(tr81, lambda: resident))
+            fed.append(window(tr81, lambda: next(ld)))
+            r21.append(window(tr21, lambda: resident21))
+    out.update(step81_images_per_s_resident=r81, step81_images_per_s_fed_by_loader=fed, step21_images_per_s_resident=r21,
+               fed_over_resident=round(float(np.median(fed) / np.median(r81)), 3),
+               c81_over_c21=round(float(np.median(r81) / np.median(r21)), 3))
+    print("(m) DSRGTrainer.step, batch %d, windows of %d steps, alternating: C = %d fed by TrainSCueMapInput %s images/s, C = %d on "
+          "resident tensors %s images/s -> x%.3f; C = 21 on resident tensors %s images/s -> C = %d runs at x%.3f of C = 21"
+          % (B, steps, C, fed, C, r81, out["fed_over_resident"], r21, C, out["c81_over_c21"]), flush=True)
+    return out
+
+
 def main(which):
     from dsrg_amd import _lib
     _lib.require_gpu()
@@ -319,7 +423,7 @@ def main(which):
     with tempfile.TemporaryDirectory() as d:
         p = _files(d)
         for key, fn in (("k", probe_k), ("j", probe_j), ("b", probe_b), ("e", probe_e), ("d", probe_d), ("a", probe_a), ("f", probe_f),
-                        ("c", probe_c)):
+                        ("c", probe_c), ("m", probe_m)):
             if key in which:
                 out[key] = fn(p)
     print(json.dumps(out))
