@@ -3,15 +3,19 @@
   TrainSInput  <-> Caffe's ImageData layer (train-s.prototxt:3-22) + AnnotationLayer (pylayers.py:346-387)
   TrainFInput  <-> ImageSegDataLayer (layer.py:17-251; train-f.prototxt:3-14)
   TrainSCueMapInput <-> AnnotationLayerCOCO (pylayers.py:432-512): stage 1 fed by 'image_path cue_path' lists, the cue a small
-                   label map (255 = no cue) — any class count up to 96; assembled by ops.train_s_cuemap_input_batch
-                   (`layout_train_s_cuemap`, `pack_train_s_cuemap`, `check_cue_map`); order and mirror draws as TrainSInput's
+                   label map (255 = no cue) — any class count up to MAX_CLASSES; order and mirror draws as TrainSInput's
+  (validate.ValInput, the one finite pass, is the fourth loader on the same core)
 
-The host decodes files (PIL, on a thread pool), packs the raw bytes of a batch — uint8 pixels, uint8 labels, int32 cue triplets
-and class ids — into ONE pinned staging buffer and uploads it with one copy; the batch itself (resize, BGR, mean, cue planes,
-image-level labels, crop, mirror) is assembled on the device by ops.train_s_input_batch / ops.train_f_input_batch.  Everything
-that decides WHAT a batch holds is plain host code that needs no device: the epoch order and its sharding over ranks
-(`epoch_items`), the random draws (`plan_batch`), the staging layout (`layout_train_s`, `layout_train_f`) and the packing
-(`pack_train_s`, `pack_train_f`).
+The host decodes files (PIL, on a thread pool), packs the raw bytes of a batch — uint8 pixels, uint8 labels or cue maps, int32
+cue triplets and class ids — into ONE pinned staging buffer and uploads it with one copy; the batch itself (resize, BGR, mean,
+cue planes, image-level labels, crop, mirror) is assembled on the device by one launch (ops.train_s_input_batch,
+ops.train_s_cuemap_input_batch, ops.train_f_input_batch).  Everything that decides WHAT a batch holds is plain host code that
+needs no device, and there is one of each: the two-field list file (`read_list`), the epoch order and its sharding over ranks
+(`epoch_items`), the staging layout (`_layout`: per image its pixels, then the feeder's further pieces, each on a 16-byte
+boundary) and the write of a piece (`_put`) — the public layout_* / pack_* functions state their pieces over these two — and the
+loader mechanics (`_StagedLoader`: slots, streams, the pool, the end of a finite pass, `stage_batch`).  A loader is a plan, a
+decode, a layout, its `pack` routine, its `out_shapes` and its launch; `_StageOneLoader` and `_PairLoader` hold what the two
+stage-1 feeders and the two feeders of image / label pairs share of these.
 
 Random numbers.  Each loader owns its generators, the global ones are never touched.  TrainSInput: the epoch shuffle comes from a
 `random.Random(seed)` — NOT Caffe's RNG, so a run does not see the reference's image order — and the mirror draws from an
@@ -55,19 +59,31 @@ def epoch_items(entries, shuffle, rng, rank=0, world_size=1):
             rng.shuffle(entries)
 
 
-def read_train_s_list(path):
-    """'name.jpg <id>' lines (the reference's list/input_list.txt) -> [(name, id)]"""
+def read_list(path, line_format, what, second=str):
+    """the list file every loader reads: two fields per line (further fields and empty lines are skipped) -> [(first,
+    second(second field))].  A line with one field raises ValueError naming the file and `line_format`, what a line should look
+    like; so does a file without a line, naming `what` it should have listed."""
     out = []
     with open(path) as f:
         for line in f:
             parts = line.split()
             if parts:
                 if len(parts) < 2:
-                    raise ValueError("%s: expected 'name.jpg <id>', got %r" % (path, line.strip()))
-                out.append((parts[0], int(parts[1])))
+                    raise ValueError("%s: expected '%s', got %r" % (path, line_format, line.strip()))
+                out.append((parts[0], second(parts[1])))
     if not out:
-        raise ValueError("%s lists no image" % path)
+        raise ValueError("%s lists no %s" % (path, what))
     return out
+
+
+def read_train_s_list(path):
+    """'name.jpg <id>' lines (the reference's list/input_list.txt) -> [(name, id)]"""
+    return read_list(path, "name.jpg <id>", "image", int)
+
+
+def read_pair_list(path):
+    """'image_path cue_path' lines (AnnotationLayerCOCO's `source`) -> [(image_path, cue_path)]"""
+    return read_list(path, "image_path cue_path", "image / cue map pair")
 
 
 def read_rgb(path):
@@ -106,45 +122,67 @@ def cue_arrays(cue_dict, image_id, num_classes=21, map_size=(41, 41)):
     return cues, labels
 
 
-def _check_batch(n, total):
+def _layout(shapes, pieces, mirror, **carried):
+    """The one layout of a staging buffer: per image its (H, W, 3) image and then, in order, one piece per entry of `pieces` — (the
+    descriptor's offset key, bytes per image) — each on a 16-byte boundary.  shapes: (H, W) per image; mirror: one flag per image
+    or None (none mirrored); carried: further per-image lists of ints the descriptor holds as they are (counts, top / left, Hs /
+    Ws) -> (bytes, desc): desc is the dict of per-image lists the batch's ops wrapper takes."""
+    n = len(shapes)
     if not 1 <= n <= MAX_BATCH:
         raise ValueError("a batch holds 1..%d images, got %d" % (MAX_BATCH, n))
-    if total >= 1 << 31:
-        raise ValueError("the staging buffer of one batch would hold %d >= 2^31 bytes" % total)
+    carried["mirror"] = [0] * n if mirror is None else [bool(m) for m in mirror]
+    for key, values in list(carried.items()) + list(pieces):
+        if len(values) != n:
+            raise ValueError("one %s entry per image, got %d for %d images" % (key, len(values), n))
+    desc = dict(image_off=[], H=[int(H) for H, _ in shapes], W=[int(W) for _, W in shapes])
+    desc.update((key, [int(v) for v in values]) for key, values in carried.items())
+    desc.update((key, []) for key, _ in pieces)
+    off = 0
+    for b, (H, W) in enumerate(zip(desc["H"], desc["W"])):
+        if H < 1 or W < 1:
+            raise ValueError("an image of %d x %d pixels" % (H, W))
+        desc["image_off"].append(off)
+        off = _align(off + H * W * 3)
+        for key, nbytes in pieces:
+            if nbytes[b] < 0:
+                raise ValueError("image %d: %s names a piece of %d bytes" % (b, key, nbytes[b]))
+            desc[key].append(off)
+            off = _align(off + nbytes[b])
+    if off >= 1 << 31:
+        raise ValueError("the staging buffer of one batch would hold %d >= 2^31 bytes" % off)
+    return off, desc
+
+
+def _put(buf, desc, key, arrays, dtype, shape, what):
+    """The one put of a piece: array b of `arrays`, which must have exactly `dtype` and `shape(b)`, goes as raw bytes to offset
+    desc[key][b] of buf (a 1-d uint8 numpy array of at least the layout's size); nothing else of buf is written."""
+    if len(arrays) != len(desc[key]):
+        raise ValueError("%d %ss for %d images" % (len(arrays), what, len(desc[key])))
+    for b, a in enumerate(arrays):
+        if a.dtype != dtype or a.shape != shape(b):
+            raise ValueError("%s %d must be %s %s" % (what, b, shape(b), np.dtype(dtype).name))
+        o = desc[key][b]
+        buf[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+
+
+def _put_images(buf, desc, images):
+    _put(buf, desc, "image_off", images, np.uint8, lambda b: (desc["H"][b], desc["W"][b], 3), "image")
 
 
 def layout_train_s(shapes, ncues, nlabels, mirror=None):
     """where the pieces of a stage-1 batch lie in its staging buffer.  shapes: (H, W) per image; ncues / nlabels: triplets / class
     ids per image -> (bytes, desc): desc is the dict of per-image lists ops.train_s_input_batch takes."""
-    n = len(shapes)
-    desc = dict(image_off=[], H=[], W=[], cue_off=[], ncues=[], label_off=[], nlabels=[],
-                mirror=[0] * n if mirror is None else [int(bool(m)) for m in mirror])
-    off = 0
-    for (H, W), K, L in zip(shapes, ncues, nlabels):
-        if H < 1 or W < 1:
-            raise ValueError("an image of %d x %d pixels" % (H, W))
-        desc["image_off"].append(off), desc["H"].append(int(H)), desc["W"].append(int(W))
-        off = _align(off + H * W * 3)
-        desc["cue_off"].append(off), desc["ncues"].append(int(K))
-        off = _align(off + 12 * K)
-        desc["label_off"].append(off), desc["nlabels"].append(int(L))
-        off = _align(off + 4 * L)
-    _check_batch(n, off)
-    return off, desc
+    return _layout(shapes, [("cue_off", [12 * int(K) for K in ncues]), ("label_off", [4 * int(L) for L in nlabels])], mirror,
+                   ncues=ncues, nlabels=nlabels)
 
 
 def pack_train_s(buf, desc, images, cues, labels):
     """write the batch's raw bytes into buf (1-d uint8 numpy array, at least the layout's size): images (H, W, 3) uint8 RGB, cues
-    (3, K) int32, labels (L,) int32"""
-    for b, (im, cue, lab) in enumerate(zip(images, cues, labels)):
-        if im.dtype != np.uint8 or im.shape != (desc["H"][b], desc["W"][b], 3):
-            raise ValueError("image %d must be (%d, %d, 3) uint8" % (b, desc["H"][b], desc["W"][b]))
-        o = desc["image_off"][b]
-        buf[o:o + im.size] = im.reshape(-1)
-        o, K = desc["cue_off"][b], desc["ncues"][b]
-        buf[o:o + 12 * K].view(np.int32)[:] = np.asarray(cue, dtype=np.int32).reshape(-1)
-        o, L = desc["label_off"][b], desc["nlabels"][b]
-        buf[o:o + 4 * L].view(np.int32)[:] = np.asarray(lab, dtype=np.int32).reshape(-1)
+    (3, K) int32, labels (L,) int32 (cues and labels: anything numpy converts to int32 with that many values)"""
+    flat = lambda arrays: [np.asarray(a, dtype=np.int32).reshape(-1) for a in arrays]        # noqa: E731
+    _put_images(buf, desc, images)
+    _put(buf, desc, "cue_off", flat(cues), np.int32, lambda b: (3 * desc["ncues"][b],), "cue triplet array")
+    _put(buf, desc, "label_off", flat(labels), np.int32, lambda b: (desc["nlabels"][b],), "class id array")
 
 
 def check_cue_map(cue, num_classes, map_size, ignore_label=255, name="cue map"):
@@ -165,39 +203,18 @@ def check_cue_map(cue, num_classes, map_size, ignore_label=255, name="cue map"):
 def layout_train_s_cuemap(shapes, map_size, mirror=None):
     """where the pieces of a cue-map stage-1 batch lie in its staging buffer.  shapes: (H, W) per image; map_size: the (Hm, Wm)
     every cue map has -> (bytes, desc): desc is the dict of per-image lists ops.train_s_cuemap_input_batch takes (and Hm, Wm)."""
-    n = len(shapes)
     Hm, Wm = int(map_size[0]), int(map_size[1])
     if Hm < 1 or Wm < 1:
         raise ValueError("a cue map of %d x %d pixels" % (Hm, Wm))
-    desc = dict(image_off=[], H=[], W=[], cue_off=[], mirror=[0] * n if mirror is None else [int(bool(m)) for m in mirror],
-                Hm=Hm, Wm=Wm)
-    if len(desc["mirror"]) != n:
-        raise ValueError("one mirror flag per image, got %d for %d images" % (len(desc["mirror"]), n))
-    off = 0
-    for H, W in shapes:
-        if H < 1 or W < 1:
-            raise ValueError("an image of %d x %d pixels" % (H, W))
-        desc["image_off"].append(off), desc["H"].append(int(H)), desc["W"].append(int(W))
-        off = _align(off + H * W * 3)
-        desc["cue_off"].append(off)
-        off = _align(off + Hm * Wm)
-    _check_batch(n, off)
-    return off, desc
+    nbytes, desc = _layout(shapes, [("cue_off", [Hm * Wm] * len(shapes))], mirror)
+    desc.update(Hm=Hm, Wm=Wm)
+    return nbytes, desc
 
 
 def pack_train_s_cuemap(buf, desc, images, cue_maps):
     """write the batch's raw bytes into buf: images (H, W, 3) uint8 RGB, cue maps (Hm, Wm) uint8"""
-    Hm, Wm = desc["Hm"], desc["Wm"]
-    for b, (im, cue) in enumerate(zip(images, cue_maps)):
-        H, W = desc["H"][b], desc["W"][b]
-        if im.dtype != np.uint8 or im.shape != (H, W, 3):
-            raise ValueError("image %d must be (%d, %d, 3) uint8" % (b, H, W))
-        if cue.dtype != np.uint8 or cue.shape != (Hm, Wm):
-            raise ValueError("cue map %d must be (%d, %d) uint8" % (b, Hm, Wm))
-        o = desc["image_off"][b]
-        buf[o:o + im.size] = im.reshape(-1)
-        o = desc["cue_off"][b]
-        buf[o:o + cue.size] = cue.reshape(-1)
+    _put_images(buf, desc, images)
+    _put(buf, desc, "cue_off", cue_maps, np.uint8, lambda b: (desc["Hm"], desc["Wm"]), "cue map")
 
 
 def layout_train_f(shapes, top, left, mirror, scaled=None):
@@ -205,39 +222,20 @@ def layout_train_f(shapes, top, left, mirror, scaled=None):
     draws; scaled: (Hs, Ws) per image, the size each is rescaled to before the crop (top / left are then offsets on the rescaled
     image), or None -> (bytes, desc): desc is the dict of per-image lists ops.train_f_input_batch takes; with `scaled` it holds
     Hs and Ws too.  The bytes are the same either way: the source image is what is staged."""
-    n = len(shapes)
-    desc = dict(image_off=[], label_off=[], H=[], W=[], top=[int(t) for t in top], left=[int(v) for v in left],
-                mirror=[int(bool(m)) for m in mirror])
+    rescaled = {}
     if scaled is not None:
-        if len(scaled) != n or min([1] + [min(s) for s in scaled]) < 1:
+        if len(scaled) != len(shapes) or min([1] + [min(s) for s in scaled]) < 1:
             raise ValueError("one rescaled size >= 1 x 1 per image, got %r" % (list(scaled),))
-        desc["Hs"], desc["Ws"] = [int(s[0]) for s in scaled], [int(s[1]) for s in scaled]
-    off = 0
-    for H, W in shapes:
-        if H < 1 or W < 1:
-            raise ValueError("an image of %d x %d pixels" % (H, W))
-        desc["image_off"].append(off), desc["H"].append(int(H)), desc["W"].append(int(W))
-        off = _align(off + H * W * 3)
-        desc["label_off"].append(off)
-        off = _align(off + H * W)
-    if min(desc["top"] + desc["left"]) < 0:
+        rescaled = dict(Hs=[s[0] for s in scaled], Ws=[s[1] for s in scaled])
+    if min([0] + [int(v) for v in list(top) + list(left)]) < 0:
         raise ValueError("negative crop offset")
-    _check_batch(n, off)
-    return off, desc
+    return _layout(shapes, [("label_off", [H * W for H, W in shapes])], mirror, top=top, left=left, **rescaled)
 
 
 def pack_train_f(buf, desc, images, labels):
-    """write the batch's raw bytes into buf: images (H, W, 3) uint8 RGB, labels (H, W) uint8"""
-    for b, (im, lab) in enumerate(zip(images, labels)):
-        H, W = desc["H"][b], desc["W"][b]
-        if im.dtype != np.uint8 or im.shape != (H, W, 3):
-            raise ValueError("image %d must be (%d, %d, 3) uint8" % (b, H, W))
-        if lab.dtype != np.uint8 or lab.shape != (H, W):
-            raise ValueError("label %d must be (%d, %d) uint8, the size of its image" % (b, H, W))
-        o = desc["image_off"][b]
-        buf[o:o + im.size] = im.reshape(-1)
-        o = desc["label_off"][b]
-        buf[o:o + lab.size] = lab.reshape(-1)
+    """write the batch's raw bytes into buf: images (H, W, 3) uint8 RGB, labels (H, W) uint8, each the size of its image"""
+    _put_images(buf, desc, images)
+    _put(buf, desc, "label_off", labels, np.uint8, lambda b: (desc["H"][b], desc["W"][b]), "label")
 
 
 class _Slot(object):
@@ -252,10 +250,11 @@ class _Slot(object):
         self.free = torch.cuda.Event()            # caller's stream: the caller's work on the slot's previous batch is enqueued before it
         self.in_flight = False
         self.desc, self.nbytes = None, 0
+        self.count = 0                            # images of the batch staged here; 0: the plan was empty, nothing is staged
 
 
 class _StagedLoader(object):
-    """The mechanics both loaders share.  Two staging slots; per __next__ call n (0-based), on the calling thread:
+    """The mechanics every loader shares.  Two staging slots; per __next__ call n (0-based), on the calling thread:
       1. batch n — uploaded during call n-1 — is assembled by ONE launch on the loader's side stream, behind an event recorded
          on the caller's current stream (the caller's work on batch n-2, this slot's previous tenant, is in front of it), and the
          caller's stream is made to wait for the assembly;
@@ -265,7 +264,10 @@ class _StagedLoader(object):
     CONTRACT: the tensors of batch n are valid until the __next__ call after next (call n+2 hands their slot to batch n+2); a
     caller that keeps a batch longer clones it.  A call that raises (a file that does not decode, say) closes the loader: later
     calls raise RuntimeError.  No stream is left current across calls: every `with torch.cuda.stream` block
-    closes inside the call that opens it."""
+    closes inside the call that opens it.
+    A FINITE pass: a loader whose plan_batch returns [] once its items are used up.  An empty plan stages nothing and marks its
+    slot empty; the __next__ call that would return it raises StopIteration, which closes the loader like any other exception.
+    The endless loaders never plan an empty batch."""
 
     def __init__(self, batch_size, workers, device):
         self.batch_size = int(batch_size)
@@ -280,6 +282,8 @@ class _StagedLoader(object):
         self._closed = False
 
     # -- what a loader defines -------------------------------------------------------------------------------------------------
+    pack = None                                   # staticmethod(pack_*): (buf, desc, *pieces) writes the batch's bytes
+
     def plan_batch(self):                         # iterating thread: the next batch's items with every random draw made
         raise NotImplementedError
 
@@ -289,16 +293,20 @@ class _StagedLoader(object):
     def _layout(self, plan, arrays):              # -> (bytes, desc, pieces to pack)
         raise NotImplementedError
 
-    def _pack(self, buf, desc, pieces):
-        raise NotImplementedError
-
-    def _outputs(self, torch):                    # a slot's output tensors
+    def out_shapes(self):                         # the shapes of a slot's float32 output tensors
         raise NotImplementedError
 
     def _assemble(self, slot):                    # one launch on the current (side) stream -> the tuple __next__ returns
         raise NotImplementedError
 
     # -- mechanics -------------------------------------------------------------------------------------------------------------
+    def stage_batch(self):
+        """-> (bytes, desc, pieces) of the next batch: planned, decoded and laid out on the calling thread, with no device touched —
+        what an upload does before its first device call, every refusal of a bad file included.  Advances the loader's item
+        stream and random draws like the batch it stands for; (0, None, ()) past the end of a finite pass."""
+        plan = self.plan_batch()
+        return self._layout(plan, [self._decode(item) for item in plan]) if plan else (0, None, ())
+
     def _submit(self):
         plan = self.plan_batch()
         return plan, [self._pool.submit(self._decode, item) for item in plan]
@@ -306,6 +314,9 @@ class _StagedLoader(object):
     def _upload(self, pending, slot):
         import torch
         plan, futures = pending
+        slot.count = len(plan)
+        if not plan:                                                    # the end of a finite pass
+            return
         arrays = [f.result() for f in futures]                          # in list order, whatever order the workers finished in
         nbytes, desc, pieces = self._layout(plan, arrays)
         if slot.in_flight:
@@ -316,7 +327,7 @@ class _StagedLoader(object):
             slot.host = slot.pinned.numpy()
             with torch.cuda.stream(self._side):                         # (allocated and freed in the side stream's order)
                 slot.dev = torch.empty(cap, dtype=torch.uint8, device=self.device)
-        self._pack(slot.host, desc, pieces)
+        self.pack(slot.host, desc, *pieces)
         with torch.cuda.stream(self._side):
             slot.dev[:nbytes].copy_(slot.pinned[:nbytes], non_blocking=True)
             slot.copied.record(self._side)
@@ -333,7 +344,8 @@ class _StagedLoader(object):
         self._pool = ThreadPoolExecutor(self.workers)
         with torch.cuda.device(self.device):
             self._side = torch.cuda.Stream(device=self.device)
-            self._slots = [_Slot(torch, self._outputs(torch)) for _ in range(2)]
+            self._slots = [_Slot(torch, tuple(torch.empty(shape, dtype=torch.float32, device=self.device) for shape in self.out_shapes()))
+                           for _ in range(2)]
             self._upload(self._submit(), self._slots[0])
         self._decoding = self._submit()
 
@@ -357,6 +369,8 @@ class _StagedLoader(object):
             self._start()
         n = self._count
         slot = self._slots[n % 2]
+        if slot.count == 0:                                             # the plan of this batch was empty: the pass is over
+            raise StopIteration
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
             slot.free.record(cur)
@@ -392,7 +406,35 @@ class _StagedLoader(object):
         return False
 
 
-class TrainSInput(_StagedLoader):
+class _StageOneLoader(_StagedLoader):
+    """What the two stage-1 feeders share: the item stream (`epoch_items` under a random.Random(seed)), the mirror draw (one
+    RandomState(seed).choice(2) per image in batch order, 0 = mirror; none drawn when `mirror` is off) and the three outputs
+    (images (B,3,Sh,Sw), labels (B,1,1,C), cues (B,C,Hm,Wm)).  A feeder sets num_classes, size (an int or (Sh, Sw)) and map_size,
+    calls _open_stream with its list, and defines _item: a list entry -> the plan's dict for it (it may validate and raise)."""
+
+    def _open_stream(self, entries, mirror, shuffle, seed, rank, world_size):
+        self.entries, self.mirror = entries, bool(mirror)
+        self._items = epoch_items(self.entries, shuffle, random.Random(seed), rank, world_size)
+        self._mirror_rng = np.random.RandomState(seed)
+
+    def _item(self, first, second):
+        raise NotImplementedError
+
+    def plan_batch(self):
+        plan = []
+        for _ in range(self.batch_size):
+            item = self._item(*next(self._items))
+            item["mirror"] = self.mirror and int(self._mirror_rng.choice(2)) == 0
+            plan.append(item)
+        return plan
+
+    def out_shapes(self):
+        B, C, (Hm, Wm) = self.batch_size, self.num_classes, self.map_size
+        Sh, Sw = self.size if isinstance(self.size, tuple) else (self.size, self.size)
+        return (B, 3, Sh, Sw), (B, 1, 1, C), (B, C, Hm, Wm)
+
+
+class TrainSInput(_StageOneLoader):
     """Iterator of (images (B,3,size,size), labels (B,1,1,21), cues (B,21,41,41)) float32 device tensors for DSRGTrainer.step:
     Caffe's ImageData layer (train-s.prototxt:3-22: read, resize to size x size, mean 104/117/123, shuffle) followed by
     AnnotationLayer (pylayers.py:346-387), assembled on the device by ops.train_s_input_batch.
@@ -404,19 +446,18 @@ class TrainSInput(_StagedLoader):
     (AnnotationLayer's draw).  The tensors of batch n are valid until the __next__ call after next (_StagedLoader)."""
 
     num_classes, map_size, mean = 21, (41, 41), (104.0, 117.0, 123.0)
+    pack = staticmethod(pack_train_s)
 
     def __init__(self, list_file, root, cues, batch_size=20, size=321, mirror=True, shuffle=True, seed=0, workers=8, rank=0,
                  world_size=1, device=None):
         _StagedLoader.__init__(self, batch_size, workers, device)
-        self.size, self.mirror, self.root = int(size), bool(mirror), root
+        self.size, self.root = int(size), root
         if isinstance(cues, dict):
             self.cues = cues
         else:
             from .layers import _open_cue_file
             self.cues = _open_cue_file(os.path.abspath(cues))
-        self.entries = read_train_s_list(list_file)
-        self._items = epoch_items(self.entries, shuffle, random.Random(seed), rank, world_size)
-        self._mirror_rng = np.random.RandomState(seed)
+        self._open_stream(read_train_s_list(list_file), mirror, shuffle, seed, rank, world_size)
         self._checked = {}
 
     def _cues_of(self, image_id):
@@ -424,14 +465,9 @@ class TrainSInput(_StagedLoader):
             self._checked[image_id] = cue_arrays(self.cues, image_id, self.num_classes, self.map_size)
         return self._checked[image_id]
 
-    def plan_batch(self):
-        plan = []
-        for _ in range(self.batch_size):
-            name, image_id = next(self._items)
-            self._cues_of(image_id)                                     # a bad triplet raises here, before any upload
-            plan.append(dict(name=name, id=image_id,
-                             mirror=bool(self.mirror) and int(self._mirror_rng.choice(2)) == 0))
-        return plan
+    def _item(self, name, image_id):
+        self._cues_of(image_id)                                         # a bad triplet raises here, before any upload
+        return dict(name=name, id=image_id)
 
     def _decode(self, item):
         return read_rgb(os.path.join(self.root, item["name"]))
@@ -443,36 +479,13 @@ class TrainSInput(_StagedLoader):
                                       [item["mirror"] for item in plan])
         return nbytes, desc, (arrays, cues, labels)
 
-    def _pack(self, buf, desc, pieces):
-        pack_train_s(buf, desc, *pieces)
-
-    def _outputs(self, torch):
-        B, C, (Hm, Wm) = self.batch_size, self.num_classes, self.map_size
-        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)      # noqa: E731
-        return mk(B, 3, self.size, self.size), mk(B, 1, 1, C), mk(B, C, Hm, Wm)
-
     def _assemble(self, slot):
         from . import ops
         return ops.train_s_input_batch(slot.dev, slot.desc, self.size, self.num_classes, self.map_size, self.mean,
                                        out=slot.outputs, nbytes=slot.nbytes)
 
 
-def read_pair_list(path):
-    """'image_path cue_path' lines (AnnotationLayerCOCO's `source`) -> [(image_path, cue_path)]"""
-    out = []
-    with open(path) as f:
-        for line in f:
-            parts = line.split()
-            if parts:
-                if len(parts) < 2:
-                    raise ValueError("%s: expected 'image_path cue_path', got %r" % (path, line.strip()))
-                out.append((parts[0], parts[1]))
-    if not out:
-        raise ValueError("%s lists no image / cue map pair" % path)
-    return out
-
-
-class TrainSCueMapInput(_StagedLoader):
+class TrainSCueMapInput(_StageOneLoader):
     """Iterator of (images (B,3,Sh,Sw), labels (B,1,1,C), cues (B,C,Hm,Wm)) float32 device tensors for DSRGTrainer.step:
     AnnotationLayerCOCO (pylayers.py:432-512), the feeder of the 81-class runs, assembled on the device by
     ops.train_s_cuemap_input_batch.
@@ -490,6 +503,8 @@ class TrainSCueMapInput(_StagedLoader):
     naming the file when its batch is laid out, before any upload.  The tensors of batch n are valid until the __next__ call
     after next (_StagedLoader)."""
 
+    pack = staticmethod(pack_train_s_cuemap)
+
     def __init__(self, list_file, root, num_classes, batch_size=20, size=321, mean=(104.0, 117.0, 123.0), mirror=True,
                  ignore_label=255, bgr=True, shuffle=True, seed=0, workers=8, rank=0, world_size=1, device=None):
         _StagedLoader.__init__(self, batch_size, workers, device)
@@ -505,18 +520,11 @@ class TrainSCueMapInput(_StagedLoader):
             raise ValueError("ignore_label must be a byte value, got %d" % self.ignore_label)
         if len(mean) != 3:
             raise ValueError("mean must hold 3 values")
-        self.mean, self.mirror, self.bgr, self.root = tuple(float(m) for m in mean), bool(mirror), bool(bgr), root
-        self.entries = read_pair_list(list_file)
-        self._items = epoch_items(self.entries, shuffle, random.Random(seed), rank, world_size)
-        self._mirror_rng = np.random.RandomState(seed)
+        self.mean, self.bgr, self.root = tuple(float(m) for m in mean), bool(bgr), root
+        self._open_stream(read_pair_list(list_file), mirror, shuffle, seed, rank, world_size)
 
-    def plan_batch(self):
-        plan = []
-        for _ in range(self.batch_size):
-            image_path, cue_path = next(self._items)
-            plan.append(dict(image=self.root + image_path, cue=self.root + cue_path,
-                             mirror=bool(self.mirror) and int(self._mirror_rng.choice(2)) == 0))
-        return plan
+    def _item(self, image_path, cue_path):
+        return dict(image=self.root + image_path, cue=self.root + cue_path)
 
     def _decode(self, item):
         return read_rgb(item["image"]), read_gray(item["cue"])
@@ -528,21 +536,35 @@ class TrainSCueMapInput(_StagedLoader):
         nbytes, desc = layout_train_s_cuemap([a.shape[:2] for a in images], self.map_size, [item["mirror"] for item in plan])
         return nbytes, desc, (images, cue_maps)
 
-    def _pack(self, buf, desc, pieces):
-        pack_train_s_cuemap(buf, desc, *pieces)
-
-    def _outputs(self, torch):
-        B, C, (Sh, Sw), (Hm, Wm) = self.batch_size, self.num_classes, self.size, self.map_size
-        mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)      # noqa: E731
-        return mk(B, 3, Sh, Sw), mk(B, 1, 1, C), mk(B, C, Hm, Wm)
-
     def _assemble(self, slot):
         from . import ops
         return ops.train_s_cuemap_input_batch(slot.dev, slot.desc, self.size, self.num_classes, self.map_size, self.mean,
                                               self.ignore_label, self.bgr, out=slot.outputs, nbytes=slot.nbytes)
 
 
-class TrainFInput(_StagedLoader):
+class _PairLoader(_StagedLoader):
+    """What the feeders of 'image_path label_path' lists share (TrainFInput, validate.ValInput): the decode, the stage-2 layout
+    and the two outputs (data (B,3,ch,cw), label (B,1,ch,cw)).  A feeder sets `crop` and plans items that hold image, label, top,
+    left and mirror (and Hs, Ws where the image is rescaled first)."""
+
+    pack = staticmethod(pack_train_f)
+
+    def _decode(self, item):
+        return read_rgb(item["image"]), read_gray(item["label"])
+
+    def _layout(self, plan, arrays):
+        images, labels = [a[0] for a in arrays], [a[1] for a in arrays]
+        scaled = [(it["Hs"], it["Ws"]) for it in plan] if plan and "Hs" in plan[0] else None
+        nbytes, desc = layout_train_f([a.shape[:2] for a in images], [it["top"] for it in plan], [it["left"] for it in plan],
+                                      [it["mirror"] for it in plan], scaled)
+        return nbytes, desc, (images, labels)
+
+    def out_shapes(self):
+        B, (ch, cw) = self.batch_size, self.crop
+        return (B, 3, ch, cw), (B, 1, ch, cw)
+
+
+class TrainFInput(_PairLoader):
     """Iterator of (data (B,3,ch,cw), label (B,1,ch,cw)) float32 device tensors for RetrainTrainer.step: ImageSegDataLayer
     (layer.py:17-251), assembled on the device by ops.train_f_input_batch.
 
@@ -570,10 +592,7 @@ class TrainFInput(_StagedLoader):
         self.is_mirror, self.phase, self.ignore_label = bool(params['mirror']), params['phase'], params['ignore_label']
         self.root_folder = params['root_folder']
         self.scale_factors = check_scale_factors(params['scale_factors'])
-        with open(params['source']) as f:
-            self.entries = [tuple(ln.split()[:2]) for ln in f if ln.strip()]
-        if not self.entries:
-            raise ValueError("%s lists no image / label pair" % params['source'])
+        self.entries = read_list(params['source'], "image_path label_path", "image / label pair")
         self._rng = random.Random(seed)
         self._np_rng = np.random.RandomState(seed)
         # One process: BatchLoader's shuffle, from the generator the crop offsets come from.  Several ranks: `randint` takes a
@@ -602,24 +621,6 @@ class TrainFInput(_StagedLoader):
             mirror = self.is_mirror and int(self._np_rng.choice(2)) == 0
             plan.append(dict(image=image_path, label=label_path, top=top, left=left, mirror=mirror, **rescaled))
         return plan
-
-    def _decode(self, item):
-        return read_rgb(item["image"]), read_gray(item["label"])
-
-    def _layout(self, plan, arrays):
-        images, labels = [a[0] for a in arrays], [a[1] for a in arrays]
-        scaled = [(it["Hs"], it["Ws"]) for it in plan] if plan and "Hs" in plan[0] else None
-        nbytes, desc = layout_train_f([a.shape[:2] for a in images], [it["top"] for it in plan], [it["left"] for it in plan],
-                                      [it["mirror"] for it in plan], scaled)
-        return nbytes, desc, (images, labels)
-
-    def _pack(self, buf, desc, pieces):
-        pack_train_f(buf, desc, *pieces)
-
-    def _outputs(self, torch):
-        B, (ch, cw) = self.batch_size, self.crop
-        return (torch.empty((B, 3, ch, cw), dtype=torch.float32, device=self.device),
-                torch.empty((B, 1, ch, cw), dtype=torch.float32, device=self.device))
 
     def _assemble(self, slot):
         from . import ops

@@ -709,22 +709,32 @@ def _i32s(values):
     return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
 
 
-def _stage_arg(stage, nbytes):
+def _train_input_args(stage, nbytes, desc, keys, mean, shapes, out):
+    """What the training-input wrappers share -> (head, mean3, outputs).  head: the leading arguments of every dsrg_train_*_input_batch
+    entry — B, the staging pointer, its byte count and one int32 array per key of `keys`, each checked to hold one entry per image;
+    mean3: the mean as float[3]; outputs: one float32 tensor of (B,) + shape per shape of `shapes`, made here or, with `out`,
+    checked to be that."""
     if not (torch.is_tensor(stage) and stage.is_cuda and stage.dtype == torch.uint8 and stage.is_contiguous() and stage.dim() == 1):
         raise ValueError("stage must be a contiguous 1-d uint8 CUDA tensor")
     nbytes = stage.numel() if nbytes is None else int(nbytes)
     if not 0 <= nbytes <= stage.numel():
         raise ValueError("the staging buffer holds %d bytes, the batch states %d" % (stage.numel(), nbytes))
-    return nbytes
-
-
-def _out_arg(out, shape, name, dev):
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=dev)
-    _f32c(out, name)
-    if tuple(out.shape) != tuple(shape):
-        raise ValueError("%s must be %s, got %s" % (name, tuple(shape), tuple(out.shape)))
-    return out
+    B = len(desc["H"])
+    if len(mean) != 3:
+        raise ValueError("mean must hold 3 values")
+    if any(len(desc[k]) != B for k in keys):
+        raise ValueError("every descriptor list must hold one entry per image")
+    outputs = []
+    for k, shape in enumerate(shapes):
+        shape, t = (B,) + shape, None if out is None else out[k]
+        if t is None:
+            t = torch.empty(shape, dtype=torch.float32, device=stage.device)
+        else:
+            _f32c(t, "out[%d]" % k)
+            if tuple(t.shape) != shape:
+                raise ValueError("out[%d] must be %s, got %s" % (k, shape, tuple(t.shape)))
+        outputs.append(t)
+    return (B, _ptr(stage), nbytes) + tuple(_i32s(desc[k]) for k in keys), (ctypes.c_float * 3)(*[float(m) for m in mean]), outputs
 
 
 def train_s_input_batch(stage, desc, size=321, num_classes=21, map_size=(41, 41), mean=MEAN_PIXEL, out=None, nbytes=None):
@@ -734,21 +744,11 @@ def train_s_input_batch(stage, desc, size=321, num_classes=21, map_size=(41, 41)
     label_off, nlabels (byte offsets and counts) — and mirror (one flag per image).  Returns (images (B,3,S,S), labels (B,1,1,C),
     cues (B,C,Hm,Wm)), float32: the arguments of DSRGTrainer.step.  out: three existing tensors of those shapes to write into.
     Runs on torch's current stream."""
-    nbytes = _stage_arg(stage, nbytes)
-    B = len(desc["H"])
     S, C, (Hm, Wm) = int(size), int(num_classes), (int(map_size[0]), int(map_size[1]))
-    if len(mean) != 3:
-        raise ValueError("mean must hold 3 values")
-    keys = ("image_off", "H", "W", "cue_off", "ncues", "label_off", "nlabels", "mirror")
-    if any(len(desc[k]) != B for k in keys):
-        raise ValueError("every descriptor list must hold one entry per image")
-    out = (None, None, None) if out is None else out
-    images = _out_arg(out[0], (B, 3, S, S), "out[0]", stage.device)
-    labels = _out_arg(out[1], (B, 1, 1, C), "out[1]", stage.device)
-    cues = _out_arg(out[2], (B, C, Hm, Wm), "out[2]", stage.device)
-    check(_lib.lib().dsrg_train_s_input_batch(B, _ptr(stage), nbytes, *[_i32s(desc[k]) for k in keys], S, C, Hm, Wm,
-                                              (ctypes.c_float * 3)(*[float(m) for m in mean]), _ptr(images), _ptr(cues), _ptr(labels),
-                                              _stream()))
+    head, mean3, (images, labels, cues) = _train_input_args(
+        stage, nbytes, desc, ("image_off", "H", "W", "cue_off", "ncues", "label_off", "nlabels", "mirror"), mean,
+        ((3, S, S), (1, 1, C), (C, Hm, Wm)), out)
+    check(_lib.lib().dsrg_train_s_input_batch(*head, S, C, Hm, Wm, mean3, _ptr(images), _ptr(cues), _ptr(labels), _stream()))
     return images, labels, cues
 
 
@@ -761,22 +761,12 @@ def train_s_cuemap_input_batch(stage, desc, size, num_classes, map_size, mean, i
     False, byte c (the layer's own).  Returns (images (B,3,h,w), labels (B,1,1,C), cues (B,C,Hm,Wm)), float32, every element
     written: the arguments of DSRGTrainer.step.  out: three existing tensors of those shapes to write into.  The launch takes no
     scratch.  Runs on torch's current stream."""
-    nbytes = _stage_arg(stage, nbytes)
-    B = len(desc["H"])
     Sh, Sw = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
     C, (Hm, Wm) = int(num_classes), (int(map_size[0]), int(map_size[1]))
-    if len(mean) != 3:
-        raise ValueError("mean must hold 3 values")
-    keys = ("image_off", "H", "W", "cue_off", "mirror")
-    if any(len(desc[k]) != B for k in keys):
-        raise ValueError("every descriptor list must hold one entry per image")
-    out = (None, None, None) if out is None else out
-    images = _out_arg(out[0], (B, 3, Sh, Sw), "out[0]", stage.device)
-    labels = _out_arg(out[1], (B, 1, 1, C), "out[1]", stage.device)
-    cues = _out_arg(out[2], (B, C, Hm, Wm), "out[2]", stage.device)
-    check(_lib.lib().dsrg_train_s_cuemap_input_batch(B, _ptr(stage), nbytes, *[_i32s(desc[k]) for k in keys], Sh, Sw, C, Hm, Wm,
-                                                     (ctypes.c_float * 3)(*[float(m) for m in mean]), int(ignore_label),
-                                                     int(bool(bgr)), _ptr(images), _ptr(cues), _ptr(labels), _stream()))
+    head, mean3, (images, labels, cues) = _train_input_args(stage, nbytes, desc, ("image_off", "H", "W", "cue_off", "mirror"), mean,
+                                                            ((3, Sh, Sw), (1, 1, C), (C, Hm, Wm)), out)
+    check(_lib.lib().dsrg_train_s_cuemap_input_batch(*head, Sh, Sw, C, Hm, Wm, mean3, int(ignore_label), int(bool(bgr)), _ptr(images),
+                                                     _ptr(cues), _ptr(labels), _stream()))
     return images, labels, cues
 
 
@@ -788,21 +778,12 @@ def train_f_input_batch(stage, desc, crop_size, mean, scale=1.0, ignore_label=25
     to write into.  A desc that carries Hs and Ws (layout_train_f's `scaled`) goes to dsrg_train_f_input_scaled_batch: every image
     is rescaled to (Hs, Ws) inside the same launch — 8-bit bilinear for the image, nearest neighbour for the label — and top /
     left are offsets on the rescaled image.  Runs on torch's current stream."""
-    nbytes = _stage_arg(stage, nbytes)
-    B = len(desc["H"])
     ch, cw = int(crop_size[0]), int(crop_size[1])
-    if len(mean) != 3:
-        raise ValueError("mean must hold 3 values")
     scaled = "Hs" in desc or "Ws" in desc
     keys = ("image_off", "label_off", "H", "W") + (("Hs", "Ws") if scaled else ()) + ("top", "left", "mirror")
-    if any(len(desc[k]) != B for k in keys):
-        raise ValueError("every descriptor list must hold one entry per image")
-    out = (None, None) if out is None else out
-    data = _out_arg(out[0], (B, 3, ch, cw), "out[0]", stage.device)
-    label = _out_arg(out[1], (B, 1, ch, cw), "out[1]", stage.device)
+    head, mean3, (data, label) = _train_input_args(stage, nbytes, desc, keys, mean, ((3, ch, cw), (1, ch, cw)), out)
     entry = _lib.lib().dsrg_train_f_input_scaled_batch if scaled else _lib.lib().dsrg_train_f_input_batch
-    check(entry(B, _ptr(stage), nbytes, *[_i32s(desc[k]) for k in keys], ch, cw, (ctypes.c_float * 3)(*[float(m) for m in mean]),
-                float(scale), float(ignore_label), _ptr(data), _ptr(label), _stream()))
+    check(entry(*head, ch, cw, mean3, float(scale), float(ignore_label), _ptr(data), _ptr(label), _stream()))
     return data, label
 
 

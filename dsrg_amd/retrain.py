@@ -16,6 +16,7 @@ import torch.nn.functional as F
 import os as _os
 
 from .backbone import VGG16ASPP, GemmConv2d, _ConvFn, _bf16_run, _landed
+from .input import MAX_CLASSES
 from .trainer import CaffeSGD
 
 _FUSE_RES = _os.environ.get("DSRG_RESNET_FUSE_RES", "1") == "1"   # tools / tests: 0 = the shortcut's add + ReLU and its backward as passes of their own
@@ -424,8 +425,8 @@ class RetrainTrainer(object):
         (copied by layer name: .caffemodel / .npz / torch file); snapshot: a solverstate written by save().  num_classes: the
         outputs of the classifiers of the net built here (21: VOC; 81: the COCO variant; at most 96); a `net` that is handed in
         keeps its own."""
-        if not 1 <= int(num_classes) <= 96:
-            raise ValueError("num_classes must be 1..96, got %r" % (num_classes,))
+        if not 1 <= int(num_classes) <= MAX_CLASSES:
+            raise ValueError("num_classes must be 1..%d, got %r" % (MAX_CLASSES, num_classes))
         torch.manual_seed(seed)
         self.device, self.amp_dtype, self.max_iter, self.base_lr = device, amp_dtype, max_iter, base_lr
         net = net if net is not None else (VGG16ASPP(num_classes=int(num_classes)) if backbone == "vgg16"

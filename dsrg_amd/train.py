@@ -93,8 +93,9 @@ def parse_args(argv=None):
         a.val_crop = VAL_CROP if a.val_crop is None else a.val_crop
         if min(a.val_every, a.val_crop) < 1 or (a.val_batch is not None and not 1 <= a.val_batch <= 32):
             p.error("--val-every and --val-crop must be >= 1, --val-batch 1..32")
-    if not 1 <= a.num_classes <= 96:
-        p.error("--class takes 1..96, got %d" % a.num_classes)
+    from .input import MAX_CLASSES
+    if not 1 <= a.num_classes <= MAX_CLASSES:
+        p.error("--class takes 1..%d, got %d" % (MAX_CLASSES, a.num_classes))
     if a.cue_maps and a.stage != "s":
         p.error("--cue-maps is for --stage s")
     if a.channel_order is not None and not a.cue_maps:

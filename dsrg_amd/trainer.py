@@ -7,6 +7,7 @@ import os
 import torch
 
 from .backbone import VGG16ASPP
+from .input import MAX_CLASSES
 from .ops import dsrg_supervision_loss
 
 
@@ -140,8 +141,8 @@ class DSRGTrainer(object):
         copied by layer name before training; snapshot: `train.py --snapshot` — a solverstate written by save().
         num_classes: the outputs of the four classifiers of the net built here (21: VOC; 81: the COCO variant; at most 96, the
         layer kernels' kMaxLabels); a `net` that is handed in keeps its own."""
-        if not 1 <= int(num_classes) <= 96:
-            raise ValueError("num_classes must be 1..96, got %r" % (num_classes,))
+        if not 1 <= int(num_classes) <= MAX_CLASSES:
+            raise ValueError("num_classes must be 1..%d, got %r" % (MAX_CLASSES, num_classes))
         torch.manual_seed(seed)            # same initial weights on every rank (the reducer also broadcasts)
         self.device = device
         self.amp_dtype = amp_dtype

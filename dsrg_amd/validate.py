@@ -24,25 +24,15 @@ import sys
 import numpy as np
 import torch
 
-from .input import _StagedLoader, image_size, layout_train_f, pack_train_f, read_gray, read_rgb
+from .input import _PairLoader, _StagedLoader, image_size, read_list
 
 
 def read_val_list(path):
     """'image_path label_path' lines -> [(image_path, label_path)]"""
-    out = []
-    with open(path) as f:
-        for line in f:
-            parts = line.split()
-            if parts:
-                if len(parts) < 2:
-                    raise ValueError("%s: expected 'image_path label_path', got %r" % (path, line.strip()))
-                out.append((parts[0], parts[1]))
-    if not out:
-        raise ValueError("%s lists no image / label pair" % path)
-    return out
+    return read_list(path, "image_path label_path", "image / label pair")
 
 
-class ValInput(_StagedLoader):
+class ValInput(_PairLoader):
     """Iterator of (data (n,3,crop,crop), label (n,1,crop,crop)) float32 device tensors, n = batch_size but for a shorter last
     batch: ONE pass over this rank's share — items rank, rank + world_size, ... — of list_file, in list order.  Every listed image
     is returned exactly once over the ranks, whatever the batch and world sizes.  An image lies at top = left = 0 of its window,
@@ -71,45 +61,15 @@ class ValInput(_StagedLoader):
             H, W = image_size(label_path)
             if H > self.crop[0] or W > self.crop[1]:
                 raise ValueError("%s is %d x %d: larger than the %d x %d validation crop" % ((label_path, H, W) + self.crop))
-            plan.append(dict(image=image_path, label=label_path))
+            plan.append(dict(image=image_path, label=label_path, top=0, left=0, mirror=False))
         self._planned += len(plan)
         return plan
 
-    def _decode(self, item):
-        return read_rgb(item["image"]), read_gray(item["label"])
-
-    def _layout(self, plan, arrays):
-        images, labels = [a[0] for a in arrays], [a[1] for a in arrays]
-        zeros = [0] * len(plan)
-        nbytes, desc = layout_train_f([a.shape[:2] for a in images], zeros, zeros, zeros)
-        return nbytes, desc, (images, labels)
-
-    def _pack(self, buf, desc, pieces):
-        pack_train_f(buf, desc, *pieces)
-
-    def _outputs(self, torch):
-        B, (ch, cw) = self.batch_size, self.crop
-        return (torch.empty((B, 3, ch, cw), dtype=torch.float32, device=self.device),
-                torch.empty((B, 1, ch, cw), dtype=torch.float32, device=self.device))
-
     def _assemble(self, slot):
         from . import ops
-        n = len(slot.desc["H"])                              # a short last batch fills the first n slices of the slot's tensors
+        n = slot.count                                       # a short last batch fills the first n slices of the slot's tensors
         return ops.train_f_input_batch(slot.dev, slot.desc, self.crop, self.mean, 1.0, self.ignore_label,
                                        out=(slot.outputs[0][:n], slot.outputs[1][:n]), nbytes=slot.nbytes)
-
-    # the pass is finite: an empty plan marks its end and is neither staged nor assembled
-    def _upload(self, pending, slot):
-        slot.count = len(pending[0])
-        if slot.count:
-            _StagedLoader._upload(self, pending, slot)
-
-    def _advance(self):
-        if self._slots is None:
-            self._start()
-        if self._slots[self._count % 2].count == 0:
-            raise StopIteration
-        return _StagedLoader._advance(self)
 
 
 def reduce_counts(hist):

@@ -424,8 +424,9 @@ int dsrg_train_s_input_batch(int B, const unsigned char *stage_dev, size_t stage
  *              kept byte gives all zeros)
  * 1 <= B <= 32, Sh, Sw, Hm, Wm >= 1, 1 <= C <= 96 (above: DSRG_ERR_UNSUPPORTED), 0 <= ignore_label <= 255, bgr 0 or 1, H_b, W_b
  * >= 1, every offset + extent inside stage_bytes < 2^31, H_b*W_b*3, B*3*Sh*Sw and B*C*Hm*Wm < 2^31, outputs aligned to 4 bytes
- * (otherwise DSRG_ERR_INVALID); every argument is checked before the first device call.  Nothing is allocated.  Stream-ordered, no
- * host synchronisation, no handle; bit-reproducible (no atomics). */
+ * (otherwise DSRG_ERR_INVALID — the 2^31 limits included: an INCONSISTENCY with the three sibling entries, which answer theirs
+ * with DSRG_ERR_UNSUPPORTED; kept, since callers may test the code); every argument is checked before the first device call.
+ * Nothing is allocated.  Stream-ordered, no host synchronisation, no handle; bit-reproducible (no atomics). */
 int dsrg_train_s_cuemap_input_batch(int B, const unsigned char *stage_dev, size_t stage_bytes, const int32_t *image_off_host,
                                     const int32_t *H_host, const int32_t *W_host, const int32_t *cue_off_host,
                                     const int32_t *mirror_host, int Sh, int Sw, int C, int Hm, int Wm, const float *mean_host,

@@ -213,9 +213,8 @@ def test_cuemap_loader_refuses_bad_cue_files_before_any_upload(tmp_path):
     lst, root, names = _write_cuemap_files(tmp_path, rng, [(9, 11), (12, 7), (8, 8)], (4, 6), 81)
     mk = lambda **kw: I.TrainSCueMapInput(lst, root, 81, batch_size=3, size=(24, 40), shuffle=False, **kw)    # noqa: E731
 
-    def laid_out(ld):                                                   # what _upload does before it touches the device
-        plan = ld.plan_batch()
-        return ld._layout(plan, [ld._decode(it) for it in plan])
+    def laid_out(ld):                                                   # what an upload does before it touches the device
+        return ld.stage_batch()
 
     ld = mk()
     assert ld.map_size == (4, 6) and ld.size == (24, 40)

@@ -88,6 +88,38 @@ def test_validator_equals_the_host_computation_and_shards_over_ranks(tmp_path):
     assert torch.cuda.current_stream() == torch.cuda.default_stream()
 
 
+@pytest.mark.parametrize("n", [1, 2, 3, 5])
+def test_val_input_is_one_finite_pass_over_the_ranks(tmp_path, n):
+    """ValInput on n images of 8 x 8 at crop 16 and batch 2, world sizes 1 and 2: every listed image comes exactly once over the
+    ranks and in list order within a rank (told apart by its label plane), a rank beyond the end of a one-image list yields nothing,
+    the pass ends in StopIteration and the loader is closed after it"""
+    from dsrg_amd.validate import ValInput
+    lst, root, labels = K.write_val_files(tmp_path, np.random.default_rng(60 + n), ((8, 8),) * n)
+    want = K.padded_labels(labels, 16)
+    assert len({w.tobytes() for w in want}) == n                       # (the label planes tell the images apart)
+    for world in (1, 2):
+        seen = []
+        for rank in range(world):
+            share = list(range(rank, n, world))
+            loader = ValInput(lst, root, crop=16, batch_size=2, workers=2, rank=rank, world_size=world)
+            got = []
+            for k in range(0, len(share), 2):
+                data, label = next(loader)
+                m = min(2, len(share) - k)
+                assert tuple(data.shape) == (m, 3, 16, 16) and tuple(label.shape) == (m, 1, 16, 16)
+                assert not data[:, :, 8:].any() and not data[:, :, :, 8:].any()         # nothing off the 8 x 8 images
+                for plane in label.cpu().numpy():
+                    got += [i for i in range(n) if np.array_equal(plane, want[i])]
+            assert got == share, (world, rank)
+            with pytest.raises(StopIteration):
+                next(loader)
+            with pytest.raises(RuntimeError, match="loader is closed"):
+                next(loader)
+            seen += got
+        assert sorted(seen) == list(range(n)), world
+    assert torch.cuda.current_stream() == torch.cuda.default_stream()
+
+
 def test_validation_between_two_steps_leaves_the_run_bit_identical(tmp_path):
     from dsrg_amd.retrain import RetrainTrainer
     from dsrg_amd.trainer import params_checksum
