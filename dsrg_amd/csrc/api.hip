@@ -592,6 +592,12 @@ extern "C" int dsrg_eval_confusion_batch(int B, int C, const float *scores, int 
     // every argument is checked before the first device call
     return launch_eval_confusion_batch(B, C, scores, h, w, labels, Hz, Wz, ignore_label, rule_lt, hist, static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_score_labels_batch(int G, int C, const int32_t *const *labels, const unsigned char *const *gt, const int32_t *H,
+                                       const int32_t *W, int ignore_label, int rule_lt, unsigned long long *hist,
+                                       unsigned char *const *mask, void *stream) {
+    // every argument is checked before the first device call
+    return launch_score_labels_batch(G, C, labels, gt, H, W, ignore_label, rule_lt, hist, mask, static_cast<hipStream_t>(stream));
+}
 extern "C" size_t dsrg_resnet_stem_packed_bytes(void) { return resnet_stem_packed_bytes(); }
 extern "C" int dsrg_pack_resnet_stem_f32(const float *w, const float *scale, void *packed, void *stream) {
     if (!w || !scale || !packed) return set_error(DSRG_ERR_INVALID, "resnet stem pack: NULL argument");

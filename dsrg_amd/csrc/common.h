@@ -343,6 +343,9 @@ int launch_train_f_input_scaled_batch(int B, const unsigned char *stage, size_t 
                                       float scale, float ignore_label, float *data, float *label, hipStream_t stream);
 int launch_eval_confusion_batch(int B, int C, const float *scores, int h, int w, const float *labels, int Hz, int Wz,
                                 float ignore_label, int rule_lt, unsigned long long *hist, hipStream_t stream);
+int launch_score_labels_batch(int G, int C, const int32_t *const *labels, const unsigned char *const *gt, const int32_t *H,
+                              const int32_t *W, int ignore_label, int rule_lt, unsigned long long *hist, unsigned char *const *mask,
+                              hipStream_t stream);
 size_t resnet_stem_packed_bytes();
 int launch_pack_resnet_stem(const float *w, const float *scale, void *packed, hipStream_t stream);
 int launch_resnet_stem(const float *x, const void *packed, const float *shift, void *y, int B, int H, int W, hipStream_t stream);

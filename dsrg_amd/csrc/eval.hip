@@ -110,4 +110,87 @@ int launch_eval_confusion_batch(int B, int C, const float *scores, int h, int w,
     return DSRG_OK;
 }
 
+// ---- scoring finished label maps: a group of differently sized int32 label maps and their uint8 ground truth -> the same counters
+//
+// The label maps are what the dense CRF's map and the arg-max outputs of the multi-scale / pseudo-label tails leave on the device.
+// The G images' pixels are numbered through the group (image g holds pixels off[g] .. off[g + 1]); the grid, the runs of 256
+// consecutive pixels, the LDS histogram and the way it is added to the global counters are eval_confusion_batch_kernel's.  A run may
+// straddle images: a lane finds its image by walking the prefix offsets upwards (its pixels only ever increase), and the reads of
+// either side of a seam are still consecutive.  A lane reads its ground-truth byte first; one that is dropped loads no label — and a
+// wave none of whose bytes is kept issues no label load — unless masks are wanted: then every pixel's label is read and written back
+// as a byte, 255 standing for everything outside 0..255 (what astype(uint8) gives the label maps the project produces, whose only
+// value outside 0..C-1 is the 255 of ignore_below).
+constexpr int kScoreMaxGroup = 16;
+
+struct ScoreLabelsArgs {
+    const int32_t *labels[kScoreMaxGroup];
+    const unsigned char *gt[kScoreMaxGroup];
+    unsigned char *mask[kScoreMaxGroup];                      // all NULL: no masks wanted
+    unsigned off[kScoreMaxGroup + 1];                         // off[G] = the group's pixels (< 2^31)
+};
+
+__global__ __launch_bounds__(kEvalThreads) void score_labels_batch_kernel(ScoreLabelsArgs a, int G, int C, int ignore_label, int rule_lt,
+                                                                          int want_mask, unsigned long long *__restrict__ hist) {
+    extern __shared__ unsigned int s_hist[];                  // [C * C + 1]
+    const int nb = C * C + 1;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < nb; i += kEvalThreads) s_hist[i] = 0u;
+    __syncthreads();
+
+    const unsigned total = a.off[G];                          // (< 2^31: p + stride below stays inside 32 bits)
+    const unsigned stride = gridDim.x * kEvalThreads;
+    int g = 0;
+#pragma unroll 1
+    for (unsigned p = blockIdx.x * kEvalThreads + tid; p < total; p += stride) {
+        while (g + 1 < G && p >= a.off[g + 1]) ++g;
+        const unsigned i = p - a.off[g];
+        const int t = (int)a.gt[g][i];
+        const bool keep = rule_lt ? t < C : t != ignore_label;
+        if (!keep && !want_mask) continue;
+        const int l = a.labels[g][i];
+        if (want_mask) a.mask[g][i] = (unsigned char)((unsigned)l <= 255u ? l : 255);
+        if (!keep) continue;
+        const bool in_range = t < C && (unsigned)l < (unsigned)C;
+        atomicAdd(&s_hist[in_range ? t * C + l : nb - 1], 1u);
+    }
+    __syncthreads();
+
+    // the workgroup's non-zero counters out
+    for (int i = tid; i < nb; i += kEvalThreads) {
+        const unsigned int v = s_hist[i];
+        if (v) atomicAdd(&hist[i], (unsigned long long)v);
+    }
+}
+
+int launch_score_labels_batch(int G, int C, const int32_t *const *labels, const unsigned char *const *gt, const int32_t *H,
+                              const int32_t *W, int ignore_label, int rule_lt, unsigned long long *hist, unsigned char *const *mask,
+                              hipStream_t stream) {
+    if (!labels || !gt || !hist || !H || !W)
+        return set_error(DSRG_ERR_INVALID, "score labels batch: NULL labels / gt / hist / size array");
+    if (G < 1 || G > kScoreMaxGroup) return set_error(DSRG_ERR_INVALID, "score labels batch: 1..%d images, got %d", kScoreMaxGroup, G);
+    if (C < 1) return set_error(DSRG_ERR_INVALID, "score labels batch: %d labels", C);
+    if (C > kMaxLabels) return set_error(DSRG_ERR_UNSUPPORTED, "score labels batch: at most %d labels, got %d", kMaxLabels, C);
+    ScoreLabelsArgs a = {};
+    long long total = 0;
+    for (int g = 0; g < G; ++g) {
+        if (!labels[g] || !gt[g] || (mask && !mask[g]))
+            return set_error(DSRG_ERR_INVALID, "score labels batch: image %d has a NULL label map, ground truth or mask", g);
+        if (H[g] < 1 || W[g] < 1) return set_error(DSRG_ERR_INVALID, "score labels batch: image %d is %dx%d", g, H[g], W[g]);
+        total += (long long)H[g] * W[g];                      // (each product < 2^62, checked before the next is added)
+        if (total >= (1LL << 31)) return set_error(DSRG_ERR_INVALID, "score labels batch: the group holds >= 2^31 pixels");
+        a.labels[g] = labels[g];
+        a.gt[g] = gt[g];
+        a.mask[g] = mask ? mask[g] : nullptr;
+        a.off[g + 1] = (unsigned)total;
+    }
+    for (int g = G + 1; g <= kScoreMaxGroup; ++g) a.off[g] = (unsigned)total;
+    const long long runs = (total + kEvalThreads - 1) / kEvalThreads;
+    const unsigned grid = (unsigned)(runs < kEvalMaxBlocks ? runs : kEvalMaxBlocks);
+    const size_t lds = ((size_t)C * C + 1) * sizeof(unsigned int);         // <= 36 868 B: inside the default dynamic-LDS limit
+    hipLaunchKernelGGL(score_labels_batch_kernel, dim3(grid), dim3(kEvalThreads), lds, stream, a, G, C, ignore_label, rule_lt,
+                       mask ? 1 : 0, hist);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
 }  // namespace dsrg

@@ -102,6 +102,26 @@ def _host_mask(labels):
     return labels.cpu().numpy().astype(np.int64)
 
 
+def _device_mask(labels):
+    """a label map on the device -> the (H,W) int32 CUDA tensor masks="device" yields: the tensor itself where it is one already
+    (the CRF's map, the kernels' arg-max), torch's int64 argmax narrowed on the device.  Nothing crosses PCIe, nothing waits"""
+    return labels if labels.dtype == torch.int32 and labels.is_contiguous() else labels.to(torch.int32).contiguous()
+
+
+def _mask_out(masks):
+    """the `masks` keyword of the *_many generators -> what turns a label map on the device into the yielded mask.  "host" (the
+    default): _host_mask, an (H,W) int64 array.  "device": _device_mask, the (H,W) int32 CUDA tensor, same values in the same order
+    with no copy to the host anywhere on the path.  A yielded tensor is final: it is ordered before anything the consumer enqueues
+    afterwards on the stream that was current when the generator was first advanced (the generators hand control back with that
+    stream current), and its memory cannot be reused by the stream that produced it while work the consumer queued there is
+    pending.  ValueError for any other value, before any stream or worker exists"""
+    if masks == "host":
+        return _host_mask
+    if masks == "device":
+        return _device_mask
+    raise ValueError('masks must be "host" or "device", got %r' % (masks,))
+
+
 class GraphedForward(object):
     """`net(x)` of an eval-mode network for the FIXED input shapes of the test-time loop (test-ms.py resizes every image to 241 / 321 /
     401 before the forward, whatever its own size) as captured HIP graphs: one backbone.GraphedForward per input shape (and autocast
@@ -237,16 +257,20 @@ def predict_mask_ms(net, image, smooth=True, sizes=(241, 321, 401), device="cuda
     runs on the image and its mirror image as one batch-2 forward, and the tail is the fused kernel (one
     dsrg_multiscale_unary_mirror launch on the 2K maps: zoom, the mirrors read reversed, sum, softmax, clamp, log) instead of the
     torch composition this function runs without flip"""
-    sizes = tuple(sizes)
+    return _host_mask(_ms_labels(net, image, smooth, tuple(sizes), device, forward, flip))
+
+
+def _ms_labels(net, image, smooth, sizes, device, forward, flip):
+    """predict_mask_ms up to the label map on the device: (H,W) int32, or int64 where it is torch's argmax (no CRF, no flip)"""
     if flip:
         _check_flip(len(sizes))
     if smooth:
         # scores, log-probabilities, CRF and arg-max all stay on the GPU; only the (H,W) mask crosses PCIe
         unary = _ms_unary(net, image, sizes, device, forward, flip)
-        return _host_mask(CRF_device(_device_image(image, unary.device), unary, scale_factor=1.0, want="map"))
+        return CRF_device(_device_image(image, unary.device), unary, scale_factor=1.0, want="map")
     if flip:
-        return _host_mask(_ms_flip_result(net, image, sizes, device, forward, "argmax"))
-    return _probs_from_scores(multiscale_scores(net, image, sizes, device, forward)).argmax(0).cpu().numpy()
+        return _ms_flip_result(net, image, sizes, device, forward, "argmax")
+    return _probs_from_scores(multiscale_scores(net, image, sizes, device, forward)).argmax(0)
 
 
 MAX_FORWARD_BATCH = 16      # images per group of the batched path (the limit of the two batched kernels)
@@ -321,7 +345,7 @@ def _group_results(net, images, shapes, device, forward, want, flip, square=Fals
 
 @torch.no_grad()
 def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", forward=None, in_flight=3, batch=1, forward_batch=1,
-                          flip=False, smooth=True):
+                          flip=False, smooth=True, masks="host"):
     """predict_mask_ms over many images (the loop of test-ms.py over a split's 1 449 / 10 582 images), as a generator of (H,W) int64
     masks in order: the forwards of image i + 1 (on the caller's stream; `forward`: a GraphedForward) run while the CRFs of the images
     before it are in flight on `in_flight` worker streams (crf.CRF_device_many; batch > 1: consecutive same-sized images share one
@@ -335,8 +359,11 @@ def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", for
     flip=True: predict_mask_ms(flip=True) image by image; with forward_batch = G (at most 8, and at most 4 sizes: ValueError
     before any stream or worker exists) a group is one dsrg_preprocess_rect_mirror_batch launch, len(sizes) batch-2G forwards
     (image g in slot 2g, its mirror image in slot 2g+1, the padding slots zero) and one dsrg_multiscale_unary_mirror_batch
-    launch."""
+    launch.
+
+    masks="device": the (H,W) int32 CUDA tensors instead, nothing copied to the host (_mask_out has the contract)."""
     sizes = tuple(sizes)
+    out = _mask_out(masks)
     if flip:
         _check_flip(len(sizes), forward_batch)
     if int(forward_batch) != 1:
@@ -351,13 +378,13 @@ def predict_masks_ms_many(net, images, sizes=(241, 321, 401), device="cuda", for
                 yield _device_image(image, unary.device), unary
     else:
         for image in images:
-            yield predict_mask_ms(net, image, False, sizes, device, forward, flip)
+            yield out(_ms_labels(net, image, False, sizes, device, forward, flip))
         return
     if smooth:
-        yield from _crf_in_flight(results(), device, in_flight, batch)
+        yield from _crf_in_flight(results(), device, in_flight, batch, masks=masks)
     else:
         for _, labels in results():
-            yield _host_mask(labels)
+            yield out(labels)
 
 
 @torch.no_grad()
@@ -381,10 +408,19 @@ def predict_masks_ms_batched(net, images, smooth=True, sizes=(241, 321, 401), de
     return [_host_mask(labels) for labels in outs]
 
 
-def _crf_in_flight(pairs, device, in_flight, batch, ignore_below=None):
+def _crf_in_flight(pairs, device, in_flight, batch, ignore_below=None, masks="host"):
     """the CRF half of the *_many generators: (image, unary) pairs -> (H,W) int64 masks in order, CRFs on worker streams while the
     pairs (the forwards) are produced on a forward stream of their own.  (image, unary, select) triples: the masks are restricted
-    to each image's label list (crf.CRF_device_many), with ignore_below as DenseCRF.map takes it"""
+    to each image's label list (crf.CRF_device_many), with ignore_below as DenseCRF.map takes it.
+
+    masks="device": the workers' (H,W) int32 label maps themselves.  Between two yields this generator keeps the forward stream
+    current, and a consumer's launches would land there, among the forwards; so a device mask is handed over with the CALLER's
+    stream — the one current when the generator was first advanced — made current again for as long as the consumer holds
+    control.  The map is final before that: the worker's library call returned with its stream drained (crf.CRF_device_many), so
+    whatever the consumer enqueues, on any stream, comes after it.  Its memory belongs to the worker stream's pool and is marked
+    as in use on the caller's stream (record_stream, as CRF_device_many marks it for the stream it was started on, here the
+    forward stream): the worker cannot get the block back while launches the consumer queued on it are pending"""
+    _mask_out(masks)
     from .crf import CRF_device_many
     from .streams import side_stream
     # the CRF workers come back from the library three times per image and need the interpreter lock for a few lines each time; the
@@ -401,7 +437,13 @@ def _crf_in_flight(pairs, device, in_flight, batch, ignore_below=None):
         with torch.cuda.stream(fstream):
             for lab in CRF_device_many(pairs, scale_factor=1.0, want="map", in_flight=in_flight, batch=batch,
                                        ignore_below=ignore_below):
-                yield _host_mask(lab)
+                if masks == "host":
+                    yield _host_mask(lab)
+                    continue
+                lab = _device_mask(lab)
+                lab.record_stream(caller)
+                with torch.cuda.stream(caller):
+                    yield lab
     finally:
         sys.setswitchinterval(interval)
         # what the forward stream still holds (a forward issued ahead of a generator that was closed early, writes into a graph's
@@ -463,10 +505,15 @@ def predict_mask_ms_f(net, image, scales=(0.75, 1.0, 1.25), smooth=True, device=
     are mirrored back and all 2K maps summed (scale 0 plain, scale 0 mirror, scale 1 plain, ...) before the softmax: one
     dsrg_multiscale_unary_mirror launch, or with fused=False torch.flip of the mirrors' scores in the torch composition (zoomed
     by _zoom_steps: its summed scores are the kernel's bit for bit)"""
-    out = _relative_unary(net, image, tuple(scales), device, forward, fused, smooth, flip)
+    return _host_mask(_ms_f_labels(net, image, tuple(scales), smooth, device, forward, fused, flip))
+
+
+def _ms_f_labels(net, image, scales, smooth, device, forward, fused, flip):
+    """predict_mask_ms_f up to the label map on the device: (H,W) int32, or int64 where it is torch's argmax (fused=False, no CRF)"""
+    out = _relative_unary(net, image, scales, device, forward, fused, smooth, flip)
     if smooth:
         out = CRF_device(_device_image(image, out.device), out, scale_factor=1.0, want="map")
-    return _host_mask(out)
+    return out
 
 
 def plan_size_groups(keys, G, window):
@@ -516,7 +563,7 @@ def _relative_shapes(H, W, scales):
 
 @torch.no_grad()
 def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda", forward=None, in_flight=3, batch=1, fused=True,
-                            same_size_batch=1, window=64, smooth=True, flip=False):
+                            same_size_batch=1, window=64, smooth=True, flip=False, masks="host"):
     """predict_mask_ms_f over many images, as predict_masks_ms_many does it for test-ms.py: a generator of (H,W) int64 masks
     in order, the forwards of the next image running while the CRFs of the images before it are in flight (smooth=False: the
     arg-max, no CRF).  Same masks as predict_mask_ms_f image by image.
@@ -534,9 +581,13 @@ def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda"
 
     flip=True: predict_mask_ms_f(flip=True) image by image; with same_size_batch = G (at most 8, and at most 4 scales:
     ValueError before any stream or worker exists) a group of n images is one dsrg_preprocess_rect_mirror_batch launch,
-    len(scales) batch-2n forwards and one dsrg_multiscale_unary_mirror_batch launch."""
+    len(scales) batch-2n forwards and one dsrg_multiscale_unary_mirror_batch launch.
+
+    masks="device": the (H,W) int32 CUDA tensors instead, nothing copied to the host (_mask_out has the contract); the reorder
+    buffer of same_size_batch > 1 then holds device tensors."""
     G = int(same_size_batch)
     scales = tuple(scales)
+    to_mask = _mask_out(masks)
     if flip:
         _check_flip(len(scales), G)
     if G != 1:
@@ -561,11 +612,11 @@ def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda"
                     yield im, out
 
         if smooth:
-            masks = _crf_in_flight(results(), device, in_flight, batch)
+            produced = _crf_in_flight(results(), device, in_flight, batch, masks=masks)
         else:
-            masks = (_host_mask(lab) for _, lab in results())
+            produced = (to_mask(lab) for _, lab in results())
         held_masks, nxt = {}, 0
-        for mask in masks:
+        for mask in produced:
             held_masks[order.popleft()] = mask
             while nxt in held_masks:
                 yield held_masks.pop(nxt)
@@ -573,7 +624,7 @@ def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda"
         return
     if not smooth:
         for image in images:
-            yield predict_mask_ms_f(net, image, scales, False, device, forward, fused, flip)
+            yield to_mask(_ms_f_labels(net, image, scales, False, device, forward, fused, flip))
         return
 
     def pairs():
@@ -581,7 +632,7 @@ def predict_masks_ms_f_many(net, images, scales=(0.75, 1.0, 1.25), device="cuda"
             unary = _relative_unary(net, image, scales, device, forward, fused, True, flip)
             yield _device_image(image, unary.device), unary
 
-    yield from _crf_in_flight(pairs(), device, in_flight, batch)
+    yield from _crf_in_flight(pairs(), device, in_flight, batch, masks=masks)
 
 
 @torch.no_grad()
@@ -599,16 +650,18 @@ def train_gt_selection(labels):
 
 
 def predict_train_gt_many(net, items, smooth=True, size=321, device="cuda", forward=None, in_flight=3, batch=1, forward_batch=1,
-                          ignore_below=None):
+                          ignore_below=None, masks="host"):
     """generate_train_gt.py:78-106 over many images (its loop over the 10 582 images of train_aug): items is an iterable of
     (image (H,W,3) RGB, image-level labels); a generator of (H,W) int64 masks in order, each restricted to background + the
     image's labels.  It is predict_train_gt_ms_many at the one size `size` without flip, which see for the groups, the CRFs and
     ignore_below: per group of forward_batch = G images one dsrg_preprocess_ms_batch launch at `size`, ONE batch-G forward and the
     pseudo-label tail on its one map per image (softmax at map resolution, zoom of the probabilities, clamp, log).
     forward_batch=1 is the per-image route on the same kernels; outside 1..16: ValueError before any launch.  A batch-G forward
-    need not round as a batch-1 forward does: the masks are predict_train_gt's except where two labels all but tie."""
+    need not round as a batch-1 forward does: the masks are predict_train_gt's except where two labels all but tie.
+    masks="device": the (H,W) int32 CUDA tensors instead (_mask_out has the contract)."""
     return predict_train_gt_ms_many(net, items, sizes=(size,), flip=False, smooth=smooth, device=device, forward=forward,
-                                    in_flight=in_flight, batch=batch, forward_batch=forward_batch, ignore_below=ignore_below)
+                                    in_flight=in_flight, batch=batch, forward_batch=forward_batch, ignore_below=ignore_below,
+                                    masks=masks)
 
 
 MAX_ENSEMBLE_MAPS = 8       # maps per image in one dsrg_train_gt_ensemble_batch: K sizes, with flip=True two maps each
@@ -661,7 +714,7 @@ def predict_train_gt_ms(net, image, labels, sizes=(241, 321, 401), flip=False, s
 
 @torch.no_grad()
 def predict_train_gt_ms_many(net, items, sizes=(241, 321, 401), flip=False, smooth=True, device="cuda", forward=None, in_flight=3,
-                             batch=1, forward_batch=1, ignore_below=None):
+                             batch=1, forward_batch=1, ignore_below=None, masks="host"):
     """The pseudo-label pass over many images as a probability ensemble over `sizes`, with flip=True each size also on the mirror
     image (no counterpart in the reference; sizes=(S,) without flip is predict_train_gt_many(size=S)): items is an iterable of
     (image (H,W,3) RGB, image-level labels); a generator of (H,W) int64 masks in order, each restricted to background + the
@@ -675,9 +728,11 @@ def predict_train_gt_ms_many(net, items, sizes=(241, 321, 401), flip=False, smoo
     own restricted arg-max of the clamped probabilities.  ignore_below: pixels whose largest probability / marginal over all
     labels is below it get 255 (the reference's commented-out line 104); None: off.  At most 8 sizes and forward_batch in 1..16;
     flip=True: at most 4 sizes and forward_batch <= 8 (ValueError before any stream or worker exists).  The masks are
-    predict_train_gt_ms's except where two labels all but tie."""
+    predict_train_gt_ms's except where two labels all but tie.  masks="device": the (H,W) int32 CUDA tensors instead, nothing
+    copied to the host (_mask_out has the contract)."""
     from . import ops
     sizes = tuple(int(S) for S in sizes)
+    to_mask = _mask_out(masks)
     _check_ensemble(len(sizes), flip, forward_batch)
     if not 1 <= int(forward_batch) <= MAX_FORWARD_BATCH:
         raise ValueError("forward_batch must be 1..%d, got %d" % (MAX_FORWARD_BATCH, int(forward_batch)))
@@ -700,10 +755,10 @@ def predict_train_gt_ms_many(net, items, sizes=(241, 321, 401), flip=False, smoo
                     yield lab
 
     if smooth:
-        yield from _crf_in_flight(group_results(), device, in_flight, batch, ignore_below)
+        yield from _crf_in_flight(group_results(), device, in_flight, batch, ignore_below, masks=masks)
         return
     for lab in group_results():
-        yield _host_mask(lab)
+        yield to_mask(lab)
 
 
 class ConfusionMatrix(object):
@@ -765,3 +820,88 @@ class ConfusionMatrix(object):
         d = np.diag(self.M)
         per = [d[i] / (np.sum(self.M[i, :]) + np.sum(self.M[:, i]) - d[i]) for i in range(self.nclass) if d[i] != 0]
         return np.sum(per) / len(per), per, self.M
+
+
+MAX_SCORE_GROUP = 16        # label maps per MaskScorer.add (the limit of dsrg_score_labels_batch)
+
+
+class MaskScorer(object):
+    """The confusion counters of device label maps (what the *_many generators yield with masks="device") against ground truth
+    read on the host, kept on the device: test-coco.py:62-81,138-173's running confusion matrix without the label maps ever
+    leaving the GPU.  rule_lt=True keeps ground truth < nclass (generateM, the rule of `python -m dsrg_amd.evaluate`), False
+    ground truth != ignore_label (ConfusionMatrix.add).
+
+    add() packs the ground truth of a group of up to 16 images into one of two pinned staging slots and uploads it with ONE copy
+    (the idea of input._StagedLoader: a slot is rewritten only after the upload of the group before last, which an event marks,
+    has finished — normally long ago, so the host does not wait), then scores the group with one dsrg_score_labels_batch launch
+    on torch's current stream.  With want_masks that launch also narrows the label maps to bytes into one device buffer, which
+    comes down with ONE copy (this the host waits for) and is returned as uint8 arrays: the PNG payloads.  Nothing else waits;
+    counts() synchronises once."""
+
+    def __init__(self, nclass, device, rule_lt=True, ignore_label=255, want_masks=False):
+        self.nclass, self.device = int(nclass), torch.device(device)
+        if not 1 <= self.nclass <= 96:
+            raise ValueError("1..96 classes, got %d" % self.nclass)
+        self.rule_lt, self.ignore_label, self.want_masks = bool(rule_lt), int(ignore_label), bool(want_masks)
+        self.hist = torch.zeros(self.nclass * self.nclass + 1, dtype=torch.int64, device=self.device)
+        self._stage, self._uploaded, self._turn = [None, None], [None, None], 0
+        self._mask_stage = None
+
+    @staticmethod
+    def _pinned(buf, nbytes):
+        """buf if it holds nbytes, else a larger pinned uint8 buffer (half as much again, so that a run's slots settle)"""
+        if buf is not None and buf.numel() >= nbytes:
+            return buf
+        return torch.empty(nbytes + nbytes // 2, dtype=torch.uint8, pin_memory=True)
+
+    def add(self, labels, gts):
+        """labels: 1..16 (H,W) int32 CUDA label maps; gts: as many (H,W) uint8 arrays of the same sizes (a mismatch: ValueError
+        before any copy or launch).  Adds the group to the counters; with want_masks returns the group's (H,W) uint8 masks as host
+        arrays (copies: they stay valid), otherwise None"""
+        from . import ops
+        labels, gts = list(labels), [np.asarray(g) for g in gts]
+        if not 1 <= len(labels) <= MAX_SCORE_GROUP or len(gts) != len(labels):
+            raise ValueError("a group holds 1..%d label maps and as many ground truths, got %d and %d"
+                             % (MAX_SCORE_GROUP, len(labels), len(gts)))
+        for g, (lab, gt) in enumerate(zip(labels, gts)):
+            if gt.dtype != np.uint8 or gt.ndim != 2 or tuple(gt.shape) != tuple(lab.shape):
+                raise ValueError("ground truth %d is %s %s, its label map %s" % (g, gt.dtype, tuple(gt.shape), tuple(lab.shape)))
+        sizes = [gt.size for gt in gts]
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        total = int(offs[-1])
+        k = self._turn
+        self._turn ^= 1
+        if self._uploaded[k] is not None:
+            self._uploaded[k].synchronize()                  # the upload that last read this slot
+        stage = self._stage[k] = self._pinned(self._stage[k], total)
+        flat = stage.numpy()
+        for gt, o in zip(gts, offs):
+            flat[o:o + gt.size] = gt.reshape(-1)
+        with torch.cuda.device(self.device):
+            packed = torch.empty(total, dtype=torch.uint8, device=self.device)
+            packed.copy_(stage[:total], non_blocking=True)
+            self._uploaded[k] = torch.cuda.Event()
+            self._uploaded[k].record()
+
+            def views(buf):
+                return [buf[o:o + n].reshape(tuple(lab.shape)) for lab, o, n in zip(labels, offs.tolist(), sizes)]
+
+            narrowed = torch.empty(total, dtype=torch.uint8, device=self.device) if self.want_masks else None
+            ops.score_labels_batch(labels, views(packed), self.nclass, self.ignore_label, self.rule_lt, hist=self.hist,
+                                   masks=None if narrowed is None else views(narrowed))
+            if narrowed is None:
+                return None
+            host = self._mask_stage = self._pinned(self._mask_stage, total)
+            host[:total].copy_(narrowed, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        return [a.copy() for a in views(host.numpy())]
+
+    def counts(self):
+        """the nclass*nclass + 1 counters so far as an int64 array; synchronises once"""
+        return self.hist.cpu().numpy()
+
+    def result(self, images):
+        """validate.result_from_counts of the counters so far: dict(miou, iou, pixel_accuracy, images, matrix, counts), miou as
+        ConfusionMatrix.jaccard gives it (the mean over the classes with a non-zero diagonal)"""
+        from .validate import result_from_counts
+        return result_from_counts(self.counts(), self.nclass, images)

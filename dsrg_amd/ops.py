@@ -448,6 +448,35 @@ def eval_confusion_batch(scores, labels, nclass, ignore_label=255, rule_lt=False
     return hist
 
 
+def score_labels_batch(labels, gts, nclass, ignore_label=255, rule_lt=False, hist=None, masks=None):
+    """Scoring of a group of finished label maps in one launch (dsrg_score_labels_batch): labels, a list of 1..16 contiguous (H_g,
+    W_g) int32 CUDA tensors (the CRF's map, the argmax / labels outputs of the multi-scale and pseudo-label tails; sizes may
+    differ), and gts, as many contiguous uint8 CUDA tensors of the same sizes.  The pixels whose ground truth passes the rule
+    (rule_lt False: gt != ignore_label; True: gt < nclass) are counted.  masks: None, or as many contiguous uint8 CUDA tensors of
+    those sizes, which get every pixel's label as a byte (255 for a label outside 0..255).  Returns the (nclass*nclass + 1) int64
+    counters of confusion_matrix (added to `hist` when given); the last counts kept pixels whose ground truth or label is not one
+    of 0..nclass-1.  Runs on torch's current stream."""
+    labels, gts = list(labels), list(gts)
+    nclass = int(nclass)
+    if not labels or len(gts) != len(labels) or (masks is not None and len(masks) != len(labels)):
+        raise ValueError("%d label maps, %d ground truths%s" % (len(labels), len(gts),
+                                                                "" if masks is None else ", %d masks" % len(masks)))
+    for name, ts, dtype in (("labels", labels, torch.int32), ("gts", gts, torch.uint8), ("masks", masks, torch.uint8)):
+        for g, t in enumerate(ts or ()):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+                raise ValueError("%s[%d] must be a contiguous %s CUDA tensor" % (name, g, str(dtype).split(".")[-1]))
+            if t.dim() != 2 or t.shape != labels[g].shape:
+                raise ValueError("%s[%d] is %s, label map %d is %s" % (name, g, tuple(t.shape), g, tuple(labels[g].shape)))
+    if hist is None:
+        hist = torch.zeros(nclass * nclass + 1, dtype=torch.int64, device=labels[0].device)
+    elif not (hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.numel() == nclass * nclass + 1):
+        raise ValueError("hist must be a contiguous int64 CUDA tensor of %d counters" % (nclass * nclass + 1))
+    check(_lib.lib().dsrg_score_labels_batch(len(labels), nclass, _ptrs(labels), _ptrs(gts), _i32s([t.shape[0] for t in labels]),
+                                             _i32s([t.shape[1] for t in labels]), int(ignore_label), int(bool(rule_lt)), _ptr(hist),
+                                             _ptrs(masks), _stream()))
+    return hist
+
+
 _MS_OUTPUTS = ("unary", "argmax", "sum")
 _TG_OUTPUTS = ("unary", "probs", "labels")
 _INT_OUTPUTS = ("argmax", "labels")                  # (H, W) int32 maps; every other output is (H, W, C) float32

@@ -27,6 +27,17 @@ takes the images N at a time through batch-N forwards (the absolute sizes are th
 --flip (ms, ms-f, gt-ms; no counterpart in the reference): mirrored test-time augmentation, every scale runs on the image and on its
 mirror image and all the score maps are summed before the softmax (gt-ms: the probabilities averaged) (at most 4 scales, batches of at most 8
 images).
+
+--gt DIR (all four modes) <-> the loop of training/tools/test-coco.py:138-173, run.sh steps 4 and 5 as one command: the label maps
+stay on the device (masks="device" of the generators) and are scored there against DIR/<id>.png, 16 images per launch
+(inference.MaskScorer, dsrg_score_labels_batch), under the rule of `python -m dsrg_amd.evaluate` (ground truth < --class kept).
+--save_path FILE: the three-line result file evaluate writes; --score-every N (default 100): '<n> images, meanIOU = <v>' with one
+synchronisation per N images (test-coco.py:150-157); the last line printed is 'meanIOU: <v>'.  The mean IoU in all three is
+evaluate.py's (ConfusionMatrix.jaccard: the classes with a non-zero diagonal only), not test-coco.py's own tp / max(1, pos + res - tp)
+averaged over all classes.  --output is optional with --gt: without it only the ground truth goes up and the counters come down,
+with it the PNGs are written from the scorer's uint8 masks.  A ground truth whose size differs from its image's stops the run with an
+error that names the id.  Without --gt everything runs as before.  --image-subdir NAME: the folder under --dir that holds the images
+(default JPEGImages; test-coco.py reads images/val2014).
 """
 import argparse
 import os
@@ -42,8 +53,19 @@ def parse_args(argv=None):
     p.add_argument("--model", required=True, help="weights (.caffemodel, .npz or torch file)")
     p.add_argument("--images", required=True, help="list of image ids, one per line (gt: lines 'name.jpg <id>')")
     p.add_argument("--cues", default=None, help="gt, gt-ms: the localisation-cue pickle holding '<id>_labels' for every image")
-    p.add_argument("--dir", required=True, help="dataset root holding JPEGImages/")
-    p.add_argument("--output", required=True, help="directory for the <id>.png label maps")
+    p.add_argument("--dir", required=True, help="dataset root holding the image folder (--image-subdir)")
+    p.add_argument("--image-subdir", default="JPEGImages",
+                   help="the folder under --dir that holds <id>.jpg (default JPEGImages; test-coco.py reads images/val2014)")
+    p.add_argument("--output", default=None, help="directory for the <id>.png label maps (optional with --gt)")
+    p.add_argument("--gt", default=None,
+                   help="directory of ground-truth label PNGs <id>.png: score the label maps against them on the GPU as they are made "
+                        "(all four modes; ground truth < --class is kept, as `python -m dsrg_amd.evaluate` keeps it) and print "
+                        "'meanIOU: <v>'.  The mean IoU is evaluate.py's (ConfusionMatrix.jaccard): the mean over the classes with a "
+                        "non-zero diagonal only — NOT test-coco.py's own tp / max(1, pos + res - tp) averaged over all classes")
+    p.add_argument("--save_path", default=None, help="with --gt: the three-line result file `python -m dsrg_amd.evaluate` writes")
+    p.add_argument("--score-every", type=int, default=None,
+                   help="with --gt: print '<n> images, meanIOU = <v>' (the same mean IoU) every N images, one synchronisation each "
+                        "(default 100; at least 1)")
     p.add_argument("--smooth", action="store_true", help="dense-CRF post-processing (as the reference's --smooth)")
     p.add_argument("--scales", default=None,
                    help="comma-separated: sizes in pixels (ms; default 241,321,401) or factors (ms-f; default 0.75,1,1.25); "
@@ -65,6 +87,16 @@ def parse_args(argv=None):
                    help="ms, ms-f, gt-ms: mirrored test-time augmentation: every scale also runs on the mirror image, whose scores are "
                         "mirrored back and summed with the others (at most 4 scales; --forward-batch / --same-size-batch at most 8)")
     a = p.parse_args(argv)
+    if a.gt is None:
+        if a.output is None:
+            p.error("--output is required without --gt")
+        if a.save_path is not None or a.score_every is not None:
+            p.error("--save_path and --score-every go with --gt")
+    else:
+        if a.score_every is None:
+            a.score_every = 100
+        if a.score_every < 1:
+            p.error("--score-every must be at least 1")
     if a.mode in ("gt", "gt-ms"):
         if not a.cues:
             p.error("--mode %s needs --cues (the pickle with the image-level labels)" % a.mode)
@@ -124,7 +156,41 @@ def write_mask(path, mask):
     Image.fromarray(np.asarray(mask).astype(np.uint8), mode="L").save(path)
 
 
-def main(argv=None):
+def score_masks(a, ids, masks, device):
+    """--gt: the loop of test-coco.py:138-173 with the label maps left on the device.  masks: a generator of (H,W) int32 CUDA label
+    maps (masks="device") in the order of ids.  They are collected 16 at a time (and whenever a progress line is due) and scored
+    against GT/<id>.png by inference.MaskScorer under evaluate's rule; with --output the PNGs are written from the scorer's uint8
+    masks.  -> (images, the result dict of validate.result_from_counts)"""
+    from . import inference as I
+    from .evaluate import read_label_png
+    scorer = I.MaskScorer(a.num_classes, device, rule_lt=True, want_masks=a.output is not None)
+    held, n = [], 0                                         # (id, label map, ground truth) of the open group
+
+    def flush():
+        if not held:
+            return
+        narrowed = scorer.add([lab for _, lab, _ in held], [gt for _, _, gt in held])
+        for (img_id, _, _), mask in zip(held, narrowed or ()):
+            write_mask(os.path.join(a.output, img_id + ".png"), mask)
+        del held[:]
+
+    for img_id, lab in zip(ids, masks):
+        gt = read_label_png(os.path.join(a.gt, img_id + ".png"))
+        if tuple(gt.shape) != tuple(lab.shape):
+            raise ValueError("%s: the ground truth is %d x %d, the image %d x %d" % ((img_id,) + tuple(gt.shape) + tuple(lab.shape)))
+        held.append((img_id, lab, gt))
+        n += 1
+        due = n % a.score_every == 0
+        if due or len(held) == I.MAX_SCORE_GROUP:
+            flush()
+        if due:                                             # (test-coco.py:150-157; one synchronisation)
+            print("%d images, meanIOU = %s" % (n, scorer.result(n)["miou"]), flush=True)
+    flush()
+    return n, scorer.result(n)
+
+
+def main(argv=None, net=None):
+    """net (tools): a network of --backbone / --class already on the device in eval mode, used instead of loading --model"""
     a = parse_args(argv)
     import torch
     from . import inference as I
@@ -143,7 +209,9 @@ def main(argv=None):
     else:
         scales = tuple(float(s) for s in a.scales.split(",")) if a.scales else (0.75, 1.0, 1.25)
     dev = torch.device("cuda", torch.cuda.current_device())
-    if a.backbone == "resnet101":
+    if net is not None:
+        pass
+    elif a.backbone == "resnet101":
         from .retrain import ResNet101DeepLab
         net = ResNet101DeepLab(num_classes=a.num_classes).to(dev).to(memory_format=torch.channels_last).eval()
         load_weights(net, a.model)
@@ -159,8 +227,10 @@ def main(argv=None):
         gt_labels = [cues['%i_labels' % num] for _, num in entries]
     else:
         ids = read_ids(a.images)
-    os.makedirs(a.output, exist_ok=True)
-    images = (read_image(os.path.join(a.dir, "JPEGImages", i + ".jpg")) for i in ids)
+    if a.output is not None:
+        os.makedirs(a.output, exist_ok=True)
+    images = (read_image(os.path.join(a.dir, a.image_subdir, i + ".jpg")) for i in ids)
+    how = {} if a.gt is None else {"masks": "device"}       # scored: the label maps stay on the device
 
     if a.mode in ("ms", "gt", "gt-ms"):
         fwd = I.GraphedForward(net)                         # one graph per fixed size
@@ -169,15 +239,27 @@ def main(argv=None):
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=not a.fp32):
         if a.mode in ("gt", "gt-ms"):                       # gt: its one size, no flip (what predict_train_gt_many is)
             masks = I.predict_train_gt_ms_many(net, zip(images, gt_labels), sizes=scales, flip=a.flip, smooth=a.smooth, device=dev,
-                                               forward=fwd, in_flight=a.in_flight, forward_batch=a.forward_batch)
+                                               forward=fwd, in_flight=a.in_flight, forward_batch=a.forward_batch, **how)
         elif a.mode == "ms":
             masks = I.predict_masks_ms_many(net, images, sizes=scales, device=dev, forward=fwd, in_flight=a.in_flight,
-                                            forward_batch=a.forward_batch, flip=a.flip, smooth=a.smooth)
+                                            forward_batch=a.forward_batch, flip=a.flip, smooth=a.smooth, **how)
         else:
             from .crf import MAX_BATCH
             masks = I.predict_masks_ms_f_many(net, images, scales=scales, device=dev, forward=fwd, in_flight=a.in_flight,
                                               batch=min(a.same_size_batch, MAX_BATCH), same_size_batch=a.same_size_batch,
-                                              window=a.window, smooth=a.smooth, flip=a.flip)
+                                              window=a.window, smooth=a.smooth, flip=a.flip, **how)
+        if a.gt is not None:
+            try:
+                n, result = score_masks(a, ids, masks, dev)
+            finally:
+                masks.close()                               # (a run stopped by an error: the CRF workers end before it is reported)
+            if a.save_path is not None:
+                from .validate import write_result
+                write_result(a.save_path, result)
+            if a.output is not None:
+                print("wrote %d masks to %s" % (n, a.output))
+            print("meanIOU: %s" % float(result["miou"]))
+            return 0
         n = 0
         for img_id, mask in zip(ids, masks):
             write_mask(os.path.join(a.output, img_id + ".png"), mask)

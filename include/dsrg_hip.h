@@ -485,6 +485,27 @@ int dsrg_train_f_input_scaled_batch(int B, const unsigned char *stage_dev, size_
  * which workgroups finish, and repeated calls give identical counters. */
 int dsrg_eval_confusion_batch(int B, int C, const float *scores_dev, int h, int w, const float *labels_dev, int Hz, int Wz,
                               float ignore_label, int rule_lt, unsigned long long *hist_dev, void *stream);
+/* Scoring of finished label maps in one launch: the confusion counters of a group of G differently sized label maps — what
+ * dsrg_crf_map / dsrg_crf_map_select and the argmax / labels outputs of the multi-scale and pseudo-label tails write — against
+ * their ground truth, and optionally the maps narrowed to bytes (the PNG payload).
+ *   labels_dev, gt_dev  HOST arrays of G device pointers, as dsrg_multiscale_unary_batch takes its per-image pointers:
+ *              labels_dev[g] the (H_g, W_g) int32 label map of image g, gt_dev[g] its (H_g, W_g) uint8 ground truth
+ *   H_host, W_host      host arrays of the G sizes (they may all differ)
+ *   hist_dev   C*C + 1 unsigned 64-bit counters that are ADDED to, dsrg_confusion_matrix's layout: row = ground truth, column =
+ *              prediction, the last one the overflow counter
+ *   mask_dev   NULL, or a HOST array of G device pointers to (H_g, W_g) uint8: EVERY pixel, kept or not, gets the byte p where
+ *              the label p is one of 0..255, and 255 otherwise
+ * A pixel is kept iff gt != ignore_label (rule_lt = 0, ConfusionMatrix.add) or gt < C (rule_lt = 1, generateM).  A kept pixel
+ * with gt and label both in 0..C-1 adds 1 to hist[gt * C + label]; any other kept pixel (a 255 written by ignore_below, a
+ * negative label, a ground truth of 254 under rule_lt = 0) adds 1 to hist[C*C].  Without mask_dev the label of a pixel that is
+ * not kept is not read.
+ * 1 <= G <= 16, 1 <= C <= 96 (above: DSRG_ERR_UNSUPPORTED), H_g, W_g >= 1, sum of H_g*W_g < 2^31; the arrays, hist_dev and every
+ * entry of the pointer arrays must not be NULL (DSRG_ERR_INVALID); every argument is checked before the first device call.
+ * Nothing is allocated.  Stream-ordered, no host synchronisation, no handle.  The counters are integers added with atomics: the
+ * result does not depend on the order in which lanes or workgroups add, and repeated calls give identical counters. */
+int dsrg_score_labels_batch(int G, int C, const int32_t *const *labels_dev, const unsigned char *const *gt_dev,
+                            const int32_t *H_host, const int32_t *W_host, int ignore_label, int rule_lt,
+                            unsigned long long *hist_dev, unsigned char *const *mask_dev, void *stream);
 /* The stem of the DeepLab-v2 ResNet-101 at test time in one launch (backbone plumbing; the reference's networks are Caffe
  * prototxts): conv 7x7 / stride 2 / zero pad 3, 3 -> 64, with a frozen BatchNorm folded in -> ReLU -> max pool 3x3 / stride 2 /
  * pad 1, ceil mode.  The convolution map never reaches memory.
