@@ -43,34 +43,12 @@
 // All: loads are issued unconditionally on clamped indices and selected afterwards; no atomics, no scratch, no dependence on the
 // order of workgroups (every output element has exactly one owner; duplicate cue triplets write the same value behind the owner's
 // barrier); LDS only for the C label flags of the cue-map kernel; -ffp-contract=off (Makefile).  Results are bit-reproducible.
-#include <string.h>
 #include "common.h"
+#include "train_input_check.h"
 
 namespace dsrg {
 
 constexpr int kTiThreads = 256;
-constexpr int kTiMaxBatch = 32;
-
-struct TsArgs {
-    int img_off[kTiMaxBatch], H[kTiMaxBatch], W[kTiMaxBatch];       // (H, W, 3) RGB uint8 at stage + img_off
-    int cue_off[kTiMaxBatch], ncue[kTiMaxBatch];                    // (3, K) int32 at stage + cue_off: classes, rows, columns
-    int lab_off[kTiMaxBatch], nlab[kTiMaxBatch];                    // L int32 class ids at stage + lab_off
-    unsigned mirror;                                                // bit b: image b is mirrored
-    float mean[3];                                                  // of the OUTPUT channels (B, G, R)
-};
-
-struct TfArgs {
-    int img_off[kTiMaxBatch], lab_off[kTiMaxBatch];                 // (H, W, 3) RGB uint8 / (H, W) uint8
-    int H[kTiMaxBatch], W[kTiMaxBatch], top[kTiMaxBatch], left[kTiMaxBatch];
-    unsigned mirror;
-    float mean[3], scale, ignore_label;
-};
-
-struct TfScaledArgs {
-    TfArgs f;
-    int Hs[kTiMaxBatch], Ws[kTiMaxBatch];                           // the size image b is rescaled to before the crop
-    double ys[kTiMaxBatch], xs[kTiMaxBatch];                        // axis_scale(H, Hs), axis_scale(W, Ws): divided once, on the host
-};
 
 // source coordinates per output coordinate on an axis of n source and S output samples.  Two IEEE double divisions: the same bits
 // from the host and from the device
@@ -208,68 +186,6 @@ __global__ __launch_bounds__(kTiThreads) void train_f_input_scaled_kernel(const 
     label[(size_t)b * P + at] = on ? lab : a.ignore_label;
 }
 
-// `n` bytes at byte offset `off` lie inside the staging buffer?
-static bool inside(long long off, long long n, size_t stage_bytes) {
-    return off >= 0 && n >= 0 && (unsigned long long)off + (unsigned long long)n <= (unsigned long long)stage_bytes;
-}
-
-int launch_train_s_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *H,
-                               const int32_t *W, const int32_t *cue_off, const int32_t *ncues, const int32_t *label_off,
-                               const int32_t *nlabels, const int32_t *mirror, int S, int C, int Hm, int Wm, const float *mean,
-                               float *images, float *cues, float *labels, hipStream_t stream) {
-    if (B < 1 || B > kTiMaxBatch) return set_error(DSRG_ERR_INVALID, "train-s input: 1..%d images, got %d", kTiMaxBatch, B);
-    if (!stage) return set_error(DSRG_ERR_INVALID, "train-s input: NULL staging buffer");
-    if (!image_off || !H || !W) return set_error(DSRG_ERR_INVALID, "train-s input: NULL image offset / image size array");
-    if (!cue_off || !ncues || !label_off || !nlabels) return set_error(DSRG_ERR_INVALID, "train-s input: NULL cue / label descriptor array");
-    if (!mirror || !mean) return set_error(DSRG_ERR_INVALID, "train-s input: NULL mirror / mean array");
-    if (!images || !cues || !labels) return set_error(DSRG_ERR_INVALID, "train-s input: NULL output");
-    if (((uintptr_t)images | (uintptr_t)cues | (uintptr_t)labels) & 3)
-        return set_error(DSRG_ERR_INVALID, "train-s input: an output is not aligned to a float");
-    if (S < 1 || C < 1 || Hm < 1 || Wm < 1) return set_error(DSRG_ERR_INVALID, "train-s input: size %d, %d classes, %dx%d planes", S, C, Hm, Wm);
-    if (stage_bytes >= ((size_t)1 << 31)) return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: staging buffer holds >= 2^31 bytes");
-    if ((long long)B * 3 * S * S >= (1LL << 31))
-        return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: images hold %lld >= 2^31 values", (long long)B * 3 * S * S);
-    if ((long long)B * C * Hm * Wm >= (1LL << 31))
-        return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: cues hold %lld >= 2^31 values", (long long)B * C * Hm * Wm);
-    TsArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int b = 0; b < B; ++b) {
-        if (H[b] < 1 || W[b] < 1) return set_error(DSRG_ERR_INVALID, "train-s input: image %d is %dx%d", b, H[b], W[b]);
-        if ((long long)H[b] * W[b] * 3 >= (1LL << 31)) return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: image %d holds >= 2^31 values", b);
-        if (!inside(image_off[b], (long long)H[b] * W[b] * 3, stage_bytes))
-            return set_error(DSRG_ERR_INVALID, "train-s input: image %d lies outside the staging buffer", b);
-        if (ncues[b] < 0 || nlabels[b] < 0) return set_error(DSRG_ERR_INVALID, "train-s input: image %d has a negative cue / label count", b);
-        if (((uintptr_t)stage + (uintptr_t)(uint32_t)cue_off[b]) & 3 || ((uintptr_t)stage + (uintptr_t)(uint32_t)label_off[b]) & 3)
-            return set_error(DSRG_ERR_INVALID, "train-s input: cues / labels of image %d are not aligned to an int32", b);
-        if (!inside(cue_off[b], 12LL * ncues[b], stage_bytes))
-            return set_error(DSRG_ERR_INVALID, "train-s input: cues of image %d lie outside the staging buffer", b);
-        if (!inside(label_off[b], 4LL * nlabels[b], stage_bytes))
-            return set_error(DSRG_ERR_INVALID, "train-s input: labels of image %d lie outside the staging buffer", b);
-        a.img_off[b] = image_off[b], a.H[b] = H[b], a.W[b] = W[b];
-        a.cue_off[b] = cue_off[b], a.ncue[b] = ncues[b];
-        a.lab_off[b] = label_off[b], a.nlab[b] = nlabels[b];
-        if (mirror[b]) a.mirror |= 1u << b;
-    }
-    for (int c = 0; c < 3; ++c) a.mean[c] = mean[c];
-    const long long n = (long long)B * S * S;
-    const int cue0 = (int)((n + kTiThreads - 1) / kTiThreads);                               // < 2^23
-    const long long blocks = (long long)cue0 + (long long)B * C;                             // B * C < 2^31 / (Hm * Wm)
-    if (blocks >= (1LL << 24))                                                               // a grid holds < 2^32 threads
-        return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: %lld workgroups >= 2^24 (pixel blocks + B * C planes)", blocks);
-    hipLaunchKernelGGL(train_s_input_kernel, dim3((unsigned)blocks), dim3(kTiThreads), 0, stream, stage, a, B, S, C, Hm, Wm, cue0, images,
-                       cues, labels);
-    DSRG_LAUNCH_CHECK();
-    return DSRG_OK;
-}
-
-struct TcArgs {
-    int img_off[kTiMaxBatch], H[kTiMaxBatch], W[kTiMaxBatch];       // (H, W, 3) RGB uint8 at stage + img_off
-    int cue_off[kTiMaxBatch];                                       // (Hm, Wm) uint8 cue bytes at stage + cue_off
-    double sh[kTiMaxBatch], sw[kTiMaxBatch];                        // zoom_axis_scale(H, Sh), zoom_axis_scale(W, Sw): divided once, on the host
-    unsigned mirror;                                                // bit b: image b is mirrored
-    float mean[3];                                                  // of the OUTPUT channels
-};
-
 __global__ __launch_bounds__(kTiThreads) void train_s_cuemap_input_kernel(const unsigned char *__restrict__ stage, TcArgs a, int B, int Sh,
                                                                           int Sw, int C, int Hm, int Wm, int ignore_label, int bgr,
                                                                           int cue0, int lab0, float *__restrict__ images,
@@ -315,46 +231,31 @@ __global__ __launch_bounds__(kTiThreads) void train_s_cuemap_input_kernel(const 
     for (int c = tid; c < C; c += kTiThreads) labels[(size_t)b * C + c] = present[c] ? 1.0f : 0.0f;
 }
 
+int launch_train_s_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *H,
+                               const int32_t *W, const int32_t *cue_off, const int32_t *ncues, const int32_t *label_off,
+                               const int32_t *nlabels, const int32_t *mirror, int S, int C, int Hm, int Wm, const float *mean,
+                               float *images, float *cues, float *labels, hipStream_t stream) {
+    TsArgs a;
+    if (int rc = check_train_s_input(B, stage, stage_bytes, image_off, H, W, cue_off, ncues, label_off, nlabels, mirror, S, C, Hm, Wm, mean,
+                                     images, cues, labels, a)) return rc;
+    const int cue0 = (int)(((long long)B * S * S + kTiThreads - 1) / kTiThreads);            // < 2^23
+    const long long blocks = (long long)cue0 + (long long)B * C;                             // B * C < 2^31 / (Hm * Wm)
+    if (blocks >= (1LL << 24))                                                               // a grid holds < 2^32 threads
+        return set_error(DSRG_ERR_UNSUPPORTED, "train-s input: %lld workgroups >= 2^24 (pixel blocks + B * C planes)", blocks);
+    hipLaunchKernelGGL(train_s_input_kernel, dim3((unsigned)blocks), dim3(kTiThreads), 0, stream, stage, a, B, S, C, Hm, Wm, cue0, images,
+                       cues, labels);
+    DSRG_LAUNCH_CHECK();
+    return DSRG_OK;
+}
+
 int launch_train_s_cuemap_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *H,
                                       const int32_t *W, const int32_t *cue_off, const int32_t *mirror, int Sh, int Sw, int C, int Hm,
                                       int Wm, const float *mean, int ignore_label, int bgr, float *images, float *cues, float *labels,
                                       hipStream_t stream) {
-    if (B < 1 || B > kTiMaxBatch) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: 1..%d images, got %d", kTiMaxBatch, B);
-    if (!stage) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL staging buffer");
-    if (!image_off || !H || !W) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL image offset / image size array");
-    if (!cue_off) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL cue offset array");
-    if (!mirror || !mean) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL mirror / mean array");
-    if (!images) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL images output");
-    if (!cues) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL cues output");
-    if (!labels) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: NULL labels output");
-    if (((uintptr_t)images | (uintptr_t)cues | (uintptr_t)labels) & 3)
-        return set_error(DSRG_ERR_INVALID, "train-s cue-map input: an output is not aligned to a float");
-    if (Sh < 1 || Sw < 1 || C < 1 || Hm < 1 || Wm < 1)
-        return set_error(DSRG_ERR_INVALID, "train-s cue-map input: size %dx%d, %d classes, %dx%d maps", Sh, Sw, C, Hm, Wm);
-    if (C > kMaxLabels) return set_error(DSRG_ERR_UNSUPPORTED, "train-s cue-map input: %d classes, at most %d", C, kMaxLabels);
-    if (ignore_label < 0 || ignore_label > 255)
-        return set_error(DSRG_ERR_INVALID, "train-s cue-map input: ignore_label %d is no byte value", ignore_label);
-    if (bgr != 0 && bgr != 1) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: bgr must be 0 or 1, got %d", bgr);
-    if (stage_bytes >= ((size_t)1 << 31)) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: staging buffer holds >= 2^31 bytes");
-    if ((long long)Sh * Sw >= (1LL << 31) || (long long)B * 3 * Sh * Sw >= (1LL << 31))
-        return set_error(DSRG_ERR_INVALID, "train-s cue-map input: images hold >= 2^31 values (%d x 3 x %d x %d)", B, Sh, Sw);
-    if ((long long)Hm * Wm >= (1LL << 31) || (long long)B * C * Hm * Wm >= (1LL << 31))
-        return set_error(DSRG_ERR_INVALID, "train-s cue-map input: cues hold >= 2^31 values (%d x %d x %d x %d)", B, C, Hm, Wm);
     TcArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int b = 0; b < B; ++b) {
-        if (H[b] < 1 || W[b] < 1) return set_error(DSRG_ERR_INVALID, "train-s cue-map input: image %d is %dx%d", b, H[b], W[b]);
-        if ((long long)H[b] * W[b] * 3 >= (1LL << 31))
-            return set_error(DSRG_ERR_INVALID, "train-s cue-map input: image %d holds >= 2^31 values", b);
-        if (!inside(image_off[b], (long long)H[b] * W[b] * 3, stage_bytes))
-            return set_error(DSRG_ERR_INVALID, "train-s cue-map input: image %d lies outside the staging buffer", b);
-        if (!inside(cue_off[b], (long long)Hm * Wm, stage_bytes))
-            return set_error(DSRG_ERR_INVALID, "train-s cue-map input: cue map %d lies outside the staging buffer", b);
-        a.img_off[b] = image_off[b], a.H[b] = H[b], a.W[b] = W[b], a.cue_off[b] = cue_off[b];
-        a.sh[b] = zoom_axis_scale(H[b], Sh), a.sw[b] = zoom_axis_scale(W[b], Sw);
-        if (mirror[b]) a.mirror |= 1u << b;
-    }
-    for (int c = 0; c < 3; ++c) a.mean[c] = mean[c];
+    if (int rc = check_train_s_cuemap_input(B, stage, stage_bytes, image_off, H, W, cue_off, mirror, Sh, Sw, C, kMaxLabels, Hm, Wm, mean,
+                                            ignore_label, bgr, images, cues, labels, a)) return rc;
+    for (int b = 0; b < B; ++b) a.sh[b] = zoom_axis_scale(H[b], Sh), a.sw[b] = zoom_axis_scale(W[b], Sw);
     const int cue0 = (int)(((long long)B * Sh * Sw + kTiThreads - 1) / kTiThreads);          // < 2^23
     const int lab0 = cue0 + (int)(((long long)B * Hm * Wm + kTiThreads - 1) / kTiThreads);   // < 2^24
     hipLaunchKernelGGL(train_s_cuemap_input_kernel, dim3((unsigned)(lab0 + B)), dim3(kTiThreads), 0, stream, stage, a, B, Sh, Sw, C, Hm, Wm,
@@ -363,52 +264,15 @@ int launch_train_s_cuemap_input_batch(int B, const unsigned char *stage, size_t 
     return DSRG_OK;
 }
 
-// every check the two stage-2 entries share, and their common argument block
-static int check_train_f_input(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *label_off,
-                               const int32_t *H, const int32_t *W, const int32_t *top, const int32_t *left, const int32_t *mirror,
-                               int ch, int cw, const float *mean, float scale, float ignore_label, float *data, float *label, TfArgs &a) {
-    if (B < 1 || B > kTiMaxBatch) return set_error(DSRG_ERR_INVALID, "train-f input: 1..%d images, got %d", kTiMaxBatch, B);
-    if (!stage) return set_error(DSRG_ERR_INVALID, "train-f input: NULL staging buffer");
-    if (!image_off || !label_off || !H || !W) return set_error(DSRG_ERR_INVALID, "train-f input: NULL offset / image size array");
-    if (!top || !left || !mirror || !mean) return set_error(DSRG_ERR_INVALID, "train-f input: NULL top / left / mirror / mean array");
-    if (!data || !label) return set_error(DSRG_ERR_INVALID, "train-f input: NULL output");
-    if (((uintptr_t)data | (uintptr_t)label) & 3) return set_error(DSRG_ERR_INVALID, "train-f input: an output is not aligned to a float");
-    if (ch < 1 || cw < 1) return set_error(DSRG_ERR_INVALID, "train-f input: crop %dx%d", ch, cw);
-    if (stage_bytes >= ((size_t)1 << 31)) return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: staging buffer holds >= 2^31 bytes");
-    if ((long long)B * 3 * ch * cw >= (1LL << 31))
-        return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: data holds %lld >= 2^31 values", (long long)B * 3 * ch * cw);
-    memset(&a, 0, sizeof(a));
-    for (int b = 0; b < B; ++b) {
-        if (H[b] < 1 || W[b] < 1) return set_error(DSRG_ERR_INVALID, "train-f input: image %d is %dx%d", b, H[b], W[b]);
-        if ((long long)H[b] * W[b] * 3 >= (1LL << 31)) return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: image %d holds >= 2^31 values", b);
-        if (top[b] < 0 || left[b] < 0) return set_error(DSRG_ERR_INVALID, "train-f input: image %d has a negative offset (%d, %d)", b, top[b], left[b]);
-        if ((long long)top[b] + ch >= (1LL << 31) || (long long)left[b] + cw >= (1LL << 31))
-            return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: image %d has an offset + crop >= 2^31", b);
-        if (!inside(image_off[b], (long long)H[b] * W[b] * 3, stage_bytes))
-            return set_error(DSRG_ERR_INVALID, "train-f input: image %d lies outside the staging buffer", b);
-        if (!inside(label_off[b], (long long)H[b] * W[b], stage_bytes))
-            return set_error(DSRG_ERR_INVALID, "train-f input: label %d lies outside the staging buffer", b);
-        a.img_off[b] = image_off[b], a.lab_off[b] = label_off[b];
-        a.H[b] = H[b], a.W[b] = W[b], a.top[b] = top[b], a.left[b] = left[b];
-        if (mirror[b]) a.mirror |= 1u << b;
-    }
-    for (int c = 0; c < 3; ++c) a.mean[c] = mean[c];
-    a.scale = scale;
-    a.ignore_label = ignore_label;
-    return DSRG_OK;
-}
-
 int launch_train_f_input_batch(int B, const unsigned char *stage, size_t stage_bytes, const int32_t *image_off, const int32_t *label_off,
                                const int32_t *H, const int32_t *W, const int32_t *top, const int32_t *left, const int32_t *mirror,
                                int ch, int cw, const float *mean, float scale, float ignore_label, float *data, float *label,
                                hipStream_t stream) {
     TfArgs a;
-    const int rc = check_train_f_input(B, stage, stage_bytes, image_off, label_off, H, W, top, left, mirror, ch, cw, mean, scale,
-                                       ignore_label, data, label, a);
-    if (rc != DSRG_OK) return rc;
-    const long long n = (long long)B * ch * cw;
-    hipLaunchKernelGGL(train_f_input_kernel, dim3((unsigned)((n + kTiThreads - 1) / kTiThreads)), dim3(kTiThreads), 0, stream, stage, a, B,
-                       ch, cw, data, label);
+    if (int rc = check_train_f_input(B, stage, stage_bytes, image_off, label_off, H, W, NULL, NULL, top, left, mirror, ch, cw, mean, scale,
+                                     ignore_label, data, label, a, NULL)) return rc;
+    const unsigned blocks = (unsigned)(((long long)B * ch * cw + kTiThreads - 1) / kTiThreads);
+    hipLaunchKernelGGL(train_f_input_kernel, dim3(blocks), dim3(kTiThreads), 0, stream, stage, a, B, ch, cw, data, label);
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
 }
@@ -418,21 +282,11 @@ int launch_train_f_input_scaled_batch(int B, const unsigned char *stage, size_t 
                                       const int32_t *top, const int32_t *left, const int32_t *mirror, int ch, int cw, const float *mean,
                                       float scale, float ignore_label, float *data, float *label, hipStream_t stream) {
     TfScaledArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    const int rc = check_train_f_input(B, stage, stage_bytes, image_off, label_off, H, W, top, left, mirror, ch, cw, mean, scale,
-                                       ignore_label, data, label, sa.f);
-    if (rc != DSRG_OK) return rc;
-    if (!Hs || !Ws) return set_error(DSRG_ERR_INVALID, "train-f input: NULL scaled size array");
-    for (int b = 0; b < B; ++b) {
-        if (Hs[b] < 1 || Ws[b] < 1) return set_error(DSRG_ERR_INVALID, "train-f input: image %d is rescaled to %dx%d", b, Hs[b], Ws[b]);
-        if ((long long)Hs[b] * Ws[b] >= (1LL << 31))
-            return set_error(DSRG_ERR_UNSUPPORTED, "train-f input: image %d rescaled to %dx%d holds >= 2^31 pixels", b, Hs[b], Ws[b]);
-        sa.Hs[b] = Hs[b], sa.Ws[b] = Ws[b];                                                 // (top + ch, left + cw < 2^31: checked above)
-        sa.ys[b] = axis_scale(H[b], Hs[b]), sa.xs[b] = axis_scale(W[b], Ws[b]);
-    }
-    const long long n = (long long)B * ch * cw;
-    hipLaunchKernelGGL(train_f_input_scaled_kernel, dim3((unsigned)((n + kTiThreads - 1) / kTiThreads)), dim3(kTiThreads), 0, stream, stage,
-                       sa, B, ch, cw, data, label);
+    if (int rc = check_train_f_input(B, stage, stage_bytes, image_off, label_off, H, W, Hs, Ws, top, left, mirror, ch, cw, mean, scale,
+                                     ignore_label, data, label, sa.f, &sa)) return rc;
+    for (int b = 0; b < B; ++b) sa.ys[b] = axis_scale(H[b], Hs[b]), sa.xs[b] = axis_scale(W[b], Ws[b]);
+    const unsigned blocks = (unsigned)(((long long)B * ch * cw + kTiThreads - 1) / kTiThreads);
+    hipLaunchKernelGGL(train_f_input_scaled_kernel, dim3(blocks), dim3(kTiThreads), 0, stream, stage, sa, B, ch, cw, data, label);
     DSRG_LAUNCH_CHECK();
     return DSRG_OK;
 }
