@@ -115,6 +115,8 @@ SIGNATURES = {
     "dsrg_eval_confusion_batch": (_i, [_i, _i, _vp, _i, _i, _vp, _i, _i, _f, _i, _vp, _vp]),
     "dsrg_score_labels_batch": (_i, [_i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp)] + [ctypes.POINTER(ctypes.c_int32)] * 2 +
                                 [_i, _i, _vp, ctypes.POINTER(_vp), _vp]),
+    "dsrg_seg_loss_zoom_workspace": (_sz, [_i] * 6),
+    "dsrg_seg_loss_zoom_batch": (_i, [_i, _i, _vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dsrg_resnet_stem_packed_bytes": (_sz, []),
     "dsrg_pack_resnet_stem_f32": (_i, [_vp, _vp, _vp, _vp]),
     "dsrg_resnet_stem_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

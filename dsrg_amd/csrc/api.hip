@@ -598,6 +598,14 @@ extern "C" int dsrg_score_labels_batch(int G, int C, const int32_t *const *label
     // every argument is checked before the first device call
     return launch_score_labels_batch(G, C, labels, gt, H, W, ignore_label, rule_lt, hist, mask, static_cast<hipStream_t>(stream));
 }
+extern "C" size_t dsrg_seg_loss_zoom_workspace(int B, int C, int h, int w, int H, int W) { return seg_loss_zoom_workspace(B, C, h, w, H, W); }
+extern "C" int dsrg_seg_loss_zoom_batch(int B, int C, const float *logits, int h, int w, const float *labels, int H, int W,
+                                        float ignore_label, float *loss, float *grad, unsigned long long *counters, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+    // every argument is checked before the first device call
+    return launch_seg_loss_zoom_batch(B, C, logits, h, w, labels, H, W, ignore_label, loss, grad, counters, workspace, workspace_bytes,
+                                      static_cast<hipStream_t>(stream));
+}
 extern "C" size_t dsrg_resnet_stem_packed_bytes(void) { return resnet_stem_packed_bytes(); }
 extern "C" int dsrg_pack_resnet_stem_f32(const float *w, const float *scale, void *packed, void *stream) {
     if (!w || !scale || !packed) return set_error(DSRG_ERR_INVALID, "resnet stem pack: NULL argument");

@@ -346,6 +346,10 @@ int launch_eval_confusion_batch(int B, int C, const float *scores, int h, int w,
 int launch_score_labels_batch(int G, int C, const int32_t *const *labels, const unsigned char *const *gt, const int32_t *H,
                               const int32_t *W, int ignore_label, int rule_lt, unsigned long long *hist, unsigned char *const *mask,
                               hipStream_t stream);
+size_t seg_loss_zoom_workspace(int B, int C, int h, int w, int H, int W);
+int launch_seg_loss_zoom_batch(int B, int C, const float *logits, int h, int w, const float *labels, int H, int W, float ignore_label,
+                               float *loss, float *grad, unsigned long long *counters, void *workspace, size_t workspace_bytes,
+                               hipStream_t stream);
 size_t resnet_stem_packed_bytes();
 int launch_pack_resnet_stem(const float *w, const float *scale, void *packed, hipStream_t stream);
 int launch_resnet_stem(const float *x, const void *packed, const float *shift, void *y, int B, int H, int W, hipStream_t stream);

@@ -448,6 +448,62 @@ def eval_confusion_batch(scores, labels, nclass, ignore_label=255, rule_lt=False
     return hist
 
 
+def seg_loss_zoom(logits, labels, ignore_label=255, counters=None):
+    """Softmax loss at label resolution in two launches (dsrg_seg_loss_zoom_batch): logits (>= B, C, h, w) and labels (B, 1, H, W),
+    contiguous float32 CUDA tensors — the network's score maps and the label maps train_f_input_batch returns.  The first B slices
+    of logits are zoomed to H x W with eval_confusion_batch's arithmetic and the loss is the mean of -log softmax(z)[label] over
+    the valid pixels of the batch (label one of 0..C-1 and not ignore_label).  Returns (loss: 0-dim float32, grad: (B, C, h, w)
+    float32 = d loss / d logits, counters: 3 int64 — valid pixels, valid pixels the argmax gets right, invalid labels — ADDED to
+    `counters` when given).  No valid pixel: loss 0 and a zero gradient.  Bit-reproducible; runs on torch's current stream."""
+    for t, name in ((logits, "logits"), (labels, "labels")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 CUDA tensor" % name)
+    if logits.dim() != 4:
+        raise ValueError("logits must be (>= B, C, h, w), got %s" % (tuple(logits.shape),))
+    if labels.dim() != 4 or labels.shape[1] != 1:
+        raise ValueError("labels must be (B, 1, H, W), got %s" % (tuple(labels.shape),))
+    B, _, H, W = labels.shape
+    C, h, w = (int(v) for v in logits.shape[1:])
+    if B > logits.shape[0]:
+        raise ValueError("%d label maps for %d logit maps" % (B, logits.shape[0]))
+    dev = logits.device
+    if counters is None:
+        counters = torch.zeros(3, dtype=torch.int64, device=dev)
+    elif not (counters.is_cuda and counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() == 3):
+        raise ValueError("counters must be a contiguous int64 CUDA tensor of 3 counters")
+    L = _lib.lib()
+    need = L.dsrg_seg_loss_zoom_workspace(int(B), C, h, w, int(H), int(W))        # (0 for a refused shape: the launch names it)
+    ws = _stream_scratch("seg_loss_zoom", dev, max(int(need), 8))
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    grad = torch.empty((int(B), C, h, w), dtype=torch.float32, device=dev)
+    check(L.dsrg_seg_loss_zoom_batch(int(B), C, _ptr(logits), h, w, _ptr(labels), int(H), int(W), float(ignore_label), _ptr(loss),
+                                     _ptr(grad), _ptr(counters), _ptr(ws), ws.numel(), _stream()))
+    return loss, grad, counters
+
+
+class SegLossZoomFn(torch.autograd.Function):
+    """seg_loss_zoom as a differentiable scalar: the launch runs in forward and leaves the gradient, backward returns grad * g —
+    float32 NCHW contiguous, where the classifier heads' backward takes it.  apply(logits, labels, ignore_label, counters)"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_label, counters):
+        x = logits.detach()
+        if not (x.dtype == torch.float32 and x.is_contiguous()):
+            x = x.float().contiguous()
+        loss, grad, _ = seg_loss_zoom(x, labels, ignore_label, counters)
+        ctx.save_for_backward(grad)
+        ctx.full = logits.shape[0]
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        out = grad * g
+        if ctx.full != out.shape[0]:                                              # (slices beyond the label maps took no part)
+            out = torch.cat([out, out.new_zeros((ctx.full - out.shape[0],) + tuple(out.shape[1:]))])
+        return out, None, None, None
+
+
 def score_labels_batch(labels, gts, nclass, ignore_label=255, rule_lt=False, hist=None, masks=None):
     """Scoring of a group of finished label maps in one launch (dsrg_score_labels_batch): labels, a list of 1..16 contiguous (H_g,
     W_g) int32 CUDA tensors (the CRF's map, the argmax / labels outputs of the multi-scale and pseudo-label tails; sizes may

@@ -4,6 +4,7 @@ backbone of BASELINE.json configs[4] (no counterpart in the reference: new work)
 
   interp_shrink        <-> DeepLab `Interp` layer, shrink_factor 8      (train-f.prototxt:721-731)
   seg_softmax_loss     <-> SoftmaxWithLoss, ignore_label 255            (train-f.prototxt:732-744)
+  seg_softmax_loss_zoom    the same loss at label resolution (loss_at="label"; no counterpart in the reference)
   seg_accuracy         <-> SegAccuracy, ignore_label 255                (train-f.prototxt:745-755)
   poly_lr              <-> lr_policy "poly", power 0.9                  (solver-f.prototxt:5-7)
 
@@ -36,6 +37,19 @@ def seg_softmax_loss(logits, label, ignore_label=255):
     """mean over the non-ignored pixels of -log softmax(logits)[label] (Caffe VALID normalisation)"""
     return F.cross_entropy(logits.float(), label.reshape(label.shape[0], *label.shape[-2:]).long(),
                            ignore_index=ignore_label, reduction="mean")
+
+
+def seg_softmax_loss_zoom(logits, label, ignore_label=255, counters=None):
+    """the same mean, taken at LABEL resolution: logits (B, C, h, w) zoomed to the (B, 1, H, W) label map with the validator's
+    align-corners blend, every valid label pixel judged (ops.seg_loss_zoom: zoom, softmax loss and their backward in one fused
+    HIP call, bit-reproducible).  No counterpart in the reference.  counters: 3 int64 on the device that the call adds to (valid
+    pixels, valid pixels the argmax gets right, labels that are neither a class nor ignore_label), or None.  Unlike
+    seg_softmax_loss, a batch without a valid pixel gives 0 and a zero gradient."""
+    from .ops import SegLossZoomFn
+    lab = label.reshape(label.shape[0], 1, *label.shape[-2:])
+    if not (lab.dtype == torch.float32 and lab.is_contiguous()):
+        lab = lab.float().contiguous()
+    return SegLossZoomFn.apply(logits, lab, float(ignore_label), counters)
 
 
 def seg_accuracy(logits, label, ignore_label=255):
@@ -420,15 +434,22 @@ class RetrainTrainer(object):
     """one train-f step: backbone -> (logits, labels shrunk by 8) -> softmax loss -> SGD with poly LR"""
 
     def __init__(self, device, world_size=1, backbone="vgg16", base_lr=1e-3, max_iter=20000, seed=0,
-                 amp_dtype=torch.bfloat16, net=None, weights=None, snapshot=None, ddp=None, num_classes=21):
-        """weights: run.sh:9 `--weights models/model-s_iter_8000.caffemodel` — stage 2 starts from the stage-1 model
+                 amp_dtype=torch.bfloat16, net=None, weights=None, snapshot=None, ddp=None, num_classes=21, loss_at="map"):
+        """loss_at: "map" (the reference's step: the loss on the network's output map against the labels shrunk by 8) or "label"
+        (the logits zoomed to the label map, every label pixel judged: seg_softmax_loss_zoom; the step then adds its counters
+        to `loss_counters`, 3 int64 on the device — valid pixels, correct ones, invalid labels — which nobody synchronises for).
+        Not part of a snapshot.  weights: run.sh:9 `--weights models/model-s_iter_8000.caffemodel` — stage 2 starts from the stage-1 model
         (copied by layer name: .caffemodel / .npz / torch file); snapshot: a solverstate written by save().  num_classes: the
         outputs of the classifiers of the net built here (21: VOC; 81: the COCO variant; at most 96); a `net` that is handed in
         keeps its own."""
         if not 1 <= int(num_classes) <= MAX_CLASSES:
             raise ValueError("num_classes must be 1..%d, got %r" % (MAX_CLASSES, num_classes))
+        if loss_at not in ("map", "label"):
+            raise ValueError("loss_at must be 'map' or 'label', got %r" % (loss_at,))
         torch.manual_seed(seed)
         self.device, self.amp_dtype, self.max_iter, self.base_lr = device, amp_dtype, max_iter, base_lr
+        self.loss_at = loss_at
+        self.loss_counters = torch.zeros(3, dtype=torch.int64, device=device) if loss_at == "label" else None
         net = net if net is not None else (VGG16ASPP(num_classes=int(num_classes)) if backbone == "vgg16"
                                            else ResNet101DeepLab(num_classes=int(num_classes)))
         if weights is not None:
@@ -467,7 +488,10 @@ class RetrainTrainer(object):
         x = images.contiguous(memory_format=torch.channels_last) if self.device.type == "cuda" else images
         with torch.autocast(self.device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None):
             logits = self.net(x)
-        loss = seg_softmax_loss(logits, interp_shrink(label, 8))
+        if self.loss_at == "label":
+            loss = seg_softmax_loss_zoom(logits, label, counters=self.loss_counters)
+        else:
+            loss = seg_softmax_loss(logits, interp_shrink(label, 8))
         from .ops import deferred_reductions
         with deferred_reductions(self.defer_bias):             # (see DSRGTrainer.step)
             loss.backward()

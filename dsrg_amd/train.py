@@ -12,7 +12,9 @@ AnnotationLayerCOCO feeds the 81-class runs (pylayers.py:432-512; TrainSCueMapIn
 lines with --root prefixed to both, a cue file is a 41 x 41 one-channel image of classes with 255 = no cue, --cues is absent and
 the images are zoomed to 321 x 321; --channel-order rgb feeds the net R G B as that layer does (the default, bgr, is what this
 project's predict and validate — and the reference's test-coco.py — feed).  Stage f's --scale-factors (not the reference's; DeepLab's augmentation for
---backbone resnet101 --crop 513, where no VOC image leaves the crop any slack) rescales each image by a drawn factor before the crop.  Batches are assembled on the GPU (dsrg_amd/input.py) while the step
+--backbone resnet101 --crop 513, where no VOC image leaves the crop any slack) rescales each image by a drawn factor before the crop.  Stage f's --loss-at label (not the reference's either) takes the softmax loss at label
+resolution — the logits zoomed to the label map, every label pixel judged, one fused HIP call (retrain.seg_softmax_loss_zoom) — and
+adds the pixel accuracy of the display window to the display line; the default, map, is the reference's step.  Batches are assembled on the GPU (dsrg_amd/input.py) while the step
 before runs.  Every --display steps the mean of the last --display losses is printed with the learning rate; snapshots
 (<prefix>_iter_N.caffemodel + .solverstate.pt) are written every --snapshot-every steps and at the end; --snapshot resumes at the
 snapshot's iteration count.  Under a launcher (torch.distributed.run: RANK / WORLD_SIZE set) every rank takes its shard of each
@@ -73,6 +75,11 @@ def parse_args(argv=None):
     p.add_argument("--scale-factors", default=None,
                    help="f: rescale every image by one of these factors, drawn per image, before the crop, e.g. 0.5,0.75,1,1.25,1.5 "
                         "(bilinear for the image, nearest neighbour for the label, done on the GPU; default: none)")
+    p.add_argument("--loss-at", choices=("map", "label"), default=None,
+                   help="f: where the softmax loss is taken.  map (default): on the network's output map against the labels shrunk "
+                        "by 8, as the reference does; label: the logits are zoomed to the label map and every label pixel is judged "
+                        "(one fused HIP call), and the display line gains the pixel accuracy.  Not stored in snapshots: a resumed "
+                        "run names it again")
     p.add_argument("--val-list", default=None, help="validate on these 'image_path label_path' lines (ground-truth label PNGs)")
     p.add_argument("--val-root", default=None, help="prefix of both paths of a --val-list line (default: --root)")
     p.add_argument("--val-every", type=int, default=None, help="validate every N steps (default: whenever a snapshot is written)")
@@ -110,7 +117,10 @@ def parse_args(argv=None):
             p.error("--class %d: the cue pickle of --cues describes 21 classes; other class counts are fed by --cue-maps" % a.num_classes)
         if a.backbone or a.crop is not None or a.mean is not None or a.no_mirror or a.scale_factors is not None:
             p.error("--backbone, --crop, --mean, --no-mirror and --scale-factors are for --stage f")
+        if a.loss_at is not None:
+            p.error("--loss-at is for --stage f")
     else:
+        a.loss_at = a.loss_at or "map"
         if a.cues:
             p.error("--cues is for --stage s")
         a.backbone = a.backbone or "vgg16"
@@ -176,7 +186,7 @@ def main(argv=None):
     else:
         from .retrain import RetrainTrainer, poly_lr
         trainer = RetrainTrainer(device, world_size=world, backbone=a.backbone, max_iter=a.iters, seed=a.seed, weights=a.weights,
-                                 snapshot=a.snapshot, num_classes=a.num_classes)
+                                 snapshot=a.snapshot, num_classes=a.num_classes, loss_at=a.loss_at)
         loader = TrainFInput(dict(source=a.list, root_folder=a.root, batch_size=batch, crop_size=(a.crop, a.crop), mean=a.mean,
                                   mirror=not a.no_mirror, scale_factors=a.scale_factors), seed=a.seed, workers=a.workers, rank=rank, world_size=world, device=device)
         names = ("loss",)
@@ -191,6 +201,26 @@ def main(argv=None):
                               mean=a.mean if a.stage == "f" else TrainSInput.mean, num_classes=a.num_classes, device=device, rank=rank, world_size=world,
                               amp_dtype=trainer.amp_dtype, workers=a.workers)
 
+    # --loss-at label: the step adds to trainer.loss_counters on the device; they are read where the display step reads the losses
+    counters = getattr(trainer, "loss_counters", None)
+    seen = [0, 0, 0]                                                     # the counters at the last display line
+
+    def accuracy_words():
+        """', accuracy = ...' over the display window, summed over the ranks (and a warning line for invalid labels), or ''"""
+        if counters is None:
+            return ""
+        import torch.distributed as dist
+        now = counters.clone()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(now, op=dist.ReduceOp.SUM)
+        now = now.tolist()
+        valid, correct, invalid = (n - s for n, s in zip(now, seen))
+        seen[:] = now
+        if invalid:
+            say("warning: %d label pixels are neither a class below %d nor 255: they were left out of the loss" % (invalid, a.num_classes),
+                flush=True)
+        return ", accuracy = %.6f" % (correct / max(valid, 1))
+
     window, saved_at = [], None
     with loader:
         while trainer.opt.iter < a.iters:
@@ -199,7 +229,8 @@ def main(argv=None):
             it = trainer.opt.iter
             if it % a.display == 0 or it == a.iters:
                 mean = DSRGTrainer.reduce_losses(trainer, torch.stack(window).mean(0)).tolist()
-                say("Iteration %d, lr = %g, %s" % (it, lr, ", ".join("%s = %.6f" % nv for nv in zip(names, mean))), flush=True)
+                tail = accuracy_words()
+                say("Iteration %d, lr = %g, %s%s" % (it, lr, ", ".join("%s = %.6f" % nv for nv in zip(names, mean)), tail), flush=True)
                 window = []
             if it % a.snapshot_every == 0 or it == a.iters:
                 paths = trainer.save(a.prefix)                           # (collective: every rank calls it)

@@ -506,6 +506,36 @@ int dsrg_eval_confusion_batch(int B, int C, const float *scores_dev, int h, int 
 int dsrg_score_labels_batch(int G, int C, const int32_t *const *labels_dev, const unsigned char *const *gt_dev,
                             const int32_t *H_host, const int32_t *W_host, int ignore_label, int rule_lt,
                             unsigned long long *hist_dev, unsigned char *const *mask_dev, void *stream);
+/* Softmax loss at label resolution (stage 2 with loss_at = "label"; the reference takes the loss on the 41 x 41 map against labels
+ * shrunk by 8, train-f.prototxt:721-744, and has no counterpart): the logits are zoomed to the label maps' size on the fly and the
+ * loss is taken against every label pixel; loss, gradient and counters in two launches, nothing of size B*C*H*W written.
+ *   logits_dev (>= B, C, h, w) f32 contiguous NCHW: the first B slices are used, the rest is not read
+ *   labels_dev (B, 1, H, W) f32: what dsrg_train_f_input_batch writes as label_dev
+ *   loss_dev   one f32, written;  grad_dev (B, C, h, w) f32, WRITTEN (not added to): d loss / d logits
+ *   counters_dev  three unsigned 64-bit counters that are ADDED to: valid pixels, valid pixels whose first-maximum argmax over c
+ *              of z equals the label (what dsrg_eval_confusion_batch counts on its diagonal), invalid pixels
+ *   workspace_dev  dsrg_seg_loss_zoom_workspace(B, C, h, w, H, W) bytes, 8-byte aligned (0 is returned for shapes the launch
+ *              refuses): one slot of loss and counts per workgroup; too small: DSRG_ERR_INVALID
+ * z(b, c, y, x) is the score dsrg_eval_confusion_batch ranks at that pixel, bit for bit: scale (in-1)/(out-1) in double (0 when
+ * out == 1), i0 = (int)src, i1 = i0 + (i0 < in-1), l1 = src - i0, l0 = 1 - l1, l0h*(l0w*v00 + l1w*v01) + l1h*(l0w*v10 + l1w*v11)
+ * in double rounded once to f32.  A pixel is IGNORED iff its label equals ignore_label; otherwise VALID iff the label is exactly
+ * one of 0..C-1, and INVALID if not (>= C, negative, non-integral).  Ignored and invalid pixels add nothing to loss or gradient.
+ * Per valid pixel: m = max_c z_c, e_c = expf(z_c - m), s = sum_c e_c in f32 with c ascending, l = logf(s) - (z_label - m),
+ * p_c = e_c * (1 / s) with r = 1 / s one IEEE division per pixel (two tied planes of a 2-label map give p = 0.5 exactly).
+ * With N the valid pixels of the whole call (Caffe's VALID normalisation):
+ *   *loss_dev = (float)((sum of l in double) / max(N, 1))
+ *   grad[b,c,i,j] = S / (float)max(N, 1), one IEEE division, S = the f32 sum over the valid pixels (y, x) of image b of
+ *     (wy(y,i) * wx(x,j)) * (p_c - [c == label]),  wy(y,i) = ((i == y0) ? (float)l0h : 0) + ((i == y1) ? (float)l1h : 0), wx alike
+ * N == 0 gives loss 0 and an all-zero gradient, never NaN.  S is a gather, summed in an order fixed by the shapes alone (the
+ * products of a cell's pixels row by row: a row's from left to right, then the rows' sums from the top); the workgroups' losses are summed in slot order; there are no floating-point atomics on memory or LDS:
+ * repeated calls give identical bits in loss_dev and grad_dev.
+ * 1 <= B <= 32, 1 <= C <= 96 (above: DSRG_ERR_UNSUPPORTED), h, w, H, W >= 1 (enlarging, shrinking, identity), B*C*h*w < 2^31,
+ * B*H*W < 2^31; every argument is checked before the first device call (NULL pointers and bad shapes: DSRG_ERR_INVALID).  Nothing
+ * is allocated.  Stream-ordered, no host synchronisation, no handle. */
+size_t dsrg_seg_loss_zoom_workspace(int B, int C, int h, int w, int H, int W);
+int dsrg_seg_loss_zoom_batch(int B, int C, const float *logits_dev, int h, int w, const float *labels_dev, int H, int W,
+                             float ignore_label, float *loss_dev, float *grad_dev, unsigned long long *counters_dev,
+                             void *workspace_dev, size_t workspace_bytes, void *stream);
 /* The stem of the DeepLab-v2 ResNet-101 at test time in one launch (backbone plumbing; the reference's networks are Caffe
  * prototxts): conv 7x7 / stride 2 / zero pad 3, 3 -> 64, with a frozen BatchNorm folded in -> ReLU -> max pool 3x3 / stride 2 /
  * pad 1, ceil mode.  The convolution map never reaches memory.
