@@ -117,6 +117,10 @@ SIGNATURES = {
                                 [_i, _i, _vp, ctypes.POINTER(_vp), _vp]),
     "dsrg_seg_loss_zoom_workspace": (_sz, [_i] * 6),
     "dsrg_seg_loss_zoom_batch": (_i, [_i, _i, _vp, _i, _i, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dsrg_msc_pyramid_batch": (_i, [_i, _vp, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_vp), _vp]),
+    "dsrg_msc_loss_workspace": (_sz, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), _i, _i]),
+    "dsrg_msc_loss_batch": (_i, [_i, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_i), _vp, _i, _i, _f, _vp,
+                                 ctypes.POINTER(_vp), _vp, _vp, _sz, _vp]),
     "dsrg_resnet_stem_packed_bytes": (_sz, []),
     "dsrg_pack_resnet_stem_f32": (_i, [_vp, _vp, _vp, _vp]),
     "dsrg_resnet_stem_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

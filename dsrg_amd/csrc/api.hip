@@ -606,6 +606,21 @@ extern "C" int dsrg_seg_loss_zoom_batch(int B, int C, const float *logits, int h
     return launch_seg_loss_zoom_batch(B, C, logits, h, w, labels, H, W, ignore_label, loss, grad, counters, workspace, workspace_bytes,
                                       static_cast<hipStream_t>(stream));
 }
+extern "C" int dsrg_msc_pyramid_batch(int B, const float *images, int H, int W, int n, const int *h, const int *w, float *const *out,
+                                      void *stream) {
+    // every argument is checked before the first device call
+    return launch_msc_pyramid_batch(B, images, H, W, n, h, w, out, static_cast<hipStream_t>(stream));
+}
+extern "C" size_t dsrg_msc_loss_workspace(int S, int B, int C, const int *h, const int *w, int H, int W) {
+    return msc_loss_workspace(S, B, C, h, w, H, W);
+}
+extern "C" int dsrg_msc_loss_batch(int S, int B, int C, const float *const *maps, const int *h, const int *w, const float *labels, int H,
+                                   int W, float ignore_label, float *losses, float *const *grads, unsigned long long *counters,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    // every argument is checked before the first device call
+    return launch_msc_loss_batch(S, B, C, maps, h, w, labels, H, W, ignore_label, losses, grads, counters, workspace, workspace_bytes,
+                                 static_cast<hipStream_t>(stream));
+}
 extern "C" size_t dsrg_resnet_stem_packed_bytes(void) { return resnet_stem_packed_bytes(); }
 extern "C" int dsrg_pack_resnet_stem_f32(const float *w, const float *scale, void *packed, void *stream) {
     if (!w || !scale || !packed) return set_error(DSRG_ERR_INVALID, "resnet stem pack: NULL argument");

@@ -350,6 +350,12 @@ size_t seg_loss_zoom_workspace(int B, int C, int h, int w, int H, int W);
 int launch_seg_loss_zoom_batch(int B, int C, const float *logits, int h, int w, const float *labels, int H, int W, float ignore_label,
                                float *loss, float *grad, unsigned long long *counters, void *workspace, size_t workspace_bytes,
                                hipStream_t stream);
+int launch_msc_pyramid_batch(int B, const float *images, int H, int W, int n, const int *h, const int *w, float *const *out,
+                             hipStream_t stream);
+size_t msc_loss_workspace(int S, int B, int C, const int *h, const int *w, int H, int W);
+int launch_msc_loss_batch(int S, int B, int C, const float *const *maps, const int *h, const int *w, const float *labels, int H, int W,
+                          float ignore_label, float *losses, float *const *grads, unsigned long long *counters, void *workspace,
+                          size_t workspace_bytes, hipStream_t stream);
 size_t resnet_stem_packed_bytes();
 int launch_pack_resnet_stem(const float *w, const float *scale, void *packed, hipStream_t stream);
 int launch_resnet_stem(const float *x, const void *packed, const float *shift, void *y, int B, int H, int W, hipStream_t stream);

@@ -35,6 +35,7 @@
 // (float)max(N, 1) — one IEEE division per element — and workgroup 0 also sums the losses in double in slot order (lane-strided,
 // then the same tree), writes *loss_dev = (float)(sum / max(N, 1)) and adds the three counters.
 #include "common.h"
+#include "zoom_gather.h"
 
 namespace dsrg {
 
@@ -49,35 +50,6 @@ struct SegLossPart {                       // a workgroup's slot of the workspac
     double loss;
     unsigned long long valid, correct, invalid;
 };
-
-// the source cell of output coordinate d on an axis of n_in samples (eval.hip: the min never binds)
-__device__ __forceinline__ int sl_cell(double scale, int d, int n_in) { return min((int)(scale * (double)d), n_in - 1); }
-
-// the first output coordinate in [0, n_out] whose source cell is >= i (source cells never decrease along the axis)
-__device__ int sl_first(double scale, int i, int n_in, int n_out) {
-    if (i <= 0) return 0;
-    if (i > n_in - 1 || !(scale > 0.0)) return n_out;
-    const double q = ceil((double)i / scale);
-    int g = q < (double)n_out ? (int)q : n_out;
-    while (g > 0 && sl_cell(scale, g - 1, n_in) >= i) --g;
-    while (g < n_out && sl_cell(scale, g, n_in) < i) ++g;
-    return g;
-}
-
-// the sum of v over the workgroup in a fixed order (a tree over the lane index); every lane gets it
-template <typename T>
-__device__ __forceinline__ T sl_block_sum(T v, T *s_red) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    s_red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int k = kSlThreads / 2; k > 0; k >>= 1) {
-        if (tid < k) s_red[tid] = s_red[tid] + s_red[tid + k];
-        __syncthreads();
-    }
-    return s_red[0];
-}
 
 __global__ __launch_bounds__(kSlThreads) void seg_loss_zoom_main_kernel(int C, const float *__restrict__ logits, int h, int w, double sh,
                                                                         double sw, const float *__restrict__ labels, int H, int W,
@@ -233,10 +205,10 @@ __global__ __launch_bounds__(kSlThreads) void seg_loss_zoom_main_kernel(int C, c
     }
 
     // the workgroup's slot
-    const double tl = sl_block_sum(loss, s_redd);
-    const unsigned int tv = sl_block_sum(n_valid, s_redu);
-    const unsigned int tc = sl_block_sum(n_correct, s_redu);
-    const unsigned int ti = sl_block_sum(n_invalid, s_redu);
+    const double tl = sl_block_sum<kSlThreads>(loss, s_redd);
+    const unsigned int tv = sl_block_sum<kSlThreads>(n_valid, s_redu);
+    const unsigned int tc = sl_block_sum<kSlThreads>(n_correct, s_redu);
+    const unsigned int ti = sl_block_sum<kSlThreads>(n_invalid, s_redu);
     if (tid == 0) {
         SegLossPart p;
         p.loss = tl, p.valid = tv, p.correct = tc, p.invalid = ti;
@@ -253,7 +225,7 @@ __global__ __launch_bounds__(kSlThreads) void seg_loss_zoom_finish_kernel(int np
     const int tid = threadIdx.x;
     unsigned long long nv = 0;
     for (int k = tid; k < nparts; k += kSlThreads) nv += parts[k].valid;
-    const unsigned long long N = sl_block_sum(nv, s_redu);
+    const unsigned long long N = sl_block_sum<kSlThreads>(nv, s_redu);
     const unsigned long long D = N > 0 ? N : 1;
     if (blockIdx.x == 0) {
         double l = 0.0;
@@ -263,9 +235,9 @@ __global__ __launch_bounds__(kSlThreads) void seg_loss_zoom_finish_kernel(int np
             nc += parts[k].correct;
             ni += parts[k].invalid;
         }
-        const double L = sl_block_sum(l, s_redd);
-        const unsigned long long NC = sl_block_sum(nc, s_redu);
-        const unsigned long long NI = sl_block_sum(ni, s_redu);
+        const double L = sl_block_sum<kSlThreads>(l, s_redd);
+        const unsigned long long NC = sl_block_sum<kSlThreads>(nc, s_redu);
+        const unsigned long long NI = sl_block_sum<kSlThreads>(ni, s_redu);
         if (tid == 0) {
             *loss_out = (float)(L / (double)D);
             counters[0] += N;

@@ -504,6 +504,89 @@ class SegLossZoomFn(torch.autograd.Function):
         return out, None, None, None
 
 
+def _int_array(values):
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def msc_pyramid(images, sizes):
+    """The smaller inputs of a multi-scale step in one launch (dsrg_msc_pyramid_batch): images (B, 3, H, W) contiguous float32 NCHW
+    (the loader's mean-subtracted crop), sizes 1..3 pairs (h, w) or single sides -> a list of (B, 3, h, w) float32 tensors in
+    torch.channels_last, each the align-corners zoom of eval_confusion_batch (blend in double, rounded once)."""
+    if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.float32 and images.is_contiguous()):
+        raise ValueError("images must be a contiguous float32 CUDA tensor")
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError("images must be (B, 3, H, W), got %s" % (tuple(images.shape),))
+    sizes = [(int(s), int(s)) if isinstance(s, int) else (int(s[0]), int(s[1])) for s in sizes]
+    if not 1 <= len(sizes) <= 3:
+        raise ValueError("1..3 sizes, got %d" % len(sizes))
+    B, _, H, W = (int(v) for v in images.shape)
+    outs = [torch.empty((B, 3, max(h, 1), max(w, 1)), dtype=torch.float32, device=images.device, memory_format=torch.channels_last)
+            for h, w in sizes]
+    check(_lib.lib().dsrg_msc_pyramid_batch(B, _ptr(images), H, W, len(sizes), _int_array([h for h, _ in sizes]),
+                                            _int_array([w for _, w in sizes]), _ptr_array(outs), _stream()))
+    return outs
+
+
+def msc_loss(maps, labels, ignore_label=255, counters=None):
+    """The S + 1 softmax losses of a multi-scale step with max fusion in three launches (dsrg_msc_loss_batch): maps, a list of
+    2..4 contiguous float32 CUDA score maps (B, C, h_s, w_s) with map 0 the full scale, and labels (B, 1, H, W) float32.  The other
+    maps are zoomed to map 0 (eval_confusion_batch's arithmetic), the element-wise maximum is the fused map (ties go to the lowest
+    scale index); the fused map and every map are judged against the nearest label sample at their own resolution.  Returns
+    (losses: S + 1 float32 — fused, map 0, map 1, ... —, grads: a list of (B, C, h_s, w_s) float32 = d (sum of the losses) / d map s,
+    counters: 3 int64 of the fused head — valid pixels, valid pixels the argmax gets right, invalid labels — ADDED to `counters`
+    when given).  Nothing valid: losses 0 and zero gradients.  Bit-reproducible; runs on torch's current stream."""
+    maps = list(maps)
+    if not 2 <= len(maps) <= 4:
+        raise ValueError("2..4 score maps, got %d" % len(maps))
+    for t, name in [(m, "maps[%d]" % k) for k, m in enumerate(maps)] + [(labels, "labels")]:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 CUDA tensor" % name)
+    if labels.dim() != 4 or labels.shape[1] != 1:
+        raise ValueError("labels must be (B, 1, H, W), got %s" % (tuple(labels.shape),))
+    B, _, H, W = (int(v) for v in labels.shape)
+    if any(m.dim() != 4 or tuple(m.shape[:2]) != tuple(maps[0].shape[:2]) for m in maps) or maps[0].shape[0] != B:
+        raise ValueError("score maps must be (%d, C, h, w) with one C, got %s" % (B, [tuple(m.shape) for m in maps]))
+    C = int(maps[0].shape[1])
+    dev = maps[0].device
+    if counters is None:
+        counters = torch.zeros(3, dtype=torch.int64, device=dev)
+    elif not (counters.is_cuda and counters.dtype == torch.int64 and counters.is_contiguous() and counters.numel() == 3):
+        raise ValueError("counters must be a contiguous int64 CUDA tensor of 3 counters")
+    L = _lib.lib()
+    S = len(maps)
+    hs, ws_ = _int_array([m.shape[2] for m in maps]), _int_array([m.shape[3] for m in maps])
+    need = L.dsrg_msc_loss_workspace(S, B, C, hs, ws_, H, W)                      # (0 for a refused shape: the launch names it)
+    ws = _stream_scratch("msc_loss", dev, max(int(need), 8))
+    losses = torch.empty(S + 1, dtype=torch.float32, device=dev)
+    grads = [torch.empty_like(m) for m in maps]
+    check(L.dsrg_msc_loss_batch(S, B, C, _ptr_array(maps), hs, ws_, _ptr(labels), H, W, float(ignore_label), _ptr(losses),
+                                _ptr_array(grads), _ptr(counters), _ptr(ws), ws.numel(), _stream()))
+    return losses, grads, counters
+
+
+class MscLossFn(torch.autograd.Function):
+    """msc_loss as a differentiable scalar: the launch runs in forward and leaves the gradients of the SUM of the S + 1 heads (each
+    of weight 1, as in the recipe); backward returns grad_s * g for every map — float32 NCHW contiguous, where the classifier
+    heads' backward takes it.  apply(labels, ignore_label, counters, map_0, map_1, ...) -> (total: 0-dim, the sum of the losses in
+    float32, differentiable; losses: S + 1 float32 — fused, map 0, map 1, ... —, not differentiable)"""
+
+    @staticmethod
+    def forward(ctx, labels, ignore_label, counters, *maps):
+        xs = [m.detach() if (m.dtype == torch.float32 and m.is_contiguous()) else m.detach().float().contiguous() for m in maps]
+        losses, grads, _ = msc_loss(xs, labels, ignore_label, counters)
+        ctx.save_for_backward(*grads)
+        ctx.mark_non_differentiable(losses)
+        return losses.sum(), losses
+
+    @staticmethod
+    def backward(ctx, g, _):
+        return (None, None, None) + tuple(grad * g for grad in ctx.saved_tensors)
+
+
 def score_labels_batch(labels, gts, nclass, ignore_label=255, rule_lt=False, hist=None, masks=None):
     """Scoring of a group of finished label maps in one launch (dsrg_score_labels_batch): labels, a list of 1..16 contiguous (H_g,
     W_g) int32 CUDA tensors (the CRF's map, the argmax / labels outputs of the multi-scale and pseudo-label tails; sizes may

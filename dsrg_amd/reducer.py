@@ -76,6 +76,7 @@ class BucketedAllReduce(object):
                 off += (n + 63) // 64 * 64
         self._handles = []
         self._next = 0
+        self._accumulate = False                                # prepare(accumulate=True): see there
         self.copies = 0                                         # gradients that had to be copied into their slot (tests, tools)
         self.copied = []                                        # ... and whose
         self.launch_log = []                                    # bucket indices in launch order of the last step (tests)
@@ -85,21 +86,27 @@ class BucketedAllReduce(object):
         dev = ps[0].device
         self.buckets.append([torch.zeros(n, dtype=torch.float32, device=dev), list(ps), len(ps), False])
 
-    def prepare(self):
-        """before backward: gradients unset, every parameter knows its slot"""
+    def prepare(self, accumulate=False):
+        """before backward: gradients unset, every parameter knows its slot.  accumulate: the step's backward hands a parameter
+        SEVERAL contributions (shared weights under more than one forward) that autograd adds up — no slot is handed out (a
+        kernel that writes its slot would overwrite the contribution before it), nothing is launched while backward runs, and
+        finish() copies every sum into its bucket and reduces all of them"""
         for b in self.buckets:
             b[2], b[3] = len(b[1]), False
         self._next = 0
         self._handles = []
         self.launch_log = []
         self._seen = set()
+        self._accumulate = bool(accumulate)
         small_ids = set(id(p) for p in self.small)
         for p in self.params:
             p.grad = None
-            p._dsrg_grad_out = self._slot[p][1] if id(p) not in small_ids else None
+            p._dsrg_grad_out = self._slot[p][1] if (id(p) not in small_ids and not accumulate) else None
 
     @torch.no_grad()
     def _ready(self, p):
+        if self._accumulate:                                    # (the gradient is final only after backward: finish() takes it)
+            return
         bi, view = self._slot[p]
         g = p.grad
         if g is None or id(p) in self._seen:                    # (one gradient per parameter and step: no accumulation across calls)

@@ -52,6 +52,47 @@ def seg_softmax_loss_zoom(logits, label, ignore_label=255, counters=None):
     return SegLossZoomFn.apply(logits, lab, float(ignore_label), counters)
 
 
+MSC_MAX_SCALES = 3                 # extra scales of a multi-scale step (ops.msc_loss takes 2..4 maps)
+MSC_MIN_SIDE = 17                  # the smallest input side a scale may give (three cells of the output map)
+
+
+def msc_sizes(crop, scales):
+    """the input sides of a multi-scale step's smaller copies, DeepLab's `Interp` sizes: int((crop - 1) * s + 0.5) + 1
+    (321 -> 241, 161 and 513 -> 385, 257 at 0.75, 0.5)"""
+    return tuple(int((int(crop) - 1) * float(s) + 0.5) + 1 for s in scales)
+
+
+def check_msc_scales(scales, crop=None):
+    """`msc_scales` as a tuple of floats: at most MSC_MAX_SCALES, each 0 < s <= 2, distinct and not 1 (and, where the crop is known, a side of at
+    least MSC_MIN_SIDE); ValueError otherwise"""
+    try:
+        scales = tuple(float(s) for s in scales)
+    except (TypeError, ValueError):
+        raise ValueError("msc_scales must be numbers, got %r" % (scales,))
+    if len(scales) > MSC_MAX_SCALES:
+        raise ValueError("msc_scales: at most %d extra scales, got %d" % (MSC_MAX_SCALES, len(scales)))
+    if not all(0.0 < s <= 2.0 for s in scales):                 # (NaN fails the comparison)
+        raise ValueError("msc_scales must be > 0 and <= 2, got %r" % (scales,))
+    if 1.0 in scales or len(set(scales)) != len(scales):        # (the crop itself is always map 0; the losses are named by their scale)
+        raise ValueError("msc_scales must be distinct and none of them 1, got %r" % (scales,))
+    if crop is not None and any(side < MSC_MIN_SIDE for side in msc_sizes(crop, scales)):
+        raise ValueError("msc_scales %r give sides %r at crop %d: at least %d" % (scales, msc_sizes(crop, scales), crop, MSC_MIN_SIDE))
+    return scales
+
+
+def seg_softmax_loss_msc(maps, label, ignore_label=255, counters=None):
+    """DeepLab-v2's multi-scale loss with max fusion: maps, 2..4 score maps (B, C, h_s, w_s) of one network on the crop (map 0)
+    and on smaller copies of it, label (B, 1, H, W).  The smaller maps are zoomed to map 0, the element-wise maximum is the fused
+    map, and the fused map and every map are judged against the labels sampled at their own resolution (ops.msc_loss: one fused
+    HIP call, bit-reproducible).  -> (total: the sum of the S + 1 losses, differentiable; losses: S + 1 float32 — fused, map 0,
+    map 1, ...).  No counterpart in the reference.  counters: as seg_softmax_loss_zoom, for the fused head."""
+    from .ops import MscLossFn
+    lab = label.reshape(label.shape[0], 1, *label.shape[-2:])
+    if not (lab.dtype == torch.float32 and lab.is_contiguous()):
+        lab = lab.float().contiguous()
+    return MscLossFn.apply(lab, float(ignore_label), counters, *maps)
+
+
 def seg_accuracy(logits, label, ignore_label=255):
     lab = label.reshape(label.shape[0], *label.shape[-2:]).long()
     keep = lab != ignore_label
@@ -434,8 +475,14 @@ class RetrainTrainer(object):
     """one train-f step: backbone -> (logits, labels shrunk by 8) -> softmax loss -> SGD with poly LR"""
 
     def __init__(self, device, world_size=1, backbone="vgg16", base_lr=1e-3, max_iter=20000, seed=0,
-                 amp_dtype=torch.bfloat16, net=None, weights=None, snapshot=None, ddp=None, num_classes=21, loss_at="map"):
-        """loss_at: "map" (the reference's step: the loss on the network's output map against the labels shrunk by 8) or "label"
+                 amp_dtype=torch.bfloat16, net=None, weights=None, snapshot=None, ddp=None, num_classes=21, loss_at="map",
+                 msc_scales=()):
+        """msc_scales: the extra input scales of DeepLab-v2's multi-scale step with max fusion, e.g. (0.75, 0.5); empty (the
+        default): the single-scale step.  With scales, step() runs the network on the crop and on every smaller copy, takes
+        seg_softmax_loss_msc on the maps and returns the vector (total, fused, res1, res<s>...); `loss_counters` counts for the fused
+        head.  The scales are distinct and none is 1 (the crop itself is always map 0).  Not part of a snapshot either: snapshots
+        are interchangeable with single-scale runs.
+        loss_at: "map" (the reference's step: the loss on the network's output map against the labels shrunk by 8) or "label"
         (the logits zoomed to the label map, every label pixel judged: seg_softmax_loss_zoom; the step then adds its counters
         to `loss_counters`, 3 int64 on the device — valid pixels, correct ones, invalid labels — which nobody synchronises for).
         Not part of a snapshot.  weights: run.sh:9 `--weights models/model-s_iter_8000.caffemodel` — stage 2 starts from the stage-1 model
@@ -446,10 +493,13 @@ class RetrainTrainer(object):
             raise ValueError("num_classes must be 1..%d, got %r" % (MAX_CLASSES, num_classes))
         if loss_at not in ("map", "label"):
             raise ValueError("loss_at must be 'map' or 'label', got %r" % (loss_at,))
+        msc_scales = check_msc_scales(msc_scales)
+        if msc_scales and loss_at != "map":
+            raise ValueError("msc_scales and loss_at=%r do not combine" % (loss_at,))
         torch.manual_seed(seed)
         self.device, self.amp_dtype, self.max_iter, self.base_lr = device, amp_dtype, max_iter, base_lr
-        self.loss_at = loss_at
-        self.loss_counters = torch.zeros(3, dtype=torch.int64, device=device) if loss_at == "label" else None
+        self.loss_at, self.msc_scales = loss_at, msc_scales
+        self.loss_counters = torch.zeros(3, dtype=torch.int64, device=device) if (loss_at == "label" or msc_scales) else None
         net = net if net is not None else (VGG16ASPP(num_classes=int(num_classes)) if backbone == "vgg16"
                                            else ResNet101DeepLab(num_classes=int(num_classes)))
         if weights is not None:
@@ -479,7 +529,35 @@ class RetrainTrainer(object):
         from .checkpoint import load_snapshot
         return load_snapshot(self, state_path)          # the poly rate is recomputed from opt.iter at every step
 
+    def _step_msc(self, images, label):
+        """the multi-scale step: three forwards share every parameter, so a parameter's gradient is the sum of three contributions
+        that autograd adds up — the reducer hands out no slots and reduces after backward (prepare(accumulate=True)), and the bias
+        gradients are finished where they are produced (inside deferred_reductions a returned bias gradient is not final, and
+        autograd's += of the next contribution would read it)"""
+        from .ops import msc_pyramid
+        H, W = (int(v) for v in images.shape[-2:])
+        sides = list(zip(msc_sizes(H, self.msc_scales), msc_sizes(W, self.msc_scales)))
+        if min(min(s) for s in sides) < MSC_MIN_SIDE:
+            raise ValueError("msc_scales %r give inputs %r at a crop of %dx%d: sides of at least %d" % (self.msc_scales, sides, H, W, MSC_MIN_SIDE))
+        if self.reducer is not None:
+            self.reducer.prepare(accumulate=True)
+        else:
+            self.opt.zero_grad()
+        self.opt.base_lr = poly_lr(self.base_lr, self.opt.iter, self.max_iter)
+        base = images if (images.dtype == torch.float32 and images.is_contiguous()) else images.float().contiguous()
+        xs = [base.contiguous(memory_format=torch.channels_last)] + msc_pyramid(base, sides)      # (the copies are channels-last as written)
+        with torch.autocast(self.device.type, dtype=self.amp_dtype, enabled=self.amp_dtype is not None):
+            maps = [self.net(x) for x in xs]
+        total, losses = seg_softmax_loss_msc(maps, label, counters=self.loss_counters)
+        total.backward()
+        if self.reducer is not None:
+            self.reducer.finish()
+        self.opt.step()
+        return torch.cat([total.detach().reshape(1), losses])
+
     def step(self, images, label):
+        if self.msc_scales:
+            return self._step_msc(images, label)
         if self.reducer is not None:
             self.reducer.prepare()
         else:

@@ -14,7 +14,11 @@ the images are zoomed to 321 x 321; --channel-order rgb feeds the net R G B as t
 project's predict and validate — and the reference's test-coco.py — feed).  Stage f's --scale-factors (not the reference's; DeepLab's augmentation for
 --backbone resnet101 --crop 513, where no VOC image leaves the crop any slack) rescales each image by a drawn factor before the crop.  Stage f's --loss-at label (not the reference's either) takes the softmax loss at label
 resolution — the logits zoomed to the label map, every label pixel judged, one fused HIP call (retrain.seg_softmax_loss_zoom) — and
-adds the pixel accuracy of the display window to the display line; the default, map, is the reference's step.  Batches are assembled on the GPU (dsrg_amd/input.py) while the step
+adds the pixel accuracy of the display window to the display line; the default, map, is the reference's step.  Stage f's
+--msc-scales 0.75,0.5 (DeepLab-v2's multi-scale inputs with max fusion, not the reference's either) runs the network on the crop and
+on the crop zoomed by every scale, fuses the score maps by their maximum and judges the fused map and every scale's own map
+(retrain.seg_softmax_loss_msc, one fused HIP call); the display line then reads loss, loss-fusion, loss-res1, loss-res<scale>...
+and the fused head's pixel accuracy.  Batches are assembled on the GPU (dsrg_amd/input.py) while the step
 before runs.  Every --display steps the mean of the last --display losses is printed with the learning rate; snapshots
 (<prefix>_iter_N.caffemodel + .solverstate.pt) are written every --snapshot-every steps and at the end; --snapshot resumes at the
 snapshot's iteration count.  Under a launcher (torch.distributed.run: RANK / WORLD_SIZE set) every rank takes its shard of each
@@ -80,6 +84,11 @@ def parse_args(argv=None):
                         "by 8, as the reference does; label: the logits are zoomed to the label map and every label pixel is judged "
                         "(one fused HIP call), and the display line gains the pixel accuracy.  Not stored in snapshots: a resumed "
                         "run names it again")
+    p.add_argument("--msc-scales", default=None,
+                   help="f: DeepLab-v2's multi-scale inputs with max fusion, e.g. 0.75,0.5 (up to 3 extra scales, distinct, each > 0, <= 2 and not 1): "
+                        "every step runs the network on the crop and on the crop zoomed by each scale, fuses the score maps by their "
+                        "maximum and judges the fused map and every scale's own map (one fused HIP call); the display line names "
+                        "the losses and gains the fused map's pixel accuracy.  Not stored in snapshots; not with --loss-at label")
     p.add_argument("--val-list", default=None, help="validate on these 'image_path label_path' lines (ground-truth label PNGs)")
     p.add_argument("--val-root", default=None, help="prefix of both paths of a --val-list line (default: --root)")
     p.add_argument("--val-every", type=int, default=None, help="validate every N steps (default: whenever a snapshot is written)")
@@ -119,6 +128,8 @@ def parse_args(argv=None):
             p.error("--backbone, --crop, --mean, --no-mirror and --scale-factors are for --stage f")
         if a.loss_at is not None:
             p.error("--loss-at is for --stage f")
+        if a.msc_scales is not None:
+            p.error("--msc-scales is for --stage f")
     else:
         a.loss_at = a.loss_at or "map"
         if a.cues:
@@ -137,6 +148,18 @@ def parse_args(argv=None):
                 p.error("--scale-factors takes numbers separated by commas, got %r" % a.scale_factors)
             if not all(0.0 < s < float("inf") for s in a.scale_factors):
                 p.error("--scale-factors must be finite and > 0, got %r" % (a.scale_factors,))
+        if a.msc_scales is None:
+            a.msc_scales = ()
+        else:
+            if a.loss_at == "label":
+                p.error("--msc-scales and --loss-at label do not combine")
+            from .retrain import check_msc_scales
+            try:
+                a.msc_scales = check_msc_scales(a.msc_scales.split(","), a.crop)
+            except ValueError as e:
+                p.error("--msc-scales: %s" % e)
+            if not a.msc_scales:
+                p.error("--msc-scales takes numbers separated by commas")
     if min(a.iters, a.snapshot_every, a.batch, a.display, a.workers) < 1:
         p.error("--iters, --snapshot-every, --batch, --display and --workers must be >= 1")
     return a
@@ -186,10 +209,12 @@ def main(argv=None):
     else:
         from .retrain import RetrainTrainer, poly_lr
         trainer = RetrainTrainer(device, world_size=world, backbone=a.backbone, max_iter=a.iters, seed=a.seed, weights=a.weights,
-                                 snapshot=a.snapshot, num_classes=a.num_classes, loss_at=a.loss_at)
+                                 snapshot=a.snapshot, num_classes=a.num_classes, loss_at=a.loss_at, msc_scales=a.msc_scales)
         loader = TrainFInput(dict(source=a.list, root_folder=a.root, batch_size=batch, crop_size=(a.crop, a.crop), mean=a.mean,
                                   mirror=not a.no_mirror, scale_factors=a.scale_factors), seed=a.seed, workers=a.workers, rank=rank, world_size=world, device=device)
         names = ("loss",)
+        if a.msc_scales:                                                 # (DeepLab's names: the fused head, the crop, every scale)
+            names = ("loss", "loss-fusion", "loss-res1") + tuple("loss-res%g" % s for s in a.msc_scales)
         rate = lambda: poly_lr(trainer.base_lr, trainer.opt.iter, trainer.max_iter)      # noqa: E731
     if trainer.opt.iter:
         say("resumed from %s at iteration %d" % (a.snapshot, trainer.opt.iter), flush=True)

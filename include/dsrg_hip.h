@@ -536,6 +536,50 @@ size_t dsrg_seg_loss_zoom_workspace(int B, int C, int h, int w, int H, int W);
 int dsrg_seg_loss_zoom_batch(int B, int C, const float *logits_dev, int h, int w, const float *labels_dev, int H, int W,
                              float ignore_label, float *loss_dev, float *grad_dev, unsigned long long *counters_dev,
                              void *workspace_dev, size_t workspace_bytes, void *stream);
+/* Multi-scale-input training with max fusion (DeepLab-v2's "MSC" recipe for ResNet-101: the shared-weight network runs on the crop
+ * and on smaller copies of it, the smaller score maps are zoomed to the full one, the element-wise maximum is taken, and the fused
+ * map and every scale's own map are judged by a softmax loss of weight 1 each; the reference retrains at one scale and has no
+ * counterpart).  All three entry points are stream-ordered, allocate nothing, keep no handle, never synchronise the host, and check
+ * every argument before the first device call (NULL pointers and bad shapes: DSRG_ERR_INVALID; C > 96: DSRG_ERR_UNSUPPORTED).
+ * h, w (and maps_dev, grads_dev, out_dev: arrays of device pointers) are HOST arrays, read before the call returns.
+ *
+ * The zoom of both is the project's align-corners zoom (dsrg_eval_confusion_batch, dsrg_seg_loss_zoom_batch): scale =
+ * (in-1)/(out-1) in double (0 when out == 1), src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in-1), l1 = src - i0, l0 = 1 - l1,
+ * l0h*(l0w*v00 + l1w*v01) + l1h*(l0w*v10 + l1w*v11) in double rounded once to f32.
+ *
+ * dsrg_msc_pyramid_batch, one launch: images_dev (B, 3, H, W) f32 NCHW -> n = 1..3 zoomed copies out_dev[s] of h[s] x w[s], each
+ * WRITTEN CHANNELS-LAST (memory order B, h, w, 3: what a (B, 3, h, w) tensor of torch.channels_last holds).  1 <= B <= 32,
+ * B*3*H*W < 2^31, the copies together < 2^31 values; a copy may be larger than the input.
+ *
+ * dsrg_msc_loss_batch, three launches: S = 2..4 score maps maps_dev[s] (B, C, h[s], w[s]) f32 NCHW contiguous, map 0 the full scale
+ * (any sizes: a map may be as large as map 0 or larger), labels_dev (B, 1, H, W) f32 as dsrg_train_f_input_batch writes them.
+ *   labels of map s: the nearest sample of the label map at the align-corners position, in integers:
+ *       y = (2*i*(H-1) + (h[s]-1)) / (2*(h[s]-1)), 0 when h[s] == 1; columns alike (at H-1 = 8 (h-1): label[::8, ::8]).
+ *       Validity as dsrg_seg_loss_zoom_batch: ignored iff == ignore_label, else valid iff exactly one of 0..C-1, else invalid.
+ *   fused map: u_0 = z_0, u_s = z_s zoomed to h[0] x w[0]; f_c = max_s u_s,c; the winner k_c(i,j) = the LOWEST s attaining it.
+ *   each of the S + 1 heads per valid pixel as dsrg_seg_loss_zoom_batch: m = first maximum over c, e_c = expf(z_c - m), s = sum
+ *       of e_c in f32 with c ascending, r = 1/s, term = logf(s) - (z_label - m), d_c = e_c*r - [c == label]; d = 0 where the pixel is
+ *       not valid.  N_s = valid pixels of map s; the fused head shares map 0's labels and N_0.
+ *   losses_dev[S+1] f32, written: fused, map 0, map 1, ...: (float)((double sum of the head's terms) / max(N_head, 1))
+ *   grads_dev[s] (B, C, h[s], w[s]) f32, WRITTEN: the gradient of the SUM of the S + 1 losses with respect to map s:
+ *       grad_0 = (d_0 + [k == 0] * d_f) / (float)max(N_0, 1)
+ *       grad_s = d_s / (float)max(N_s, 1) + G_s / (float)max(N_0, 1)  for s > 0, with
+ *       G_s,c(a,b) = the f32 sum over the map-0 pixels (y, x) whose taps touch cell (a,b) of (wy*wx) * [k_c(y,x) == s] * d_f,c(y,x),
+ *       wy = ((a == y0) ? (float)l0h : 0) + ((a == y1) ? (float)l1h : 0), wx alike — a GATHER per cell, rows from the top, a row's
+ *       products from the left, the row's sum added to the cell's: an order fixed by the shapes alone.
+ *   counters_dev: three unsigned 64-bit counters ADDED to, for the fused head: valid pixels, valid pixels whose first-maximum
+ *       argmax of f equals the label, invalid labels of map 0's sampling.
+ *   workspace_dev: dsrg_msc_loss_workspace(...) bytes (0 for what the launch refuses), 8-byte aligned: d_f and the winner bytes
+ *       (5 bytes per element of map 0) plus a 32-byte slot per 64 pixels of the maps; too small: DSRG_ERR_INVALID.  After the call
+ *       its first S unsigned 64-bit words hold N_0 .. N_{S-1}.
+ * No floating-point atomics on memory or LDS: repeated calls give identical bits.  Nothing valid: losses 0, zero gradients.
+ * 1 <= B <= 32, 1 <= C <= 96, every size >= 1, B*C*sum(h*w) < 2^31, B*H*W < 2^31. */
+int dsrg_msc_pyramid_batch(int B, const float *images_dev, int H, int W, int n, const int *h, const int *w, float *const *out_dev,
+                           void *stream);
+size_t dsrg_msc_loss_workspace(int S, int B, int C, const int *h, const int *w, int H, int W);
+int dsrg_msc_loss_batch(int S, int B, int C, const float *const *maps_dev, const int *h, const int *w, const float *labels_dev, int H,
+                        int W, float ignore_label, float *losses_dev, float *const *grads_dev, unsigned long long *counters_dev,
+                        void *workspace_dev, size_t workspace_bytes, void *stream);
 /* The stem of the DeepLab-v2 ResNet-101 at test time in one launch (backbone plumbing; the reference's networks are Caffe
  * prototxts): conv 7x7 / stride 2 / zero pad 3, 3 -> 64, with a frozen BatchNorm folded in -> ReLU -> max pool 3x3 / stride 2 /
  * pad 1, ceil mode.  The convolution map never reaches memory.
